@@ -15,6 +15,11 @@ local gradients, one flat fp32 bucket is all-reduced over RCCL/xGMI, every rank 
 (weak scaling: B per GPU fixed).  One JSON line is printed by rank 0.
 
 Other workloads (parity-test configurations and secondary probes, not the headline line): --workload gemm | mlp | knn | attention | umap | lm.
+
+A plain run sets up, warms up, times exactly K steps in one window and prints the line.  Everything else the benchmark can measure or
+check - the CPU baseline, the roofline / per-kernel-class passes, the reference's other precisions and batch sizes, the epoch variants,
+the UMAP phases, the multi-rank self-verification - runs only with --full, outside the timed steps.  --dump-outputs DIR writes what the
+timed path computed in its last step as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -46,12 +51,19 @@ def parse():
     ap.add_argument("--umap-points", default="mixed", choices=["mixed", "weyl"], help="umap-e2e: closed form of the points (see the workload's comment)")
     ap.add_argument("--no-graph", action="store_true", help="resnet: issue the step eagerly instead of replaying forward + backprop from a HIP graph")
     ap.add_argument("--dry-launch", action="store_true", help="launch + rendezvous of the N ranks only (no GPU work): prints {\"dry_launch\": true, \"ranks\": N}")
-    ap.add_argument("--min-window-s", type=float, default=0.5, help="repeat the K-step timed window until this much time is covered; the median window is reported")
+    ap.add_argument("--min-window-s", type=float, default=0.0,
+                    help="repeat the K-step timed window until this much time is covered and report the median window (default 0: one window of exactly K steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: CPU baseline, roofline passes, other precisions / batch sizes / variants, multi-rank self-check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     a = ap.parse_args()
     if a.steps is None:
         a.steps = 1 if a.workload == "umap-e2e" else (2 if a.workload == "epoch" else 20)
     if a.warmup is None:
         a.warmup = 1 if a.workload in ("umap-e2e", "epoch") else 10
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     return a
 
 
@@ -102,6 +114,38 @@ def closed_form_np(n, salt=0, scale=1.0):
     import numpy as np
     i = np.arange(n, dtype=np.int64) + salt
     return ((((i * 7919) % 1009).astype(np.float64) / 1009.0) - 0.5) * scale
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_KEEP_WHOLE = 4096          # arrays up to this many values are never sampled
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` = [(name, ndarray)] -> path/<name>.npy, float64 for float64 and integer sources, float32 otherwise.
+    When they would exceed DUMP_LIMIT_BYTES in all, every array of more than DUMP_KEEP_WHOLE values is replaced by a fixed sample of its
+    flattened values (seed 0, sorted indices: the same positions for the same shape in every run), sized in proportion to the array."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = []
+    for name, arr in arrays:
+        arr = np.asarray(arr)
+        arr = arr.astype(np.float64 if arr.dtype == np.float64 or arr.dtype.kind in "iub" else np.float32)
+        out.append((name, arr))
+    total = sum(arr.nbytes for _, arr in out)
+    sampled = []
+    if total > DUMP_LIMIT_BYTES:
+        room = DUMP_LIMIT_BYTES - sum(arr.nbytes for _, arr in out if arr.size <= DUMP_KEEP_WHOLE) - 256 * len(out)   # 256: .npy headers
+        big = sum(arr.nbytes for _, arr in out if arr.size > DUMP_KEEP_WHOLE)
+        for i, (name, arr) in enumerate(out):
+            if arr.size > DUMP_KEEP_WHOLE:
+                k = max(1, int(arr.size * room / big))
+                idx = np.sort(np.random.default_rng(0).choice(arr.size, k, replace=False))
+                out[i] = (name, arr.reshape(-1)[idx])
+                sampled.append(name)
+    for name, arr in out:
+        np.save(os.path.join(path, f"{name}.npy"), arr)
+    if sampled:
+        print(f"bench.py: --dump-outputs: {len(sampled)} of {len(out)} arrays sampled to stay within {DUMP_LIMIT_BYTES >> 20} MB", file=sys.stderr)
 
 
 def kernel_report(lib):
@@ -294,9 +338,9 @@ def main():
         cp.close()
         return
 
-    # CPU baseline first, in a child process, on rank 0 at N = 1 only (before this process touches the GPU)
+    # --full: CPU baseline first, in a child process, on rank 0 at N = 1 only (before this process touches the GPU)
     cpu_baseline = None
-    if rank == 0 and a.gpus == 1 and not a.no_cpu_baseline and a.workload in ("resnet", "gemm", "mlp", "knn", "umap", "umap-e2e"):
+    if a.full and rank == 0 and a.gpus == 1 and not a.no_cpu_baseline and a.workload in ("resnet", "gemm", "mlp", "knn", "umap", "umap-e2e"):
         try:
             wl = a.workload                   # kNN / UMAP: a bounded sample scaled to the unit of the line (oracle/cpu_baseline.py says how)
             out = subprocess.run([sys.executable, os.path.join(ROOT, "oracle", "cpu_baseline.py"), "--workload", wl, "--budget-s", "15"],
@@ -335,6 +379,15 @@ def main():
 
     dtype = {"bf16": S.BF16, "f32": S.F32, "f64": S.F64}[a.dtype]
     result_extra = {}
+
+    def model_outputs(acc, module):
+        """--dump-outputs of a training step: the loss accumulator, the gradients of the last step (those the replayed graph writes when
+        there is one) and the module state after it"""
+        grads = captured_grads if graph is not None else [p.partialDerivative for p in module.parameters]
+        return ([("loss_sum", acc.to_numpy())] + [(f"grad_{i:03d}", g.to_numpy()) for i, g in enumerate(grads) if g is not None]
+                + [(f"state_{i:03d}", v.value.to_numpy()) for i, v in enumerate(module.state)])
+
+    # outputs(r): [(name, ndarray)] of what the step returning r computed (--dump-outputs)
     if a.workload == "resnet":
         B = a.batch
         lib.lamp_manual_seed(1234)                                   # same initial weights on every rank
@@ -346,6 +399,7 @@ def main():
         opt = nn.AdamW_factory(weightDecay=0.0, learningRate=1e-3, mixedPrecision=(a.dtype == "bf16"))([p.value for p in model_mod.parameters])
         acc = S.STen.zeros([1], dtype, local_rank)
         step = lambda: model.train_step(opt, x, target, acc, comm)
+        outputs = lambda r: model_outputs(acc, model_mod)
         units_per_step = B
         metric, unit = "training-step samples/sec", "samples/s"
         config = {"workload": "example-cifar100 Cnn.resnet(100) training step (fwd+backprop+AdamW), synthetic CIFAR batch",
@@ -400,22 +454,24 @@ def main():
             import gc; gc.collect()
             return rate
 
-        epoch_variants = {}
-        for kind in os.environ.get("LAMP_EPOCH_VARIANTS", "device_resident,host_f32_pinned,host_u8_pinned").split(","):
-            for B in sorted({a.batch, 256}, reverse=True):
-                epoch_variants[f"{kind}_B{B}"] = epoch_rate(kind, B, a.steps)
+        if a.full:
+            epoch_variants = {}
+            for kind in os.environ.get("LAMP_EPOCH_VARIANTS", "device_resident,host_f32_pinned,host_u8_pinned").split(","):
+                for B in sorted({a.batch, 256}, reverse=True):
+                    epoch_variants[f"{kind}_B{B}"] = epoch_rate(kind, B, a.steps)
+            result_extra["epoch_variants_instances_per_s"] = epoch_variants
         # headline: the records stay on the host as the u8 pixels of the CIFAR file and the cast Cifar.loadImageFile applies (castToFloat) runs
         # inside the gather: 3 KB instead of 12 KB per record over PCIe.  (Measured: shader reads of host memory do not overlap the training
         # step - the float variant, 25 MB per batch, costs its full 0.4 ms per batch - while a DMA-engine copy of the same bytes is free;
         # scripts/epoch_interference_probe.py.)
         headline = stream_of("host_u8_pinned", a.batch)
         step = lambda: loops.oneEpoch(0, model, opt, headline)
+        outputs = lambda r: [("training_loss", np.array([r], np.float64))] + [(f"state_{i:03d}", v.value.to_numpy()) for i, v in enumerate(model_mod.state)]
         units_per_step = NREC
         metric, unit = "epoch instances/sec (IOLoops.oneEpoch over minibatchesFromFull)", "samples/s"
         config = {"workload": "example-cifar100 Cnn.resnet(100): one epoch of 50 000 CIFAR-shaped records through BatchStream.minibatchesFromFull "
                               "(host-resident u8 records in pinned memory, minibatch gathered over PCIe and cast by a GPU kernel queued one batch ahead), eager training step",
                   "per_gpu_batch": a.batch, "records": NREC, "parallelism": "single"}
-        result_extra["epoch_variants_instances_per_s"] = epoch_variants
     elif a.workload == "lm":
         # example-autoregressivelm (model.scala:9-37, train.scala:40-66): byte-level GPT, 12 blocks x 768 x 12 heads, context 384,
         # bf16 parameters + mixed-precision AdamW (weight decay on the attention / MLP matrices only, clip 1), DP over the ranks
@@ -435,6 +491,7 @@ def main():
         opt = nn.AdamW_tagged([p.value for p in params], wd, 1e-4, 0.9, 0.95, clip=1.0, mixedPrecision=(a.dtype == "bf16"))
         acc = S.STen.zeros([1], dtype, local_rank)
         step = lambda: model.train_step(opt, x, target, acc, comm)
+        outputs = lambda r: model_outputs(acc, net)
         units_per_step = B * ctx
         metric, unit = "language-model training tokens/sec", "tokens/s"
         config = {"workload": "example-autoregressivelm LanguageModelLoss training step (12 x 768 x 12 heads, context 384, vocabulary 256), synthetic tokens",
@@ -458,6 +515,7 @@ def main():
             S.STen.addmm_out_transposed1(dW, dW, A_, P_, 1.0, 1.0)          # dW += x^T p
             S.STen.addmm_out_transposed2(dX, dX, P_, W_, 1.0, 1.0)          # dX += p W^T
             return y
+        outputs = lambda y: [("y", y.to_numpy()), ("dW", dW.to_numpy()), ("dX", dX.to_numpy())]
         units_per_step = 3 * 2.0 * n ** 3 / 1e12
         metric, unit = "4096x4096 addmm fwd+bwd", "TFLOP/s"
         config = {"workload": "lamp Linear(4096,4096,bias) on x[4096,4096]: fwd addmm + dW (A^T.p) + dX (p.W^T)", "parallelism": "replicas"}
@@ -473,6 +531,7 @@ def main():
             i = C.c_void_p()
             lib.lamp_knn_squared_euclidean(C.byref(i), None, X, Qs, k)
             return S.STen(i)
+        outputs = lambda r: [("neighbours", r.to_numpy())]
         units_per_step = nq
         metric, unit = "kNN queries/sec (1M x 128 f32 points, k = 10)", "queries/s"
         config = {"workload": "lamp.knn.knnSearch squared Euclidean, 131072 queries x 1M points x 128 features, k = 10 (split-f16 filter with the top-k fused in, exact f32 re-rank with a per-query proof, exact f32 MFMA kernel for the unproven queries)",
@@ -490,7 +549,8 @@ def main():
             O_, L_ = S.STen(o), S.STen(l)
             out3 = (C.c_void_p * 3)()
             lib.lamp_scaled_dot_product_attention_backward(out3, g_, q_, k_, v_, O_, L_, 0, 0.0)
-            return [S.STen(h) for h in out3]
+            return [O_, L_] + [S.STen(h) for h in out3]
+        outputs = lambda r: [(nm, t.to_numpy()) for nm, t in zip(("out", "logsumexp", "grad_q", "grad_k", "grad_v"), r)]
         units_per_step = 14.0 * Bz * H * Sq * Sq * D / 1e12      # 4 fwd + 10 bwd model flops per (query, key, feature)
         metric, unit = "attention fwd+bwd (model flops)", "TFLOP/s"
         config = {"workload": "ScaledDotProductAttention fwd + bwd, bf16, batch 8 x 16 heads x 4096 x 128, non-causal", "parallelism": "replicas"}
@@ -538,6 +598,7 @@ def main():
             mark("layout_500_iterations_s", t0)
             return layout, loss, ew.shape[0]
         step = lambda: run()
+        outputs = lambda r: [("layout", r[0].to_numpy()), ("loss", np.array([r[1]], np.float64))]
         units_per_step = n
         metric, unit = "UMAP end-to-end points/sec (1M x 128: kNN graph + edge weights + 500-iteration layout)", "points/s"
         config = {"workload": "lamp.umap.Umap.umap on 1M x 128 synthetic points (closed form: murmur3-finalised index + 16 clusters) already resident in HBM: knnSearch (f32, k = 10) -> f64 neighbour distances -> "
@@ -556,6 +617,7 @@ def main():
 
         def step():
             state["r"] = U.optimize(ew, n, 0.1, 1, 0.0, 5, 42 + len(state), True, 1.0, local_rank, 2)
+        outputs = lambda r: [("layout", state["r"][0].to_numpy()), ("loss", np.array([state["r"][1]], np.float64))]
         units_per_step = 1
         metric, unit = "UMAP layout iterations/sec (1M points)", "iterations/s"
         config = {"workload": "Umap.optimize, 1 iteration per step: 1M points, ~9M edges, 5 negatives per edge, f64, AdamW; includes the per-call "
@@ -569,6 +631,7 @@ def main():
         model = nn.SupervisedModel(model_mod, 0, S.STen.ones([10], S.F32, local_rank))
         acc = S.STen.zeros([1], S.F32, local_rank)
         step = lambda: model.addTotalLossAndReturnGradientsAndNumExamples(x, target, acc)
+        outputs = lambda r: model_outputs(acc, model_mod)
         units_per_step = B
         metric, unit = "MLP fwd+bwd samples/sec", "samples/s"
         config = {"workload": "MLP 784-256-10 fwd+bwd fp32 batch 1024", "parallelism": "replicas"}
@@ -631,8 +694,8 @@ def main():
         model.sync_state(opt, comm, 0)
         config["dp_state_sync"] = "module + optimiser state broadcast from rank 0 before the first step"
     # ---- timed region: EXACTLY K steps between barrier + device synchronize on both sides, no instrumentation inside (kernel timers
-    # off).  A K-step window shorter than --min-window-s is repeated and the MEDIAN window reported (every window is a complete
-    # measurement by the contract; 20 ResNet steps are 30 ms, which one scheduling hiccup of the host distorts).
+    # off).  By default one window; with --min-window-s a K-step window shorter than that is repeated and the MEDIAN window reported
+    # (every window is a complete measurement by the contract).  The last step's return value is kept for --dump-outputs.
     def measure(fn):
         for _ in range(a.warmup):
             fn()
@@ -642,8 +705,9 @@ def main():
         while True:
             barrier()
             t0 = time.perf_counter()
-            for _ in range(a.steps):
+            for _ in range(a.steps - 1):
                 fn()
+            last = fn()
             enq = time.perf_counter() - t0            # host time to issue the steps (the device may still be running)
             barrier()
             w = time.perf_counter() - t0
@@ -655,39 +719,49 @@ def main():
                 break
         order = sorted(range(len(windows)), key=lambda k: windows[k])
         mid = order[len(order) // 2]
-        return windows[mid], enqueues[mid], windows
+        return windows[mid], enqueues[mid], windows, last
 
     alt_mode = None
     if modes:
         timed = [(name, fn) + measure(fn) for name, fn in modes]
+        last = timed[-1][5]                        # the state on the device is that of the mode timed last
         timed.sort(key=lambda t: t[2])             # the medians are already the MAX over ranks: every rank sorts alike
-        name, step, elapsed, enqueue, windows = timed[0]
+        name, step, elapsed, enqueue, windows, _ = timed[0]
         config["exchange_mode"] = name
         alt_mode = [{"mode": t[0], "ms_per_step": t[2] / a.steps * 1e3, "value": units_per_step * a.gpus * a.steps / t[2],
                      "windows": len(t[4])} for t in timed[1:]]
     else:
-        elapsed, enqueue, windows = measure(step)
+        elapsed, enqueue, windows, last = measure(step)
 
-    # ---- multi-rank self-verification (untimed, after the measurement): the line is only printed when the
+    # ---- what the timed path computed in its last step, before anything below runs the step again
+    if a.dump_outputs:
+        if rank == 0:
+            dump_outputs(a.dump_outputs, outputs(last))
+        if dist is not None:
+            dist.barrier()
+    del last
+
+    # ---- --full: multi-rank self-verification (untimed, after the measurement): the line is only printed when the
     # replicas hold bit-identical state and the averaged gradients are the example-weighted mean of the per-rank gradients
     verify = None
-    if comm is not None and a.workload == "resnet":
+    if a.full and comm is not None and a.workload == "resnet":
         verify = verify_data_parallel(lib, S, np, C, dist, comm, model, model_mod, opt, x, target, acc, B, rank, world, local_rank, modes)
 
-    # ---- untimed passes for the roofline object (after the measurement, so they cannot disturb it)
+    # ---- --full: untimed passes for the roofline object (after the measurement, so they cannot disturb it)
     # 1. classification: every tagged launch bracketed by HIP events (on the stream it is launched on) -> per-class table
     PROFILE_STEPS = 2
-    barrier()
-    lib.lamp_kernel_timer_filter(None)
-    lib.lamp_kernel_timer_enable(1)
-    for _ in range(PROFILE_STEPS):
-        step_eager()
-    barrier()
-    lib.lamp_kernel_timer_enable(0)
-    class_rows = kernel_report(lib)
-    dominant = max(class_rows, key=lambda r: r["total_ms"])["tag"] if class_rows else None
+    class_rows, rows, dominant = [], [], None
+    if a.full:
+        barrier()
+        lib.lamp_kernel_timer_filter(None)
+        lib.lamp_kernel_timer_enable(1)
+        for _ in range(PROFILE_STEPS):
+            step_eager()
+        barrier()
+        lib.lamp_kernel_timer_enable(0)
+        class_rows = kernel_report(lib)
+        dominant = max(class_rows, key=lambda r: r["total_ms"])["tag"] if class_rows else None
     # 2. the dominant class alone (events on ~10 launches per step instead of ~100: the kernels around it run as in the timed region)
-    rows = []
     if dominant:
         lib.lamp_kernel_timer_filter(dominant.encode())
         lib.lamp_kernel_timer_enable(1)
@@ -704,7 +778,7 @@ def main():
         nf = C.c_int64(0); lib.lamp_knn_split_last_failed(C.byref(nf))
         result_extra["knn_path"] = (f"split-f16 filter ({pl.value} planes) + exact re-rank; {nf.value} of {units_per_step} queries went to the exact kernel"
                                     if pl.value else "exact f32 kernel for every query (the filter's sample predicted too few provable queries)")
-    if a.workload == "umap-e2e":
+    if a.full and a.workload == "umap-e2e":
         ph = {}
         _, last_loss, n_edges = run(ph)            # untimed, instrumented pass: seconds per phase (device synchronised between phases)
         result_extra["phases"] = ph
@@ -730,11 +804,11 @@ def main():
             result_extra["roofline_layout"] = roofline_of(lay_rows)
         if knn_rows:
             result_extra["roofline_knn"] = roofline_of(knn_rows)
-    # ---- the same K-step protocol, after the headline measurement and its roofline passes (never inside its timed region),
-    # for the step in the reference example's own precisions (cifar100.scala:127-129) and at the small batch SURVEY 8d config 3 also asks for:
-    # fresh model, one eager step, forward + backprop captured into a HIP graph, warm-up, K-step windows between device synchronisations, median.
+    # ---- --full, VERDICT r4 item 5: the same K-step protocol, after the headline measurement and its roofline passes (never inside its timed
+    # region), for the step in the reference example's own precisions (cifar100.scala:127-129) and at the small batch SURVEY 8d config 3 also asks
+    # for: fresh model, one eager step, forward + backprop captured into a HIP graph, warm-up, K-step windows between device synchronisations, median.
     also = None
-    if a.workload == "resnet" and a.gpus == 1 and rank == 0 and os.environ.get("LAMP_BENCH_ALSO", "1") != "0" and not under_profiler:
+    if a.full and a.workload == "resnet" and a.gpus == 1 and rank == 0 and os.environ.get("LAMP_BENCH_ALSO", "1") != "0" and not under_profiler:
         def variant_ms(dt_name, Bv):
             dtv = {"bf16": S.BF16, "f32": S.F32, "f64": S.F64}[dt_name]
             lib.lamp_manual_seed(1234)
@@ -779,13 +853,16 @@ def main():
                 also[key] = f"failed: {e}"
     if rank == 0:
         value = units_per_step * a.gpus * a.steps / elapsed
-        roof = roofline_of(rows)
         line = {"metric": metric, "value": value, "unit": unit, "n_gpus": a.gpus, "steps": a.steps, "warmup": a.warmup,
                 "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-                "dtype": a.dtype, "data": "synthetic", "config": config, "roofline": roof, "cpu_baseline": cpu_baseline,
-                "rccl_ranks": rccl_ranks,
-                "timed_windows": {"count": len(windows), "steps_each": a.steps, "reported": "median",
-                                  "min_ms_per_step": min(windows) / a.steps * 1e3, "max_ms_per_step": max(windows) / a.steps * 1e3}}
+                "dtype": a.dtype, "data": "synthetic", "config": config}
+        if a.full:
+            line["roofline"] = roofline_of(rows)
+            line["cpu_baseline"] = cpu_baseline
+        line["rccl_ranks"] = rccl_ranks
+        line["timed_windows"] = {"count": len(windows), "steps_each": a.steps, "reported": "median",
+                                 "min_ms_per_step": min(windows) / a.steps * 1e3, "max_ms_per_step": max(windows) / a.steps * 1e3}
+        line["full"] = a.full
         line.update(result_extra)
         if also is not None:
             line["also"] = also
@@ -793,7 +870,7 @@ def main():
             line["alt_mode"] = alt_mode
         if verify is not None:
             line.update(verify)
-        if a.workload == "resnet":
+        if a.full and a.workload == "resnet":
             # whole-step figures against SURVEY.md 8(d): 153.3 MFLOP and ~1.4 MB algorithmic HBM bytes per sample per step
             per_gpu = value / a.gpus
             # bytes / flops per step as the launchers of this run declared them (sum over the kernel classes of the classification pass)
@@ -810,9 +887,10 @@ def main():
                                                          "frac_bf16_mfma_peak": per_gpu * 153.3e6 / 1e12 / PEAK_BF16_TFLOPS,
                                                          "frac_hbm_peak": per_gpu * 1.4e6 / 1e9 / PEAK_HBM_GBS}}
         line["host_enqueue_ms_per_step"] = enqueue / a.steps * 1e3
-        top = sorted(class_rows, key=lambda r: -r["total_ms"])[:int(os.environ.get("LAMP_BENCH_TOP", "10"))]
-        line["kernel_classes"] = [{"tag": r["tag"], "launches_per_step": r["launches"] / PROFILE_STEPS, "ms_per_step": r["total_ms"] / PROFILE_STEPS}
-                                  for r in top]
+        if a.full:
+            top = sorted(class_rows, key=lambda r: -r["total_ms"])[:int(os.environ.get("LAMP_BENCH_TOP", "10"))]
+            line["kernel_classes"] = [{"tag": r["tag"], "launches_per_step": r["launches"] / PROFILE_STEPS, "ms_per_step": r["total_ms"] / PROFILE_STEPS}
+                                      for r in top]
         print(json.dumps(line), file=line_out, flush=True)
     if comm is not None:
         lib.lamp_comm_destroy(comm)

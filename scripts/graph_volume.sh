@@ -17,7 +17,7 @@ if [ "${GV_PART:-1}" = 1 ]; then
 run bench_8_launches python3 $R/bench.py --steps 5 --warmup 3 --no-cpu-baseline --min-window-s 0
 run bench_40_launches python3 $R/bench.py --steps 30 --warmup 10 --no-cpu-baseline --min-window-s 0
 run bench_150_launches python3 $R/bench.py --steps 140 --warmup 10 --no-cpu-baseline --min-window-s 0
-run bench_default_window python3 $R/bench.py --steps 5 --warmup 3 --no-cpu-baseline
+run bench_default_window python3 $R/bench.py --steps 5 --warmup 3 --no-cpu-baseline --min-window-s 0.5
 run toy_3_kernels_x_2000 python3 $R/scripts/graph_toy.py 2000
 run toy_3_kernels_x_30000 python3 $R/scripts/graph_toy.py 30000
 run ew200_x_50 python3 $R/scripts/graph_bisect.py ew200 50

@@ -6,12 +6,12 @@ set -u
 R=$PWD; O=$R/gpurun_out/refresh4; mkdir -p $O
 export TMPDIR=/tmp
 ulimit -c 0
-python bench.py --dtype f32 > $O/resnet_f32_bench.log 2>$O/resnet_f32_bench.err
-python bench.py --dtype f64 --no-cpu-baseline > $O/resnet_f64_bench.log 2>$O/resnet_f64_bench.err
+python bench.py --dtype f32 --full --min-window-s 0.5 > $O/resnet_f32_bench.log 2>$O/resnet_f32_bench.err
+python bench.py --dtype f64 --no-cpu-baseline --full --min-window-s 0.5 > $O/resnet_f64_bench.log 2>$O/resnet_f64_bench.err
 # what the step cost before round 4's f64 kernels (direct convolutions): two steps are enough
 LAMP_IGEMM_F64=0 LAMP_CONV_SMALL2=0 python bench.py --dtype f64 --no-cpu-baseline --steps 2 --warmup 1 --min-window-s 0 > $O/resnet_f64_before_bench.log 2>/dev/null
-python bench.py --workload epoch > $O/epoch_bench.log 2>$O/epoch_bench.err
-python bench.py --workload mlp > $O/mlp_bench.log 2>/dev/null
+python bench.py --workload epoch --full --min-window-s 0.5 > $O/epoch_bench.log 2>$O/epoch_bench.err
+python bench.py --workload mlp --full --min-window-s 0.5 > $O/mlp_bench.log 2>/dev/null
 python scripts/igemm_f32_layers_probe.py > $O/resnet_f32_layers.txt 2>&1
 python scripts/epoch_interference_probe.py > $O/epoch_interference.txt 2>&1
 python scripts/epoch_stream_probe.py > $O/epoch_stream.txt 2>&1

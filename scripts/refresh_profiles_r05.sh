@@ -7,12 +7,12 @@ R=$PWD; O=$R/gpurun_out/refresh5; mkdir -p $O
 export TMPDIR=/tmp
 ulimit -c 0
 for B in 256 32; do for D in bf16 f32; do
-  LAMP_BENCH_ALSO=0 python bench.py --batch $B --dtype $D --no-cpu-baseline > $O/resnet_b${B}_${D}_bench.log 2>/dev/null
+  LAMP_BENCH_ALSO=0 python bench.py --batch $B --dtype $D --no-cpu-baseline --full --min-window-s 0.5 > $O/resnet_b${B}_${D}_bench.log 2>/dev/null
 done; done
-python bench.py --dtype f32 > $O/resnet_f32_bench.log 2>$O/resnet_f32_bench.err
-python bench.py --dtype f64 --no-cpu-baseline > $O/resnet_f64_bench.log 2>$O/resnet_f64_bench.err
-python bench.py --workload epoch > $O/epoch_bench.log 2>$O/epoch_bench.err
-python bench.py --workload mlp > $O/mlp_bench.log 2>/dev/null
+python bench.py --dtype f32 --full --min-window-s 0.5 > $O/resnet_f32_bench.log 2>$O/resnet_f32_bench.err
+python bench.py --dtype f64 --no-cpu-baseline --full --min-window-s 0.5 > $O/resnet_f64_bench.log 2>$O/resnet_f64_bench.err
+python bench.py --workload epoch --full --min-window-s 0.5 > $O/epoch_bench.log 2>$O/epoch_bench.err
+python bench.py --workload mlp --full --min-window-s 0.5 > $O/mlp_bench.log 2>/dev/null
 cd /tmp
 prof() { # name, bench args...
   n=$1; shift

@@ -23,7 +23,7 @@ rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/pf -o f --
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d /tmp/pw -o w -- python3 $R/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-graph > /tmp/pw.log 2>&1
 python3 $R/scripts/pmc_traffic.py $(find /tmp/pf -name "*counter_collection.csv" | head -1) $(find /tmp/pw -name "*counter_collection.csv" | head -1) $O/pmc_traffic.json > $O/pmc_traffic.txt 2>&1
 cp $O/pmc_traffic.json $R/profiles/r06_pmc_traffic.json
-cd $R; python bench.py > $O/bench.log 2>$O/bench.err; cd /tmp
+cd $R; python bench.py --full --min-window-s 0.5 > $O/bench.log 2>$O/bench.err; cd /tmp
 prof resnet_b256 --batch 256
 prof resnet_b32 --batch 32
 prof resnet_f32 --dtype f32
@@ -32,6 +32,6 @@ for w in gemm knn attention umap lm; do
   cp $(find /tmp/ks_$w -name "*kernel_stats.csv" | head -1) $O/${w}_kernel_stats.csv
 done
 cd $R
-for w in gemm knn attention umap umap-e2e lm mlp epoch; do python bench.py --workload $w > $O/${w}_bench.log 2>/dev/null; done
+for w in gemm knn attention umap umap-e2e lm mlp epoch; do python bench.py --workload $w --full --min-window-s 0.5 > $O/${w}_bench.log 2>/dev/null; done
 python scripts/gemm_ab.py > $O/gemm_ab.txt 2>&1 || true
 cat $O/pytest_gpu.txt; tail -c 700 $O/bench.log; head -12 $O/pmc_traffic.txt; cat $O/class_rocprof.txt

@@ -516,7 +516,7 @@ def test_bench_multi_rank_line_verifies_itself(gpu, tmp_path):
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()),
                LAMP_BENCH_FORCE_COMM="1", LAMP_RDZV_FILE=str(tmp_path / "r.json"))
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--no-cpu-baseline",
-                          "--batch", "256", "--min-window-s", "0.05"], env=env, capture_output=True, text=True, timeout=900)
+                          "--batch", "256", "--min-window-s", "0.05", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-4000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert line["rccl_ranks"] == 1 and line["replicas_identical"] is True
