@@ -114,16 +114,19 @@ struct Storage {
   std::atomic<uint64_t> version{0};
   uint64_t uid = next_uid();    // never reused (a freed Storage's address can be)
   static uint64_t next_uid() { static std::atomic<uint64_t> c{1}; return c.fetch_add(1, std::memory_order_relaxed); }
-  // Set while a deferred kernel still has to produce the contents (kernels/wgrad_reduce.hip: the reductions of a backward pass's
-  // weight-gradient partial sums run batched in one launch).  Every pointer into the storage goes through lamp_tensor::raw(), which
-  // resolves the deferral first - so nobody can observe the tensor before it is complete.
+  // Deferred work on the storage (kernels/wgrad_reduce.hip: weight-gradient launches parked for a second layer, the batched reductions of
+  // their partial sums), counted per registry entry.  pending: entries that still have to produce the contents - every pointer into the
+  // storage goes through lamp_tensor::raw(), which resolves them first, so nobody can observe the tensor before it is complete.
+  // deferred_reads: parked launches that still have to read it - the mutable accessor (data()) resolves them first, so a write into a
+  // parked layer's input is queued after the launch that reads it.
   std::atomic<uint32_t> pending{0};
+  std::atomic<uint32_t> deferred_reads{0};
   // a strided filter's contiguous copy made inside a convolution entry point (kernels/conv.hip): it dies with the call, so no packed-weight
   // cache keeps an image of it (an entry under its never-reused uid could only be evicted, and a pair image would outlive one of its sources)
   bool scratch = false;
 };
-void resolve_deferred(Storage* st);   // runs every pending deferred kernel now (on the streams they were registered on)
-void flush_deferred();                // the same, called at the natural batching points (end of backprop, lamp_flush_deferred)
+void resolve_deferred(Storage* st);   // runs the deferred work of every thread that has some on st now (on the streams it was registered on)
+void flush_deferred();                // runs the calling thread's deferred work, at the natural batching points (end of backprop, lamp_flush_deferred)
 
 }  // namespace lamp
 
@@ -149,7 +152,12 @@ struct lamp_tensor {
     if (st->pending.load(std::memory_order_acquire)) lamp::resolve_deferred(st);
     return (char*)st->ptr + offset * (int64_t)itemsize();
   }
-  void* data() { if (st) st->version.fetch_add(1, std::memory_order_relaxed); return raw(); }
+  void* data() {
+    if (!st) return nullptr;
+    st->version.fetch_add(1, std::memory_order_relaxed);
+    if (st->deferred_reads.load(std::memory_order_acquire)) lamp::resolve_deferred(st);
+    return raw();
+  }
   const void* data() const { return raw(); }
   template <class T> T* ptr() { return (T*)data(); }
   template <class T> const T* ptr() const { return (const T*)raw(); }

@@ -2608,85 +2608,26 @@ static int wgrad_min_ips(int64_t N) {
   return v ? v : (N <= 512 ? 2 : 8);
 }
 // ---- the eight-wave weight-gradient kernel: one launch for one layer (optionally with its sibling 1x1: `second`) or for TWO layers (round 6) ----
-struct SecondWgradConv;
-struct Wg8hProblem { const Tensor* dy; const Tensor* x; Tensor* dw; ConvGeom g; const Tensor* affine; };
-static void wg8h_launch(const Wg8hProblem& a, const Wg8hProblem* b, hipStream_t st, const SecondWgradConv* second);
 // Two layers in one launch.  A layer's launch leaves (256 workgroups) x (its accumulators) of partial sums - 33 MB written by the kernel and read
 // again by the batched reduction, whatever the layer's size; with two layers' workgroups side by side each layer is walked by half the workgroups,
 // twice as many images each, and leaves half of that.  Nothing in backprop waits for a weight gradient (only the optimiser reads it), so a layer
-// that qualifies is PARKED here - its tensors retained, its gradient's storage marked pending like a deferred reduction's - until the next one
-// arrives (res4's second convolution waits for res3's, three kernels later) or anything flushes: the end of backprop, a read of the gradient
-// (Tensor::raw -> resolve_deferred), a stream / device synchronisation, the end of a graph capture.  LAMP_WGRAD_GROUP=0: every layer at once.
-namespace {
-struct ParkedWgrad { Tensor* dy; Tensor* x; Tensor* dw; ConvGeom g; Tensor* affine; hipStream_t st; int device; uint64_t vdy, vx; std::thread::id owner; };
-std::mutex g_wgpark_mu;
-std::vector<ParkedWgrad> g_wgpark;
-void wgpark_release(ParkedWgrad& p) { release(p.dy); release(p.x); release(p.dw); if (p.affine) release(p.affine); }
-void wgpark_check(const ParkedWgrad& p) {
-  // (x is a forward activation: nothing writes it during backprop, but the batch-norm backward that runs meanwhile takes its pointer through the
-  // mutable accessor, which counts as a write - only the gradient's version is held to its value at parking)
-  LAMP_CHECK(p.dy->st->version.load(std::memory_order_relaxed) == p.vdy, "internal: the output gradient of a parked weight gradient was written before its launch");
-}
-}  // namespace
-// the parked layers, each alone (called with nothing of this file's locks held).  An entry belongs to the thread that parked it, like a deferred
-// reduction: flush_deferred() launches the CALLER's (all = false) - a replica thread of the single-process data-parallel step must not launch
-// another's half-finished pass early -, a read of a pending gradient (resolve_deferred) launches everybody's: the launch goes to the entry's stream
-void igemm_wgrad_flush_parked(bool all) {
-  std::vector<ParkedWgrad> v;
-  {
-    std::lock_guard<std::mutex> lk(g_wgpark_mu);
-    const std::thread::id me = std::this_thread::get_id();
-    size_t keep = 0;
-    for (size_t i = 0; i < g_wgpark.size(); i++) {
-      if (all || g_wgpark[i].owner == me) v.push_back(g_wgpark[i]);
-      else g_wgpark[keep++] = g_wgpark[i];
-    }
-    g_wgpark.resize(keep);
-  }
-  for (auto& p : v) {
-    struct Rel { ParkedWgrad& p; ~Rel() { wgpark_release(p); } } rel{p};
-    wgpark_check(p);
-    const int prev = current_device();
-    if (prev != p.device) set_device(p.device);
-    struct Back { int prev, dev; ~Back() { if (prev != dev) set_device(prev); } } back{prev, p.device};
-    Wg8hProblem a{p.dy, p.x, p.dw, p.g, p.affine};
-    wg8h_launch(a, nullptr, p.st, nullptr);
-  }
-}
+// that qualifies is PARKED in the registry of deferred work (wgrad_park) until the next one of its thread, stream, device and batch arrives (res4's
+// second convolution waits for res3's, three kernels later) or its owner's entries are flushed: the end of backprop, a read of the gradient, a write
+// into one of its inputs (queued after the launch), a stream / device synchronisation, the end of a graph capture.  LAMP_WGRAD_GROUP=0: every layer at once.
 static bool wg8h_group_defer(const Tensor* dy, const Tensor* x, Tensor* dw, const ConvGeom& g, hipStream_t st, const Tensor* affine) {
   static const bool on = [] { const char* e = getenv("LAMP_WGRAD_GROUP"); return !(e && e[0] == '0'); }();
   static const int shift_dy = [] { const char* e = getenv("LAMP_WGRAD_SHIFT_DY"); return e ? atoi(e) : 2; }();
-  // large batches only (a workgroup still walks >= 16 images with half the workgroups), gradients the library owns (the pending flag is honoured
-  // by every reader that goes through Tensor::raw), deferred reductions on
-  if (!on || shift_dy < 2 || !wgrad_reduce_deferred() || !dw->st->owned || g.N < 8 * (int64_t)num_cus()) return false;
-  ParkedWgrad mate{};
-  bool have = false;
-  {
-    std::lock_guard<std::mutex> lk(g_wgpark_mu);
-    const std::thread::id me = std::this_thread::get_id();
-    for (size_t i = 0; i < g_wgpark.size(); i++)
-      if (g_wgpark[i].owner == me && g_wgpark[i].st == st && g_wgpark[i].device == dw->device() && g_wgpark[i].g.N == g.N && g_wgpark[i].dw->st != dw->st) {
-        mate = g_wgpark[i]; g_wgpark.erase(g_wgpark.begin() + i); have = true; break;
-      }
-    if (!have) {
-      ParkedWgrad p{retain(const_cast<Tensor*>(dy)), retain(const_cast<Tensor*>(x)), retain(dw), g, affine ? retain(const_cast<Tensor*>(affine)) : nullptr, st,
-                    dw->device(), dy->st->version.load(std::memory_order_relaxed), x->st->version.load(std::memory_order_relaxed), me};
-      g_wgpark.push_back(p);
-      dw->st->version.fetch_add(1, std::memory_order_relaxed);  // a writer like any other
-      dw->st->pending.store(1, std::memory_order_release);
-      return true;
-    }
-  }
-  struct Rel { ParkedWgrad& p; ~Rel() { wgpark_release(p); } } rel{mate};
-  wgpark_check(mate);
-  Wg8hProblem a{mate.dy, mate.x, mate.dw, mate.g, mate.affine}, b{dy, x, dw, g, affine};
-  wg8h_launch(a, &b, st, nullptr);
+  // large batches only (a workgroup still walks >= 16 images with half the workgroups), deferred reductions on, tensors the library owns (the
+  // deferral is honoured by every access through Tensor::raw / data: a caller's own memory can change without the library seeing it)
+  if (!on || shift_dy < 2 || !wgrad_reduce_deferred() || g.N < 8 * (int64_t)num_cus()) return false;
+  if (!dy->st->owned || !x->st->owned || !dw->st->owned || (affine && !affine->st->owned)) return false;
+  wgrad_park(Wg8hProblem{dy, x, dw, g, affine}, st);
   return true;
 }
 // second (optional, the eight-wave kernel only): the output gradient of a sibling 1x1 convolution of the same x and the tensor that receives ITS
 // weight gradient - both from the one launch (igemm_conv_wgrad_pair checks the conditions first)
 struct SecondWgradConv { const Tensor* dy; Tensor* dw; const ConvGeom* g; };
-static void wg8h_launch(const Wg8hProblem& pa, const Wg8hProblem* pb, hipStream_t st, const SecondWgradConv* second) {
+void wg8h_launch(const Wg8hProblem& pa, const Wg8hProblem* pb, hipStream_t st, const SecondWgradConv* second, std::vector<WgradReduction>* out) {
   const bool pair = second != nullptr;
   LAMP_CHECK(!(pair && pb), "internal: the sibling pair and the two-layer group do not combine");
   const int RS = 9;
@@ -2711,8 +2652,8 @@ static void wg8h_launch(const Wg8hProblem& pa, const Wg8hProblem* pb, hipStream_
     B = plan(*pb, cus / 2);
     if (A.wgs % 8 != 0) {                                     // (a ragged first problem would shift the second one's XCDs: not grouped)
       Wg8hProblem a1 = pa, b1 = *pb;
-      wg8h_launch(a1, nullptr, st, nullptr);
-      wg8h_launch(b1, nullptr, st, nullptr);
+      wg8h_launch(a1, nullptr, st, nullptr, out);
+      wg8h_launch(b1, nullptr, st, nullptr, out);
       return;
     }
   }
@@ -2763,7 +2704,8 @@ static void wg8h_launch(const Wg8hProblem& pa, const Wg8hProblem* pb, hipStream_
     const int64_t cols = (int64_t)RS * IG_M * q.CIP / 4;
     WgradReduceArgs ra{};
     ra.kind = 0; ra.CO = (int)p.g.Cout; ra.CI = (int)p.g.Cin; ra.CIP = q.CIP; ra.COP = IG_M; ra.RS = RS; ra.nsplit = q.nsplit; ra.blocks = (int)((cols + 31) / 32);
-    wgrad_reduce_enqueue(ra, q.partial.get(), p.dw, st);
+    if (!out) { wgrad_reduce_enqueue(ra, q.partial.get(), p.dw, st); return; }
+    out->push_back(WgradReduction{ra, std::move(q.partial), Hold(retain(p.dw))});
   };
   enqueue(pa, A);
   if (pb) enqueue(*pb, B);
@@ -2785,7 +2727,7 @@ static bool igemm_conv_wgrad_impl(const Tensor* dy, const Tensor* x, Tensor* dw,
     // eight-wave kernel: the v2 decomposition (32-channel slice of Cin, image range) with two waves per SIMD
     if (!second && wg8h_group_defer(dy, x, dw, g, st, affine)) return true;      // launched with the next such layer's, or by the flush (below)
     Wg8hProblem a{dy, x, dw, g, affine};
-    wg8h_launch(a, nullptr, st, second);
+    wg8h_launch(a, nullptr, st, second, nullptr);
     return true;
   }
   {

@@ -1657,22 +1657,26 @@ static int bn_backward_impl(lamp_tensor* out3[3], const lamp_tensor* grad_out, c
     LAMP_LAUNCH_CHECK();
     mean_t = mean_h.get(); invstd_t = invstd_h.get();
   }
+  // the inputs are only read: through const handles (a mutable access would launch the weight-gradient work parked on them early)
+  const Tensor* X = xc.get();
+  const Tensor* G = gc.get();
+  const Tensor* AD = addc.get();
   Hold dx(mask[0] ? new_like(xc.get()) : nullptr);
   Hold dw(mask[1] ? new_tensor(cs, 1, x->dtype, x->device()) : nullptr);
   Hold db(mask[2] ? new_tensor(cs, 1, x->dtype, x->device()) : nullptr);
   const int64_t total = x->numel();
   LAMP_DISPATCH_FLOAT(x->dtype, T, {
     using A = acc_t<T>;
-    const int vec = (g.HW % (16 / sizeof(T)) == 0) && (((uintptr_t)xc->data() | (uintptr_t)gc->data() | (uintptr_t)(dx.get() ? dx->data() : nullptr) |
-                                                          (uintptr_t)(addc.get() ? addc->data() : nullptr) | (uintptr_t)(dadd.get() ? dadd->data() : nullptr)) & 15) == 0;
+    const int vec = (g.HW % (16 / sizeof(T)) == 0) && (((uintptr_t)X->data() | (uintptr_t)G->data() | (uintptr_t)(dx.get() ? dx->data() : nullptr) |
+                                                          (uintptr_t)(AD ? AD->data() : nullptr) | (uintptr_t)(dadd.get() ? dadd->data() : nullptr)) & 15) == 0;
     const bool col = g.HW < 64;
     bool fused_done = false;
     if constexpr (std::is_same<T, bf16_t>::value) {
       if (training && vec && !col && total > 0 && (dx.get() || dadd.get()))
-        fused_done = bn_bwd_fused_launch(gc.get(), xc.get(), mean_t, invstd_t, weight, bias, dw.get(), db.get(), dx.get(), dadd.get(), addc.get(), g, relu, st);
+        fused_done = bn_bwd_fused_launch(G, X, mean_t, invstd_t, weight, bias, dw.get(), db.get(), dx.get(), dadd.get(), AD, g, relu, st);
     } else if constexpr (std::is_same<T, float>::value || std::is_same<T, double>::value) {
       if (training && vec && !col && total > 0 && (dx.get() || dadd.get()))
-        fused_done = bn_bwd_fused_fp_launch<T>(gc.get(), xc.get(), mean_t, invstd_t, weight, bias, dw.get(), db.get(), dx.get(), dadd.get(), addc.get(), g, relu, st);
+        fused_done = bn_bwd_fused_fp_launch<T>(G, X, mean_t, invstd_t, weight, bias, dw.get(), db.get(), dx.get(), dadd.get(), AD, g, relu, st);
     }
     if (!fused_done) {
     const int64_t blocks = col ? (g.C + 255) / 256 : g.C;
@@ -1682,10 +1686,10 @@ static int bn_backward_impl(lamp_tensor* out3[3], const lamp_tensor* grad_out, c
     Hold partial(new_tensor(ps, 1, acc_dtype<A>(), x->device())), sums(new_tensor(ss, 1, acc_dtype<A>(), x->device()));
     {
       KernelTimer kt1("bn_bwd_reduce", 0, 2.0 * (double)total * sizeof(T), st);
-      if (col) hipLaunchKernelGGL((bn_bwd_reduce_col_kernel<T>), dim3((unsigned)blocks, nsplit), dim3(256), 0, st, gc->ptr<T>(), xc->ptr<T>(), mean_t->ptr<T>(), partial->ptr<A>(), g.N, g.C, g.HW, nsplit);
-      else hipLaunchKernelGGL((bn_bwd_reduce_kernel<T>), dim3((unsigned)g.C, nsplit), dim3(256), 0, st, gc->ptr<T>(), xc->ptr<T>(), mean_t->ptr<T>(), partial->ptr<A>(), g.N, g.C, g.HW, nsplit, vec,
+      if (col) hipLaunchKernelGGL((bn_bwd_reduce_col_kernel<T>), dim3((unsigned)blocks, nsplit), dim3(256), 0, st, G->ptr<T>(), X->ptr<T>(), mean_t->ptr<T>(), partial->ptr<A>(), g.N, g.C, g.HW, nsplit);
+      else hipLaunchKernelGGL((bn_bwd_reduce_kernel<T>), dim3((unsigned)g.C, nsplit), dim3(256), 0, st, G->ptr<T>(), X->ptr<T>(), mean_t->ptr<T>(), partial->ptr<A>(), g.N, g.C, g.HW, nsplit, vec,
                               relu, invstd_t->ptr<T>(), weight ? weight->ptr<T>() : (const T*)nullptr, bias ? bias->ptr<T>() : (const T*)nullptr,
-                              addc.get() ? addc->ptr<T>() : (const T*)nullptr);
+                              AD ? AD->ptr<T>() : (const T*)nullptr);
     }
     LAMP_LAUNCH_CHECK();
     T* dwp = dw.get() ? dw->ptr<T>() : (T*)nullptr;
@@ -1697,9 +1701,9 @@ static int bn_backward_impl(lamp_tensor* out3[3], const lamp_tensor* grad_out, c
       const int do_apply = ((dx.get() || dadd.get()) && total > 0) ? 1 : 0;
       const int nblk = do_apply ? nsplit : 1;
       KernelTimer kt2("bn_bwd_apply", 0, 3.0 * (double)total * sizeof(T), st);
-      hipLaunchKernelGGL((bn_bwd_apply2_kernel<T>), dim3((unsigned)g.C, nblk), dim3(256), 0, st, gc->ptr<T>(), xc->ptr<T>(), mean_t->ptr<T>(), invstd_t->ptr<T>(),
+      hipLaunchKernelGGL((bn_bwd_apply2_kernel<T>), dim3((unsigned)g.C, nblk), dim3(256), 0, st, G->ptr<T>(), X->ptr<T>(), mean_t->ptr<T>(), invstd_t->ptr<T>(),
                          wp, bp, partial->ptr<A>(), nsplit, dwp, dbp, dx.get() ? dx->ptr<T>() : (T*)nullptr, g.N, g.C, g.HW, nblk,
-                         1.0 / (double)(g.N * g.HW), training, vec, relu, do_apply, addc.get() ? addc->ptr<T>() : (const T*)nullptr,
+                         1.0 / (double)(g.N * g.HW), training, vec, relu, do_apply, AD ? AD->ptr<T>() : (const T*)nullptr,
                          dadd.get() ? dadd->ptr<T>() : (T*)nullptr);
       LAMP_LAUNCH_CHECK();
     } else {
@@ -1708,7 +1712,7 @@ static int bn_backward_impl(lamp_tensor* out3[3], const lamp_tensor* grad_out, c
       LAMP_LAUNCH_CHECK();
       if (dx.get() && total > 0) {
         KernelTimer kt2("bn_bwd_apply", 0, 3.0 * (double)total * sizeof(T), st);
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<T>), dim3(grid_for(total, 256)), dim3(256), 0, st, gc->ptr<T>(), xc->ptr<T>(), mean_t->ptr<T>(),
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<T>), dim3(grid_for(total, 256)), dim3(256), 0, st, G->ptr<T>(), X->ptr<T>(), mean_t->ptr<T>(),
                            invstd_t->ptr<T>(), wp, sums->ptr<A>(), dx->ptr<T>(), total, g.C, g.HW, 1.0 / (double)(g.N * g.HW), training, vec, relu, bp);
         LAMP_LAUNCH_CHECK();
       }
@@ -1815,13 +1819,13 @@ int lamp_native_batch_norm2_add_relu_backward(lamp_tensor* out6[6], const lamp_t
     Hold dx(mask[0] ? new_like(xc.get()) : nullptr), dx2(mask[3] ? new_like(xc.get()) : nullptr);
     Hold dw(mask[1] ? new_tensor(cs, 1, x->dtype, x->device()) : nullptr), db(mask[2] ? new_tensor(cs, 1, x->dtype, x->device()) : nullptr);
     Hold dw2(mask[4] ? new_tensor(cs, 1, x->dtype, x->device()) : nullptr), db2(mask[5] ? new_tensor(cs, 1, x->dtype, x->device()) : nullptr);
-    const bool aligned = g.HW % 8 == 0 && (((uintptr_t)xc->data() | (uintptr_t)(gc.get() ? gc->data() : nullptr) | (uintptr_t)x2c->data() |
+    const bool aligned = g.HW % 8 == 0 && (((uintptr_t)xc->raw() | (uintptr_t)(gc.get() ? gc->raw() : nullptr) | (uintptr_t)x2c->raw() |
                                             (uintptr_t)(dx.get() ? dx->data() : nullptr) | (uintptr_t)(dx2.get() ? dx2->data() : nullptr)) & 15) == 0;
     BnDualHost dh{save_mean2, save_invstd2, weight2, bias2, dw2.get(), db2.get()};
     bool done = aligned && bn_bwd_fused_launch(gc.get(), xc.get(), save_mean, save_invstd, weight, bias, dw.get(), db.get(), dx.get(), dx2.get(), x2c.get(), g, 1, st, &dh, gplanes);
     if (!done && !gc.get()) {                               // the plane form did not take it: the same kernel on the materialised gradient
       gc = Hold(contiguous(grad_out));
-      done = (((uintptr_t)gc->data()) & 15) == 0 && g.HW % 8 == 0 &&
+      done = (((uintptr_t)gc->raw()) & 15) == 0 && g.HW % 8 == 0 &&
              bn_bwd_fused_launch(gc.get(), xc.get(), save_mean, save_invstd, weight, bias, dw.get(), db.get(), dx.get(), dx2.get(), x2c.get(), g, 1, st, &dh);
     }
     if (done) {

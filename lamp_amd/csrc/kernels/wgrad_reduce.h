@@ -3,6 +3,8 @@
 // (b) the multi-tensor kernel of wgrad_reduce.hip, which runs ALL reductions a backward pass has registered in one launch:
 // the ResNet step had 13 of these ~5 us launches, each at the ~4.5 us launch floor.
 #pragma once
+#include <vector>
+#include "conv_geom.h"
 #include "device_utils.h"
 
 namespace lamp {
@@ -70,10 +72,19 @@ __device__ __forceinline__ void wgrad_reduce_narrow(const WgradReduceArgs& a, in
   if (lane == 0) { if (a.dw_f32) static_cast<float*>(a.dw)[o] = s; else static_cast<bf16_t*>(a.dw)[o] = bf16_t(s); }
 }
 
-// Registers the reduction (wgrad_reduce.hip): it runs with every other pending one at the next flush_deferred() - the end of
-// backprop - or the moment anything asks for a pointer into dw's storage (Tensor::raw()), whichever comes first.
-// LAMP_DEFER_WGRAD_REDUCE=0: launch it now.
+// The registry of deferred weight-gradient work (wgrad_reduce.hip).  wgrad_reduce_enqueue registers a reduction: it runs with every other
+// pending one at the owner's next flush_deferred() - the end of backprop - or the moment anything asks for a pointer into dw's storage
+// (Tensor::raw()), whichever comes first.  LAMP_DEFER_WGRAD_REDUCE=0: launch it now.
 void wgrad_reduce_enqueue(const WgradReduceArgs& a, lamp_tensor* partial, lamp_tensor* dw, hipStream_t st);
 bool wgrad_reduce_deferred();      // false: LAMP_DEFER_WGRAD_REDUCE=0 (the producers then leave their partial sums in the caches)
+// wgrad_park parks one layer of the eight-wave kernel the same way - dw pending, and dy / x / affine marked as read by deferred work, so a write
+// into them (Tensor::data()) launches it first - or, if the caller has one of the same batch parked on st's device, launches the two together
+struct Wg8hProblem { const lamp_tensor* dy; const lamp_tensor* x; lamp_tensor* dw; ConvGeom g; const lamp_tensor* affine; };
+void wgrad_park(const Wg8hProblem& p, hipStream_t st);
+// conv_igemm.hip: the eight-wave launch of layer a (with layer b, or with a sibling 1x1) on st; it appends the reductions it leaves to `out`
+// (nullptr: wgrad_reduce_enqueue)
+struct WgradReduction { WgradReduceArgs a; Hold partial, dw; };
+struct SecondWgradConv;
+void wg8h_launch(const Wg8hProblem& a, const Wg8hProblem* b, hipStream_t st, const SecondWgradConv* second, std::vector<WgradReduction>* out);
 
 }  // namespace lamp

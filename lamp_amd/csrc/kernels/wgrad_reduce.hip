@@ -1,5 +1,6 @@
-// Deferred, batched reduction of the convolutions' weight-gradient partial sums (see wgrad_reduce.h).
+// Deferred weight-gradient work (see wgrad_reduce.h): parked eight-wave launches and the batched reduction of the partial sums.
 #include "wgrad_reduce.h"
+#include <algorithm>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -18,30 +19,63 @@ __global__ __launch_bounds__(256) void wgrad_reduce_many_kernel(WgradReduceMany 
 }
 
 namespace {
+// One registry, one mutex.  An entry is a parked eight-wave launch (p.dy set: wgrad_park - its tensors retained, dy / x / affine counted in
+// their storages' `deferred_reads`) or a pending reduction (partial set); either way it is counted in dw's storage's `pending`.
 // Ownership: an entry belongs to the host thread that registered it.  flush_deferred() - the natural batching point - only
-// takes the CALLING thread's entries, so the replica threads of the single-process data-parallel step never flush (or clear the flags
-// of) each other's reductions; resolve_deferred(storage), reached from raw() of any thread, takes the entries of the thread that owns
-// that storage's entry.  g_mu is held from the moment entries leave the list until their kernels are queued and only then are the
-// `pending` flags cleared: a concurrent raw() of a pending tensor blocks on the mutex and returns with the reduction already queued
-// in front of whatever the caller launches next.
-struct Pending { WgradReduceArgs a; Tensor* partial; Tensor* dw; hipStream_t st; int device; std::thread::id owner; };
+// takes the CALLING thread's entries, so the replica threads of the single-process data-parallel step never flush each other's work;
+// resolve_deferred(storage), reached from raw() / data() of any thread, takes the entries of the thread that owns an entry naming that
+// storage, and of that thread only.  A flush does all of its work with g_mu held: the entries leave the list, the parked layers are
+// launched in the order they were parked, the reductions they leave join the batch, the batch is launched, and only then are the counts
+// dropped - a concurrent accessor blocks on the mutex and returns with the work queued in front of whatever it launches next.
+struct Entry { Wg8hProblem p; WgradReduceArgs a; Tensor* partial; hipStream_t st; int device; std::thread::id owner; };
 std::mutex g_mu;
-std::vector<Pending> g_pending;
+std::vector<Entry> g_list;
 
-// called with g_mu held.  Pointers are taken from the storages directly (raw() would recurse into resolve_deferred).
-void launch_batch(const std::vector<Pending>& v) {
-  // one launch per (device, stream) group of at most WR_MAX reductions; order of registration kept
+void count_reads(const Wg8hProblem& p, uint32_t d) {
+  for (const Tensor* t : {p.dy, p.x, p.affine}) if (t) t->st->deferred_reads.fetch_add(d, std::memory_order_acq_rel);
+}
+bool names(const Entry& e, const Storage* st) {
+  return e.p.dw->st == st || (e.p.dy && (e.p.dy->st == st || e.p.x->st == st || (e.p.affine && e.p.affine->st == st)));
+}
+// Entries out of the list: when this goes out of scope - launched, or skipped by an exception - their counts are dropped (after the launches
+// are queued) and their handles released.  Nothing leaves the list except into one of these.
+struct Taken {
+  std::vector<Entry> v;
+  ~Taken() {
+    for (auto& e : v) { e.p.dw->st->pending.fetch_sub(1, std::memory_order_release); if (e.p.dy) count_reads(e.p, (uint32_t)-1); }
+    for (auto& e : v) for (const Tensor* t : {e.p.dy, e.p.x, e.p.affine, (const Tensor*)e.p.dw, (const Tensor*)e.partial}) release(const_cast<Tensor*>(t));
+  }
+};
+// called with g_mu held: launches parked layer e (with b) on its stream; the reductions it leaves are appended to `into` as pending entries of e's owner
+void wg8h_launch_locked(const Entry e, const Wg8hProblem* b, std::vector<Entry>& into) {
+  const int prev = current_device();
+  if (prev != e.device) set_device(e.device);
+  struct Back { int prev, dev; ~Back() { if (prev != dev) set_device(prev); } } back{prev, e.device};
+  std::vector<WgradReduction> out;
+  wg8h_launch(e.p, b, e.st, nullptr, &out);
+  for (auto& r : out) {
+    // another thread's layer: its partial sums come from this thread's stream pool and are used on the owner's stream
+    if (e.st != current_stream(e.device)) record_stream(r.partial.get(), e.device, e.st);
+    into.push_back(Entry{Wg8hProblem{nullptr, nullptr, r.dw.get(), {}, nullptr}, r.a, r.partial.get(), e.st, e.device, e.owner});
+    r.dw->st->pending.fetch_add(1, std::memory_order_release);
+    r.dw.take(); r.partial.take();
+  }
+}
+
+// called with g_mu held: one launch per (device, stream) group of at most WR_MAX pending reductions; order of registration kept.
+// Pointers are taken from the storages directly (raw() would recurse into resolve_deferred).
+void launch_batch(const std::vector<Entry>& v) {
   std::vector<bool> done(v.size(), false);
   for (size_t i = 0; i < v.size(); i++) {
-    if (done[i]) continue;
+    if (done[i] || !v[i].partial) continue;
     WgradReduceMany m;
     int cnt = 0, maxb = 0;
     for (size_t j = i; j < v.size() && cnt < WR_MAX; j++) {
-      if (done[j] || v[j].st != v[i].st || v[j].device != v[i].device) continue;
+      if (done[j] || !v[j].partial || v[j].st != v[i].st || v[j].device != v[i].device) continue;
       m.e[cnt] = v[j].a;
       m.e[cnt].partial = reinterpret_cast<const float*>(static_cast<const char*>(v[j].partial->st->ptr)) + v[j].partial->offset;
-      m.e[cnt].dw = static_cast<char*>(v[j].dw->st->ptr) + v[j].dw->offset * (v[j].a.dw_f32 ? 4 : 2);
-      v[j].dw->st->version.fetch_add(1, std::memory_order_relaxed);   // a writer like any other: bumps dw's version
+      m.e[cnt].dw = static_cast<char*>(v[j].p.dw->st->ptr) + v[j].p.dw->offset * (v[j].a.dw_f32 ? 4 : 2);
+      v[j].p.dw->st->version.fetch_add(1, std::memory_order_relaxed);   // a writer like any other: bumps dw's version
       maxb = std::max(maxb, v[j].a.blocks);
       done[j] = true;
       cnt++;
@@ -52,7 +86,7 @@ void launch_batch(const std::vector<Pending>& v) {
     hipError_t e = hipGetLastError();
     if (prev != v[i].device) set_device(prev);
     if (e != hipSuccess) throw Error(std::string("wgrad reduce launch failed: ") + hipGetErrorString(e));
-    // a reader on another stream of that device must see the result: order it behind the reduction
+    // a reader on another stream of that device must see the result: order it behind the reduction (and the parked launch in front of it)
     hipStream_t cur = current_stream(v[i].device);
     if (cur != v[i].st) {
       hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -73,41 +107,53 @@ void launch_batch(const std::vector<Pending>& v) {
   }
 }
 
-// takes the entries of `owner` out of the list, queues their kernels and clears their flags - all under g_mu
+// takes the entries of `owner` out of the list, launches its parked layers and then the batch, drops the counts - all under g_mu
 void flush_owner_locked(std::thread::id owner) {
-  std::vector<Pending> v;
+  Taken t;
   size_t keep = 0;
-  for (size_t i = 0; i < g_pending.size(); i++) {
-    if (g_pending[i].owner == owner) v.push_back(g_pending[i]);
-    else g_pending[keep++] = g_pending[i];
+  for (size_t i = 0; i < g_list.size(); i++) {
+    if (g_list[i].owner == owner) t.v.push_back(g_list[i]);
+    else g_list[keep++] = g_list[i];
   }
-  g_pending.resize(keep);
-  if (v.empty()) return;
-  struct Finish {
-    std::vector<Pending>& v;
-    ~Finish() {
-      for (auto& p : v) p.dw->st->pending.store(0, std::memory_order_release);   // after the launches are queued (or have failed)
-      for (auto& p : v) { release(p.partial); release(p.dw); }
-    }
-  } fin{v};
-  launch_batch(v);
+  g_list.resize(keep);
+  const size_t n = t.v.size();
+  for (size_t i = 0; i < n; i++)
+    if (t.v[i].p.dy) wg8h_launch_locked(t.v[i], nullptr, t.v);
+  launch_batch(t.v);
 }
 }  // namespace
 
-void igemm_wgrad_flush_parked(bool all);     // conv_igemm.hip: weight-gradient LAUNCHES that wait for a second layer to share the chip with (they register their reductions here)
 void flush_deferred() {
-  igemm_wgrad_flush_parked(false);
   std::lock_guard<std::mutex> lk(g_mu);
-  if (g_pending.empty()) return;
   flush_owner_locked(std::this_thread::get_id());
 }
 
 void resolve_deferred(Storage* st) {
-  igemm_wgrad_flush_parked(true);
   std::lock_guard<std::mutex> lk(g_mu);
-  for (auto& p : g_pending)
-    if (p.dw->st == st) { flush_owner_locked(p.owner); return; }
-  // not in the list any more: another thread queued it while this one waited for the mutex
+  // every owner of an entry naming st (one input may be read by several threads' parked layers); none: already queued by another thread
+  auto hit = [&] { return std::find_if(g_list.begin(), g_list.end(), [&](const Entry& e) { return names(e, st); }); };
+  for (auto it = hit(); it != g_list.end(); it = hit()) flush_owner_locked(it->owner);
+}
+
+void wgrad_park(const Wg8hProblem& p, hipStream_t st) {
+  (void)p.dy->raw(); (void)p.x->raw();          // (their own deferred work, if any, first: a launch under g_mu must not resolve anything)
+  const int dev = p.dw->device();
+  const std::thread::id me = std::this_thread::get_id();
+  std::lock_guard<std::mutex> lk(g_mu);
+  auto m = std::find_if(g_list.begin(), g_list.end(), [&](const Entry& e) {
+    return e.p.dy && e.owner == me && e.st == st && e.device == dev && e.p.g.N == p.g.N && e.p.dw->st != p.dw->st;
+  });
+  if (m != g_list.end()) {                      // the mate: both layers in one launch
+    Taken t{{*m}};
+    g_list.erase(m);
+    wg8h_launch_locked(t.v[0], &p, g_list);
+    return;
+  }
+  Entry e{Wg8hProblem{retain(p.dy), retain(p.x), retain(p.dw), p.g, p.affine ? retain(p.affine) : nullptr}, {}, nullptr, st, dev, me};
+  g_list.push_back(e);
+  count_reads(e.p, 1);
+  p.dw->st->version.fetch_add(1, std::memory_order_relaxed);  // a writer like any other
+  p.dw->st->pending.fetch_add(1, std::memory_order_release);
 }
 
 bool wgrad_reduce_deferred() {
@@ -126,10 +172,10 @@ void wgrad_reduce_enqueue(const WgradReduceArgs& a, lamp_tensor* partial, lamp_t
     LAMP_LAUNCH_CHECK();
     return;
   }
-  Pending p{a, retain(partial), retain(dw), st, dw->device(), std::this_thread::get_id()};
+  Entry e{Wg8hProblem{nullptr, nullptr, retain(dw), {}, nullptr}, a, retain(partial), st, dw->device(), std::this_thread::get_id()};
   std::lock_guard<std::mutex> lk(g_mu);
-  g_pending.push_back(p);
-  dw->st->pending.store(1, std::memory_order_release);
+  g_list.push_back(e);
+  dw->st->pending.fetch_add(1, std::memory_order_release);
 }
 
 }  // namespace lamp

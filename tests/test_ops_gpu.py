@@ -1638,6 +1638,13 @@ def test_weight_gradient_reductions_are_deferred_and_batched(gpu):
         assert torch.equal(a, f)
 
 
+def _launch_counts():
+    """Launches per kernel-timer tag since the last report (the report starts a new count)."""
+    buf = C.create_string_buffer(1 << 16)
+    lib.lamp_kernel_timer_report(buf, len(buf))
+    return {l.split()[0]: int(l.split()[1]) for l in buf.value.decode().splitlines() if l.strip()}
+
+
 def test_two_layers_weight_gradients_share_one_launch(gpu):
     """Round 6: at large batches the eight-wave weight-gradient kernel takes TWO layers in one launch - a layer that qualifies is parked (its gradient
     marked pending) until the next one arrives, each then gets half the workgroups, twice the images per workgroup and leaves half the partial
@@ -1659,17 +1666,12 @@ def test_two_layers_weight_gradients_share_one_launch(gpu):
         ref = aten.convolution_backward(gy.double(), x.double(), w.double(), [0], [1, 1], [1, 1], [1, 1], False, [0, 0], 1, [False, True, False])[1]
         return S.STen(out3[1]), ref
 
-    def launches():
-        buf = C.create_string_buffer(1 << 16)
-        lib.lamp_kernel_timer_report(buf, len(buf))
-        return {l.split()[0]: int(l.split()[1]) for l in buf.value.decode().splitlines() if l.strip()}
-
     lib.lamp_device_synchronize()
     lib.lamp_kernel_timer_enable(1)
     hs = [wgrad(*l) for l in layers]                       # layers 0 and 1 in one launch; layer 2 parked
-    mid = launches().get("conv_wgrad_igemm", 0)
+    mid = _launch_counts().get("conv_wgrad_igemm", 0)
     got2 = to_torch(hs[2][0])                              # the read launches it alone
-    after = launches()
+    after = _launch_counts()
     lib.lamp_kernel_timer_enable(0)
     assert mid == 1 and after.get("conv_wgrad_igemm", 0) == 1, (mid, after)        # (the report starts a new count)
     got = [to_torch(hs[0][0]), to_torch(hs[1][0]), got2]
@@ -1961,6 +1963,107 @@ def test_deferred_reductions_belong_to_the_thread_that_registered_them(gpu):
         t.join()
     lib.lamp_device_synchronize()
     assert not errors, errors
+
+
+def _parking_layer(cin, cout, seed):
+    """A layer of the two-layer test's geometry (N = 2048, 8 x 8 maps, 3 x 3): its weight gradient is parked by the eight-wave kernel."""
+    dt = torch.bfloat16
+    x = closed_form((2048, cin, 8, 8), seed, 2.0, dt)
+    w = closed_form((cout, cin, 3, 3), 17, 1.0, dt)
+    gy = closed_form((2048, cout, 8, 8), seed + 16, 1.0, dt)
+    return x, w, gy
+
+
+@pytest.mark.parametrize("written", ["x", "dy"])
+def test_parked_weight_gradient_inputs_written_after_the_call(gpu, written):
+    """a parked layer reads its x and dy when it is launched, after lamp_convolution_backward has returned.  An in-place write to either
+    is a mutable access of a storage marked as read by deferred work: it launches the parked layer first, so the write is ordered after the read
+    - no error, and dw is that of the original inputs, bit for bit the layer flushed alone."""
+    x, w, gy = _parking_layer(128, 128, 7)
+    ref = aten.convolution_backward(gy.double(), x.double(), w.double(), [0], [1, 1], [1, 1], [1, 1], False, [0, 0], 1, [False, True, False])[1]
+    W = to_sten(w)
+    alone = _conv_wgrad_bf16(to_sten(x), W, to_sten(gy), 3)
+    lib.lamp_flush_deferred()
+    alone = to_torch(alone)
+    X, GY = to_sten(x), to_sten(gy)
+    lib.lamp_device_synchronize()
+    _launch_counts()
+    lib.lamp_kernel_timer_enable(1)
+    try:
+        dw = _conv_wgrad_bf16(X, W, GY, 3)
+        parked = _launch_counts().get("conv_wgrad_igemm", 0)
+        assert lib.lamp_mul_scalar_(X if written == "x" else GY, 3.0) == 0
+        got = to_torch(dw)
+    finally:
+        lib.lamp_kernel_timer_enable(0)
+    assert parked == 0, "the layer was not parked"
+    assert_close(got, ref, 2.0 ** -7, f"weight gradient after a write to {written}")
+    assert torch.equal(got, alone)
+
+
+def test_a_read_of_another_threads_parked_gradient_launches_that_thread_only(gpu):
+    """a read of a pending gradient launches the deferred work of the thread that owns it, and only that thread's.  Thread A parks
+    layer L1 on its stream; thread B parks L2 on its own and reads A's gradient: one launch, A's; B's layer stays parked until B flushes.
+    Both gradients are those of the layers flushed alone on one thread, bit for bit."""
+    import threading
+    layers = [_parking_layer(128, 128, 7), _parking_layer(100, 100, 11)]
+    args = [(to_sten(x), to_sten(w), to_sten(gy)) for (x, w, gy) in layers]
+    want = []
+    for X, W, GY in args:
+        d = _conv_wgrad_bf16(X, W, GY, 3)
+        lib.lamp_flush_deferred()
+        want.append(to_torch(d))
+    lib.lamp_device_synchronize()
+    a_parked, b_done = threading.Event(), threading.Event()
+    dws, counts, errors = [None, None], {}, []
+
+    def on_own_stream():
+        st = C.c_void_p()
+        lib.lamp_stream_get_from_pool(0, 0, C.byref(st))
+        lib.lamp_stream_set_current(st)
+
+    def thread_a():
+        try:
+            on_own_stream()
+            dws[0] = _conv_wgrad_bf16(*args[0], 3)
+        except Exception as e:                             # noqa: BLE001
+            errors.append(f"thread A: {e}")
+        finally:
+            a_parked.set()
+        b_done.wait(600)
+
+    def thread_b():
+        try:
+            a_parked.wait(600)
+            on_own_stream()
+            dws[1] = _conv_wgrad_bf16(*args[1], 3)
+            counts["parked"] = _launch_counts().get("conv_wgrad_igemm", 0)
+            got_a = to_torch(dws[0])                       # A's gradient: A's parked layer is launched
+            counts["read"] = _launch_counts().get("conv_wgrad_igemm", 0)
+            lib.lamp_flush_deferred()                      # B's own
+            counts["flush"] = _launch_counts().get("conv_wgrad_igemm", 0)
+            dws.append(got_a)
+        except Exception as e:                             # noqa: BLE001
+            errors.append(f"thread B: {e}")
+        finally:
+            b_done.set()
+
+    _launch_counts()
+    lib.lamp_kernel_timer_enable(1)
+    try:
+        ths = [threading.Thread(target=thread_a), threading.Thread(target=thread_b)]
+        for t in ths:
+            t.start()
+        for t in ths:
+            t.join()
+    finally:
+        lib.lamp_kernel_timer_enable(0)
+    lib.lamp_device_synchronize()
+    assert not errors, errors
+    assert counts == {"parked": 0, "read": 1, "flush": 1}, counts
+    assert torch.equal(dws[2], want[0])
+    assert torch.equal(to_torch(dws[0]), want[0])
+    assert torch.equal(to_torch(dws[1]), want[1])
 
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32, torch.float64])
