@@ -11,6 +11,7 @@
 #include <cstring>
 #include "strided.h"
 #include "../kernels/device_utils.h"
+#include "switches.h"
 
 #include <climits>
 #include <chrono>
@@ -60,7 +61,7 @@ struct PinnedCache {
   std::mutex mu;
   std::multimap<size_t, void*> blocks;      // capacity -> pointer
   size_t cached = 0;
-  size_t limit = [] { const char* e = getenv("LAMP_PINNED_CACHE_MB"); return (size_t)(e ? std::max(0, atoi(e)) : 2048) << 20; }();
+  size_t limit = (size_t)sw().pinned_cache_mb << 20;
 };
 PinnedCache& pinned_cache() { static PinnedCache* c = new PinnedCache(); return *c; }      // never destroyed: storages may outlive static destructors
 }  // namespace

@@ -25,6 +25,7 @@
 
 #include "../../../include/lamp_host.h"
 #include "nn.h"
+#include "../core/switches.h"
 
 namespace lamp {
 namespace host {
@@ -425,7 +426,7 @@ int lamp_batch_stream_from_full_host(lamp_batch_stream** out, const lamp_tensor*
   // a kernel that reads host memory does not run beside the training step anyway, so the side stream bought nothing at B = 2048 (1.64 M
   // samples/s either way), cost 12 % at B = 256 (three cross-stream waits per batch) and, for some streams of a process, put the whole
   // epoch into a 3 x slower mode (EXPERIMENTS (17)): the default queues the gather on the consumer's stream.
-  static const bool use_side = [] { const char* e = getenv("LAMP_HOST_STREAM_SIDE"); return e && e[0] == '1'; }();
+  const bool use_side = sw().host_stream_side;
   if (use_side) HCALL(lamp_stream_get_from_pool(0, device, &s.side));
   *out = stream.release();
   LAMP_API_END

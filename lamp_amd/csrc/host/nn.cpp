@@ -1,5 +1,6 @@
 // lamp.nn over the C ABI - see nn.h for the reference map.
 #include "nn.h"
+#include "../core/switches.h"
 #include <thread>
 #include <unordered_map>
 
@@ -77,7 +78,7 @@ Var Residual::forward_relu(const Var& x, int64_t pool_tail) {
     BatchNorm* lbn = (lseq && !lseq->mods.empty()) ? dynamic_cast<BatchNorm*>(lseq->mods.back().get()) : nullptr;
     // Both branches START with a Conv2D on x (every block of Cnn.resnet: cnn.scala:38-45 and 64-72): the two convolutions are one call, which
     // is one launch where a kernel keeps the staged input for both products (LAMP_CONV_SIBLING=0: two calls).  Same nodes, same values.
-    static const bool pair_on = [] { const char* e = getenv("LAMP_CONV_SIBLING"); return !(e && e[0] == '0'); }();
+    const bool pair_on = sw().conv_sibling;
     auto* c3 = head.mods.empty() ? nullptr : dynamic_cast<Conv2D*>(head.mods[0].get());
     auto* c1 = (lbn && lseq->mods.size() == 2) ? dynamic_cast<Conv2D*>(lseq->mods[0].get()) : nullptr;
     Var v, lconv;                                  // lconv: the left branch's convolution output when it came with the right one
@@ -93,7 +94,7 @@ Var Residual::forward_relu(const Var& x, int64_t pool_tail) {
     auto left_branch = [&]() -> Var { return lconv ? lbn->forward(lconv) : (left ? left->forward(x) : x); };
     // both branches end in a batch norm (every block of Cnn.resnet: the left branch is Conv2D 1x1 -> BatchNorm2D): one op for
     // relu(bn(right) + bn(left)) - the left batch norm's output is never written (LAMP_FUSE_BN_PAIR=0: the chain)
-    static const bool fuse_pair = [] { const char* e = getenv("LAMP_FUSE_BN_PAIR"); return !(e && e[0] == '0'); }();
+    const bool fuse_pair = sw().fuse_bn_pair;
     if (fuse_pair && lbn && bn->can_fuse_add_relu(v)) {
       Var lv = lconv;
       if (!lv) {
@@ -152,8 +153,8 @@ Var Sequential::forward(const Var& x) {
       // module -> Fun(avgpool2d, stride 1) -> Fun(flatten the last three dims) -> Fun(logsoftmax over dim 1) where the module ends in a residual
       // block under a relu (Cnn.resnet: the Sequential of the four blocks, cnn.scala:118-136): the last block and the tail as one node - the
       // block's output, which only the pool reads, is never written (LAMP_FUSE_BLOCK_TAIL=0: off)
-      static const bool fuse_tail0 = [] { const char* e = getenv("LAMP_FUSE_POOL_LOGSOFTMAX"); return !(e && e[0] == '0'); }();
-      static const bool fuse_block_tail = [] { const char* e = getenv("LAMP_FUSE_BLOCK_TAIL"); return !(e && e[0] == '0'); }();
+      const bool fuse_tail0 = sw().fuse_pool_logsoftmax;
+      const bool fuse_block_tail = sw().fuse_block_tail;
       auto* pool = dynamic_cast<Fun*>(mods[i + 1].get());
       auto* flat = dynamic_cast<Fun*>(mods[i + 2].get());
       auto* lsm = dynamic_cast<Fun*>(mods[i + 3].get());
@@ -170,7 +171,7 @@ Var Sequential::forward(const Var& x) {
       if (bn && fn && fn->tag == "relu" && bn->can_fuse_relu(v)) {
         // BatchNorm2D -> relu -> [Dropout(p <= 0)] -> Conv2D (the middle of every residual block, cnn.scala:38-60): the convolution applies
         // the batch norm + relu while staging its input, bitwise the chain's values (LAMP_FUSE_BN_CONV=0: the chain)
-        static const bool fuse_conv = [] { const char* e = getenv("LAMP_FUSE_BN_CONV"); return !(e && e[0] == '0'); }();
+        const bool fuse_conv = sw().fuse_bn_conv;
         size_t j = i + 2;
         auto* drop = j < mods.size() ? dynamic_cast<Dropout*>(mods[j].get()) : nullptr;
         if (drop && drop->prob <= 0) j++;
@@ -195,7 +196,7 @@ Var Sequential::forward(const Var& x) {
       // Fun(avgpool2d over the whole map) -> Fun(flatten the last three dims) -> Fun(logsoftmax over dim 1): one node, values of the chain
       auto* pool = dynamic_cast<Fun*>(mods[i].get());
       auto* lsm = i + 2 < mods.size() ? dynamic_cast<Fun*>(mods[i + 2].get()) : nullptr;
-      static const bool fuse_tail = [] { const char* e = getenv("LAMP_FUSE_POOL_LOGSOFTMAX"); return !(e && e[0] == '0'); }();
+      const bool fuse_tail = sw().fuse_pool_logsoftmax;
       if (fuse_tail && pool && fn && lsm && pool->tag == "avgpool2d" && fn->tag == "flatten_last" && fn->a == 3 && lsm->tag == "logsoftmax" && lsm->a == 1 &&
           v->value.ndim() == 4 && v->value.size(2) == (int64_t)pool->a && v->value.size(3) == (int64_t)pool->a && v->value.h()->is_device()) {
         v = F::global_avg_pool_log_softmax(v);
@@ -370,7 +371,7 @@ std::pair<Var, int64_t> SupervisedModel::loss(const Var& output, const Ten& targ
 }
 // NLL on the device with an accumulator of the loss's dtype: `acc += n * loss` rides in the loss kernel (one launch less per step)
 static bool loss_accumulates_in_kernel(const SupervisedModel& m, const Var& output, const Ten& acc) {
-  static const bool on = [] { const char* e = getenv("LAMP_FUSE_LOSS_ACCUMULATE"); return !(e && e[0] == '0'); }();
+  const bool on = sw().fuse_loss_accumulate;
   return on && m.loss_kind == 0 && m.reduction != 0 && acc.defined() && acc.h()->is_device() && output->value.h()->is_device() &&
          acc.dtype() == output->value.dtype() && acc.numel() == 1 && acc.device() == output->value.device() && output->value.ndim() == 2;
 }

@@ -10,6 +10,7 @@
 // exactly), later closures add in place.  In-place native forms (addmm_out_transposed*, the fused
 // relu backward) take their beta = 0 / out-of-place variant for that first accumulation.
 #include "ops.h"
+#include "../core/switches.h"
 #include <cstring>
 #include <map>
 #include <tuple>
@@ -496,10 +497,10 @@ Var nll_loss_accumulate(const Var& input, const Ten& target, const Ten& weights,
   LAMP_CHECK(target.ndim() == 1, "Target should be a 1D tensor with [0,C-1] integers, C number of classes.");
   auto op = new_op("NllLoss");
   lamp_tensor *v = nullptr, *tw = nullptr, *pgh = nullptr;
-  static const bool fuse_tail = [] { const char* e = getenv("LAMP_FUSE_LOSS_BACKWARD"); return !(e && e[0] == '0'); }();
+  const bool fuse_tail = sw().fuse_loss_backward;
   // Cnn.resnet's tail with the loss as the root (SupervisedModel.scala:190-211): the loss launch also produces, for a derivative of one, the
   // pooled LogSoftMax's input gradient as one value per plane (LAMP_FUSE_LOSS_TAIL=0: the separate backward launch)
-  static const bool fuse_ahead = [] { const char* e = getenv("LAMP_FUSE_LOSS_TAIL"); return !(e && e[0] == '0'); }();
+  const bool fuse_ahead = sw().fuse_loss_tail;
   const bool from_tail = input->op && input->op->params.size() == 1 && std::strcmp(input->op->name, "GlobalAvgPoolLogSoftMax") == 0 &&
                          input->value.h()->is_device() && input->op->params[0].first->needsGrad() && input->op->params[0].first->value.ndim() == 4;
   // ... or from the node that holds the last block too (batch_norm2_add_relu_pool_log_softmax_2d): its first input has the pooled tensor's shape
@@ -742,8 +743,8 @@ static Var convolution_node(const Var& input, const Var& weight, const Var& bias
   auto op = new_op("Convolution");
   const int ns = (int)stride.size();
   Ten iv = input->value, wv = weight->value;
-  static const bool fuse_accumulate = [] { const char* e = getenv("LAMP_CONV_DGRAD_ACCUMULATE"); return !(e && e[0] == '0'); }();
-  static const bool fuse_pair = [] { const char* e = getenv("LAMP_CONV_DGRAD_PAIR"); return !(e && e[0] == '0'); }();
+  const bool fuse_accumulate = sw().conv_dgrad_accumulate;
+  const bool fuse_pair = sw().conv_dgrad_pair;
   auto back = [=](int which) {
     // (a plain function object: the pair's deferred form calls it again)
     std::function<void(const Ten&, Variable&)> single;
@@ -763,7 +764,7 @@ static Var convolution_node(const Var& input, const Var& weight, const Var& bias
                                       outputPadding.data(), groups, mask));
       out.accumulate(Ten(o3[which]), true);
     };
-    static const bool fuse_wpair = [] { const char* e = getenv("LAMP_CONV_WGRAD_PAIR"); return !(e && e[0] == '0'); }();
+    const bool fuse_wpair = sw().conv_wgrad_pair;
     if (which == 1 && pair && fuse_wpair && !transposed) {
       // the two weight gradients from one call (x is staged once).  The fallback sits on the INPUT variable, which backprop reaches after
       // both convolutions (a parameter is reached right after its own node, before the sibling has run)

@@ -1,5 +1,6 @@
 // lamp.nn's transformer family - see transformer.h for the reference map.
 #include "transformer.h"
+#include "../core/switches.h"
 
 namespace lamp {
 namespace host {
@@ -17,7 +18,7 @@ Var mm1(const Var& a, const Var& b, bool reshape_first = false) {
 }
 // mm1(a, w) + b with the bias folded into the GEMM epilogue (same values as the chain, see F::linear_bias)
 Var mm1_bias(const Var& a, const Var& w, const Var& b) {
-  static const bool fused = !(getenv("LAMP_LINEAR_BIAS_FUSED") && atoi(getenv("LAMP_LINEAR_BIAS_FUSED")) == 0);
+  const bool fused = sw().linear_bias_fused;
   const auto bsh = b->shape();
   if (!fused || bsh.size() != 2 || bsh[0] != 1 || bsh[1] != w->value.size(1)) return F::add(mm1(a, w), b);
   auto shape = a->shape();
@@ -27,7 +28,7 @@ Var mm1_bias(const Var& a, const Var& w, const Var& b) {
 }
 // x * scale + residual (Transformer.scala:244-247) in one pass with the values of the chain
 Var mult_add(const Var& x, const Var& scale, const Var& residual) {
-  static const bool fused = !(getenv("LAMP_MULT_ADD_FUSED") && atoi(getenv("LAMP_MULT_ADD_FUSED")) == 0);
+  const bool fused = sw().mult_add_fused;
   if (!fused || x->value.dtype() != scale->value.dtype() || x->value.dtype() != residual->value.dtype()) return F::add(F::mult(x, scale), residual);
   return F::mult_add(x, scale, residual);
 }
@@ -125,7 +126,7 @@ Var MultiheadAttention::linearizedAttention(const Var& q, const Var& k, const Va
   return F::div(enumerator, F::const_add(denom, 1e-5));
 }
 bool& MultiheadAttention::fused_call_as_written() {
-  static bool v = [] { const char* e = getenv("LAMP_ATTENTION_AS_WRITTEN_FOR_CUDA"); return e && e[0] == '1'; }();
+  static bool v = sw().attention_as_written_for_cuda;
   return v;
 }
 Var MultiheadAttention::multiheadAttention(const Var& query, const Var& keys, const Var& values, const Ten& maxLength, double dropout,
@@ -144,7 +145,7 @@ Var MultiheadAttention::multiheadAttention(const Var& query, const Var& keys, co
     return F::reshape(t, {s2[0], s2[1], -1});
   };
   // self-attention on bf16 with the fused kernels' head widths: one projection product, packed operands (LAMP_FUSE_QKV=0: three products)
-  static const bool fuse_qkv = [] { const char* e = getenv("LAMP_FUSE_QKV"); return !(e && e[0] == '0'); }();
+  const bool fuse_qkv = sw().fuse_qkv;
   if (fuse_qkv && !fused_call_as_written() && query.get() == keys.get() && keys.get() == values.get() && causalMask && !maxLength.defined() && !linearized &&
       (dropout == 0.0 || !trainDropout) && query->value.dtype() == kBF16 && query->value.ndim() == 3 && query->value.h()->is_device() &&
       wQuery->shape() == wKeys->shape() && wKeys->shape() == wValues->shape() && wQuery->value.size(1) % numHeads == 0 &&

@@ -18,6 +18,7 @@
 // K / V tiles arrive by LDS-DMA into two buffers (swizzled images, swizzle on the per-lane source address), the
 // next tile is in flight while the current one is consumed.
 #include "device_utils.h"
+#include "../core/switches.h"
 #include <type_traits>
 
 namespace lamp {
@@ -351,7 +352,7 @@ bool flash_attention_fwd(const Tensor* q, const Tensor* k, const Tensor* v, Tens
   const int64_t B = q->sizes[0], H = q->sizes[1], Sq = q->sizes[2], D = q->sizes[3], Sk = k->sizes[2], Dv = v->sizes[3], BH = B * H;
   if (q->is_contiguous() && k->is_contiguous() && v->is_contiguous() && out->is_contiguous() &&
       small_attention_fwd(q, k, v, out, lse, BH, Sq, Sk, D, Dv, is_causal, scale, st)) return true;
-  static const bool enabled = [] { const char* e = getenv("LAMP_FLASH_ATTENTION"); return !(e && e[0] == '0'); }();
+  const bool enabled = sw().flash_attention;
   if (!enabled) return false;
   if (q->dtype != kBF16 || lse->dtype != kF32 || D != Dv || !(D == 64 || D == 128) || Sq < 1 || Sk < 1 || Sq > (1 << 30) || Sk > (1 << 30)) return false;
   AtLay lq, lk, lv, lo;
@@ -754,7 +755,7 @@ bool flash_attention_bwd(const Tensor* go, const Tensor* q, const Tensor* k, con
   bool contig = true;
   for (auto* t : all) contig = contig && t->is_contiguous();
   if (contig && small_attention_bwd(go, q, k, v, out, lse, dq, dk, dv, BH, Sq, Sk, D, Dv, is_causal, scale, st)) return true;
-  static const bool enabled = [] { const char* e = getenv("LAMP_FLASH_ATTENTION"); return !(e && e[0] == '0'); }();
+  const bool enabled = sw().flash_attention;
   if (!enabled) return false;
   if (q->dtype != kBF16 || lse->dtype != kF32 || D != Dv || !(D == 64 || D == 128) || Sq < 1 || Sk < 1 || Sq > (1 << 30) || Sk > (1 << 30)) return false;
   AtLay lq, lk, lv, lg, lo, ldq, ldk, ldv;

@@ -11,6 +11,7 @@
 // Softmax statistics in f32 with the same definition as the flash kernels (lse = ln sum exp(scale * s)); P stays f32.
 #include "device_utils.h"
 #include "../core/tensor.h"
+#include "../core/switches.h"
 
 namespace lamp {
 
@@ -205,7 +206,7 @@ __global__ __launch_bounds__(64 * SA_WAVES) void sdpa_small_bwd_kernel(const bf1
 }
 
 static bool small_attention_enabled() {
-  static const bool enabled = [] { const char* e = getenv("LAMP_SMALL_ATTENTION"); return !(e && e[0] == '0'); }();
+  const bool enabled = sw().small_attention;
   return enabled;
 }
 static bool small_attention_fits(const Tensor* q, int64_t Sq, int64_t Sk, int64_t D, int64_t Dv) {

@@ -33,6 +33,7 @@
 #include "wgrad_reduce.h"
 #include <thread>
 #include "conv_narrow_pack.h"
+#include "../core/switches.h"
 
 namespace lamp {
 
@@ -1757,9 +1758,7 @@ __global__ __launch_bounds__(256) void ig_wgrad8v2_kernel(const bf16_t* __restri
 #ifdef LAMP_WG8H_STAMPS
 __device__ unsigned int g_wg8h_stamps[1024 * 8 * 8];
 #endif
-#ifndef LAMP_WG8H_DMA
-#define LAMP_WG8H_DMA 1          // SHIFT_DY = 2: the dY tiles arrive by LDS-DMA (0: through registers and ds_write, the A/B form)
-#endif
+// (LAMP_WG8H_DMA, default 1: core/switches.h - SHIFT_DY = 2: the dY tiles arrive by LDS-DMA; 0: through registers and ds_write, the A/B form)
 // A SECOND PROBLEM in the same launch (round 6, igemm_wgrad_group; wgs0 = 0: none): workgroups [0, wgs0) belong to the kernel's own arguments,
 // [wgs0, gridDim.x) to this one - another layer's weight gradient of the same batch.  Two layers share the CUs, so each workgroup walks twice as
 // many images and each layer leaves HALF the partial sums (they are the kernel's store phase and the reduction's whole input: EXPERIMENTS 73).
@@ -2230,7 +2229,7 @@ static Tensor* packed_weights(const Tensor* w, const ConvGeom& g, int KS, hipStr
   const int64_t ntf = ig_tail_ok((int)g.Cin, KS) ? IG_TAIL_ELEMS : 0, ntd = ig_tail_ok((int)g.Cout, KS) ? IG_TAIL_ELEMS : 0;
   *dgrad_offset = nf;
   if (tail_offset) { tail_offset[0] = ntf ? nf + nd : -1; tail_offset[1] = ntd ? nf + nd + ntf : -1; }
-  static const bool cache_on = [] { const char* e = getenv("LAMP_PACK_CACHE"); return !(e && e[0] == '0'); }();
+  const bool cache_on = sw().pack_cache;
   const bool cacheable = cache_on && w->st->owned && !w->st->scratch;
   const PackKey key{w->st->uid, w->offset, KS, (int)g.Cout, (int)g.Cin, st};
   const uint64_t ver = w->st->version.load(std::memory_order_relaxed);
@@ -2271,7 +2270,7 @@ void narrow_repack_cached(lamp_tensor* const* params, int n, hipStream_t st, Ncv
 void narrow_pack_launch(const NcvPackMany& a, int cnt, hipStream_t st);
 // (round 5: ... and the narrow convolutions' fragment images ride in the last of these launches - the step had two pack launches of 4 - 6 us)
 void igemm_repack_cached(lamp_tensor* const* params, int n, hipStream_t st) {
-  static const bool on = [] { const char* e = getenv("LAMP_PACK_AFTER_STEP"); return !(e && e[0] == '0'); }();
+  const bool on = sw().pack_after_step;
   if (!on) return;
   NcvPackMany nb;
   int ncnt = 0;
@@ -2320,6 +2319,24 @@ void igemm_repack_cached(lamp_tensor* const* params, int n, hipStream_t st) {
   }
 }
 
+// The kernel form run_conv8 launches for a geometry - asked here by run_conv8 itself and by everyone who has to know beforehand what it will do:
+//   IgForm::Plain   ig_conv8_kernel:  LAMP_IG_VARIANT=a only
+//   IgForm::Eight   ig_conv8d_kernel: eight images per workgroup, one workgroup per CU, wave = image x all channels - more than 64 output channels
+//                   (narrow outputs too unless LAMP_IG_SMALL_D=0: NCT = 1 / 4 channel tiles per wave - the 16-channel layers of the ResNet, 128 -> 16
+//                   dgrad and 16 -> 16, spent 16 - 30 us in the 64-row kernel multiplying padding; here they are bound by their image reads) and
+//                   enough images to give every CU a workgroup of eight (LAMP_IG_VARIANT=d: at any batch, =b: never)
+//   IgForm::Two64   ig_conv8c_kernel: two images, 64-row weight stages, four-slot ring - at most 64 output channels (not under =b)
+//   IgForm::Two128  ig_conv8b_kernel: two images (or one), 128-row weight stages - the rest
+// Two co-resident workgroups per CU (every form but Plain) are the default: A/B on one device, 7 % faster per launch.
+enum class IgForm { Plain, Eight, Two64, Two128 };
+static IgForm ig_form(const ConvGeom& g, bool dgrad) {
+  const char variant = sw_now().ig_variant;                        // (read per call: the A/B test flips it)
+  if (variant == 'a') return IgForm::Plain;
+  const int64_t CO = dgrad ? g.Cin : g.Cout;
+  if ((CO > 64 || sw().ig_small_d) && variant != 'b' && (variant == 'd' || g.N >= 4 * (int64_t)num_cus())) return IgForm::Eight;
+  return (CO <= 64 && variant != 'b') ? IgForm::Two64 : IgForm::Two128;
+}
+
 // addend (dgrad, optional): out = round(round(conv) + addend) where the kernel chosen can do it in its epilogue; *addend_fused says whether it did
 // affine (fprop, optional): f32 [Cin][4] = (mean, invstd * weight, bias, -) of the batch norm + relu that stands between the producer of
 // `in` and this convolution; applied while staging where the kernel chosen can do it - *affine_used says whether it did (else the caller
@@ -2347,14 +2364,14 @@ static void run_conv8(const Tensor* in, const Tensor* w, const Tensor* bias, Ten
   Hold wpk(packed_weights(w, g, KS, st, &dgrad_off, tail_off));
   const bf16_t* wpp = static_cast<const Tensor*>(wpk.get())->ptr<bf16_t>() + (dgrad ? dgrad_off : 0);
   // the K-tail image of this direction (1 .. 8 channels beyond the last whole chunk of a 3x3's K side): LAMP_IG_KTAIL=0 multiplies the padded chunk
-  const bool ktail_on = [] { const char* e = getenv("LAMP_IG_KTAIL"); return !(e && e[0] == '0'); }();      // (read per call: the A/B test flips it)
+  const bool ktail_on = sw_now().ig_ktail;      // (read per call: the A/B test flips it)
+  const IgForm form = ig_form(g, dgrad);
   const bf16_t* wtailp = (ktail_on && tail_off[dgrad ? 1 : 0] >= 0) ? static_cast<const Tensor*>(wpk.get())->ptr<bf16_t>() + tail_off[dgrad ? 1 : 0] : (const bf16_t*)nullptr;
   {
-    const char* variant = getenv("LAMP_IG_VARIANT");
-    if (!(variant && variant[0] == 'a')) {   // default: two co-resident workgroups per CU (A/B on one device: 7 % faster per launch)
+    if (form != IgForm::Plain) {
       const int blocksb = (int)((g.N + 1) / 2);
       // fprop: per-image batch-norm statistics of the output from the epilogue (LAMP_CONV_BN_STATS=0 turns the hand-off off)
-      static const bool bn_stats = [] { const char* e = getenv("LAMP_CONV_BN_STATS"); return !(e && e[0] == '0'); }();
+      const bool bn_stats = sw().conv_bn_stats;
       Hold statt;
       float* statp = nullptr;
       if (bn_stats && !dgrad && g.N >= 2) {
@@ -2370,13 +2387,7 @@ static void run_conv8(const Tensor* in, const Tensor* w, const Tensor* bias, Ten
                                     : second ? conv_bytes(*second->g, 2) - (double)g.N * g.Cin * 64 * 2 : 0.0;   // (one output for both)
       KernelTimer kt("conv_igemm_fprop_dgrad", conv_flops(g) + sib_fl, conv_bytes(g, 2) + sib_by, st);
       const bf16_t* bpb = bias ? bias->ptr<bf16_t>() : (const bf16_t*)nullptr;
-      // more than 64 output channels and enough images to give every CU a workgroup of eight: one workgroup per CU, wave = image x all
-      // channels (LAMP_IG_VARIANT=d forces it for any batch, =b keeps the two-image kernel)
-      const bool force_d = variant && variant[0] == 'd';
-      // ... and for narrow outputs too (NCT = 1 / 4 channel tiles per wave): the 16-channel layers of the ResNet (128 -> 16 dgrad,
-      // 16 -> 16) spent 16 - 30 us in the 64-row kernel multiplying padding; here they are bound by their image reads (LAMP_IG_SMALL_D=0: off)
-      static const bool small_d = [] { const char* e = getenv("LAMP_IG_SMALL_D"); return !(e && e[0] == '0'); }();
-      if ((CO > 64 || small_d) && !(variant && variant[0] == 'b') && (force_d || g.N >= 4 * (int64_t)num_cus())) {
+      if (form == IgForm::Eight) {
         const int blocksd = (int)((g.N + 7) / 8);
         // 3 weight slots + the 32-channel image chunks (+ 9 spare pixels behind them for the taps of a 3x3 kernel) - and at least the
         // 8 x 16 KiB the epilogue stages the output through
@@ -2395,10 +2406,9 @@ static void run_conv8(const Tensor* in, const Tensor* w, const Tensor* bias, Ten
         if (affine_used) *affine_used = affine != nullptr;
         if (addend_fused) *addend_fused = addend != nullptr;
         // the sibling 1x1 of a residual block's first 3x3 (same input, same output channels): second product of this launch
-        static const bool sib_on = [] { const char* e = getenv("LAMP_CONV_SIBLING"); return !(e && e[0] == '0'); }();
         IgSibling sibk{nullptr, nullptr, nullptr, nullptr, nullptr};
         Hold sib_wpk, sib_statt;
-        const bool sib = sib_on && sibling && !dgrad && KS == 3 && !addend && sibling->g->kh == 1 && sibling->g->Cout == g.Cout &&
+        const bool sib = sw().conv_sibling && sibling && !dgrad && KS == 3 && !addend && sibling->g->kh == 1 && sibling->g->Cout == g.Cout &&
                          sibling->g->Cin == g.Cin && sibling->g->N == g.N;
         struct PublishSib { Hold& t; const Tensor* y; int P; ~PublishSib() { if (t.get()) conv_stats_publish(y, t.get(), P); } }
             publish_sib{sib_statt, sib ? sibling->out : nullptr, per_wg ? blocksd : (int)g.N};
@@ -2441,9 +2451,8 @@ static void run_conv8(const Tensor* in, const Tensor* w, const Tensor* bias, Ten
       Hold sibb_wpk, sibb_statt;
       const bool same_shape2 = second && second->g->kh == 1 && second->g->Cout == g.Cout && second->g->Cin == g.Cin && second->g->N == g.N;
       const bool dg2b = second && dgrad && KS == 3 && same_shape2;
-      const bool kernel_c = CO <= 64 && !(variant && variant[0] == 'b');
-      static const bool sib_on_b = [] { const char* e = getenv("LAMP_CONV_SIBLING"); return !(e && e[0] == '0'); }();
-      const bool sibf = sib_on_b && sibling && !dgrad && KS == 3 && !addend && !kernel_c && sibling->g->kh == 1 && sibling->g->Cout == g.Cout &&
+      const bool kernel_c = form == IgForm::Two64;
+      const bool sibf = sw().conv_sibling && sibling && !dgrad && KS == 3 && !addend && !kernel_c && sibling->g->kh == 1 && sibling->g->Cout == g.Cout &&
                         sibling->g->Cin == g.Cin && sibling->g->N == g.N;
       struct PublishSibB { Hold& t; const Tensor* y; int P; ~PublishSibB() { if (t.get()) conv_stats_publish(y, t.get(), P); } }
           publish_sibb{sibb_statt, sibf ? sibling->out : nullptr, (int)g.N};
@@ -2466,7 +2475,7 @@ static void run_conv8(const Tensor* in, const Tensor* w, const Tensor* bias, Ten
         }
         if (sibling_fused) *sibling_fused = true;
       }
-      if (kernel_c) {   // 64-row weight stages, four-slot ring (LAMP_IG_VARIANT=b: the 128-row kernel)
+      if (kernel_c) {
         const size_t ldsc = (size_t)2 * 64 * KP * 2 + KP * 2 + 4 * (64 * 64 * 2);
         if (dg2b) {
           allow_big_lds((const void*)ig_conv8c_kernel<3, 2>);
@@ -2483,8 +2492,8 @@ static void run_conv8(const Tensor* in, const Tensor* w, const Tensor* bias, Ten
       }
       // at most one workgroup per CU (small batches): eight waves per image pair (LAMP_IG_W8=0: always four); at most one IMAGE per CU: one
       // image per workgroup (LAMP_IG_ONE_IMAGE=0: pairs)
-      static const bool w8_on = [] { const char* e = getenv("LAMP_IG_W8"); return !(e && e[0] == '0'); }();
-      static const bool one_on = [] { const char* e = getenv("LAMP_IG_ONE_IMAGE"); return !(e && e[0] == '0'); }();
+      const bool w8_on = sw().ig_w8;
+      const bool one_on = sw().ig_one_image;
       const bool w8 = w8_on && blocksb <= num_cus();
       const bool one = one_on && w8 && g.N <= num_cus();
       const size_t ldsb = (size_t)(one ? 1 : 2) * 64 * KP * 2 + KP * 2 + (one ? 4 : 2) * IG_WTILE;
@@ -2530,12 +2539,11 @@ static void run_conv8(const Tensor* in, const Tensor* w, const Tensor* bias, Ten
 bool igemm_conv_dgrad_pair(const Tensor* dy, const Tensor* w, const ConvGeom& g, const Tensor* dy1, const Tensor* w1, const ConvGeom& g1, Tensor* dx,
                            hipStream_t st, const Tensor* addend, bool* addend_fused) {
   if (addend_fused) *addend_fused = false;
-  static const bool on = [] { const char* e = getenv("LAMP_CONV_DGRAD_PAIR"); return !(e && e[0] == '0'); }();
+  const bool on = sw().conv_dgrad_pair;
   if (!on || !ig_qualifies(g, dy->dtype) || !ig_qualifies(g1, dy1->dtype) || g.kh != 3 || g1.kh != 1) return false;
   if (g.Cout != g1.Cout || g.Cin != g1.Cin || g.N != g1.N) return false;
-  // every kernel of run_conv8's default variant takes a second source (eight images per workgroup at large batches, two below)
-  const char* variant = getenv("LAMP_IG_VARIANT");
-  if (variant && variant[0] == 'a') return false;
+  // every form but the plain one takes a second source (eight images per workgroup at large batches, two below)
+  if (ig_form(g, true) == IgForm::Plain) return false;
   const SecondGradConv sg{dy1, w1, &g1};
   bool fused = false;
   run_conv8(dy, w, nullptr, dx, g, true, st, addend, addend_fused, nullptr, nullptr, nullptr, nullptr, &sg, &fused);
@@ -2548,7 +2556,6 @@ bool igemm_conv_fwd(const Tensor* x, const Tensor* w, const Tensor* bias, Tensor
   run_conv8(x, w, bias, y, g, false, st);
   return true;
 }
-static bool ig_fwd_folds_affine(const ConvGeom& g, int dtype);
 // y = conv3x3(x, w, bias) and y1 = conv1x1(x, w1, bias1) - two convolutions of ONE input with the same number of output channels (the two
 // branches of lamp's residual block, cnn.scala:16-20) - in one launch of the eight-image kernel: false (nothing launched) when that kernel
 // does not take the geometry; the values of both outputs and of the statistics hand-offs are those of the two separate launches
@@ -2556,12 +2563,10 @@ bool igemm_conv_fwd_pair(const Tensor* x, const Tensor* w, const Tensor* bias, T
                          Tensor* y1, const ConvGeom& g1, hipStream_t st) {
   if (!ig_qualifies(g, x->dtype) || !ig_qualifies(g1, x->dtype) || g.kh != 3 || g1.kh != 1) return false;
   if (g.Cout != g1.Cout || g.Cin != g1.Cin || g.N != g1.N) return false;
-  // the eight-image kernel (its conditions), or - small batches - the two-image kernel with 128-row weight stages (more than 64 output channels)
-  const char* variant = getenv("LAMP_IG_VARIANT");
-  if (variant && variant[0] == 'a') return false;
-  if (!ig_fwd_folds_affine(g, x->dtype) && !(g.Cout > 64 || (variant && variant[0] == 'b'))) return false;
-  static const bool sib_on = [] { const char* e = getenv("LAMP_CONV_SIBLING"); return !(e && e[0] == '0'); }();
-  if (!sib_on) return false;
+  // the eight-image kernel, or - small batches - the two-image kernel with 128-row weight stages (more than 64 output channels)
+  const IgForm form = ig_form(g, false);
+  if (form != IgForm::Eight && form != IgForm::Two128) return false;
+  if (!sw().conv_sibling) return false;
   const SiblingConv sc{w1, bias1, y1, &g1};
   bool fused = false;
   run_conv8(x, w, bias, y, g, false, st, nullptr, nullptr, nullptr, nullptr, &sc, &fused);
@@ -2569,20 +2574,12 @@ bool igemm_conv_fwd_pair(const Tensor* x, const Tensor* w, const Tensor* bias, T
   return true;
 }
 // y = conv(relu(bn(x))) with the batch norm given as its per-channel table: true only if a kernel that applies it while staging ran
-// the eight-image kernel's conditions (run_conv8)
-static bool ig_fwd_folds_affine(const ConvGeom& g, int dtype) {
-  if (!ig_qualifies(g, dtype)) return false;
-  const char* variant = getenv("LAMP_IG_VARIANT");
-  if (variant && (variant[0] == 'a' || variant[0] == 'b')) return false;
-  static const bool small_d = [] { const char* e = getenv("LAMP_IG_SMALL_D"); return !(e && e[0] == '0'); }();
-  const bool force_d = variant && variant[0] == 'd';
-  return (g.Cout > 64 || small_d) && (force_d || g.N >= 4 * (int64_t)num_cus());
-}
-// the eight-wave weight-gradient kernel's conditions (igemm_conv_wgrad)
-static bool ig_wgrad_folds_affine(const ConvGeom& g, int dtype) {
-  static const bool wide_on = [] { const char* e = getenv("LAMP_WGRAD_WIDE"); return !(e && e[0] == '0'); }();
-  return ig_qualifies(g, dtype) && wide_on && g.kh == 3 && g.Cin > WG_CI && g.Cout > 64;
-}
+// (only the eight-image kernel does)
+static bool ig_fwd_folds_affine(const ConvGeom& g, int dtype) { return ig_qualifies(g, dtype) && ig_form(g, false) == IgForm::Eight; }
+// the weight gradient of a geometry that qualifies runs in the eight-wave kernel (ig_wgrad8h_kernel; else the four-wave one, ig_wgrad8v2_kernel)
+static bool wgrad_takes_eight_wave(const ConvGeom& g) { return sw().wgrad_wide && g.kh == 3 && g.Cin > WG_CI && g.Cout > 64; }
+// (only the eight-wave kernel rebuilds relu(bn(x)) while staging)
+static bool ig_wgrad_folds_affine(const ConvGeom& g, int dtype) { return ig_qualifies(g, dtype) && wgrad_takes_eight_wave(g); }
 // both directions apply the batch-norm table while staging: only then does folding the batch norm into this convolution save a pass
 bool igemm_conv_folds_affine(const ConvGeom& g, int dtype) { return ig_fwd_folds_affine(g, dtype) && ig_wgrad_folds_affine(g, dtype); }
 bool igemm_conv_fwd_affine(const Tensor* x, const Tensor* affine, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, hipStream_t st) {
@@ -2604,7 +2601,7 @@ bool igemm_conv_dgrad(const Tensor* dy, const Tensor* w, Tensor* dx, const ConvG
 // N <= 512, where the launch is a latency chain and the partial sums are small (B = 256: 0.5606 -> 0.5538 ms per step, round 5).
 // LAMP_WGRAD_MIN_IPS overrides both.
 static int wgrad_min_ips(int64_t N) {
-  static const int v = [] { const char* e = getenv("LAMP_WGRAD_MIN_IPS"); return e ? std::max(2, atoi(e)) : 0; }();
+  const int v = (int)sw().wgrad_min_ips;
   return v ? v : (N <= 512 ? 2 : 8);
 }
 // ---- the eight-wave weight-gradient kernel: one launch for one layer (optionally with its sibling 1x1: `second`) or for TWO layers (round 6) ----
@@ -2615,8 +2612,8 @@ static int wgrad_min_ips(int64_t N) {
 // second convolution waits for res3's, three kernels later) or its owner's entries are flushed: the end of backprop, a read of the gradient, a write
 // into one of its inputs (queued after the launch), a stream / device synchronisation, the end of a graph capture.  LAMP_WGRAD_GROUP=0: every layer at once.
 static bool wg8h_group_defer(const Tensor* dy, const Tensor* x, Tensor* dw, const ConvGeom& g, hipStream_t st, const Tensor* affine) {
-  static const bool on = [] { const char* e = getenv("LAMP_WGRAD_GROUP"); return !(e && e[0] == '0'); }();
-  static const int shift_dy = [] { const char* e = getenv("LAMP_WGRAD_SHIFT_DY"); return e ? atoi(e) : 2; }();
+  const bool on = sw().wgrad_group;
+  const int shift_dy = (int)sw().wgrad_shift_dy;
   // large batches only (a workgroup still walks >= 16 images with half the workgroups), deferred reductions on, tensors the library owns (the
   // deferral is honoured by every access through Tensor::raw / data: a caller's own memory can change without the library seeing it)
   if (!on || shift_dy < 2 || !wgrad_reduce_deferred() || g.N < 8 * (int64_t)num_cus()) return false;
@@ -2657,7 +2654,7 @@ void wg8h_launch(const Wg8hProblem& pa, const Wg8hProblem* pb, hipStream_t st, c
       return;
     }
   }
-  static const int shift_dy = [] { const char* e = getenv("LAMP_WGRAD_SHIFT_DY"); return e ? atoi(e) : 2; }();   // 0: off, 1: dY rows, 2: + X columns in registers
+  const int shift_dy = (int)sw().wgrad_shift_dy;   // 0: off, 1: dY rows, 2: + X columns in registers
   LAMP_CHECK(!(pair || pb) || shift_dy >= 2, "internal: the weight-gradient pair / group needs the register-shifted X fragments");
   Hold partial2;
   if (pair) { int64_t ps2[1] = {(int64_t)A.nsplit * IG_M * A.CIP}; partial2 = Hold(new_tensor(ps2, 1, kF32, pa.x->device())); }
@@ -2677,11 +2674,11 @@ void wg8h_launch(const Wg8hProblem& pa, const Wg8hProblem* pb, hipStream_t st, c
       sp.affine = pb->affine ? reinterpret_cast<const float4*>(pb->affine->ptr<float>()) : (const float4*)nullptr;
       sp.wgs0 = A.wgs;
     }
-    static const bool wg_stagger = [] { const char* e = getenv("LAMP_WGRAD_STAGGER"); return !(e && e[0] == '0'); }();
-    static const bool wg_prio = [] { const char* e = getenv("LAMP_WGRAD_PRIO"); return !(e && e[0] == '0'); }();
+    const bool wg_stagger = sw().wgrad_stagger;
+    const bool wg_prio = sw().wgrad_prio;
     // LAMP_WG8H_DMA=0 (run time): the dY tiles through registers and ds_write instead of LDS-DMA - the same arithmetic in the same order, kept
     // as the fallback and the bitwise A/B of the hand-counted vmcnt waits (tests/test_ops_gpu.py)
-    static const bool wg_dma = [] { const char* e = getenv("LAMP_WG8H_DMA"); return e ? e[0] != '0' : (LAMP_WG8H_DMA != 0); }();
+    const bool wg_dma = sw().wg8h_dma;
     const int grid = A.wgs + (pb ? B.wgs : 0);
 #define IG_LAUNCH_WG8H(M_, P_)                                                                                                              \
   do {                                                                                                                                      \
@@ -2720,10 +2717,9 @@ static bool igemm_conv_wgrad_impl(const Tensor* dy, const Tensor* x, Tensor* dw,
                                   const SecondWgradConv* second) {
   if (!ig_qualifies(g, x->dtype)) return false;
   const int KS = g.kh, RS = KS * KS;
-  static const bool wide_on = [] { const char* e = getenv("LAMP_WGRAD_WIDE"); return !(e && e[0] == '0'); }();
   const float4* affp = affine ? reinterpret_cast<const float4*>(affine->ptr<float>()) : (const float4*)nullptr;
   if (affine && !ig_wgrad_folds_affine(g, x->dtype)) return false;
-  if (wide_on && KS == 3 && g.Cin > WG_CI && g.Cout > 64) {
+  if (wgrad_takes_eight_wave(g)) {
     // eight-wave kernel: the v2 decomposition (32-channel slice of Cin, image range) with two waves per SIMD
     if (!second && wg8h_group_defer(dy, x, dw, g, st, affine)) return true;      // launched with the next such layer's, or by the flush (below)
     Wg8hProblem a{dy, x, dw, g, affine};
@@ -2738,9 +2734,9 @@ static bool igemm_conv_wgrad_impl(const Tensor* dy, const Tensor* x, Tensor* dw,
     const int CIP = g.Cin <= 16 ? 16 : (all_ci ? 4 : ntile) * WG_CI;   // columns of a partial-sum tile (see tile_active in the kernel)
     const bool narrow = g.Cout <= 64 || g.Cin <= 16;               // the NARROW instantiation (branches in the MFMA chain) only where it pays
     const int COP = narrow ? (int)((g.Cout + 15) / 16) * 16 : IG_M;  // rows
-    static const int wgs_per_cu = [] { const char* e = getenv("LAMP_WGRAD_WGS_PER_CU"); return e ? std::max(1, atoi(e)) : 1; }();
+    const int wgs_per_cu = (int)sw().wgrad_wgs_per_cu;
     // one workgroup per CU: half the partial-sum traffic of two, same speed
-    static const int narrow_per_cu = [] { const char* e = getenv("LAMP_WGRAD_NARROW_PER_CU"); return e ? std::max(1, atoi(e)) : 1; }();   // measured: 2 and 3 are 1 % slower on the step
+    const int narrow_per_cu = (int)sw().wgrad_narrow_per_cu;   // measured: 2 and 3 are 1 % slower on the step
     int target = std::max(1, (num_cus() * (narrow ? narrow_per_cu : wgs_per_cu)) / ntile);
     int ips = (int)std::max<int64_t>(1, (g.N + target - 1) / target);
     if (ips < wgrad_min_ips(g.N) && g.N >= wgrad_min_ips(g.N)) ips = wgrad_min_ips(g.N);
@@ -2757,7 +2753,7 @@ static bool igemm_conv_wgrad_impl(const Tensor* dy, const Tensor* x, Tensor* dw,
       const double sec_fl = pair ? conv_flops(*second->g) : 0.0;
       const double sec_by = pair ? conv_bytes(*second->g, 2) - (double)g.N * g.Cin * 64 * 2 : 0.0;
       KernelTimer kt("conv_wgrad_igemm", conv_flops(g) + sec_fl, conv_bytes(g, 2) + sec_by, st);
-      static const bool ci16_on = [] { const char* e = getenv("LAMP_WGRAD_CI16"); return !(e && e[0] == '0'); }();
+      const bool ci16_on = sw().wgrad_ci16;
       const bool ci16 = ci16_on && KS == 3 && CIP == 16;           // (then `narrow` holds: Cin <= 16)
       const void* kfn = ci16    ? (pair ? (const void*)ig_wgrad8v2_kernel<3, true, 1, true, true> : (const void*)ig_wgrad8v2_kernel<3, true, 1, false, true>)
                       : pair    ? (narrow ? (const void*)ig_wgrad8v2_kernel<3, true, 1, true> : (const void*)ig_wgrad8v2_kernel<3, false, 1, true>)
@@ -2795,10 +2791,8 @@ bool igemm_conv_wgrad(const Tensor* dy, const Tensor* x, Tensor* dw, const ConvG
 // the LDS the shifted X copies no longer need): the values of the two separate launches up to the order the image ranges are summed in for dw1;
 // false = nothing launched
 bool igemm_conv_wgrad_pair(const Tensor* dy, const Tensor* dy1, const Tensor* x, Tensor* dw, Tensor* dw1, const ConvGeom& g, const ConvGeom& g1, hipStream_t st) {
-  static const bool on = [] { const char* e = getenv("LAMP_CONV_WGRAD_PAIR"); return !(e && e[0] == '0'); }();
-  static const bool wide_on = [] { const char* e = getenv("LAMP_WGRAD_WIDE"); return !(e && e[0] == '0'); }();
-  static const int shift_dy = [] { const char* e = getenv("LAMP_WGRAD_SHIFT_DY"); return e ? atoi(e) : 2; }();
-  if (!on || !wide_on || shift_dy < 2) return false;
+  // (the switch alone, not wgrad_takes_eight_wave: with it on, BOTH weight-gradient kernels take a pair - the comment below)
+  if (!sw().conv_wgrad_pair || !sw().wgrad_wide || sw().wgrad_shift_dy < 2) return false;
   if (!ig_qualifies(g, x->dtype) || !ig_qualifies(g1, x->dtype) || g.kh != 3 || g1.kh != 1) return false;
   if (g.Cin != g1.Cin || g.N != g1.N) return false;
   // (more than 32 input and 64 output channels: the eight-wave kernel; else the four-wave kernel, one Cin slice per workgroup)

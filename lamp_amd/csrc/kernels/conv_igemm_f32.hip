@@ -33,6 +33,7 @@
 #include "device_utils.h"
 #include "conv_geom.h"
 #include "wgrad_reduce.h"
+#include "../core/switches.h"
 
 namespace lamp {
 
@@ -476,8 +477,8 @@ __global__ void ig64_wgrad_reduce_kernel(const double* __restrict__ partial, dou
 
 // ---- host ---------------------------------------------------------------------------------------------
 static bool ig32_qualifies(const ConvGeom& g, int dtype) {
-  static const bool on = [] { const char* e = getenv("LAMP_IGEMM_F32"); return !(e && e[0] == '0'); }();
-  static const bool on64 = [] { const char* e = getenv("LAMP_IGEMM_F64"); return !(e && e[0] == '0'); }();
+  const bool on = sw().igemm_f32;
+  const bool on64 = sw().igemm_f64;
   if (!((on && dtype == kF32) || (on64 && dtype == kF64))) return false;
   if (g.groups != 1 || g.transposed) return false;
   if (g.H != 8 || g.W != 8 || g.Ho != 8 || g.Wo != 8) return false;
@@ -516,7 +517,7 @@ static Tensor* packed_weights32(const Tensor* w, const ConvGeom& g, int KS, hipS
   const int KPf = pad16(g.Cin), KPd = pad16(g.Cout);
   const int64_t nf = (int64_t)RS * F_ROWS * KPf, nd = (int64_t)RS * F_ROWS * KPd;
   *dgrad_offset = nf;
-  static const bool cache_on = [] { const char* e = getenv("LAMP_PACK_CACHE"); return !(e && e[0] == '0'); }();
+  const bool cache_on = sw().pack_cache;
   const bool cacheable = cache_on && w->st->owned && !w->st->scratch;
   const PackKey32 key{w->st->uid, w->offset, KS, (int)g.Cout, (int)g.Cin, w->dtype, st};
   const uint64_t ver = w->st->version.load(std::memory_order_relaxed);
@@ -604,7 +605,7 @@ static void run_conv8_t(const Tensor* in, const Tensor* w, const Tensor* bias, T
   const int blocks = (int)((g.N + NI - 1) / NI);
   const size_t lds = 16 * sizeof(T) + (size_t)NI * (KP / 4) * ig_pstr<T>();
   // fprop in f32: per-image batch-norm statistics of the output from the epilogue, handed to the batch norm that follows (LAMP_CONV_BN_STATS=0: off)
-  static const bool bn_stats = [] { const char* e = getenv("LAMP_CONV_BN_STATS"); return !(e && e[0] == '0'); }();
+  const bool bn_stats = sw().conv_bn_stats;
   Hold statt;
   float* statp = nullptr;
   if (std::is_same<T, float>::value && bn_stats && !dgrad && g.N >= 2 && nct > 1) {

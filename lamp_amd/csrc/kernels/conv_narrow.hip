@@ -29,6 +29,7 @@
 #include <tuple>
 #include <vector>
 #include "conv_narrow_pack.h"
+#include "../core/switches.h"
 
 namespace lamp {
 
@@ -834,7 +835,7 @@ static void ncv_pack_launch(const NcvPackMany& a, int cnt, hipStream_t st) {
 
 // returns a +1 handle on the fragment image of `w` for this direction
 static Tensor* ncv_packed_weights(const Tensor* w, const NcvW& wq, hipStream_t st, const Tensor* w2 = nullptr) {
-  static const bool cache_on = [] { const char* e = getenv("LAMP_PACK_CACHE"); return !(e && e[0] == '0'); }();
+  const bool cache_on = sw().pack_cache;
   const bool cacheable = cache_on && w->st->owned && !w->st->scratch && (!w2 || (w2->st->owned && !w2->st->scratch));
   const NcvPackKey key{w->st->uid, w->offset, wq.Cout, wq.Cin, wq.kh, wq.kw, wq.dgrad, wq.ns + 16 * wq.nke, wq.sw, st,
                        w2 ? w2->st->uid : 0, w2 ? w2->offset : 0, w2 ? wq.Cout2 : 0};
@@ -875,7 +876,7 @@ static Tensor* ncv_packed_weights(const Tensor* w, const NcvW& wq, hipStream_t s
 // in conv_igemm.hip packs them in the launch that packs the implicit-GEMM images; earlier full batches are still launched here
 void narrow_repack_cached(lamp_tensor* const* params, int n, hipStream_t st, NcvPackMany* fill, int* fill_cnt) {
   if (fill_cnt) *fill_cnt = 0;
-  static const bool on = [] { const char* e = getenv("LAMP_PACK_AFTER_STEP"); return !(e && e[0] == '0'); }();
+  const bool on = sw().pack_after_step;
   if (!on) return;
   std::lock_guard<std::mutex> lk(g_ncv_mu);
   if (g_ncv_cache.empty()) return;
@@ -982,7 +983,7 @@ static bool ncv_run(const Tensor* in, const Tensor* w, const Tensor* bias, Tenso
   // round 6: the input gradient of a stride-2 pair runs its super-tiles by row parity over K pairs packed by the parity of the filter row
   // (ncv_fwd2_kernel<.., PAR>; LAMP_NCV_DGRAD_PARITY=0: the plain form): half the k-steps per super-tile
   int nke = 0;
-  static const bool par_on = [] { const char* e = getenv("LAMP_NCV_DGRAD_PARITY"); return !(e && e[0] == '0'); }();
+  const bool par_on = sw().ncv_dgrad_parity;
   if (par_on && aligned && dgrad && second && q.dil == 2 && g.kh == 3 && NK > 5) {
     const int nk2 = NK <= 6 ? 6 : NK <= 8 ? 8 : 16;
     const int need_e = (q.C1 * 2 + 3) / 4, need_o = (q.C + 3) / 4;      // pairs (c, r even) / (c, 1) and the second source's centre rows
@@ -993,7 +994,7 @@ static bool ncv_run(const Tensor* in, const Tensor* w, const Tensor* bias, Tenso
   // DIFFERENT 16-byte bank slots iff (RS * sh * Ws / 8) mod 16 is an odd multiple of ncg.  (Round 6: the res2 pair's image had a 64-byte pitch -
   // rows a_tr and a_tr + 4 on the same banks, and with the parity tiles' two-apart rows a_tr and a_tr + 2: the halved k-loop read twice as slowly
   // and the launch gained nothing.)  The pitch is widened by at most 15 x 16 bytes to the next such value.
-  static const bool pitch_on = [] { const char* e = getenv("LAMP_NCV_PITCH"); return !(e && e[0] == '0'); }();
+  const bool pitch_on = sw().ncv_pitch;
   if (pitch_on && aligned) {
     const int rs = (nke > 0 ? 2 : 1) * q.sh;
     for (int k = 0; k < 16; k++) {
@@ -1004,13 +1005,13 @@ static bool ncv_run(const Tensor* in, const Tensor* w, const Tensor* bias, Tenso
   const size_t lds = (size_t)q.C * q.Hs * q.Ws * 2;
   if (lds > 64 * 1024) return false;
   // two output phases per MFMA where the columns allow it (see NcvW)
-  static const bool two_shift_on = [] { const char* e = getenv("LAMP_NCV_TWO_SHIFT"); return !(e && e[0] == '0'); }();
+  const bool two_shift_on = sw().ncv_two_shift;
   const int NS = (two_shift_on && aligned && q.CO <= 8 && g.kw + q.sw <= 8) ? 2 : 1;
   const Tensor* wsecond = sib ? sib->w : second ? second->w : nullptr;
   const NcvW wq{w->ptr<bf16_t>(), (int)g.Cout, (int)g.Cin, g.kh, g.kw, dgrad ? 1 : 0, NS, q.sw, wsecond ? wsecond->ptr<bf16_t>() : (const bf16_t*)nullptr, cout2, nke};
   Hold wpk_h(ncv_packed_weights(w, wq, st, wsecond));
   const nv_bf8* wpk = reinterpret_cast<const nv_bf8*>(static_cast<const Tensor*>(wpk_h.get())->ptr<bf16_t>());
-  static const int max_per_cu = [] { const char* e = getenv("LAMP_NCV_PER_CU"); return e ? std::max(1, atoi(e)) : 4; }();   // A/B on one device: 4 beats 8 and 2
+  const int max_per_cu = (int)sw().ncv_per_cu;   // A/B on one device: 4 beats 8 and 2
   const int lds_per_cu = (int)std::max<size_t>(1, std::min<size_t>(max_per_cu, (size_t)(150 * 1024) / std::max<size_t>(lds, 1)));
   const bf16_t* bp = bias ? bias->ptr<bf16_t>() : (const bf16_t*)nullptr;
   if (aligned) {
@@ -1025,11 +1026,7 @@ static bool ncv_run(const Tensor* in, const Tensor* w, const Tensor* bias, Tenso
     const void* kfn = nullptr;
     const bool with_add = addend != nullptr && q.sw == 1;
     // fprop: per-image batch-norm statistics of the output(s) from the epilogue (LAMP_CONV_BN_STATS=0 turns the hand-off off)
-    static const bool bn_stats = [] {
-      const char* e = getenv("LAMP_CONV_BN_STATS");
-      const char* n = getenv("LAMP_NCV_BN_STATS");          // the narrow kernels' alone (A/B)
-      return !(e && e[0] == '0') && !(n && n[0] == '0');
-    }();
+    const bool bn_stats = sw().conv_bn_stats && sw().ncv_bn_stats;          // (the second: the narrow kernels' alone, A/B)
     // (a filter whose output's statistics nobody took last time - the stem of Cnn.resnet feeds res1's convolutions directly - stops paying for them)
     const bool with_stats = bn_stats && !dgrad && !addend && g.N >= 2 && (int64_t)q.Ho * q.Wo >= 64 && (sib || conv_stats_wanted(w->st->uid));
 #define NCV_F2(NKv, SWv, PHv, ADDv, STv) kfn = NS == 2 ? (const void*)ncv_fwd2_kernel<NKv, SWv, PHv, 2, ADDv, STv> : (const void*)ncv_fwd2_kernel<NKv, SWv, PHv, 1, ADDv, STv>
@@ -1121,7 +1118,7 @@ bool narrow_conv_fwd(const Tensor* x, const Tensor* w, const Tensor* bias, Tenso
 // output columns); false = nothing launched
 bool narrow_conv_fwd_pair(const Tensor* x, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, const Tensor* w1, const Tensor* bias1,
                           Tensor* y1, const ConvGeom& g1, hipStream_t st) {
-  static const bool on = [] { const char* e = getenv("LAMP_CONV_SIBLING"); return !(e && e[0] == '0'); }();
+  const bool on = sw().conv_sibling;
   if (!on || x->dtype != kBF16) return false;
   if (g.kh != 3 || g.kw != 3 || g.ph != 1 || g.pw != 1 || g1.kh != 1 || g1.kw != 1 || g1.ph != 0 || g1.pw != 0) return false;
   if (g.sh != g1.sh || g.sw != g1.sw || g.Ho != g1.Ho || g.Wo != g1.Wo || g.Cin != g1.Cin || g.N != g1.N || g.groups != 1 || g1.groups != 1) return false;
@@ -1139,7 +1136,7 @@ bool narrow_conv_dgrad(const Tensor* dy, const Tensor* w, Tensor* dx, const Conv
 bool narrow_conv_dgrad_pair(const Tensor* dy, const Tensor* w, const ConvGeom& g, const Tensor* dy1, const Tensor* w1, const ConvGeom& g1, Tensor* dx,
                             hipStream_t st, const Tensor* addend, bool* addend_fused) {
   if (addend_fused) *addend_fused = false;
-  static const bool on = [] { const char* e = getenv("LAMP_CONV_DGRAD_PAIR"); return !(e && e[0] == '0'); }();
+  const bool on = sw().conv_dgrad_pair;
   if (!on || dy->dtype != kBF16 || dy1->dtype != kBF16) return false;
   if (g.kh != 3 || g.kw != 3 || g.ph != 1 || g.pw != 1 || g1.kh != 1 || g1.kw != 1 || g1.ph != 0 || g1.pw != 0) return false;
   if (g.sh != g1.sh || g.sw != g1.sw || g.Ho != g1.Ho || g.Wo != g1.Wo || g.H != g1.H || g.W != g1.W || g.Cin != g1.Cin || g.N != g1.N) return false;
@@ -1284,7 +1281,7 @@ bool narrow_conv_wgrad(const Tensor* dy, const Tensor* x, Tensor* dw, const Conv
 // (cnn.scala:16-20) - from one launch that stages x once: the values of the two separate launches (the second gradient tensor rides in the
 // spare rows of the MFMA tile, its weight gradient is the centre tap of those rows); false = nothing launched
 bool narrow_conv_wgrad_pair(const Tensor* dy, const Tensor* dy1, const Tensor* x, Tensor* dw, Tensor* dw1, const ConvGeom& g, const ConvGeom& g1, hipStream_t st) {
-  static const bool on = [] { const char* e = getenv("LAMP_CONV_WGRAD_PAIR"); return !(e && e[0] == '0'); }();
+  const bool on = sw().conv_wgrad_pair;
   if (!on || x->dtype != kBF16 || dy->dtype != kBF16 || dy1->dtype != kBF16) return false;
   if (g1.kh != 1 || g1.kw != 1 || g1.ph != 0 || g1.pw != 0) return false;
   if (g.sh != g1.sh || g.sw != g1.sw || g.Ho != g1.Ho || g.Wo != g1.Wo || g.H != g1.H || g.W != g1.W || g.Cin != g1.Cin || g.N != g1.N) return false;

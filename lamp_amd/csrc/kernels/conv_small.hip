@@ -13,6 +13,7 @@
 #include "device_utils.h"
 #include "conv_geom.h"
 #include "wgrad_reduce.h"
+#include "../core/switches.h"
 
 namespace lamp {
 
@@ -388,7 +389,7 @@ void small_repack_cached(lamp_tensor* const* params, int n, hipStream_t st) {
 
 static int cs2_shift_of(int64_t v) { int sh = 0; while ((1LL << sh) < v) sh++; return (1LL << sh) == v ? sh : -1; }
 static bool cs2_qualifies(const ConvGeom& g) {
-  static const bool on = [] { const char* e = getenv("LAMP_CONV_SMALL2"); return !(e && e[0] == '0'); }();
+  const bool on = sw().conv_small2;
   if (!on || g.groups != 1 || g.transposed || g.dh != 1 || g.dw != 1) return false;
   if (g.Cin > 16 || g.Cout > 16 || g.N < 1) return false;
   if (g.kh != g.kw || !(g.kh == 1 || g.kh == 3 || g.kh == 5) || g.ph != g.kh / 2 || g.pw != g.kh / 2) return false;
@@ -689,7 +690,7 @@ __global__ __launch_bounds__(512) void cs2_wgrad_kernel(const T* __restrict__ dy
 
 template <class T> static bool cs2_wgrad_run(const Tensor* dy, const Tensor* x, Tensor* dw, const ConvGeom& g, hipStream_t st) {
   using A = typename CsAccOf<T>::type;
-  static const bool on = [] { const char* e = getenv("LAMP_CONV_SMALL2_WGRAD"); return !(e && e[0] == '0'); }();
+  const bool on = sw().conv_small2_wgrad;
   if (!on || !cs2_qualifies(g)) return false;
   if (!(g.Cout == 6 || g.Cout == 16) || g.Ho < 8) return false;
   const int KS = g.kh, ST = g.sh, PAD = KS / 2;

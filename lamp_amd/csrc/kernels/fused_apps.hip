@@ -12,6 +12,7 @@
 #include "device_utils.h"
 #include "philox.h"
 #include "../core/strided.h"
+#include "../core/switches.h"
 
 namespace lamp {
 
@@ -567,7 +568,7 @@ static void umap_loss_grad_impl(lamp_tensor** loss, lamp_tensor* grad_accum, con
   const int64_t* keptp = kept.get() ? static_cast<const Tensor*>(kept.get())->ptr<int64_t>() : nullptr;
   const double w[4] = {term_weights ? term_weights[0] : 1.0, term_weights ? term_weights[1] : 1.0, term_weights ? term_weights[2] : 1.0,
                        term_weights ? term_weights[3] : 1.0};
-  static const bool pairs2 = [] { const char* e = getenv("LAMP_UMAP_PAIRS2"); return !(e && e[0] == '0'); }();
+  const bool pairs2 = sw().umap_pairs2;
   const int64_t* i3p = index3 ? index3->ptr<int64_t>() : nullptr;
   const int64_t* i4p = index4 ? index4->ptr<int64_t>() : nullptr;
   if ((pairs2 || sampled) && locations->sizes[1] == 2 && E1 + E2 > 0) {

@@ -25,6 +25,7 @@
 #include <sstream>
 #include "device_utils.h"
 #include "../core/strided.h"
+#include "../core/switches.h"
 
 namespace lamp {
 
@@ -1025,7 +1026,7 @@ static void gemm_dispatch(Tensor* out, const Tensor* self, const Tensor* a, cons
   const double g_flops = 2.0 * (double)g.M * (double)g.N * (double)g.K * g.batch;
   const double g_bytes = ((double)g.M * g.K + (double)g.K * g.N + (double)g.M * g.N * (g.S ? 2 : 1)) * g.batch * (double)dtype_size(a->dtype);
   const char* kt_tag = a->dtype == kBF16 ? "gemm_bf16" : (a->dtype == kF16 ? "gemm_f16" : (a->dtype == kF32 ? "gemm_f32" : "gemm_f64"));
-  static const bool shape_tags = getenv("LAMP_GEMM_SHAPE_TAGS") != nullptr;   // profiling aid: one timer class per shape and layout
+  const bool shape_tags = sw().gemm_shape_tags;   // profiling aid: one timer class per shape and layout
   if (shape_tags) {
     static std::mutex mu;
     static std::map<std::string, std::unique_ptr<std::string>> interned;
@@ -1060,7 +1061,7 @@ static void gemm_dispatch(Tensor* out, const Tensor* self, const Tensor* a, cons
       if (c2 < c1) big2 = true;
     }
     // few output tiles over a long K (the weight gradients x^T . p of a token batch): split K over blockIdx.z
-    static const bool allow_split = !(getenv("LAMP_GEMM_SPLITK") && atoi(getenv("LAMP_GEMM_SPLITK")) == 0);
+    const bool allow_split = sw().gemm_splitk;
     if (allow_split && !big2 && g.batch == 1 && g.a_vec && g.b_vec && g.M % QM == 0 && g.N % QN == 0 && g.K % PK == 0 && g.K >= 512) {
       const int64_t tiles = (g.M / QM) * (g.N / QN), nk_total = g.K / PK;
       // one workgroup per CU.  Cost of a split d in us: rounds x k-steps per chunk x ~1.7 us (one 256 x 256 x 64 stage at the
@@ -1161,7 +1162,7 @@ static void gemm_dispatch(Tensor* out, const Tensor* self, const Tensor* a, cons
     // The 256 x 256 kernel runs one workgroup per CU, so a tile count just above a multiple of the CU count costs a whole extra round
     // (288 tiles: 155 us, 255 tiles: 101 us at K = 3072).  When the last round would be less than a quarter full, the rows of that
     // remainder become a second product, which the split-K path spreads over the idle CUs.
-    static const bool tail_split = !(getenv("LAMP_GEMM_TAIL_SPLIT") && atoi(getenv("LAMP_GEMM_TAIL_SPLIT")) == 0);
+    const bool tail_split = sw().gemm_tail_split;
     const int64_t cus = num_cus();
     if (tail_split && g.batch == 1 && !g.knn_q && g.M % QM == 0 && g.N % QN == 0 && g.K % PK == 0 && g.K >= 2048) {   // shorter K: the second launch costs more than the round
       const int64_t tn = g.N / QN, t2 = (g.M / QM) * tn, rem = t2 % cus;
@@ -1214,10 +1215,10 @@ static void gemm_dispatch(Tensor* out, const Tensor* self, const Tensor* a, cons
     // `split` depends on the tile count, i.e. on M and N - the same input row can give different last bits at another batch size (within
     // the 1e-5 the f32 path is held to; deterministic for a given shape).  The slices carry no epilogue: only (alpha, beta, S) of GemmArgs
     // are applied, by the reduction - any other epilogue field keeps the un-split path (the condition below lists them).
-    static const bool allow_fp_split = !(getenv("LAMP_GEMM_SPLITK") && atoi(getenv("LAMP_GEMM_SPLITK")) == 0);
+    const bool allow_fp_split = sw().gemm_splitk;
     const int64_t fp_tiles = (int64_t)g.tiles_m * g.tiles_n;
     if (allow_fp_split && g.batch == 1 && !g.knn_q && fp_tiles < 128 && g.K >= 128) {
-      static const int64_t fp_split_wgs = [] { const char* e = getenv("LAMP_GEMM_FP_SPLIT_WGS"); return e ? std::max(1, atoi(e)) : 512; }();
+      const int64_t fp_split_wgs = sw().gemm_fp_split_wgs;
       int64_t split = std::min<int64_t>(std::min<int64_t>((fp_split_wgs + fp_tiles - 1) / fp_tiles, g.K / 64), 32);
       if (split > 1) {
         const int64_t kc = ((g.K + split - 1) / split + FK - 1) / FK * FK;

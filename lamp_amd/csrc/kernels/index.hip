@@ -12,6 +12,7 @@
 #include "philox.h"
 #include <cstring>
 #include "../core/strided.h"
+#include "../core/switches.h"
 
 namespace lamp {
 
@@ -970,7 +971,7 @@ int lamp_index_select_pinned(lamp_tensor** out, const lamp_tensor* pinned, const
     // The reads cross PCIe: ~50 GB/s whatever the grid, as long as ~100 KB of requests are in flight - a few dozen workgroups do that.
     // A grid that covers the chip (tried first: two workgroups on every CU for the 0.5 ms a 25 MB batch takes) starved the training step it is
     // meant to run beside: the step's first kernel waited 300 us for a slot and then ran 10 x slower (rocprofv3 timeline, scripts/epoch_overlap_probe.py)
-    static const int64_t gp_wgs = [] { const char* e = getenv("LAMP_PINNED_GATHER_WGS"); return (int64_t)(e ? std::max(1, atoi(e)) : 48); }();
+    const int64_t gp_wgs = sw().pinned_gather_wgs;
     const dim3 grid((unsigned)std::min<int64_t>((rows + 3) / 4, gp_wgs));
     int* aw = device_assert_word(index->device());
 #define GP_LAUNCH(S_, D_) hipLaunchKernelGGL((gather_pinned_rows_kernel<S_, D_>), grid, dim3(256), 0, st, pinned->ptr<S_>(), ic->ptr<int64_t>(), r->ptr<D_>(), rows, width, pinned->sizes[0], aw)

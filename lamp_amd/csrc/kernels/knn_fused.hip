@@ -14,6 +14,7 @@
 // private LDS buffer (ballot + mbcnt, no atomics) and lane r inserts the entries of row r into that row's sorted (value, index)
 // list.  Ties resolve by the lower index, as the unfused path does.
 #include "device_utils.h"
+#include "../core/switches.h"
 #include <type_traits>
 
 namespace lamp {
@@ -331,7 +332,7 @@ static void knn_fused_launch(const Tensor* q, const Tensor* x, const Tensor* qn,
 
 bool knn_fused(const Tensor* q, const Tensor* x, const Tensor* qn, const Tensor* dn, Tensor* idx, Tensor* val, int64_t Q, int64_t N, int64_t dim,
                int64_t k, hipStream_t st, int kind) {
-  static const bool enabled = [] { const char* e = getenv("LAMP_KNN_FUSED"); return !(e && e[0] == '0'); }();
+  const bool enabled = sw().knn_fused;
   const bool f32 = q->dtype == kF32, f64 = q->dtype == kF64;
   if (!enabled || !(f32 || f64) || !(dim == 64 || dim == 128) || k < 1 || k > KF_KMAX || N > 0x7fffff00 || Q > 0x7fffff00 || N < k || Q < 1) return false;
   if ((((uintptr_t)q->data() | (uintptr_t)x->data()) & 15) != 0) return false;

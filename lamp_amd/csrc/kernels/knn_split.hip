@@ -31,6 +31,7 @@
 // The result is that of an exact f32 search; only the time depends on the data.
 #include "device_utils.h"
 #include "../core/tensor.h"
+#include "../core/switches.h"
 #include <type_traits>
 #include <vector>
 
@@ -488,8 +489,7 @@ int split_pass(const Tensor* q, const Tensor* x, const Tensor* qn, const Tensor*
     constexpr int BC = ks_tile_points(DIM, PL);
     const size_t lds = (size_t)2 * BC * 2 * PL * DIM + 4 * sizeof(KsWaveState);
     const float m2 = -2.f / (scale * scale);
-    const char* dbg = getenv("LAMP_KNN_SPLIT_DBG");
-    const int dm = dbg ? atoi(dbg) : 0;
+    const int dm = (int)sw_now().knn_split_dbg;
 #define KS_LAUNCH(DB) do { allow_big_lds((const void*)knn_split_kernel<DIM, PL, DB>); hipLaunchKernelGGL((knn_split_kernel<DIM, PL, DB>), dim3((unsigned)((Q + KS_BQ - 1) / KS_BQ)), dim3(256), lds, st, reinterpret_cast<const _Float16*>(qs->raw()), reinterpret_cast<const _Float16*>(xs->raw()), qnc->ptr<float>(), dnc->ptr<float>(), ci->ptr<int>(), cv->ptr<float>(), (int)Q, (int)N, m2); } while (0)
     if (dm == 3) KS_LAUNCH(3); else KS_LAUNCH(0);
 #undef KS_LAUNCH
@@ -574,7 +574,7 @@ static bool knn_split_run(const Tensor* q, const Tensor* x, const Tensor* qn, co
   const float big = std::sqrt(std::max(mx[0], mx[1]));
   if (!std::isfinite(big)) return false;                          // NaN / Inf in the data or the queries: the exact kernel's behaviour, not an error of this path
   const float scale = big > 0.f ? std::exp2(std::floor(14.f - std::log2(big))) : 1.f;
-  static const int env_planes = [] { const char* e = getenv("LAMP_KNN_SPLIT_PLANES"); return e ? atoi(e) : 0; }();
+  const int env_planes = (int)sw().knn_split_planes;
   const int planes = env_planes == 3 ? 3 : 2;
   const int nf = planes == 2 ? split_pass<DIM, 2, T>(q, x, qn, dn, dn_max.get(), mean.get(), scale, dnc.get(), dnc_max.get(), qnc.get(), idx, val, failed.get(), Q, N, k, st)
                              : split_pass<DIM, 3, T>(q, x, qn, dn, dn_max.get(), mean.get(), scale, dnc.get(), dnc_max.get(), qnc.get(), idx, val, failed.get(), Q, N, k, st);
@@ -588,7 +588,7 @@ static bool knn_split_run(const Tensor* q, const Tensor* x, const Tensor* qn, co
 // (f64 - lamp's default DoublePrecision: the same f16 filter on the rows rounded to f32 after centring; the re-rank and the proof in f64.)
 bool knn_split(const Tensor* q, const Tensor* x, const Tensor* qn, const Tensor* dn, Tensor* idx, Tensor* val, int64_t Q, int64_t N, int64_t dim, int64_t k,
                hipStream_t st) {
-  static const int env_mode = [] { const char* e = getenv("LAMP_KNN_SPLIT"); return e ? atoi(e) : -1; }();
+  const int env_mode = (int)sw().knn_split;
   const int mode = env_mode >= 0 ? env_mode : g_knn_split_mode;
   g_knn_split_planes = 0;
   const bool f32 = q->dtype == kF32, f64 = q->dtype == kF64;

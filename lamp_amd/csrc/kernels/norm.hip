@@ -18,6 +18,7 @@
 #include <mutex>
 #include <type_traits>
 #include "../core/strided.h"
+#include "../core/switches.h"
 
 namespace lamp {
 
@@ -1276,8 +1277,8 @@ static unsigned* bn_fused_sync_state(int device, hipStream_t st) {
 template <class T>
 static bool bn_bwd_fused_fp_launch(const Tensor* gc, const Tensor* xc, const Tensor* mean_t, const Tensor* invstd_t, const Tensor* weight, const Tensor* bias,
                                    Tensor* dw, Tensor* db, Tensor* dx, Tensor* dadd, const Tensor* addc, const BnGeom& g, int relu, hipStream_t st) {
-  static const bool env_on = [] { const char* e = getenv("LAMP_BN_FUSED_BWD"); return !(e && e[0] == '0'); }();
-  static const bool fp_on = [] { const char* e = getenv("LAMP_BN_FUSED_FP"); return !(e && e[0] == '0'); }();
+  const bool env_on = sw().bn_fused_bwd;
+  const bool fp_on = sw().bn_fused_fp;
   const int mode = g_bn_bwd_mode.load(std::memory_order_relaxed);
   const bool on = mode < 0 ? (env_on && fp_on) : mode >= 1;
   if (on && mode != 2 && device_shared(xc->device()) > 0) return false;
@@ -1293,7 +1294,7 @@ static bool bn_bwd_fused_fp_launch(const Tensor* gc, const Tensor* xc, const Ten
   if (per_thread(s) > 16) s = (packets + 16 * 512 - 1) / (16 * 512);
   const int ppt = (int)per_thread(s);
   const int NP = ppt <= 1 ? 1 : ppt <= 2 ? 2 : ppt <= 4 ? 4 : ppt <= 8 ? 8 : 16;
-  static const int np_mask = [] { const char* e = getenv("LAMP_BN_FUSED_NP_MASK"); return e ? atoi(e) : 24; }();   // as the bf16 form: the large activations
+  const int np_mask = (int)sw().bn_fused_np_mask;   // as the bf16 form: the large activations
   if (!(np_mask & NP)) return false;
 #define BN_FP_K(NPv) (addc ? (const void*)bn_bwd_fused_fp_kernel<T, NPv, true, true> : relu ? (const void*)bn_bwd_fused_fp_kernel<T, NPv, true, false> \
                            : (const void*)bn_bwd_fused_fp_kernel<T, NPv, false, false>)
@@ -1337,7 +1338,7 @@ struct BnPlaneGrad { const bf16_t* p = nullptr; int sn = 0, sc = 0; };
 static bool bn_bwd_fused_launch(const Tensor* gc, const Tensor* xc, const Tensor* mean_t, const Tensor* invstd_t, const Tensor* weight, const Tensor* bias,
                                 Tensor* dw, Tensor* db, Tensor* dx, Tensor* dadd, const Tensor* addc, const BnGeom& g, int relu, hipStream_t st,
                                 const BnDualHost* dualh = nullptr, BnPlaneGrad gplanes = BnPlaneGrad()) {
-  static const bool env_on = [] { const char* e = getenv("LAMP_BN_FUSED_BWD"); return !(e && e[0] == '0'); }();
+  const bool env_on = sw().bn_fused_bwd;
   const int mode = g_bn_bwd_mode.load(std::memory_order_relaxed);
   const bool on = mode < 0 ? env_on : mode >= 1;
   // a device that is also running kernels this library does not schedule (the overlapped RCCL all-reduce of the eager data-parallel
@@ -1348,7 +1349,7 @@ static bool bn_bwd_fused_launch(const Tensor* gc, const Tensor* xc, const Tensor
   if (packets <= 0 || packets >= (int64_t)1 << 30) return false;
   if (addc && !relu) return false;
   const int cus = num_cus();
-  static const int per_cu = [] { const char* e = getenv("LAMP_BN_FUSED_PER_CU"); return e ? std::max(1, atoi(e)) : 1; }();   // measured: 2 is slower
+  const int per_cu = (int)sw().bn_fused_per_cu;   // measured: 2 is slower
   auto per_thread = [&](int64_t s) { return (packets + s * 512 - 1) / (s * 512); };
   // the scalar-load form of a plane gradient: 8 x 8 maps, class-major values in whole 16-byte groups (a wave's 64 packets are eight whole planes), the
   // dual form (the only consumer of the loss tail's gradient in Cnn.resnet); anything else gets the materialised tensor from the caller
@@ -1366,11 +1367,11 @@ static bool bn_bwd_fused_launch(const Tensor* gc, const Tensor* xc, const Tensor
     // exchange between the workgroups (two memory round trips, ~3 us) costs what the second pass over an L2 / MALL-resident tensor
     // costs: the ResNet step's six small layers were 4 us SLOWER in total with it, the six large ones 50 us faster.
     // The dual form replaces FOUR kernels (two reductions, two applies) and two passes more: taken at every size.
-    static const int np_mask = [] { const char* e = getenv("LAMP_BN_FUSED_NP_MASK"); return e ? atoi(e) : 24; }();
+    const int np_mask = (int)sw().bn_fused_np_mask;
     // Activations of at most 4 MiB (the B <= 256 steps): both kernels of the two-pass form sit at the launch floor there, and one launch with an
     // exchange beats two (A/B: B = 256 0.5433 -> 0.5359 ms per step, B = 32 0.4671 -> 0.4545; the 4 MiB layer itself 0.5137 -> 0.5115); above
     // (B = 2048's small maps, 4 - 8 MB) it is even.
-    static const int64_t small_bytes = [] { const char* e = getenv("LAMP_BN_FUSED_SMALL_BYTES"); return e ? (int64_t)atoll(e) : ((int64_t)4 << 20) + 1; }();
+    const int64_t small_bytes = sw().bn_fused_small_bytes;
     if (!dualh && !(np_mask & NP) && !(xc->numel() * 2 < small_bytes)) continue;
 #define BN_FUSED_K(NPv) (dualh ? (planes ? (const void*)bn_bwd_fused_kernel<NPv, true, true, true, true> : (const void*)bn_bwd_fused_kernel<NPv, true, true, true>) \
                                : addc ? (const void*)bn_bwd_fused_kernel<NPv, true, true> \

@@ -1,5 +1,6 @@
 // Deferred weight-gradient work (see wgrad_reduce.h): parked eight-wave launches and the batched reduction of the partial sums.
 #include "wgrad_reduce.h"
+#include "../core/switches.h"
 #include <algorithm>
 #include <mutex>
 #include <thread>
@@ -157,7 +158,7 @@ void wgrad_park(const Wg8hProblem& p, hipStream_t st) {
 }
 
 bool wgrad_reduce_deferred() {
-  static const bool defer = [] { const char* e = getenv("LAMP_DEFER_WGRAD_REDUCE"); return !(e && e[0] == '0'); }();
+  const bool defer = sw().defer_wgrad_reduce;
   return defer;
 }
 void wgrad_reduce_enqueue(const WgradReduceArgs& a, lamp_tensor* partial, lamp_tensor* dw, hipStream_t st) {
