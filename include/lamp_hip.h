@@ -392,6 +392,32 @@ int lamp_baddbmm_out_transposed2(lamp_tensor* out, const lamp_tensor* self, cons
 int lamp_linear_bias(lamp_tensor** out, const lamp_tensor* x, const lamp_tensor* w, const lamp_tensor* bias_or_null);
 
 /* ------------------------------------------------------------------------------------------
+ * fused recurrent cells (optional: lamp-core runs without them; f32 / f64, GPU tensors)
+ * One time step of lamp.nn.{LSTM, GRU, RNN} behind the GEMMs.  `gates` is [B, nG * H] with the gates of one cell side by
+ * side (LSTM i | f | o | c, GRU r | z | h, RNN h) and already holds x_t.Wx + h_{t-1}.Wh + bias (GRU's h block: without the
+ * (r * h).Whh term until lamp_gru_gates_forward has produced r * h).  Every other tensor is [B, H]; all need unit column
+ * stride, any row pitch.  The activated gates replace the pre-activations in place: the backward kernels read them.
+ * ------------------------------------------------------------------------------------------ */
+/* LSTM.scala:67-74: three sigmoids, two tanh, three products, one add -> h_t, c_t */
+int lamp_lstm_cell_forward(lamp_tensor* gates, const lamp_tensor* c_prev, lamp_tensor* h_out, lamp_tensor* c_out);
+/* the backward closures of that chain: dgates [B, 4H] w.r.t. the pre-activations and dc_prev from dout + dh (h_t's two consumers)
+ * and dc (c_t's); absent derivatives are zeros.  dc_prev may be the tensor passed as dc. */
+int lamp_lstm_cell_backward(lamp_tensor* dgates, lamp_tensor* dc_prev, const lamp_tensor* gates, const lamp_tensor* c_prev, const lamp_tensor* c,
+                            const lamp_tensor* dout_or_null, const lamp_tensor* dh_or_null, const lamp_tensor* dc_or_null);
+/* GRU.scala:52-53 and the r * h of :54: r, z = sigmoid in place, rh_out = r * h_prev */
+int lamp_gru_gates_forward(lamp_tensor* gates, const lamp_tensor* h_prev, lamp_tensor* rh_out);
+/* GRU.scala:54-56: h^ = tanh in place, h_out = z * h_prev + (1 - z) * h^ */
+int lamp_gru_output_forward(lamp_tensor* gates, const lamp_tensor* h_prev, lamp_tensor* h_out);
+/* backward of lamp_gru_output_forward: the z and h blocks of dgates, dh_prev = (dout + dh) * z (may be the tensor passed as dh) */
+int lamp_gru_output_backward(lamp_tensor* dgates, lamp_tensor* dh_prev, const lamp_tensor* gates, const lamp_tensor* h_prev, const lamp_tensor* dout_or_null,
+                             const lamp_tensor* dh_or_null);
+/* backward of lamp_gru_gates_forward given drh = dgates_h . Whh^T: the r block of dgates, dh_prev += drh * r */
+int lamp_gru_gates_backward(lamp_tensor* dgates, lamp_tensor* dh_prev, const lamp_tensor* gates, const lamp_tensor* h_prev, const lamp_tensor* drh);
+/* RNN.scala:40: h_out = tanh(gates) ; backward: dgates = (dout + dh) * (1 - h^2) */
+int lamp_rnn_cell_forward(const lamp_tensor* gates, lamp_tensor* h_out);
+int lamp_rnn_cell_backward(lamp_tensor* dgates, const lamp_tensor* h, const lamp_tensor* dout_or_null, const lamp_tensor* dh_or_null);
+
+/* ------------------------------------------------------------------------------------------
  * convolution / pooling   (ATen.convolution, convolution_backward(output_mask[3]),
  * avg_pool2d(+_backward), max_pool2d_with_indices(+_backward): ops.scala:1547-1651,
  * 1721-1825).  NCHW / NCL contiguous, groups supported, transposed supported.

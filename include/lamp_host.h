@@ -95,6 +95,28 @@ int lamp_language_model_forward(lamp_module* m, lamp_var* tokens, const lamp_ten
                                 lamp_var** encoded, lamp_var** logits);
 int lamp_sequence_mask(lamp_var** out, const lamp_tensor* max_length, lamp_var* maskable, double fill);   /* MultiheadAttention.sequenceMask :667-749 */
 int lamp_masked_softmax(lamp_var** out, lamp_var* input, const lamp_tensor* max_length);                  /* MultiheadAttention.maskedSoftmax :751-762 */
+/* ---- recurrent family (lamp-core nn/RNN.scala, GRU.scala, LSTM.scala, SeqLinear.scala, StatefulSeq.scala).  Inputs [time, batch, in], outputs
+ * [time, batch, hidden].  State order = the reference's `state` (LSTM: Xi Xf Xo Hi Hf Ho Xc Hc bI bF bO bC; GRU: Xh Hh Xr Xz Hr Hz bR bZ bH;
+ * RNN: Xh Hh bH; SeqLinear: weight, bias).  The plain constructors are the factories (normal(0, sqrt(2 / (fanIn + fanOut))), zero [1, hidden]
+ * biases); the _from forms are the case classes' constructors over the caller's tensors in that order (biases [hidden] or [1, hidden]). */
+int lamp_module_rnn(lamp_module** out, int64_t in, int64_t hidden, int dtype, int device);
+int lamp_module_gru(lamp_module** out, int64_t in, int64_t hidden, int dtype, int device);
+int lamp_module_lstm(lamp_module** out, int64_t in, int64_t hidden, int dtype, int device);
+int lamp_module_seq_linear(lamp_module** out, int64_t in, int64_t outf, int dtype, int device);
+int lamp_module_rnn_from(lamp_module** out, const lamp_tensor* const* tensors, int n);
+int lamp_module_gru_from(lamp_module** out, const lamp_tensor* const* tensors, int n);
+int lamp_module_lstm_from(lamp_module** out, const lamp_tensor* const* tensors, int n);
+int lamp_module_seq_linear_from(lamp_module** out, const lamp_tensor* const* tensors, int n);
+/* statefulSequence(m1, ..., mn): stateless members (Embedding, Fun, SeqLinear) are lifted; the state is the members' states side by side */
+int lamp_module_stateful_sequence(lamp_module** out, lamp_module* const* mods, int n);
+/* number of Variables in a stateful module's state: LSTM 2 (h, c), GRU / RNN 1, a stateful sequence the sum over its members */
+int lamp_module_num_state_slots(lamp_module* m, int* out);
+/* StatefulModule.forward((x, state)): `state` holds nstate Variables (NULL entries, or nstate = 0: the reference's None - zeros); returns the
+ * output and the next state (state_out: capacity lamp_module_num_state_slots, +1 handles).  Gradients flow through the returned state. */
+int lamp_module_forward_stateful(lamp_module* m, lamp_var* x, lamp_var* const* state, int nstate, lamp_var** out, lamp_var** state_out);
+/* RNN / GRU / LSTM / SeqLinear as one node per sequence over the fused cell kernels (1, the default unless LAMP_RECURRENT_FUSED=0) or as the
+ * reference's fold over the time steps built from the plain operators (0).  Process-wide; returns the previous value in *previous_or_null. */
+int lamp_recurrent_fused(int on, int* previous_or_null);
 /* GenericModule[A, B].forward for a tuple / case-class A: its Variables and its plain tensors in the reference's order; a NULL tensor = None */
 int lamp_module_forward_multi(lamp_module* m, lamp_var* const* vars, int nvars, const lamp_tensor* const* tensors, int ntensors, lamp_var** out);
 int lamp_module_forward(lamp_module* m, lamp_var* x, lamp_var** out);
@@ -123,7 +145,8 @@ int lamp_optimizer_release(lamp_optimizer* o);
 int lamp_gradient_clipping_in_place(lamp_tensor* const* gradients, int n, double theta);
 
 /* ---- supervised model + training steps ---- */
-/* loss_kind 0: LossFunctions.NLL(numClasses, classWeights, reduction, ignore) ; 1: MSE ; 2: Identity */
+/* loss_kind 0: LossFunctions.NLL(numClasses, classWeights, reduction, ignore) ; 1: MSE ; 2: Identity ;
+ * 3: SequenceNLL(numClasses, classWeights, ignore) over outputs [time, batch, classes] and targets [time, batch] (LossFunctions.scala:76-108) */
 int lamp_model_create(lamp_model** out, lamp_module* module, int loss_kind, const lamp_tensor* class_weights_or_null, int64_t reduction,
                       int64_t ignore_index);
 /* SupervisedModel.addTotalLossAndReturnGradientsAndNumExamples (SupervisedModel.scala:190-211):

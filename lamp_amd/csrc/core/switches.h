@@ -35,6 +35,7 @@ constexpr int64_t SW_NO_CLAMP = INT64_MIN;
   X(linear_bias_fused, "LAMP_LINEAR_BIAS_FUSED", BOOL, 1, 0, "a linear layer's bias in the GEMM epilogue (0: mm then add)")               \
   X(mult_add_fused, "LAMP_MULT_ADD_FUSED", BOOL, 1, 0, "x * scale + residual in one pass (0: mult then add)")                             \
   X(attention_as_written_for_cuda, "LAMP_ATTENTION_AS_WRITTEN_FOR_CUDA", BOOL, 0, 0, "multi-head attention as the reference's op chain instead of the fused kernels") \
+  X(recurrent_fused, "LAMP_RECURRENT_FUSED", BOOL, 1, 0, "RNN / GRU / LSTM as one node per sequence with fused cell kernels (0: the fold over time steps)") \
   X(fuse_qkv, "LAMP_FUSE_QKV", BOOL, 1, 0, "self-attention's three projections as one product (0: three)")                                \
   X(host_stream_side, "LAMP_HOST_STREAM_SIDE", BOOL, 0, 0, "batch streams gather on a side stream instead of the consumer's")             \
   /* tensors and indexing (core/tensor.hip, kernels/index.hip) */                                                                         \

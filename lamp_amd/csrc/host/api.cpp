@@ -1,6 +1,7 @@
 // extern "C" surface of the host layer (include/lamp_host.h).
 #include "nn.h"
 #include "transformer.h"
+#include "recurrent.h"
 #include "../../../include/lamp_host.h"
 
 #include <cstring>
@@ -254,6 +255,73 @@ int lamp_sequence_mask(lamp_var** out, const lamp_tensor* max_length, lamp_var* 
 int lamp_masked_softmax(lamp_var** out, lamp_var* input, const lamp_tensor* max_length) {
   LAMP_API_BEGIN *out = wrap(MultiheadAttention::maskedSoftmax(input->v, borrow(max_length))); LAMP_API_END
 }
+// ---- recurrent family (RNN.scala, GRU.scala, LSTM.scala, SeqLinear.scala, StatefulSeq.scala) ------------------------------
+int lamp_module_rnn(lamp_module** out, int64_t in, int64_t hidden, int dtype, int device) {
+  LAMP_API_BEGIN *out = wrapm(Recurrent::make(Recurrent::kRNN, in, hidden, dtype, device)); LAMP_API_END
+}
+int lamp_module_gru(lamp_module** out, int64_t in, int64_t hidden, int dtype, int device) {
+  LAMP_API_BEGIN *out = wrapm(Recurrent::make(Recurrent::kGRU, in, hidden, dtype, device)); LAMP_API_END
+}
+int lamp_module_lstm(lamp_module** out, int64_t in, int64_t hidden, int dtype, int device) {
+  LAMP_API_BEGIN *out = wrapm(Recurrent::make(Recurrent::kLSTM, in, hidden, dtype, device)); LAMP_API_END
+}
+int lamp_module_seq_linear(lamp_module** out, int64_t in, int64_t outf, int dtype, int device) {
+  LAMP_API_BEGIN *out = wrapm(SeqLinear::make(in, outf, dtype, device)); LAMP_API_END
+}
+static std::vector<Var> params_of(const lamp_tensor* const* tensors, int n) {
+  std::vector<Var> w;
+  for (int i = 0; i < n; i++) { LAMP_CHECK(tensors[i], "NULL state tensor"); w.push_back(make_param(borrow(tensors[i]))); }
+  return w;
+}
+int lamp_module_rnn_from(lamp_module** out, const lamp_tensor* const* tensors, int n) {
+  LAMP_API_BEGIN *out = wrapm(std::make_shared<Recurrent>(Recurrent::kRNN, params_of(tensors, n))); LAMP_API_END
+}
+int lamp_module_gru_from(lamp_module** out, const lamp_tensor* const* tensors, int n) {
+  LAMP_API_BEGIN *out = wrapm(std::make_shared<Recurrent>(Recurrent::kGRU, params_of(tensors, n))); LAMP_API_END
+}
+int lamp_module_lstm_from(lamp_module** out, const lamp_tensor* const* tensors, int n) {
+  LAMP_API_BEGIN *out = wrapm(std::make_shared<Recurrent>(Recurrent::kLSTM, params_of(tensors, n))); LAMP_API_END
+}
+int lamp_module_seq_linear_from(lamp_module** out, const lamp_tensor* const* tensors, int n) {
+  LAMP_API_BEGIN
+  LAMP_CHECK(n == 2, "SeqLinear(weight, bias)");
+  auto w = params_of(tensors, n);
+  *out = wrapm(std::make_shared<SeqLinear>(w[0], w[1]));
+  LAMP_API_END
+}
+int lamp_module_stateful_sequence(lamp_module** out, lamp_module* const* mods, int n) {
+  LAMP_API_BEGIN
+  std::vector<Mod> ms;
+  for (int i = 0; i < n; i++) ms.push_back(mods[i]->m);
+  *out = wrapm(std::make_shared<StatefulSequence>(ms));
+  LAMP_API_END
+}
+int lamp_module_num_state_slots(lamp_module* m, int* out) {
+  LAMP_API_BEGIN
+  auto* s = dynamic_cast<StatefulModule*>(m->m.get());
+  LAMP_CHECK(s, "not a stateful module");
+  *out = s->slots();
+  LAMP_API_END
+}
+int lamp_module_forward_stateful(lamp_module* m, lamp_var* x, lamp_var* const* state, int nstate, lamp_var** out, lamp_var** state_out) {
+  LAMP_API_BEGIN
+  auto* s = dynamic_cast<StatefulModule*>(m->m.get());
+  LAMP_CHECK(s, "lamp_module_forward_stateful: not a stateful module");
+  LAMP_CHECK(nstate == 0 || nstate == s->slots(), "lamp_module_forward_stateful: " << nstate << " state Variables, the module has " << s->slots() << " slots");
+  std::vector<Var> st, so;
+  bool none = true;
+  for (int i = 0; i < nstate; i++) { st.push_back(state && state[i] ? state[i]->v : nullptr); if (st.back()) none = false; }
+  if (none) st.clear();
+  *out = wrap(s->forward_stateful(x->v, st, so));
+  if (state_out) for (size_t i = 0; i < so.size(); i++) state_out[i] = wrap(so[i]);
+  LAMP_API_END
+}
+int lamp_recurrent_fused(int on, int* previous) {
+  LAMP_API_BEGIN
+  const bool prev = F::set_recurrent_fused(on != 0);
+  if (previous) *previous = prev ? 1 : 0;
+  LAMP_API_END
+}
 int lamp_module_forward_multi(lamp_module* m, lamp_var* const* vars, int nvars, const lamp_tensor* const* tensors, int ntensors, lamp_var** out) {
   LAMP_API_BEGIN
   std::vector<Var> xs;
@@ -347,6 +415,7 @@ int lamp_model_create(lamp_model** out, lamp_module* module, int loss_kind, cons
   m->model.module = module->m;
   m->model.loss_kind = loss_kind;
   if (class_weights) m->model.classWeights = borrow(class_weights);
+  if (loss_kind == 3) LAMP_CHECK(class_weights, "LossFunctions.SequenceNLL takes class weights (LossFunctions.scala:76-80)");
   if (loss_kind == 0) LAMP_CHECK(class_weights, "LossFunctions.NLL always passes class weights (LossFunctions.scala:39-55)");
   m->model.reduction = reduction;
   m->model.ignore = ignore;

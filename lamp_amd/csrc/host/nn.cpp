@@ -1,5 +1,6 @@
 // lamp.nn over the C ABI - see nn.h for the reference map.
 #include "nn.h"
+#include "recurrent.h"
 #include "../core/switches.h"
 #include <thread>
 #include <unordered_map>
@@ -360,6 +361,12 @@ static void accumulate_loss(const Ten& acc, const Ten& loss, int64_t n) {
   if (acc.dtype() == loss.dtype()) ops::add_(acc, ops::reshape(loss, acc.shape()), (double)n);
   else HCALL(lamp_add_scaled_mixed_(acc.h(), loss.h(), (double)n));
 }
+// SequenceNLL: loss * n IS the sum-reduced loss the mean was divided from, a device value - adding that keeps the accumulator independent of
+// the host's copy of the count (which a captured evaluation cannot read)
+static void accumulate_sequence_or_loss(const Ten& acc, const Ten& total, const std::pair<Var, int64_t>& ln) {
+  if (total.defined()) accumulate_loss(acc, total, 1);
+  else accumulate_loss(acc, ln.first->value, ln.second);
+}
 static Var run_module(SupervisedModel& m, const Ten& samples, const Ten& target) {
   if (m.loss_kind == 2) return m.module->forward_multi({make_const(samples)}, {target});
   return m.module->forward(make_const(samples));
@@ -367,6 +374,7 @@ static Var run_module(SupervisedModel& m, const Ten& samples, const Ten& target)
 std::pair<Var, int64_t> SupervisedModel::loss(const Var& output, const Ten& target) {
   if (loss_kind == 0) return {F::nll_loss(output, target, classWeights, reduction, ignore), output->value.size(0)};
   if (loss_kind == 1) return {F::mse_loss(output, target, 1), output->value.size(0)};
+  if (loss_kind == 3) return F::sequence_nll(output, target, classWeights, ignore);
   return {output, target.size(0)};
 }
 // NLL on the device with an accumulator of the loss's dtype: `acc += n * loss` rides in the loss kernel (one launch less per step)
@@ -385,16 +393,18 @@ int64_t SupervisedModel::addTotalLossAndReturnGradientsAndNumExamples(const Ten&
     if (gradients) *gradients = g;
     return n;
   }
-  auto ln = loss(output, target);
+  Ten total;
+  auto ln = loss_kind == 3 ? F::sequence_nll(output, target, classWeights, ignore, &total) : loss(output, target);
   std::vector<Ten> g = module->gradients(ln.first, zeroGrad);
-  accumulate_loss(acc, ln.first->value, ln.second);
+  accumulate_sequence_or_loss(acc, total, ln);
   if (gradients) *gradients = g;
   return ln.second;
 }
 int64_t SupervisedModel::addTotalLossAndReturnNumExamples(const Ten& samples, const Ten& target, const Ten& acc) {
   Var output = run_module(*this, samples, target);
-  auto ln = loss(output, target);
-  accumulate_loss(acc, ln.first->value, ln.second);
+  Ten total;
+  auto ln = loss_kind == 3 ? F::sequence_nll(output, target, classWeights, ignore, &total) : loss(output, target);
+  accumulate_sequence_or_loss(acc, total, ln);
   return ln.second;
 }
 

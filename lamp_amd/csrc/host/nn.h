@@ -168,7 +168,7 @@ struct SGDW : Optimizer {       // nn/SGD.scala:19-99
 // ---- supervised model (nn/SupervisedModel.scala:151-211, LossFunctions.scala:39-55) -------------
 struct SupervisedModel {
   Mod module;
-  int loss_kind = 0;            // 0 NLL, 1 MSE, 2 identity
+  int loss_kind = 0;            // 0 NLL, 1 MSE, 2 identity, 3 SequenceNLL
   Ten classWeights; int64_t reduction = 1, ignore = -100;
   std::pair<Var, int64_t> loss(const Var& output, const Ten& target);
   // addTotalLossAndReturnGradientsAndNumExamples: acc += loss * n ; returns (n, gradients)
