@@ -91,7 +91,7 @@ constexpr int64_t SW_NO_CLAMP = INT64_MIN;
 
 // ---- read at EVERY call of sw_now(): a test flips these inside one process -----------------------------------------------------------
 #define LAMP_SWITCHES_PER_CALL(X)                                                                                                         \
-  X(ig_variant, "LAMP_IG_VARIANT", LETTER, 0, 0, "bf16 implicit GEMM kernel form: a plain, b two-image 128-row, d eight-image at any batch; unset: by geometry") \
+  X(ig_variant, "LAMP_IG_VARIANT", LETTER, 0, 0, "bf16 implicit GEMM kernel form: b two-image 128-row, d eight-image at any batch; unset or any other letter: by geometry") \
   X(ig_ktail, "LAMP_IG_KTAIL", BOOL, 1, 0, "a 3x3's 1 .. 8 channels beyond the last whole K chunk from their own packed image (0: the padded chunk)") \
   X(knn_split_dbg, "LAMP_KNN_SPLIT_DBG", INT, 0, SW_NO_CLAMP, "3: the k-NN filter's kernel counts visits, candidates and selection cycles per wave and prints them")
 

@@ -6,25 +6,32 @@
 // Scope of the fast path: bf16, NCHW, H = W = 8, kernel 3x3 (pad 1) or 1x1 (pad 0), stride 1,
 // dilation 1, groups 1, Cin <= 128, Cout <= 128.  Everything else stays on the direct kernels.
 //
-// fprop and dgrad share ONE kernel (dgrad = fprop of dy with the weights transposed and the taps
+// fprop and dgrad share their kernels (dgrad = fprop of dy with the weights transposed and the taps
 // mirrored):   Out[p][co] = sum_{r,s,ci} X[ci][p + (r,s) - pad] * Wp[rs][co][ci]
-//   M = pixels (256 = four images per workgroup), N = output channels (128, zero padded),
-//   K = taps * Cin; v_mfma_f32_16x16x32_bf16, fp32 accumulation; 8 waves, wave tile 64 px x 64 co.
-//   * the input images live in LDS channel-LAST ([10x10 padded pixel][ci]) so that a pixel fragment
-//     (8 consecutive ci of one shifted pixel) is one ds_read_b128; the NCHW -> channel-last
-//     transposition is an 8x8 register transpose per thread between coalesced 16-byte global loads
-//     and 16-byte LDS writes.
-//   * weights are pre-packed by a tiny kernel to [tap][co][ci] (ci contiguous) and streamed by LDS-DMA
-//     (global_load_lds_dwordx4) through a three-slot ring, one (tap, 64-channel chunk) per stage.
-//   * both LDS images are XOR-swizzled on 16-byte chunks so every fragment read is conflict-free
-//     (see the lane -> pixel permutation in px_of_col); the same permutation makes a lane's four
-//     accumulator rows four consecutive pixels, so the epilogue stores 8 bytes per lane.
-//   * the two waves of every SIMD run the READ and MFMA phases of a stage in ping-pong (raw s_barrier,
-//     counted vmcnt), see the main loop.
+//   M = pixels, N = output channels (128, zero padded), K = taps * Cin; v_mfma_f32_16x16x32_bf16, fp32 accumulation.
+// Common to every form: the input images live in LDS channel-LAST so that a pixel fragment (8 consecutive ci of one shifted
+// pixel) is one ds_read_b128 - the NCHW -> channel-last transposition is an 8x8 register transpose per thread between coalesced
+// 16-byte global loads and 16-byte LDS writes; the weights are pre-packed by a tiny kernel to [tap][co][ci] (ci contiguous) and
+// streamed by LDS-DMA (global_load_lds_dwordx4) through a ring of stages; both LDS images are XOR-swizzled on 16-byte chunks so
+// every fragment read is conflict-free (see the lane -> pixel permutation in px_of_col), and the same permutation makes a lane's
+// four accumulator rows four consecutive pixels.  ig_form chooses the form by geometry:
+//   * the eight-image form (ig_conv8d_kernel): large batches.  One workgroup per CU, eight images and eight waves, wave = one image
+//     x all output channels; weight stages of 128 rows x 32 k in a three-slot ring; the images as [32-channel chunk][image][pixel]
+//     rows of 64 bytes; READ and MFMA phases of the two waves of a SIMD in ping-pong (raw s_barrier, counted vmcnt); the output
+//     leaves through LDS as whole cache lines.  It folds a batch norm + relu into its staging, an addend into its stores, and takes
+//     a sibling 1x1 convolution or a second gradient source into the same launch.
+//   * the two-image form (ig_conv8b_kernel, ig_conv8c_kernel): small batches.  Two images (or one) per workgroup without halo - taps outside the
+//     image read a shared zero pixel -, several workgroups per CU.  With 128-row weight stages (8b: more than 64 output channels) four
+//     or eight waves own 64 / 32 / 16 output channels of one image each and two slots suffice (four with one image per workgroup);
+//     with 64-row stages (8c: at most 64 output channels) no wave multiplies zero rows, and four slots are requested three stages
+//     ahead behind a counted vmcnt.
 // wgrad is a plain NT GEMM per tap, dW[rs][co][ci] = sum_{n,p} dY[n][co][p] * Xshift_rs[n][ci][p]:
 //   the K dimension runs over pixels of many images; the tap shift is applied while staging X
 //   (row select + a 16-bit funnel shift inside the 16-byte row), partial sums of the image
 //   splits go to an fp32 workspace and a small kernel reduces them into dW[co][ci][r][s].
+//   * ig_wgrad8v2_kernel: four waves, workgroup = (32-channel slice of Cin, image range), all taps in registers - narrow layers and 1x1s;
+//   * ig_wgrad8h_kernel: eight waves, two per SIMD, the same decomposition - 3x3 layers with more than 32 input and 64 output
+//     channels; takes a sibling 1x1's weight gradient or a second layer into the same launch.
 #include <map>
 #include <mutex>
 #include <tuple>
@@ -142,199 +149,6 @@ __global__ void ig_ncv_pack_many_kernel(PackMany a, NcvPackMany b, int nig, int 
 
 // ---- fprop / dgrad -----------------------------------------------------------------------------------
 // x [N][CI][64], wp [RS][128][KP], y [N][CO][64].  KP = padded K per tap (32, 64 or 128).
-template <int KS, int NW>
-__global__ __launch_bounds__(NW * 128) void ig_conv8_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp, const bf16_t* __restrict__ bias,
-                                                            bf16_t* __restrict__ y, int N, int CI, int KP, int CO) {
-  // NW images per workgroup, 2 * NW waves: wave (wr, wc) owns output channels [64 wr, 64 wr + 64) of image wc.
-  // One weight stage feeds NW images, so a wider workgroup halves the L2 weight traffic and the barriers per MFMA.
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int RS = KS * KS;
-  constexpr int PAD = (KS - 1) / 2;
-  constexpr int NT = NW * 128;
-  constexpr int LPT = 1024 / NT;            // 16-byte weight chunks per thread and stage
-  const int RB = KP * 2;                    // bytes per pixel row of the channel-last image
-  const int XIMG = 100 * RB;                // one padded 10x10 image
-  char* Xl = smem;                          // [NW][100][KP]
-  char* Wl = smem + NW * XIMG;              // 3 x IG_WTILE (ring)
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);   // provably wave-uniform: guards raw s_barriers below
-  const int wr = wid / NW, wc = wid % NW;
-  const int n0 = blockIdx.x * NW;
-  const int cmask = (KP >> 3) - 1;
-
-  // halo pixels of the padded 10x10 images must read as 0 (a 1x1 kernel never leaves the interior)
-  if (KS > 1) {
-    const int cpp = RB >> 4;                                   // 16-byte chunks per pixel
-    for (int o = tid; o < NW * 36 * cpp; o += NT) {
-      const int ch = o % cpp, hidx = (o / cpp) % 36, img = o / (cpp * 36);
-      int hp, wpx;
-      if (hidx < 10) { hp = 0; wpx = hidx; }
-      else if (hidx < 20) { hp = 9; wpx = hidx - 10; }
-      else { hp = 1 + ((hidx - 20) >> 1); wpx = ((hidx - 20) & 1) * 9; }
-      *reinterpret_cast<uint4*>(Xl + img * XIMG + (hp * 10 + wpx) * RB + (ch << 4)) = make_uint4(0, 0, 0, 0);
-    }
-  }
-  // NCHW -> channel-last.  A thread takes 8 channels x one image row: eight coalesced 16-byte loads (8 pixels of one
-  // channel each), an 8x8 transposition of the 16-bit elements in registers, eight 16-byte LDS writes (8 channels of one
-  // pixel each).  Lanes run along the channel groups, so the 8 lanes of a ds_write_b128 group hit 8 different chunks.
-  {
-    const int ncgp = KP >> 3;
-    for (int e = tid; e < NW * 8 * ncgp; e += NT) {
-      const int cg = e % ncgp, h = (e / ncgp) & 7, img = e / (ncgp * 8);
-      const int n = n0 + img;
-      unsigned int w[8][4];
-#pragma unroll
-      for (int k = 0; k < 8; k++) {
-        const int c = cg * 8 + k;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (c < CI && n < N) v = *reinterpret_cast<const uint4*>(x + ((int64_t)n * CI + c) * 64 + h * 8);
-        w[k][0] = v.x; w[k][1] = v.y; w[k][2] = v.z; w[k][3] = v.w;
-      }
-      char* xi = Xl + img * XIMG;
-#pragma unroll
-      for (int p = 0; p < 8; p++) {
-        unsigned int d[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-          const unsigned int lo = w[2 * j][p >> 1], hi = w[2 * j + 1][p >> 1];
-          d[j] = (p & 1) ? ((lo >> 16) | (hi & 0xffff0000u)) : ((lo & 0xffffu) | (hi << 16));
-        }
-        const int hp = h + 1, wpx = p + 1;
-        *reinterpret_cast<uint4*>(xi + (hp * 10 + wpx) * RB + ((cg ^ x_swz(hp, wpx, cmask)) << 4)) = make_uint4(d[0], d[1], d[2], d[3]);
-      }
-    }
-  }
-
-  f4v acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; i++)
-#pragma unroll
-    for (int j = 0; j < 4; j++) acc[i][j] = f4v{0.f, 0.f, 0.f, 0.f};
-
-  constexpr int KW = 64;                    // k per stage (KP is 64 or 128)
-  const int CC = KP / KW;                   // chunks per tap
-  const int T = RS * CC;
-  // Weight stages arrive by LDS-DMA (global_load_lds_dwordx4: no staging registers, no ds_write) into a ring of THREE
-  // slots, two stages ahead of their use.  The DMA destination is lane-linear (wave base + lane * 16), so the XOR swizzle
-  // of the tile is applied to the per-lane SOURCE address; ig_kc_off() applies the same involution on the read side.
-  typedef __attribute__((address_space(3))) char lds_char_t;
-  typedef const __attribute__((address_space(1))) char glb_char_t;
-  auto stage_dma = [&](int t, int slot) {
-    const int rs1 = t / CC, cc1 = t - rs1 * CC;
-    const bf16_t* base = wp + (int64_t)rs1 * IG_M * KP + cc1 * KW;
-#pragma unroll
-    for (int i = 0; i < LPT; i++) {
-      const int piece = wid * LPT + i;                 // 1 KiB piece of the 16 KiB slot written by this wave-instruction
-      const int p = piece * 64 + lane;                 // 16-byte position inside the slot
-      const int row = p >> 3, chunk = (p & 7) ^ (row & 7);
-      __builtin_amdgcn_global_load_lds((glb_char_t*)(base + row * KP + chunk * 8), (lds_char_t*)(Wl + slot * IG_WTILE + piece * 1024), 16, 0, 0);
-    }
-  };
-  stage_dma(0, 0);
-  if (T > 1) stage_dma(1, 1);
-
-  // B-fragment addresses.  For tap (r, s) and n-tile j a lane reads pixel (2j + rowsel + r, wpix + s) of image wc, chunk
-  // (k-chunk ^ swizzle).  k-chunk = uniform part (cc, ks: bits 2..) ^ lane part (lane >> 4: bits 0..1), and XOR is
-  // bitwise, so everything except the uniform part is folded into ONE precomputed byte offset per (tap, j); the hot loop
-  // then needs a single v_xor per ds_read instead of ~10 integer instructions.
-  int rowsel, wpix;
-  px_of_col(lane & 15, rowsel, wpix);
-  int pre[RS][4];
-#pragma unroll
-  for (int rs = 0; rs < RS; rs++) {
-    const int r = rs / KS, s = rs - r * KS;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      const int hp = 2 * j + rowsel + r + (1 - PAD), wpx = wpix + s + (1 - PAD);
-      pre[rs][j] = wc * XIMG + (hp * 10 + wpx) * RB + ((((lane >> 4) & cmask) ^ x_swz(hp, wpx, cmask)) << 4);
-    }
-  }
-  // A-fragment (weight tile) addresses: row = wr*64 + i*16 + (lane & 15), chunk = (ks*4 + (lane >> 4)) ^ (row & 7)
-  const int a_row = (wr * 64 + (lane & 15)) * 128;
-  const int a_ch0 = ((lane >> 4) ^ (lane & 7)) << 4, a_ch1 = ((4 + (lane >> 4)) ^ (lane & 7)) << 4;
-
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();                      // image tiles and weight stages 0, 1 are in LDS
-
-  // Two-phase ping-pong.  A stage is a READ phase (16 ds_read_b128: both k-steps' fragments, plus the DMA of stage t+2)
-  // and an MFMA phase (32 MFMAs), each closed by a raw s_barrier.  The waves with wr == 1 - the second wave of every
-  // SIMD - run one phase behind the waves with wr == 0, so while one wave of a SIMD feeds the matrix core the other one
-  // reads LDS.  Ordering of the DMA ring (slot = stage % 3):
-  //   * DMA(t+2) is issued in READ(t); its slot was last read in READ(t-1), and every read is retired (lgkmcnt(0))
-  //     before the barrier that closes its phase;
-  //   * each wave retires its own DMA(t+1) with a counted vmcnt before the barrier closing READ(t) (DMA(t+2) stays in
-  //     flight), which for both groups is passed before anyone starts READ(t+1).
-  bf8v fa0[4], fb0[4], fa1[4], fb1[4];
-  if (wr == 1) __builtin_amdgcn_s_barrier();          // measured in one process: 8 % faster than no stagger, 13 % than odd/even
-  int t = 0, slot = 0;                               // slot = t % 3
-#pragma unroll
-  for (int rs = 0; rs < RS; rs++) {
-    for (int cc = 0; cc < CC; cc++, t++) {
-      const char* wl = Wl + slot * IG_WTILE + a_row;
-      const int slot1 = slot == 2 ? 0 : slot + 1, slot2 = slot1 == 2 ? 0 : slot1 + 1;
-      // ---- READ(t)
-      if (t + 2 < T) stage_dma(t + 2, slot2);
-      const int u = ((cc * (KW >> 3)) & cmask) << 4;
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        fa0[i] = __builtin_bit_cast(bf8v, *reinterpret_cast<const s8v*>(wl + i * 16 * 128 + a_ch0));
-        fa1[i] = __builtin_bit_cast(bf8v, *reinterpret_cast<const s8v*>(wl + i * 16 * 128 + a_ch1));
-      }
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        fb0[j] = __builtin_bit_cast(bf8v, *reinterpret_cast<const s8v*>(Xl + (pre[rs][j] ^ u)));
-        fb1[j] = __builtin_bit_cast(bf8v, *reinterpret_cast<const s8v*>(Xl + (pre[rs][j] ^ u ^ (4 << 4))));
-      }
-      if (t + 2 < T) {
-        if (LPT == 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-      } else {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      }
-      __builtin_amdgcn_s_barrier();
-      // ---- MFMA(t)
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb0[j], fa0[i], acc[i][j], 0, 0, 0);
-#pragma unroll
-      for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb1[j], fa1[i], acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-      __builtin_amdgcn_s_barrier();
-      slot = slot1;
-    }
-  }
-  if (wr == 0) __builtin_amdgcn_s_barrier();
-
-  // epilogue.  The pixels are the A operand, so D rows = pixels and D cols = output channels: a lane holds, per (i, j),
-  // output channel i*16 + (lane & 15) and the four MFMA rows 4q..4q+3 (q = lane >> 4), which px_of_col maps to four
-  // CONSECUTIVE pixels of one image row -> one 8-byte store.
-  const int n = n0 + wc;
-  if (n < N) {
-    bf16_t* yp = y + (int64_t)n * CO * 64;
-    const int q = lane >> 4;
-    const int qrow = (q == 1 || q == 2) ? 1 : 0, qw = (q >= 2) ? 4 : 0;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const int co = wr * 64 + i * 16 + (lane & 15);
-      if (co < CO) {
-        const float b = bias ? (float)bias[co] : 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-          const bf16_t o0(acc[i][j][0] + b), o1(acc[i][j][1] + b), o2(acc[i][j][2] + b), o3(acc[i][j][3] + b);
-          uint2 pk;
-          pk.x = (unsigned)o0.bits | ((unsigned)o1.bits << 16);
-          pk.y = (unsigned)o2.bits | ((unsigned)o3.bits << 16);
-          *reinterpret_cast<uint2*>(yp + co * 64 + (2 * j + qrow) * 8 + qw) = pk;
-        }
-      }
-    }
-  }
-}
-
 // Welford triple (count, mean, M2) of the 16 output values a lane holds for one output channel, merged over the four lanes that share
 // the channel (xor 16, 32): the statistics of the wave's 64 pixels of that channel, from the bf16-ROUNDED values the batch norm reads.
 __device__ __forceinline__ void ig_stats_merge(float& n, float& mean, float& m2, float n2, float mean2, float m22) {
@@ -364,12 +178,21 @@ __device__ __forceinline__ void ig_stats_wave(const float (&v)[16], float& n, fl
 // wtail (round 6, ig_conv8d_kernel only; not a sibling's): the K-tail image of the launch's OWN filter (ig_pack_body), or null
 struct IgSibling { const bf16_t* wp; const bf16_t* bias; bf16_t* y; float* stats; const bf16_t* x2; const bf16_t* wtail; };
 
-// DEFAULT variant, TWO co-resident workgroups per CU (LAMP_IG_VARIANT=a selects the 4-image kernel above): two images and four waves per
-// workgroup, the images WITHOUT halo (taps outside the image read a shared zero pixel), two weight slots: 32 + 0.25 + 32 KiB of
-// LDS.  The two workgroups of a CU are independent, so the prologue / epilogue of one overlaps the main loop of the other and
-// their READ / MFMA phases interleave without an explicit stagger.
-// NWV = 4: waves = 2 images x 2 halves of 64 output channels (two such workgroups per CU at large batches).  NWV = 8 (round 5, batches of at
-// most 2 x CUs images, where a CU holds ONE workgroup and the kernel is the latency chain of one wave: 18 stages x 32 dependent MFMAs behind
+// The two-image form, several co-resident workgroups per CU: two images per workgroup, the images WITHOUT halo (taps outside the
+// image read a shared zero pixel).  The workgroups of a CU are independent, so the prologue / epilogue of one overlaps the main loop
+// of the other and their READ / MFMA phases interleave without an explicit stagger.
+// A weight stage is 128 rows x 64 k (16 KiB), two weight slots: 32 + 0.25 + 32 KiB of LDS, two workgroups per CU (ig_conv8c_kernel below:
+// the same with 64-row stages).
+// Weight stages arrive by LDS-DMA (global_load_lds_dwordx4: no staging registers, no ds_write).  The DMA destination is lane-linear
+// (wave base + lane * 16), so the XOR swizzle of the tile (16-byte chunk c of row r at c ^ (r & 7)) is applied to the per-lane SOURCE
+// address and again on the read side.  Ring discipline (slot = stage % NSLOT): stage g + NSLOT - 1 is requested at the top of stage g
+// into the slot read in stage g - 1, whose reads every wave retired (lgkmcnt(0)) before the barrier that closed that stage; each wave
+// retires its own pieces of stage g + 1 with a (counted) vmcnt before the barrier closing stage g, which everyone passes before
+// reading stage g + 1.
+// Pixel-fragment addresses: for tap (r, s) and n-tile j a lane reads pixel (2j + rowsel + r, wpix + s) of image wc, chunk (k-chunk ^
+// swizzle).  k-chunk = uniform part ^ lane part and XOR is bitwise, so everything except the uniform part is folded into ONE
+// precomputed byte offset per (tap, j): the hot loop needs a single v_xor per ds_read.
+// NWV = 4: waves = 2 images x 2 halves of 64 output channels (two such workgroups per CU at large batches).  NWV = 8 (round 5, batches of at most 2 x CUs images, where a CU holds ONE workgroup and the kernel is the latency chain of one wave: 18 stages x 32 dependent MFMAs behind
 // 16 fragment reads each - 17 us per 128-channel 3x3 launch at B = 32 ... 256 whatever the batch): 2 images x 4 quarters of 32 channels,
 // half the MFMAs and 12 instead of 16 fragment reads per wave and stage.
 // SIBM (round 5, the small-batch forms of ig_conv8d_kernel's): 1 = a sibling 1x1 convolution of the same input (fprop) runs first on the staged
@@ -852,7 +675,7 @@ __device__ __forceinline__ uint4 ig_bn_relu_x8(uint4 v, float mu, float scale, f
 //    stores 4k.  Tried and dropped: fetching chunk kc + 1 of the wave's own image during chunk kc (two 32-channel chunks in LDS,
 //    four-slot ring, the loads queued behind the ring's requests so the in-order vmcnt waits leave them three stages to land): the
 //    prologue fell to 4.7k but every round stalled the barrier-coupled waves on HBM latency - main loop 54.7k, 71k in total vs 65k.
-//  * READ / MFMA phases in ping-pong between the two waves of a SIMD (waves 4-7 one phase behind), as in ig_conv8_kernel.
+//  * READ / MFMA phases in ping-pong between the two waves of a SIMD (waves 4-7 one phase behind): see the main loop.
 //  * Epilogue: the accumulators go through the (now free) LDS as [channel][64 pixels] rows and leave as 16-byte stores, eight lanes
 //    per 128-byte row: full cache lines instead of 8-byte pieces (ig_conv8b writes 1.5x its algorithmic bytes to HBM).
 #ifdef IG8D_STAMP
@@ -1079,7 +902,9 @@ __global__ __launch_bounds__(512) void ig_conv8d_kernel(const bf16_t* __restrict
   }
   IG_STAMP(2);
 
-  // Two-phase ping-pong, ring discipline as in ig_conv8_kernel: DMA(t+2) is issued in READ(t) into the slot last read in READ(t-1)
+  // Two-phase ping-pong.  A stage is a READ phase (the fragments' ds_reads, plus the DMA of stage t+2) and an MFMA phase, each closed by a raw
+  // s_barrier; the second wave of every SIMD runs one phase behind the first, so while one feeds the matrix core the other reads LDS.
+  // Ring discipline (slot = stage % 3): DMA(t+2) is issued in READ(t) into the slot last read in READ(t-1)
   // (every read is retired before the barrier closing its phase); each wave retires its own piece of DMA(t+1) before the barrier
   // closing READ(t), which both groups pass before anyone starts READ(t+1).
   bf8v fa[NCT], fb[4];
@@ -2319,44 +2144,112 @@ void igemm_repack_cached(lamp_tensor* const* params, int n, hipStream_t st) {
   }
 }
 
-// The kernel form run_conv8 launches for a geometry - asked here by run_conv8 itself and by everyone who has to know beforehand what it will do:
-//   IgForm::Plain   ig_conv8_kernel:  LAMP_IG_VARIANT=a only
+// The kernel form a geometry takes:
 //   IgForm::Eight   ig_conv8d_kernel: eight images per workgroup, one workgroup per CU, wave = image x all channels - more than 64 output channels
 //                   (narrow outputs too unless LAMP_IG_SMALL_D=0: NCT = 1 / 4 channel tiles per wave - the 16-channel layers of the ResNet, 128 -> 16
 //                   dgrad and 16 -> 16, spent 16 - 30 us in the 64-row kernel multiplying padding; here they are bound by their image reads) and
 //                   enough images to give every CU a workgroup of eight (LAMP_IG_VARIANT=d: at any batch, =b: never)
 //   IgForm::Two64   ig_conv8c_kernel: two images, 64-row weight stages, four-slot ring - at most 64 output channels (not under =b)
 //   IgForm::Two128  ig_conv8b_kernel: two images (or one), 128-row weight stages - the rest
-// Two co-resident workgroups per CU (every form but Plain) are the default: A/B on one device, 7 % faster per launch.
-enum class IgForm { Plain, Eight, Two64, Two128 };
+// Any other letter in LAMP_IG_VARIANT leaves the choice to the geometry.  Two co-resident workgroups per CU are the default of the two-image
+// forms: A/B on one device, 7 % faster per launch than four images per workgroup.
+enum class IgForm { Eight, Two64, Two128 };
 static IgForm ig_form(const ConvGeom& g, bool dgrad) {
   const char variant = sw_now().ig_variant;                        // (read per call: the A/B test flips it)
-  if (variant == 'a') return IgForm::Plain;
   const int64_t CO = dgrad ? g.Cin : g.Cout;
   if ((CO > 64 || sw().ig_small_d) && variant != 'b' && (variant == 'd' || g.N >= 4 * (int64_t)num_cus())) return IgForm::Eight;
   return (CO <= 64 && variant != 'b') ? IgForm::Two64 : IgForm::Two128;
 }
 
-// addend (dgrad, optional): out = round(round(conv) + addend) where the kernel chosen can do it in its epilogue; *addend_fused says whether it did
-// affine (fprop, optional): f32 [Cin][4] = (mean, invstd * weight, bias, -) of the batch norm + relu that stands between the producer of
-// `in` and this convolution; applied while staging where the kernel chosen can do it - *affine_used says whether it did (else the caller
-// materialises relu(bn(in)) and calls again without it)
-// sibling (fprop of a 3x3, optional): a 1x1 convolution of the same input with the same number of output channels, computed by the same launch
-// where the eight-image kernel runs - *sibling_fused says whether it did (else the caller runs it as its own convolution)
+// What a caller may ask a launch to fold in beside the convolution itself (all optional):
+//   addend  (dgrad): out = round(round(conv) + addend), added in the epilogue
+//   affine  (fprop): f32 [Cin][4] = (mean, invstd * weight, bias, -) of the batch norm + relu that stands between the producer of `in` and
+//           this convolution, applied while staging
+//   sibling (fprop of a 3x3): a 1x1 convolution of the same input with the same number of output channels - the two branches of lamp's
+//           residual block, cnn.scala:16-20 - as a second product of the launch, into its own tensor
+//   second  (dgrad of a 3x3): the output gradient and the filter of such a sibling 1x1; its input gradient is accumulated by the same launch
+//           (one rounding for the sum)
 struct SiblingConv { const Tensor* w; const Tensor* bias; Tensor* out; const ConvGeom* g; };
-// second (dgrad of a 3x3, optional): the output gradient and the filter of a sibling 1x1 convolution of the same input; its input gradient is
-// accumulated by the same launch (ig_conv8d_kernel<3, ., 2>) - *second_fused says whether it was (igemm_conv_dgrad_pair checks the
-// conditions first, so that nothing is launched otherwise)
 struct SecondGradConv { const Tensor* dy; const Tensor* w; const ConvGeom* g; };
+struct IgRequest {
+  const Tensor* addend = nullptr;
+  const Tensor* affine = nullptr;
+  const SiblingConv* sibling = nullptr;
+  const SecondGradConv* second = nullptr;
+};
+// What run_conv8 launches for (geometry, direction, request): THE place where "which form folds what" is written.  A caller that must launch
+// nothing unless its extra is folded asks here first and hands the same plan to run_conv8.
+struct IgPlan {
+  IgForm form;
+  bool folds_addend, folds_affine;   // the form adds an addend in its stores / applies a batch-norm table while staging, when the request has one
+  bool sibling, second;              // the request's sibling / second gradient runs in this launch
+  bool stats, per_wg;                // fprop hands per-image statistics of its output to the batch norm that follows; merged per workgroup
+  bool w8, one;                      // Two128: eight waves per image pair; one image per workgroup
+  int blocks;
+  size_t lds;
+};
+static IgPlan ig_plan(const ConvGeom& g, bool dgrad, const IgRequest& rq) {
+  IgPlan p{};
+  p.form = ig_form(g, dgrad);
+  const int KS = g.kh, CI = (int)(dgrad ? g.Cout : g.Cin), KP = pad_k(CI);
+  const bool eight = p.form == IgForm::Eight;
+  // a second product: the 1x1 beside a 3x3, same channels and batch
+  auto beside = [&](const ConvGeom* o) { return KS == 3 && o->kh == 1 && o->Cout == g.Cout && o->Cin == g.Cin && o->N == g.N; };
+  p.folds_addend = eight || dgrad;
+  p.folds_affine = eight;
+  // (the 64-row form has no forward sibling; a sibling's epilogue takes no addend)
+  p.sibling = sw().conv_sibling && rq.sibling && !dgrad && !rq.addend && p.form != IgForm::Two64 && beside(rq.sibling->g);
+  p.second = sw().conv_dgrad_pair && rq.second && dgrad && beside(rq.second->g);
+  // fprop: per-image batch-norm statistics of the output from the epilogue (LAMP_CONV_BN_STATS=0 turns the hand-off off)
+  p.stats = sw().conv_bn_stats && !dgrad && g.N >= 2;
+  const int pairs = (int)((g.N + 1) / 2);
+  if (eight) {
+    p.blocks = (int)((g.N + 7) / 8);
+    p.per_wg = p.stats && g.N % 8 == 0;
+    // 3 weight slots + the 32-channel image chunks (+ 9 spare pixels behind them for the taps of a 3x3 kernel) - and at least the
+    // 8 x 16 KiB the epilogue stages the output through
+    // (+ 8 KiB behind the epilogue's staging area: the eight images' statistics of every channel, merged per workgroup)
+    p.lds = std::max<size_t>((size_t)3 * (128 * 32 * 2) + (size_t)((CI + 31) / 32) * 8 * 4096 + (KS == 3 ? 9 * 64 : 0), (size_t)8 * 16384 + 8 * 128 * 8);
+  } else if (p.form == IgForm::Two64) {
+    p.blocks = pairs;
+    p.lds = (size_t)2 * 64 * KP * 2 + KP * 2 + 4 * (64 * 64 * 2);
+  } else {
+    // at most one workgroup per CU (small batches): eight waves per image pair (LAMP_IG_W8=0: always four); at most one IMAGE per CU: one
+    // image per workgroup (LAMP_IG_ONE_IMAGE=0: pairs)
+    p.w8 = sw().ig_w8 && pairs <= num_cus();
+    p.one = sw().ig_one_image && p.w8 && g.N <= num_cus();
+    p.blocks = p.one ? (int)g.N : pairs;
+    p.lds = (size_t)(p.one ? 1 : 2) * 64 * KP * 2 + KP * 2 + (p.one ? 4 : 2) * IG_WTILE;
+  }
+  return p;
+}
+
+// publishes a statistics table (if one was allocated) when the launch that fills it has been enqueued
+struct StatsPublish { Hold& t; const Tensor* y; int P; ~StatsPublish() { if (t.get()) conv_stats_publish(y, t.get(), P); } };
+
+// The second product of a planned launch as the kernels take it: the forward sibling's packed filter, bias, output and - when the launch hands
+// statistics on (stat_elems) - a table of its own in *statt; or the second gradient's transposed filter and its output gradient as the images
+static IgSibling ig_second_product(const IgRequest& rq, const IgPlan& pl, int64_t stat_elems, hipStream_t st, Hold* wpk, Hold* statt) {
+  IgSibling s{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (!pl.sibling && !pl.second) return s;
+  int64_t dgrad_off = 0;
+  *wpk = Hold(pl.second ? packed_weights(rq.second->w, *rq.second->g, 1, st, &dgrad_off) : packed_weights(rq.sibling->w, *rq.sibling->g, 1, st, &dgrad_off));
+  s.wp = static_cast<const Tensor*>(wpk->get())->ptr<bf16_t>() + (pl.second ? dgrad_off : 0);
+  if (pl.second) { s.x2 = rq.second->dy->ptr<bf16_t>(); return s; }
+  s.bias = rq.sibling->bias ? rq.sibling->bias->ptr<bf16_t>() : (const bf16_t*)nullptr;
+  s.y = rq.sibling->out->ptr<bf16_t>();
+  if (stat_elems) {
+    int64_t ps[1] = {stat_elems};
+    *statt = Hold(new_tensor(ps, 1, kF32, rq.sibling->out->device()));
+    s.stats = (*statt)->ptr<float>();
+  }
+  return s;
+}
+
+// launches pl = ig_plan(g, dgrad, rq): extras of the request that the plan does not fold are NOT computed (the caller has read the plan)
 static void run_conv8(const Tensor* in, const Tensor* w, const Tensor* bias, Tensor* out, const ConvGeom& g, bool dgrad, hipStream_t st,
-                      const Tensor* addend = nullptr, bool* addend_fused = nullptr, const Tensor* affine = nullptr, bool* affine_used = nullptr,
-                      const SiblingConv* sibling = nullptr, bool* sibling_fused = nullptr, const SecondGradConv* second = nullptr,
-                      bool* second_fused = nullptr) {
-  if (addend_fused) *addend_fused = false;
-  if (affine_used) *affine_used = false;
-  if (sibling_fused) *sibling_fused = false;
-  if (second_fused) *second_fused = false;
-  const int KS = g.kh, RS = KS * KS;
+                      const IgRequest& rq, const IgPlan& pl) {
+  const int KS = g.kh;
   const int CI = (int)(dgrad ? g.Cout : g.Cin), CO = (int)(dgrad ? g.Cin : g.Cout);
   const int KP = pad_k(CI);
   int64_t dgrad_off = 0;
@@ -2365,217 +2258,110 @@ static void run_conv8(const Tensor* in, const Tensor* w, const Tensor* bias, Ten
   const bf16_t* wpp = static_cast<const Tensor*>(wpk.get())->ptr<bf16_t>() + (dgrad ? dgrad_off : 0);
   // the K-tail image of this direction (1 .. 8 channels beyond the last whole chunk of a 3x3's K side): LAMP_IG_KTAIL=0 multiplies the padded chunk
   const bool ktail_on = sw_now().ig_ktail;      // (read per call: the A/B test flips it)
-  const IgForm form = ig_form(g, dgrad);
   const bf16_t* wtailp = (ktail_on && tail_off[dgrad ? 1 : 0] >= 0) ? static_cast<const Tensor*>(wpk.get())->ptr<bf16_t>() + tail_off[dgrad ? 1 : 0] : (const bf16_t*)nullptr;
-  {
-    if (form != IgForm::Plain) {
-      const int blocksb = (int)((g.N + 1) / 2);
-      // fprop: per-image batch-norm statistics of the output from the epilogue (LAMP_CONV_BN_STATS=0 turns the hand-off off)
-      const bool bn_stats = sw().conv_bn_stats;
-      Hold statt;
-      float* statp = nullptr;
-      if (bn_stats && !dgrad && g.N >= 2) {
-        int64_t ps[1] = {(int64_t)g.N * CO * 3};
-        statt = Hold(new_tensor(ps, 1, kF32, in->device()));
-        statp = statt->ptr<float>();
-      }
-      struct Publish { Hold& t; const Tensor* y; int P; ~Publish() { if (t.get()) conv_stats_publish(y, t.get(), P); } } publish{statt, out, (int)g.N};
-      // (a sibling, when given, always runs in this launch - igemm_conv_fwd_pair checks the eight-image kernel's conditions first: its work
-      // is declared with the launch; its input is the one already counted)
-      const double sib_fl = sibling ? conv_flops(*sibling->g) : second ? conv_flops(*second->g) : 0.0;
-      const double sib_by = sibling ? conv_bytes(*sibling->g, 2) - (double)g.N * g.Cin * 64 * 2
-                                    : second ? conv_bytes(*second->g, 2) - (double)g.N * g.Cin * 64 * 2 : 0.0;   // (one output for both)
-      KernelTimer kt("conv_igemm_fprop_dgrad", conv_flops(g) + sib_fl, conv_bytes(g, 2) + sib_by, st);
-      const bf16_t* bpb = bias ? bias->ptr<bf16_t>() : (const bf16_t*)nullptr;
-      if (form == IgForm::Eight) {
-        const int blocksd = (int)((g.N + 7) / 8);
-        // 3 weight slots + the 32-channel image chunks (+ 9 spare pixels behind them for the taps of a 3x3 kernel) - and at least the
-        // 8 x 16 KiB the epilogue stages the output through
-        // (+ 8 KiB behind the epilogue's staging area: the eight images' statistics of every channel, merged per workgroup)
-        const size_t ldsd = std::max<size_t>((size_t)3 * (128 * 32 * 2) + (size_t)((CI + 31) / 32) * 8 * 4096 + (KS == 3 ? 9 * 64 : 0), (size_t)8 * 16384 + 8 * 128 * 8);
-        const int per_wg = (statp && g.N % 8 == 0) ? 1 : 0;
-        if (per_wg) publish.P = blocksd;
-#define IG_LAUNCH_D(KS_, NCT_, SIB_)                                                                                                        \
-  do {                                                                                                                                      \
-    allow_big_lds((const void*)ig_conv8d_kernel<KS_, NCT_, SIB_>);                                                                         \
-    hipLaunchKernelGGL((ig_conv8d_kernel<KS_, NCT_, SIB_>), dim3(blocksd), dim3(512), ldsd, st, in->ptr<bf16_t>(), wpp, bpb,               \
-                       out->ptr<bf16_t>(), (int)g.N, CI, KP, CO, statp, per_wg, addp, affp, sibk);                                         \
-  } while (0)
-        const bf16_t* addp = addend ? addend->ptr<bf16_t>() : (const bf16_t*)nullptr;
-        const float4* affp = affine ? reinterpret_cast<const float4*>(affine->ptr<float>()) : (const float4*)nullptr;
-        if (affine_used) *affine_used = affine != nullptr;
-        if (addend_fused) *addend_fused = addend != nullptr;
-        // the sibling 1x1 of a residual block's first 3x3 (same input, same output channels): second product of this launch
-        IgSibling sibk{nullptr, nullptr, nullptr, nullptr, nullptr};
-        Hold sib_wpk, sib_statt;
-        const bool sib = sw().conv_sibling && sibling && !dgrad && KS == 3 && !addend && sibling->g->kh == 1 && sibling->g->Cout == g.Cout &&
-                         sibling->g->Cin == g.Cin && sibling->g->N == g.N;
-        struct PublishSib { Hold& t; const Tensor* y; int P; ~PublishSib() { if (t.get()) conv_stats_publish(y, t.get(), P); } }
-            publish_sib{sib_statt, sib ? sibling->out : nullptr, per_wg ? blocksd : (int)g.N};
-        if (sib) {
-          int64_t off1 = 0;
-          sib_wpk = Hold(packed_weights(sibling->w, *sibling->g, 1, st, &off1));
-          sibk.wp = static_cast<const Tensor*>(sib_wpk.get())->ptr<bf16_t>();
-          sibk.bias = sibling->bias ? sibling->bias->ptr<bf16_t>() : (const bf16_t*)nullptr;
-          sibk.y = sibling->out->ptr<bf16_t>();
-          if (statp) {
-            int64_t ps[1] = {(int64_t)g.N * CO * 3};
-            sib_statt = Hold(new_tensor(ps, 1, kF32, in->device()));
-            sibk.stats = sib_statt->ptr<float>();
-          }
-          if (sibling_fused) *sibling_fused = true;
-        }
-        // dgrad: the input gradient of the sibling 1x1 accumulated by this launch (its output gradient is a second source of images)
-        const bool dg2 = second && dgrad && KS == 3 && second->g->kh == 1 && second->g->Cout == g.Cout && second->g->Cin == g.Cin && second->g->N == g.N;
-        if (dg2) {
-          int64_t off1 = 0;
-          sib_wpk = Hold(packed_weights(second->w, *second->g, 1, st, &off1));
-          sibk.wp = static_cast<const Tensor*>(sib_wpk.get())->ptr<bf16_t>() + off1;
-          sibk.x2 = second->dy->ptr<bf16_t>();
-          if (second_fused) *second_fused = true;
-        }
-        if (KS == 3 && CO > 16 && !sib) sibk.wtail = wtailp;        // (not in the whole-tap stages of the one-tile form, not beside a forward sibling)
-        if (dg2) { if (CO <= 16) IG_LAUNCH_D(3, 1, 2); else if (CO <= 64) IG_LAUNCH_D(3, 4, 2); else if (CO <= 112) IG_LAUNCH_D(3, 7, 2); else IG_LAUNCH_D(3, 8, 2); }
-        else if (sib) { if (CO <= 16) IG_LAUNCH_D(3, 1, true); else if (CO <= 64) IG_LAUNCH_D(3, 4, true); else if (CO <= 112) IG_LAUNCH_D(3, 7, true); else IG_LAUNCH_D(3, 8, true); }
-        else if (KS == 3) { if (CO <= 16) IG_LAUNCH_D(3, 1, false); else if (CO <= 64) IG_LAUNCH_D(3, 4, false); else if (CO <= 112) IG_LAUNCH_D(3, 7, false); else IG_LAUNCH_D(3, 8, false); }
-        else { if (CO <= 16) IG_LAUNCH_D(1, 1, false); else if (CO <= 64) IG_LAUNCH_D(1, 4, false); else if (CO <= 112) IG_LAUNCH_D(1, 7, false); else IG_LAUNCH_D(1, 8, false); }
-#undef IG_LAUNCH_D
-        LAMP_LAUNCH_CHECK();
-        return;
-      }
-      // the two-image kernels add the second contribution of a residual block's input gradient in their stores too (B <= 512: two add launches less)
-      const bf16_t* addbc = (addend && dgrad) ? addend->ptr<bf16_t>() : (const bf16_t*)nullptr;
-      if (addend_fused) *addend_fused = addbc != nullptr;
-      // ... and take the sibling 1x1 of a block's first 3x3 (fprop, the 128-row kernel) or its output gradient as a second source (dgrad) too
-      IgSibling sibb{nullptr, nullptr, nullptr, nullptr, nullptr};
-      Hold sibb_wpk, sibb_statt;
-      const bool same_shape2 = second && second->g->kh == 1 && second->g->Cout == g.Cout && second->g->Cin == g.Cin && second->g->N == g.N;
-      const bool dg2b = second && dgrad && KS == 3 && same_shape2;
-      const bool kernel_c = form == IgForm::Two64;
-      const bool sibf = sw().conv_sibling && sibling && !dgrad && KS == 3 && !addend && !kernel_c && sibling->g->kh == 1 && sibling->g->Cout == g.Cout &&
-                        sibling->g->Cin == g.Cin && sibling->g->N == g.N;
-      struct PublishSibB { Hold& t; const Tensor* y; int P; ~PublishSibB() { if (t.get()) conv_stats_publish(y, t.get(), P); } }
-          publish_sibb{sibb_statt, sibf ? sibling->out : nullptr, (int)g.N};
-      if (dg2b) {
-        int64_t off1 = 0;
-        sibb_wpk = Hold(packed_weights(second->w, *second->g, 1, st, &off1));
-        sibb.wp = static_cast<const Tensor*>(sibb_wpk.get())->ptr<bf16_t>() + off1;
-        sibb.x2 = second->dy->ptr<bf16_t>();
-        if (second_fused) *second_fused = true;
-      } else if (sibf) {
-        int64_t off1 = 0;
-        sibb_wpk = Hold(packed_weights(sibling->w, *sibling->g, 1, st, &off1));
-        sibb.wp = static_cast<const Tensor*>(sibb_wpk.get())->ptr<bf16_t>();
-        sibb.bias = sibling->bias ? sibling->bias->ptr<bf16_t>() : (const bf16_t*)nullptr;
-        sibb.y = sibling->out->ptr<bf16_t>();
-        if (statp) {
-          int64_t ps[1] = {(int64_t)g.N * CO * 3};
-          sibb_statt = Hold(new_tensor(ps, 1, kF32, in->device()));
-          sibb.stats = sibb_statt->ptr<float>();
-        }
-        if (sibling_fused) *sibling_fused = true;
-      }
-      if (kernel_c) {
-        const size_t ldsc = (size_t)2 * 64 * KP * 2 + KP * 2 + 4 * (64 * 64 * 2);
-        if (dg2b) {
-          allow_big_lds((const void*)ig_conv8c_kernel<3, 2>);
-          hipLaunchKernelGGL((ig_conv8c_kernel<3, 2>), dim3(blocksb), dim3(256), ldsc, st, in->ptr<bf16_t>(), wpp, bpb, out->ptr<bf16_t>(), (int)g.N, CI, KP, CO, statp, addbc, sibb);
-        } else if (KS == 3) {
-          allow_big_lds((const void*)ig_conv8c_kernel<3>);
-          hipLaunchKernelGGL((ig_conv8c_kernel<3>), dim3(blocksb), dim3(256), ldsc, st, in->ptr<bf16_t>(), wpp, bpb, out->ptr<bf16_t>(), (int)g.N, CI, KP, CO, statp, addbc, sibb);
-        } else {
-          allow_big_lds((const void*)ig_conv8c_kernel<1>);
-          hipLaunchKernelGGL((ig_conv8c_kernel<1>), dim3(blocksb), dim3(256), ldsc, st, in->ptr<bf16_t>(), wpp, bpb, out->ptr<bf16_t>(), (int)g.N, CI, KP, CO, statp, addbc, sibb);
-        }
-        LAMP_LAUNCH_CHECK();
-        return;
-      }
-      // at most one workgroup per CU (small batches): eight waves per image pair (LAMP_IG_W8=0: always four); at most one IMAGE per CU: one
-      // image per workgroup (LAMP_IG_ONE_IMAGE=0: pairs)
-      const bool w8_on = sw().ig_w8;
-      const bool one_on = sw().ig_one_image;
-      const bool w8 = w8_on && blocksb <= num_cus();
-      const bool one = one_on && w8 && g.N <= num_cus();
-      const size_t ldsb = (size_t)(one ? 1 : 2) * 64 * KP * 2 + KP * 2 + (one ? 4 : 2) * IG_WTILE;
-#define IG_LAUNCH_B(KS_, NWV_, SIBM_, NW_)                                                                                                      \
-  do {                                                                                                                                          \
-    allow_big_lds((const void*)ig_conv8b_kernel<KS_, NWV_, SIBM_, NW_>);                                                                       \
-    hipLaunchKernelGGL((ig_conv8b_kernel<KS_, NWV_, SIBM_, NW_>), dim3(NW_ == 1 ? (int)g.N : blocksb), dim3(NWV_ * 64), ldsb, st,               \
-                       in->ptr<bf16_t>(), wpp, bpb, out->ptr<bf16_t>(), (int)g.N, CI, KP, CO, statp, addbc, sibb);                               \
-  } while (0)
-      if (dg2b) { if (one) IG_LAUNCH_B(3, 8, 2, 1); else if (w8) IG_LAUNCH_B(3, 8, 2, 2); else IG_LAUNCH_B(3, 4, 2, 2); }
-      else if (sibf) { if (one) IG_LAUNCH_B(3, 8, 1, 1); else if (w8) IG_LAUNCH_B(3, 8, 1, 2); else IG_LAUNCH_B(3, 4, 1, 2); }
-      else if (KS == 3) { if (one) IG_LAUNCH_B(3, 8, 0, 1); else if (w8) IG_LAUNCH_B(3, 8, 0, 2); else IG_LAUNCH_B(3, 4, 0, 2); }
-      else { if (one) IG_LAUNCH_B(1, 8, 0, 1); else if (w8) IG_LAUNCH_B(1, 8, 0, 2); else IG_LAUNCH_B(1, 4, 0, 2); }
-#undef IG_LAUNCH_B
-      LAMP_LAUNCH_CHECK();
-      return;
-    }
+  const int64_t stat_elems = pl.stats ? (int64_t)g.N * CO * 3 : 0;
+  Hold statt;
+  float* statp = nullptr;
+  if (stat_elems) {
+    int64_t ps[1] = {stat_elems};
+    statt = Hold(new_tensor(ps, 1, kF32, in->device()));
+    statp = statt->ptr<float>();
   }
-  const int NW = g.N >= 1024 ? 4 : 2;        // images per workgroup (keep >= 256 workgroups before widening)
-  const size_t lds = (size_t)NW * 100 * KP * 2 + 3 * IG_WTILE;
-  const int blocks = (int)((g.N + NW - 1) / NW);
-  // fprop and dgrad are the SAME kernel (ig_conv8_kernel), so they share one timer class
-  KernelTimer kt("conv_igemm_fprop_dgrad", conv_flops(g), conv_bytes(g, 2), st);
+  const int per_wg = pl.per_wg ? 1 : 0;
+  StatsPublish publish{statt, out, per_wg ? pl.blocks : (int)g.N};
+  // the second product's work is declared with the launch; its input is the one already counted (one output for both gradients)
+  const ConvGeom* g2 = pl.sibling ? rq.sibling->g : pl.second ? rq.second->g : nullptr;
+  const double fl2 = g2 ? conv_flops(*g2) : 0.0, by2 = g2 ? conv_bytes(*g2, 2) - (double)g.N * g.Cin * 64 * 2 : 0.0;
+  // fprop and dgrad are the same kernels, so they share one timer class
+  KernelTimer kt("conv_igemm_fprop_dgrad", conv_flops(g) + fl2, conv_bytes(g, 2) + by2, st);
   const bf16_t* bp = bias ? bias->ptr<bf16_t>() : (const bf16_t*)nullptr;
-#define IG_LAUNCH(KS_, NW_)                                                                                                        \
-  do {                                                                                                                             \
-    static bool attr = false;                                                                                                      \
-    if (!attr) {                                                                                                                   \
-      allow_big_lds((const void*)ig_conv8_kernel<KS_, NW_>); \
-      attr = true;                                                                                                                 \
-    }                                                                                                                              \
-    hipLaunchKernelGGL((ig_conv8_kernel<KS_, NW_>), dim3(blocks), dim3(NW_ * 128), lds, st, in->ptr<bf16_t>(), wpp, bp, \
-                       out->ptr<bf16_t>(), (int)g.N, CI, KP, CO);                                                                  \
+  const bf16_t* addp = (rq.addend && pl.folds_addend) ? rq.addend->ptr<bf16_t>() : (const bf16_t*)nullptr;
+  const float4* affp = (rq.affine && pl.folds_affine) ? reinterpret_cast<const float4*>(rq.affine->ptr<float>()) : (const float4*)nullptr;
+  Hold sib_wpk, sib_statt;
+  StatsPublish publish_sib{sib_statt, pl.sibling ? rq.sibling->out : nullptr, publish.P};
+  IgSibling sib = ig_second_product(rq, pl, stat_elems, st, &sib_wpk, &sib_statt);
+  const int sibm = pl.second ? 2 : pl.sibling ? 1 : 0;
+  const int N = (int)g.N;
+  const bf16_t* inp = in->ptr<bf16_t>();
+  bf16_t* outp = out->ptr<bf16_t>();
+// the (KS, SIBM) pairs the forms are instantiated for (a 1x1 has no second product): L_(KS, SIBM)
+#define IG_FOR_KS_SIBM(L_)                                                                                                                     \
+  do { if (KS == 1) L_(1, 0); else if (sibm == 2) L_(3, 2); else if (sibm == 1) L_(3, 1); else L_(3, 0); } while (0)
+  if (pl.form == IgForm::Eight) {
+    if (KS == 3 && CO > 16 && !pl.sibling) sib.wtail = wtailp;        // (not in the whole-tap stages of the one-tile form, not beside a forward sibling)
+#define IG_LAUNCH_D(KS_, NCT_, SIBM_)                                                                                                          \
+  do {                                                                                                                                         \
+    allow_big_lds((const void*)ig_conv8d_kernel<KS_, NCT_, SIBM_>);                                                                            \
+    hipLaunchKernelGGL((ig_conv8d_kernel<KS_, NCT_, SIBM_>), dim3(pl.blocks), dim3(512), pl.lds, st, inp, wpp, bp, outp, N, CI, KP, CO, statp, \
+                       per_wg, addp, affp, sib);                                                                                               \
   } while (0)
-  if (KS == 3) { if (NW == 4) IG_LAUNCH(3, 4); else IG_LAUNCH(3, 2); }
-  else { if (NW == 4) IG_LAUNCH(1, 4); else IG_LAUNCH(1, 2); }
-#undef IG_LAUNCH
+// NCT = output-channel tiles of 16 per wave
+#define IG_LAUNCH_D_CO(KS_, SIBM_)                                                                                                             \
+  do { if (CO <= 16) IG_LAUNCH_D(KS_, 1, SIBM_); else if (CO <= 64) IG_LAUNCH_D(KS_, 4, SIBM_); else if (CO <= 112) IG_LAUNCH_D(KS_, 7, SIBM_); \
+       else IG_LAUNCH_D(KS_, 8, SIBM_); } while (0)
+    IG_FOR_KS_SIBM(IG_LAUNCH_D_CO);
+#undef IG_LAUNCH_D_CO
+#undef IG_LAUNCH_D
+  } else {
+// K_ = the kernel with its template arguments, in parentheses; NT_ = its threads
+#define IG_LAUNCH_TWO(K_, NT_)                                                                                                                 \
+  do {                                                                                                                                         \
+    allow_big_lds((const void*)K_);                                                                                                            \
+    hipLaunchKernelGGL(K_, dim3(pl.blocks), dim3(NT_), pl.lds, st, inp, wpp, bp, outp, N, CI, KP, CO, statp, addp, sib);                       \
+  } while (0)
+#define IG_LAUNCH_B(KS_, SIBM_)                                                                                                                \
+  do { if (pl.one) IG_LAUNCH_TWO((ig_conv8b_kernel<KS_, 8, SIBM_, 1>), 512); else if (pl.w8) IG_LAUNCH_TWO((ig_conv8b_kernel<KS_, 8, SIBM_, 2>), 512); \
+       else IG_LAUNCH_TWO((ig_conv8b_kernel<KS_, 4, SIBM_, 2>), 256); } while (0)
+    if (pl.form == IgForm::Two128) IG_FOR_KS_SIBM(IG_LAUNCH_B);
+    else if (KS == 1) IG_LAUNCH_TWO((ig_conv8c_kernel<1>), 256);       // (the plan gives the 64-row form no forward sibling)
+    else if (sibm == 2) IG_LAUNCH_TWO((ig_conv8c_kernel<3, 2>), 256);
+    else IG_LAUNCH_TWO((ig_conv8c_kernel<3>), 256);
+#undef IG_LAUNCH_B
+#undef IG_LAUNCH_TWO
+  }
+#undef IG_FOR_KS_SIBM
   LAMP_LAUNCH_CHECK();
-}
-
-// dx = dgrad3x3(dy, w) + dgrad1x1(dy1, w1) [+ addend] in one launch of the eight-image kernel (the two products share the accumulators: one
-// rounding); false (nothing launched) when that kernel does not take the geometry
-bool igemm_conv_dgrad_pair(const Tensor* dy, const Tensor* w, const ConvGeom& g, const Tensor* dy1, const Tensor* w1, const ConvGeom& g1, Tensor* dx,
-                           hipStream_t st, const Tensor* addend, bool* addend_fused) {
-  if (addend_fused) *addend_fused = false;
-  const bool on = sw().conv_dgrad_pair;
-  if (!on || !ig_qualifies(g, dy->dtype) || !ig_qualifies(g1, dy1->dtype) || g.kh != 3 || g1.kh != 1) return false;
-  if (g.Cout != g1.Cout || g.Cin != g1.Cin || g.N != g1.N) return false;
-  // every form but the plain one takes a second source (eight images per workgroup at large batches, two below)
-  if (ig_form(g, true) == IgForm::Plain) return false;
-  const SecondGradConv sg{dy1, w1, &g1};
-  bool fused = false;
-  run_conv8(dy, w, nullptr, dx, g, true, st, addend, addend_fused, nullptr, nullptr, nullptr, nullptr, &sg, &fused);
-  LAMP_CHECK(fused, "internal: the eight-image kernel did not take the second gradient");
-  return true;
 }
 
 bool igemm_conv_fwd(const Tensor* x, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, hipStream_t st) {
   if (!ig_qualifies(g, x->dtype)) return false;
-  run_conv8(x, w, bias, y, g, false, st);
+  const IgRequest rq;
+  run_conv8(x, w, bias, y, g, false, st, rq, ig_plan(g, false, rq));
   return true;
 }
-// y = conv3x3(x, w, bias) and y1 = conv1x1(x, w1, bias1) - two convolutions of ONE input with the same number of output channels (the two
-// branches of lamp's residual block, cnn.scala:16-20) - in one launch of the eight-image kernel: false (nothing launched) when that kernel
-// does not take the geometry; the values of both outputs and of the statistics hand-offs are those of the two separate launches
+// y = conv3x3(x, w, bias) and y1 = conv1x1(x, w1, bias1) - two convolutions of ONE input with the same number of output channels - in one
+// launch of the eight-image kernel or, at small batches, of the two-image kernel with 128-row weight stages: false (nothing launched) when
+// the plan does not fold the sibling; the values of both outputs and of the statistics hand-offs are those of the two separate launches
 bool igemm_conv_fwd_pair(const Tensor* x, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, const Tensor* w1, const Tensor* bias1,
                          Tensor* y1, const ConvGeom& g1, hipStream_t st) {
-  if (!ig_qualifies(g, x->dtype) || !ig_qualifies(g1, x->dtype) || g.kh != 3 || g1.kh != 1) return false;
-  if (g.Cout != g1.Cout || g.Cin != g1.Cin || g.N != g1.N) return false;
-  // the eight-image kernel, or - small batches - the two-image kernel with 128-row weight stages (more than 64 output channels)
-  const IgForm form = ig_form(g, false);
-  if (form != IgForm::Eight && form != IgForm::Two128) return false;
-  if (!sw().conv_sibling) return false;
+  if (!ig_qualifies(g, x->dtype) || !ig_qualifies(g1, x->dtype)) return false;
   const SiblingConv sc{w1, bias1, y1, &g1};
-  bool fused = false;
-  run_conv8(x, w, bias, y, g, false, st, nullptr, nullptr, nullptr, nullptr, &sc, &fused);
-  LAMP_CHECK(fused, "internal: the eight-image kernel did not take the sibling convolution");
+  IgRequest rq;
+  rq.sibling = &sc;
+  const IgPlan pl = ig_plan(g, false, rq);
+  if (!pl.sibling) return false;
+  run_conv8(x, w, bias, y, g, false, st, rq, pl);
   return true;
 }
-// y = conv(relu(bn(x))) with the batch norm given as its per-channel table: true only if a kernel that applies it while staging ran
-// (only the eight-image kernel does)
-static bool ig_fwd_folds_affine(const ConvGeom& g, int dtype) { return ig_qualifies(g, dtype) && ig_form(g, false) == IgForm::Eight; }
+// dx = dgrad3x3(dy, w) + dgrad1x1(dy1, w1) [+ addend] in one launch (the two products share the accumulators: one rounding; every form takes
+// a second source): false (nothing launched) when the plan does not fold the second gradient
+bool igemm_conv_dgrad_pair(const Tensor* dy, const Tensor* w, const ConvGeom& g, const Tensor* dy1, const Tensor* w1, const ConvGeom& g1, Tensor* dx,
+                           hipStream_t st, const Tensor* addend, bool* addend_fused) {
+  if (addend_fused) *addend_fused = false;
+  if (!ig_qualifies(g, dy->dtype) || !ig_qualifies(g1, dy1->dtype)) return false;
+  const SecondGradConv sg{dy1, w1, &g1};
+  IgRequest rq;
+  rq.addend = addend;
+  rq.second = &sg;
+  const IgPlan pl = ig_plan(g, true, rq);
+  if (!pl.second) return false;
+  run_conv8(dy, w, nullptr, dx, g, true, st, rq, pl);
+  if (addend_fused) *addend_fused = addend && pl.folds_addend;
+  return true;
+}
+// y = conv(relu(bn(x))) with the batch norm given as its per-channel table: true only if the plan applies it while staging (else the caller
+// materialises relu(bn(x)) and convolves that)
+static bool ig_fwd_folds_affine(const ConvGeom& g, int dtype) { return ig_qualifies(g, dtype) && ig_plan(g, false, IgRequest{}).folds_affine; }
 // the weight gradient of a geometry that qualifies runs in the eight-wave kernel (ig_wgrad8h_kernel; else the four-wave one, ig_wgrad8v2_kernel)
 static bool wgrad_takes_eight_wave(const ConvGeom& g) { return sw().wgrad_wide && g.kh == 3 && g.Cin > WG_CI && g.Cout > 64; }
 // (only the eight-wave kernel rebuilds relu(bn(x)) while staging)
@@ -2583,16 +2369,23 @@ static bool ig_wgrad_folds_affine(const ConvGeom& g, int dtype) { return ig_qual
 // both directions apply the batch-norm table while staging: only then does folding the batch norm into this convolution save a pass
 bool igemm_conv_folds_affine(const ConvGeom& g, int dtype) { return ig_fwd_folds_affine(g, dtype) && ig_wgrad_folds_affine(g, dtype); }
 bool igemm_conv_fwd_affine(const Tensor* x, const Tensor* affine, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, hipStream_t st) {
-  if (!ig_fwd_folds_affine(g, x->dtype)) return false;           // checked up front: nothing must be launched when the conditions do not hold
-  bool used = false;
-  run_conv8(x, w, bias, y, g, false, st, nullptr, nullptr, affine, &used);
-  LAMP_CHECK(used, "internal: the eight-image kernel did not run");
+  if (!ig_qualifies(g, x->dtype)) return false;
+  IgRequest rq;
+  rq.affine = affine;
+  const IgPlan pl = ig_plan(g, false, rq);
+  if (!pl.folds_affine) return false;                             // nothing is launched when the table would not be applied
+  run_conv8(x, w, bias, y, g, false, st, rq, pl);
   return true;
 }
+// addend (optional): *addend_fused says whether the launch added it (else the caller adds it afterwards)
 bool igemm_conv_dgrad(const Tensor* dy, const Tensor* w, Tensor* dx, const ConvGeom& g, hipStream_t st, const Tensor* addend, bool* addend_fused) {
   if (addend_fused) *addend_fused = false;
   if (!ig_qualifies(g, dy->dtype)) return false;
-  run_conv8(dy, w, nullptr, dx, g, true, st, addend, addend_fused);
+  IgRequest rq;
+  rq.addend = addend;
+  const IgPlan pl = ig_plan(g, true, rq);
+  run_conv8(dy, w, nullptr, dx, g, true, st, rq, pl);
+  if (addend_fused) *addend_fused = addend && pl.folds_addend;
   return true;
 }
 // affine (optional): x is the raw output of the producing convolution and the forward multiplied relu(bn(x)) - only the eight-wave kernel
@@ -2603,6 +2396,22 @@ bool igemm_conv_dgrad(const Tensor* dy, const Tensor* w, Tensor* dx, const ConvG
 static int wgrad_min_ips(int64_t N) {
   const int v = (int)sw().wgrad_min_ips;
   return v ? v : (N <= 512 ? 2 : 8);
+}
+// the split of N images over workgroups: wg_budget workgroups shared by the ntile slices of Cin, at least wgrad_min_ips images each (where
+// the batch has that many)
+struct WgradSplit { int ips, nsplit; };
+static WgradSplit wgrad_split(int64_t N, int wg_budget, int ntile) {
+  const int target = std::max(1, wg_budget / ntile);
+  int ips = (int)std::max<int64_t>(1, (N + target - 1) / target);
+  if (ips < wgrad_min_ips(N) && N >= wgrad_min_ips(N)) ips = wgrad_min_ips(N);
+  return {ips, (int)((N + ips - 1) / ips)};
+}
+// the reduction of nsplit partial-sum tiles [RS][COP][CIP] into dW[CO][CI][r][s]: one block per 32 float4 columns
+static WgradReduceArgs wgrad_reduce_args(int CO, int CI, int CIP, int COP, int RS, int nsplit) {
+  WgradReduceArgs ra{};
+  ra.kind = 0; ra.CO = CO; ra.CI = CI; ra.CIP = CIP; ra.COP = COP; ra.RS = RS; ra.nsplit = nsplit;
+  ra.blocks = (int)(((int64_t)RS * COP * CIP / 4 + 31) / 32);
+  return ra;
 }
 // ---- the eight-wave weight-gradient kernel: one launch for one layer (optionally with its sibling 1x1: `second`) or for TWO layers (round 6) ----
 // Two layers in one launch.  A layer's launch leaves (256 workgroups) x (its accumulators) of partial sums - 33 MB written by the kernel and read
@@ -2634,10 +2443,8 @@ void wg8h_launch(const Wg8hProblem& pa, const Wg8hProblem* pb, hipStream_t st, c
     Plan q;
     q.ntile = (int)((p.g.Cin + WG_CI - 1) / WG_CI);
     q.CIP = q.ntile * WG_CI;
-    const int target = std::max(1, wg_budget / q.ntile);
-    q.ips = (int)std::max<int64_t>(1, (p.g.N + target - 1) / target);
-    if (q.ips < wgrad_min_ips(p.g.N) && p.g.N >= wgrad_min_ips(p.g.N)) q.ips = wgrad_min_ips(p.g.N);
-    q.nsplit = (int)((p.g.N + q.ips - 1) / q.ips);
+    const WgradSplit sp = wgrad_split(p.g.N, wg_budget, q.ntile);
+    q.ips = sp.ips; q.nsplit = sp.nsplit;
     q.wgs = q.ntile * q.nsplit;
     int64_t ps[1] = {(int64_t)q.nsplit * RS * IG_M * q.CIP};
     q.partial = Hold(new_tensor(ps, 1, kF32, p.x->device()));
@@ -2698,20 +2505,13 @@ void wg8h_launch(const Wg8hProblem& pa, const Wg8hProblem* pb, hipStream_t st, c
     LAMP_LAUNCH_CHECK();
   }
   auto enqueue = [&](const Wg8hProblem& p, Plan& q) {
-    const int64_t cols = (int64_t)RS * IG_M * q.CIP / 4;
-    WgradReduceArgs ra{};
-    ra.kind = 0; ra.CO = (int)p.g.Cout; ra.CI = (int)p.g.Cin; ra.CIP = q.CIP; ra.COP = IG_M; ra.RS = RS; ra.nsplit = q.nsplit; ra.blocks = (int)((cols + 31) / 32);
+    const WgradReduceArgs ra = wgrad_reduce_args((int)p.g.Cout, (int)p.g.Cin, q.CIP, IG_M, RS, q.nsplit);
     if (!out) { wgrad_reduce_enqueue(ra, q.partial.get(), p.dw, st); return; }
     out->push_back(WgradReduction{ra, std::move(q.partial), Hold(retain(p.dw))});
   };
   enqueue(pa, A);
   if (pb) enqueue(*pb, B);
-  if (pair) {
-    const int64_t cols2 = (int64_t)IG_M * A.CIP / 4;
-    WgradReduceArgs rb{};
-    rb.kind = 0; rb.CO = (int)second->g->Cout; rb.CI = (int)pa.g.Cin; rb.CIP = A.CIP; rb.COP = IG_M; rb.RS = 1; rb.nsplit = A.nsplit; rb.blocks = (int)((cols2 + 31) / 32);
-    wgrad_reduce_enqueue(rb, partial2.get(), second->dw, st);
-  }
+  if (pair) wgrad_reduce_enqueue(wgrad_reduce_args((int)second->g->Cout, (int)pa.g.Cin, A.CIP, IG_M, 1, A.nsplit), partial2.get(), second->dw, st);
 }
 static bool igemm_conv_wgrad_impl(const Tensor* dy, const Tensor* x, Tensor* dw, const ConvGeom& g, hipStream_t st, const Tensor* affine,
                                   const SecondWgradConv* second) {
@@ -2737,10 +2537,8 @@ static bool igemm_conv_wgrad_impl(const Tensor* dy, const Tensor* x, Tensor* dw,
     const int wgs_per_cu = (int)sw().wgrad_wgs_per_cu;
     // one workgroup per CU: half the partial-sum traffic of two, same speed
     const int narrow_per_cu = (int)sw().wgrad_narrow_per_cu;   // measured: 2 and 3 are 1 % slower on the step
-    int target = std::max(1, (num_cus() * (narrow ? narrow_per_cu : wgs_per_cu)) / ntile);
-    int ips = (int)std::max<int64_t>(1, (g.N + target - 1) / target);
-    if (ips < wgrad_min_ips(g.N) && g.N >= wgrad_min_ips(g.N)) ips = wgrad_min_ips(g.N);
-    const int nsplit = (int)((g.N + ips - 1) / ips);
+    const WgradSplit split = wgrad_split(g.N, num_cus() * (narrow ? narrow_per_cu : wgs_per_cu), ntile);
+    const int ips = split.ips, nsplit = split.nsplit;
     int64_t ps[1] = {(int64_t)nsplit * RS * COP * CIP};
     Hold partial(new_tensor(ps, 1, kF32, x->device()));
     const bool pair = second != nullptr;
@@ -2771,16 +2569,8 @@ static bool igemm_conv_wgrad_impl(const Tensor* dy, const Tensor* x, Tensor* dw,
       HIP_CHECK(hipLaunchKernel(kfn, dim3(ntile * nsplit), dim3(256), args, lds, st));
       LAMP_LAUNCH_CHECK();
     }
-    const int64_t cols = (int64_t)RS * COP * CIP / 4;
-    WgradReduceArgs ra{};
-    ra.kind = 0; ra.CO = (int)g.Cout; ra.CI = (int)g.Cin; ra.CIP = CIP; ra.COP = COP; ra.RS = RS; ra.nsplit = nsplit; ra.blocks = (int)((cols + 31) / 32);
-    wgrad_reduce_enqueue(ra, partial.get(), dw, st);
-    if (pair) {
-      const int64_t cols2 = (int64_t)COP2 * CIP / 4;
-      WgradReduceArgs rb{};
-      rb.kind = 0; rb.CO = (int)second->g->Cout; rb.CI = (int)g.Cin; rb.CIP = CIP; rb.COP = COP2; rb.RS = 1; rb.nsplit = nsplit; rb.blocks = (int)((cols2 + 31) / 32);
-      wgrad_reduce_enqueue(rb, partial2.get(), second->dw, st);
-    }
+    wgrad_reduce_enqueue(wgrad_reduce_args((int)g.Cout, (int)g.Cin, CIP, COP, RS, nsplit), partial.get(), dw, st);
+    if (pair) wgrad_reduce_enqueue(wgrad_reduce_args((int)second->g->Cout, (int)g.Cin, CIP, COP2, 1, nsplit), partial2.get(), second->dw, st);
     return true;
   }
 }

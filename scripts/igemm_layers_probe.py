@@ -1,5 +1,6 @@
 """Back-to-back timing of the implicit-GEMM layer shapes of the CIFAR ResNet step (fprop; dgrad = the same kernel with the channel
-counts swapped).  Run once per LAMP_IG_VARIANT to compare kernel variants on one device."""
+counts swapped).  Run once per LAMP_IG_VARIANT (b: the two-image form with 128-row stages, d: the eight-image
+form at any batch, unset: by geometry) to compare the kernel forms on one device."""
 import ctypes as C, sys, time, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lamp_amd._capi import lib, i64_array
