@@ -9,11 +9,6 @@
 #pragma once
 #include <cstdint>
 
-// the compile-time default of the run-time switch of the same name (make EXTRA=-DLAMP_WG8H_DMA=0: the whole build, so that this table sees it too)
-#ifndef LAMP_WG8H_DMA
-#define LAMP_WG8H_DMA 1          // SHIFT_DY = 2: the dY tiles arrive by LDS-DMA (0: through registers and ds_write, the A/B form)
-#endif
-
 namespace lamp {
 
 constexpr int64_t SW_NO_CLAMP = INT64_MIN;
@@ -77,16 +72,9 @@ constexpr int64_t SW_NO_CLAMP = INT64_MIN;
   X(ig_w8, "LAMP_IG_W8", BOOL, 1, 0, "two-image 128-row kernel: eight waves per image pair at one workgroup per CU or fewer (0: four)")  \
   X(ig_one_image, "LAMP_IG_ONE_IMAGE", BOOL, 1, 0, "... one image per workgroup at one image per CU or fewer (0: pairs)")                 \
   /* bf16 implicit GEMM, weight gradient */                                                                                               \
-  X(wgrad_wide, "LAMP_WGRAD_WIDE", BOOL, 1, 0, "the eight-wave weight-gradient kernel (3x3, more than 32 input and 64 output channels)") \
   X(wgrad_group, "LAMP_WGRAD_GROUP", BOOL, 1, 0, "two layers' eight-wave weight gradients parked and launched as one (0: every layer at once)") \
   X(wgrad_min_ips, "LAMP_WGRAD_MIN_IPS", INT, 0, 2, "fewest images per weight-gradient workgroup; unset (0): 2 up to 512 images, 8 above") \
-  X(wgrad_shift_dy, "LAMP_WGRAD_SHIFT_DY", INT, 2, SW_NO_CLAMP, "eight-wave kernel's tap shifts: 0 off, 1 dY rows, 2 and X columns in registers") \
-  X(wgrad_stagger, "LAMP_WGRAD_STAGGER", BOOL, 1, 0, "eight-wave kernel: each SIMD's second wave multiplies before it stores / requests the next image pairs")                           \
-  X(wgrad_prio, "LAMP_WGRAD_PRIO", BOOL, 1, 0, "eight-wave kernel: the multiplying wave runs at raised priority")                           \
-  X(wg8h_dma, "LAMP_WG8H_DMA", BOOL, LAMP_WG8H_DMA != 0, 0, "eight-wave kernel: dY tiles by LDS-DMA (0: through registers); default from the macro of the same name") \
-  X(wgrad_wgs_per_cu, "LAMP_WGRAD_WGS_PER_CU", INT, 1, 1, "four-wave weight-gradient kernel: workgroups per CU aimed at")                 \
-  X(wgrad_narrow_per_cu, "LAMP_WGRAD_NARROW_PER_CU", INT, 1, 1, "... of its narrow instantiation")                                        \
-  X(wgrad_ci16, "LAMP_WGRAD_CI16", BOOL, 1, 0, "four-wave kernel's form for at most 16 input channels")                                   \
+  X(wg8h_dma, "LAMP_WG8H_DMA", BOOL, 1, 0, "eight-wave weight-gradient kernel: dY tiles by LDS-DMA (0: through registers, the bitwise reference of the DMA's hand-counted waits)") \
   X(defer_wgrad_reduce, "LAMP_DEFER_WGRAD_REDUCE", BOOL, 1, 0, "weight-gradient partial sums are reduced in batches, deferred until someone reads them")
 
 // ---- read at EVERY call of sw_now(): a test flips these inside one process -----------------------------------------------------------

@@ -1555,45 +1555,45 @@ __global__ __launch_bounds__(256) void ig_wgrad8v2_kernel(const bf16_t* __restri
 // ig_wgrad8v2_kernel<3> runs ONE wave per SIMD (144 accumulator + ~100 other registers per lane, and the compiler fills the rest of
 // the file): rocprofv3 shows the matrix pipe 40 % busy, the waves 34 % of their time in s_waitcnt and the rest at the per-image
 // barrier, with nobody to fill the gaps; two workgroups per CU cannot co-reside (registers).  Here the same 128 co x 32 ci x 9 taps
-// tile is owned by EIGHT waves (32 co x 16 ci each: 72 accumulator registers, launch bound 512 => two waves per SIMD) that overlap
-// each other's stalls.  The X fragments are read by four instead of two waves (LDS reads per image 104 -> 176 KB, still under the
-// MFMA time); image ranges, partial sums and their reduction are exactly those of the v2 kernel.
+// tile is owned by EIGHT waves (16 co x 32 ci each: 72 accumulator registers, launch bound 512 => two waves per SIMD) that overlap
+// each other's stalls; image ranges, partial sums and their reduction are exactly those of the v2 kernel.
 // (A 128 co x 64 ci tile per workgroup - dY read half as often - was 10 us faster on the class but doubles the partial sums for
 // a fixed number of workgroups: +15 us on the step through the reduction; removed.)
-// SHIFT_DY (round 3): the three filter ROWS are taken on the dY side.  A filter-row shift is a shift of the pixel index k by one image row =
-// one 16-byte chunk = one lane group of the fragment, and a product summed over k does not care which operand carries the shift:
-// sum_k dY[k] X[k + 8 (r - 1)] = sum_k dY[k - 8 (r - 1)] X[k].  So a k-step reads 3 row-shifted dY fragments per channel tile (rows that fall
-// outside the image are zeroed in registers) and 3 column-shifted X fragments, 6 + 3 = 9 fragment reads for its 18 MFMAs instead of 2 + 9 = 11:
-// the kernel is bound by its LDS fragment reads (176 KB per image and CU against 1152 matrix cycles).
-// SHIFT_DY = 2 (round 5): ... and the two column-shifted X fragments are cut from the centre one in registers (the shifts store_x used to write as
-// two more LDS copies: out[w] = in[w -/+ 1] with a zero at the border, four shift / or pairs each): 6 + 1 = 7 fragment reads for the 18 MFMAs of a
-// k-step instead of 9 - the LDS array falls from the matrix pipe's 1152 cycles per image to 896 - and one LDS write per X packet instead of three.
-// PAIR (round 5, with SHIFT_DY = 2): the output gradient dy2 [N][CO2][64] of a sibling 1x1 convolution of the same x is staged beside dY (the LDS the
-// two shifted X copies no longer need holds it: 2 x 16 KiB + 5.5 KiB per image), and its weight gradient [CO2][CI] - the centre-tap product
-// dy2 . x - accumulates in 8 more registers per lane: 2 more fragment reads and 2 more MFMAs per k-step (18 -> 20) instead of a launch of its own
-// that reads x again.  partial2[split][128][CIP].
-// SHIFT_DY = 2, later in round 5 (EXPERIMENTS 51 - 57; the cycle counts above assumed 8 LDS cycles per ds_read_b128 - it is 4, and the LDS array
-// is ~40 % busy here): a wave's tile is 16 co x 32 ci (3 dY + 2 X fragment reads per k-step; PAIR: + 1), X is the MFMA's A operand (a lane
-// holds four consecutive ci of one co: 16-byte partial-sum stores), the fragments of k-step j + 1 are requested before the MFMAs of k-step j
-// (rd / mul below), no image request sits in a branch (clamped rows / channels / images, the missing image of an odd range zeroed when it is
-// stored), dY rows outside the image are read from a zero slot of the stage, the centre column's MFMAs come first with the shifts of the other
-// two columns spread between MFMAs, and the multiplying wave runs at s_setprio 2; the dY tiles arrive by LDS-DMA (dma_tile below: swizzle on the
-// source address, inline asm, one vmcnt wait in front of the pair's barrier), x through registers (one packet per thread and pair; the batch-norm
-// fold transforms it on the way).  -DLAMP_WG8H_STAMPS: s_memtime per phase (scripts/wg8h_stamps.py); -DLAMP_WG8H_DMA=0: dY through registers.
+// What bounds it is the LDS fragment reads beside the matrix pipe's 1152 cycles per image, so the nine taps come from as few reads as possible
+// (EXPERIMENTS 34, 51 - 57: 3 dY + 2 X fragment reads for the 18 MFMAs of a k-step; PAIR: + 1 for 20):
+//  - the three filter ROWS are taken on the dY side.  A filter-row shift is a shift of the pixel index k by one image row = one 16-byte chunk =
+//    one lane group of the fragment, and a product summed over k does not care which operand carries the shift:
+//    sum_k dY[k] X[k + 8 (r - 1)] = sum_k dY[k - 8 (r - 1)] X[k].  With every shift on X a k-step reads nine X fragments, one per tap.  A dY row that falls
+//    outside the image is read from a ZERO SLOT of the stage: the address is chosen once, outside the loop, where a select per register would take
+//    the vector issue slots the MFMAs leave (rd below);
+//  - the two column-shifted X fragments, out[w] = in[w -/+ 1] with a zero at the border, are cut from the centre one in registers (four shift / or
+//    pairs each) - one LDS write per X packet and one read per half tile.  The centre column's MFMAs come first and the shifts of the other two
+//    columns are spread between MFMAs: a clump of vector instructions in front of them drains the matrix pipe (mul below);
+//  - X is the MFMA's A operand, so a lane holds four consecutive ci of one co and the partial sums leave as 16-byte stores;
+//  - the fragments of k-step j + 1 are requested before the MFMAs of k-step j, the two waves of a SIMD run out of step (`late`) and the one that
+//    multiplies runs at s_setprio 2 (EXPERIMENTS 45, 53);
+//  - no image request sits in a branch: rows / channels / images beyond the end are clamped (they reach accumulator rows and columns that are never
+//    stored) and the missing image of an odd range is zeroed when it is stored.
+// The dY tiles arrive by LDS-DMA with the swizzle on the source address (EXPERIMENTS 59).  The DMA is inline asm and its arrival is counted by hand, one
+// vmcnt wait in front of the pair's barrier: through the builtin hipcc would wait for it where it is issued (dma_tile below).  x goes through registers
+// (one packet per thread and pair; the batch-norm fold transforms it on the way).  DMA = false (LAMP_WG8H_DMA=0) brings dY through registers and
+// ds_write too - the same arithmetic in the same order with hipcc's own waits, the bitwise reference of the hand-counted ones.
+// PAIR: the output gradient dy2 [N][CO2][64] of a sibling 1x1 convolution of the same x is staged beside dY, and its weight gradient [CO2][CI] - the
+// centre-tap product dy2 . x - accumulates in 8 more registers per lane: one more fragment read and 2 more MFMAs per k-step instead of a launch of
+// its own that reads x again.  partial2[split][128][CIP].
+// -DLAMP_WG8H_STAMPS: s_memtime per phase (scripts/wg8h_stamps.py).
 #ifdef LAMP_WG8H_STAMPS
 __device__ unsigned int g_wg8h_stamps[1024 * 8 * 8];
 #endif
-// (LAMP_WG8H_DMA, default 1: core/switches.h - SHIFT_DY = 2: the dY tiles arrive by LDS-DMA; 0: through registers and ds_write, the A/B form)
 // A SECOND PROBLEM in the same launch (round 6, igemm_wgrad_group; wgs0 = 0: none): workgroups [0, wgs0) belong to the kernel's own arguments,
 // [wgs0, gridDim.x) to this one - another layer's weight gradient of the same batch.  Two layers share the CUs, so each workgroup walks twice as
 // many images and each layer leaves HALF the partial sums (they are the kernel's store phase and the reduction's whole input: EXPERIMENTS 73).
 struct WgSecondProblem { const bf16_t* dy; const bf16_t* x; float* partial; int CO, CI, CIP, images_per_split, ntile; const float4* affine; int wgs0; };
-template <int SHIFT_DY, bool PAIR = false, bool DMA = (LAMP_WG8H_DMA != 0)>
+template <bool PAIR, bool DMA>
 __global__ __launch_bounds__(512) void ig_wgrad8h_kernel(const bf16_t* __restrict__ dy_, const bf16_t* __restrict__ x_, float* __restrict__ partial_,
                                                          int N, int CO_, int CI_, int CIP_, int images_per_split_, int ntile_, const float4* __restrict__ affine_,
-                                                         int stream_out, const bf16_t* __restrict__ dy2, float* __restrict__ partial2, int CO2,
+                                                         const bf16_t* __restrict__ dy2, float* __restrict__ partial2, int CO2,
                                                          const WgSecondProblem sp) {
-  static_assert(!PAIR || SHIFT_DY == 2, "the pair uses the LDS of the shifted X copies");
   const bool second_problem = !PAIR && sp.wgs0 > 0 && (int)blockIdx.x >= sp.wgs0;          // (uniform per workgroup)
   const bf16_t* __restrict__ dy = second_problem ? sp.dy : dy_;
   const bf16_t* __restrict__ x = second_problem ? sp.x : x_;
@@ -1603,10 +1603,11 @@ __global__ __launch_bounds__(512) void ig_wgrad8h_kernel(const bf16_t* __restric
   const float4* __restrict__ affine = second_problem ? sp.affine : affine_;
   const int wg_index = second_problem ? (int)blockIdx.x - sp.wgs0 : (int)blockIdx.x;
   const int wg_count = second_problem ? (int)gridDim.x - sp.wgs0 : ((!PAIR && sp.wgs0 > 0) ? sp.wgs0 : (int)gridDim.x);
-  // stage layout: [dY tile | X copies ...] or, PAIR, [dY tile | dY2 tile | X]; XC = offset of the unshifted X copy
+  // stage layout (one image): [dY tile | unused | X | unused] - WG_STAGE, shared with ig_wgrad8v2_kernel<3>: the two unused slots once held
+  // column-shifted copies of X and are still part of the measured footprint - or, PAIR, [dY tile | dY2 tile | X]; XC = offset of X
   constexpr int XC = PAIR ? 2 * IG_WTILE : IG_WTILE + WG_XCOPY;
   constexpr int STG = PAIR ? 2 * IG_WTILE + WG_XCOPY + 512 : WG_STAGE;
-  constexpr int ZSLOT = STG - 512;                          // 16 zero bytes per image stage (in the padding; SHIFT_DY = 2 reads them for dY rows outside the image)
+  constexpr int ZSLOT = STG - 512;                          // 16 zero bytes per image stage (in the padding), read for dY rows outside the image
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int KS = 3, RS = 9, PAD = 1;
   const int nsplit = wg_count / ntile;
@@ -1619,61 +1620,31 @@ __global__ __launch_bounds__(512) void ig_wgrad8h_kernel(const bf16_t* __restric
   const int ci0 = tile * WG_CI;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wq = wid >> 1, wc = wid & 1;                      // 32-channel block of co, 16-channel half of ci
-  // SHIFT_DY = 2: the wave's tile is 16 co x 32 ci instead (wave = co block, both ci halves): 3 dY fragments and 2 X fragments serve the
-  // 18 MFMAs of a k-step - 5 LDS reads instead of 6 + 1 (the LDS pipe: 640 + 288 cycles per image instead of 896 + 288, next to 1152 MFMA cycles)
-  constexpr bool W16 = SHIFT_DY == 2;
   const int nbeg = split * images_per_split, nend = min(nbeg + images_per_split, N);
-  // (the shifted X copies kept zero rows / columns that are never written again; with SHIFT_DY = 2 every byte that is read - the dY tiles, rows
-  // 1 .. 8 of the unshifted X copy - is written for every image, so nothing has to be cleared)
-  if (SHIFT_DY != 2) {
-    for (int o = tid * 16; o < 4 * STG; o += 512 * 16) *reinterpret_cast<uint4*>(smem + o) = make_uint4(0, 0, 0, 0);   // 2 stages x 2 images
-    __syncthreads();
-  } else if (tid < 4) {
-    *reinterpret_cast<uint4*>(smem + tid * STG + ZSLOT) = make_uint4(0, 0, 0, 0);   // (the barrier behind the first pair's stores publishes it)
-  }
+  // every byte that is read - the dY tiles, rows 1 .. 8 of X - is written for every image, so only the zero slots have to be cleared
+  if (tid < 4) *reinterpret_cast<uint4*>(smem + tid * STG + ZSLOT) = make_uint4(0, 0, 0, 0);   // (the barrier behind the first pair's stores publishes it)
 
-  const bool xthread = tid < 256;
-  const int xci = (tid & 255) >> 3, xh = tid & 7;             // (channel, image row) of the X tile: threads 0..255
+  // the X tiles of a PAIR of images are 512 packets - one per thread: (channel, image row, image) - requested without a branch: channels beyond CI
+  // read channel CI - 1 (accumulator rows that are never stored), an image beyond nend reads image nend - 1 (its dY is stored as zeros)
+  const int xci = (tid & 255) >> 3, xh = tid & 7, xim = tid >> 8, xcc = min(ci0 + xci, CI - 1);
   // affine: x is a convolution's raw output and the forward multiplied relu(bn(x)) (ig_conv8d_kernel): the same values are rebuilt here
-  const float4 aff = (affine && xthread && ci0 + xci < CI) ? affine[ci0 + xci] : make_float4(0.f, 0.f, 0.f, 0.f);
+  const float4 aff = affine ? affine[xcc] : make_float4(0.f, 0.f, 0.f, 0.f);
   auto load_x = [&](int n) -> uint4 {
-    if (xthread && ci0 + xci < CI) {
-      return *reinterpret_cast<const uint4*>(x + ((int64_t)n * CI + ci0 + xci) * 64 + xh * 8);
-    }
-    return make_uint4(0, 0, 0, 0);
-  };
-  // W16: the X tiles of a PAIR of images are 512 packets - one per thread (image tid >> 8), requested without a branch: channels beyond CI read
-  // channel CI - 1 (accumulator rows that are never stored), an image beyond nend reads image nend - 1 (its dY is stored as zeros)
-  const int xim = tid >> 8, xcc = min(ci0 + xci, CI - 1);
-  const float4 aff2 = affine ? affine[xcc] : make_float4(0.f, 0.f, 0.f, 0.f);
-  auto load_x2 = [&](int n) -> uint4 {
     return *reinterpret_cast<const uint4*>(x + ((int64_t)min(n + xim, nend - 1) * CI + xcc) * 64 + xh * 8);
   };
-  auto store_x2 = [&](char* stage, uint4 v) {
-    if (affine) v = ig_bn_relu_x8(v, aff2.x, aff2.y, aff2.z);
-    *reinterpret_cast<uint4*>(stage + xim * STG + XC + xci * WG_XCH + (xh + 1) * 16) = v;
-  };
-  auto store_x = [&](char* stage, uint4 v) {                  // copy s holds out[w] = in[w + s - 1]
-    if (!xthread) return;
-    // the table is applied HERE, a pair after the load was requested (at the load it would wait for the data and undo the prefetch).
-    // Images beyond nend arrive as zeros and leave as relu(bn(0)): their dY is zero, so they add nothing
+  auto store_x = [&](char* stage, uint4 v) {
+    // the table is applied HERE, a pair after the load was requested (at the load it would wait for the data and undo the prefetch)
     if (affine) v = ig_bn_relu_x8(v, aff.x, aff.y, aff.z);
-    if (SHIFT_DY == 2) { *reinterpret_cast<uint4*>(stage + XC + xci * WG_XCH + (xh + 1) * 16) = v; return; }   // the shifted fragments are cut from this one after the read
-    char* xb = stage + IG_WTILE + xci * WG_XCH + (xh + 1) * 16;
-    *reinterpret_cast<uint4*>(xb + WG_XCOPY) = v;
-    *reinterpret_cast<uint4*>(xb) = make_uint4(v.x << 16, (v.y << 16) | (v.x >> 16), (v.z << 16) | (v.y >> 16), (v.w << 16) | (v.z >> 16));
-    *reinterpret_cast<uint4*>(xb + 2 * WG_XCOPY) = make_uint4((v.x >> 16) | (v.y << 16), (v.y >> 16) | (v.z << 16), (v.z >> 16) | (v.w << 16), v.w >> 16);
+    *reinterpret_cast<uint4*>(stage + xim * STG + XC + xci * WG_XCH + (xh + 1) * 16) = v;   // (rows sit one slot down; the column-shifted fragments are cut from this one after the read)
   };
-  // dY tile [128 co][64 px]: 1024 16-byte packets, two per thread
+  // dY tile [128 co][64 px]: 1024 16-byte packets, two per thread (the register form; the last reader of dY: streaming loads)
   auto load_dy = [&](uint4 (&r)[2], int n) {
     const bf16_t* base = dy + (int64_t)n * CO * 64;
 #pragma unroll
     for (int i = 0; i < 2; i++) {
       const int c = tid + i * 512, gr = c >> 3;
-      // (W16: rows beyond CO load row CO - 1 again - they only reach accumulator columns that are never stored - so the request needs no branch)
-      if constexpr (W16) r[i] = nt_load16(reinterpret_cast<const uint4*>(base + min(gr, CO - 1) * 64 + ((c & 7) << 3)));
-      else r[i] = gr < CO ? nt_load16(reinterpret_cast<const uint4*>(base + gr * 64 + ((c & 7) << 3))) : make_uint4(0, 0, 0, 0);   // dY's last reader
+      // (rows beyond CO load row CO - 1 again - they only reach accumulator columns that are never stored - so the request needs no branch)
+      r[i] = nt_load16(reinterpret_cast<const uint4*>(base + min(gr, CO - 1) * 64 + ((c & 7) << 3)));
     }
   };
   auto store_dy = [&](const uint4 (&r)[2], char* stage) {
@@ -1685,7 +1656,7 @@ __global__ __launch_bounds__(512) void ig_wgrad8h_kernel(const bf16_t* __restric
 #pragma unroll
     for (int i = 0; i < 2; i++) {
       const int c = tid + i * 512, gr = c >> 3;
-      r[i] = nt_load16(reinterpret_cast<const uint4*>(base + min(gr, CO2 - 1) * 64 + ((c & 7) << 3)));   // (PAIR implies W16: as above)
+      r[i] = nt_load16(reinterpret_cast<const uint4*>(base + min(gr, CO2 - 1) * 64 + ((c & 7) << 3)));   // (as above)
     }
   };
 
@@ -1694,7 +1665,7 @@ __global__ __launch_bounds__(512) void ig_wgrad8h_kernel(const bf16_t* __restric
   for (int t = 0; t < RS; t++)
 #pragma unroll
     for (int i = 0; i < 2; i++) acc[t][i] = f4v{0.f, 0.f, 0.f, 0.f};
-  f4v acc2[2] = {f4v{0.f, 0.f, 0.f, 0.f}, f4v{0.f, 0.f, 0.f, 0.f}};      // PAIR: the sibling's [32 co][16 ci] block of this wave
+  f4v acc2[2] = {f4v{0.f, 0.f, 0.f, 0.f}, f4v{0.f, 0.f, 0.f, 0.f}};      // PAIR: the sibling's [16 co][32 ci] block of this wave
 
   // Image PAIRS: an LDS stage holds two images, and per pair the loop is
   //     LDS-store the NEXT pair (its registers were requested one pair ago)  ->  request the pair after that  ->  multiply THIS pair  ->  barrier
@@ -1703,56 +1674,7 @@ __global__ __launch_bounds__(512) void ig_wgrad8h_kernel(const bf16_t* __restric
   // 1060 multiplying (the matrix pipe's share), 546 storing, 482 at the barrier, 430 issuing loads - every wave in the same phase
   // at the same time, so the matrix pipe idled 58 % of the loop.  (The barrier is a raw s_barrier behind lgkmcnt(0): __syncthreads()
   // would drain vmcnt and with it the prefetch.)
-  // (SHIFT_DY = 0 / 1 only - the A/B forms kept behind LAMP_WGRAD_SHIFT_DY; SHIFT_DY = 2 multiplies through rd() / mul() below)
-  auto compute = [&](const char* st) {
-    const char* xl = st + IG_WTILE + (wc * 16 + (lane & 15)) * WG_XCH;   // (xl + WG_XCOPY = the unshifted copy)
-    if (SHIFT_DY) {
-      const bf8v zero8 = __builtin_bit_cast(bf8v, s8v{0, 0, 0, 0, 0, 0, 0, 0});
-#pragma unroll
-      for (int ks = 0; ks < 2; ks++) {
-        const int h = 4 * ks + (lane >> 4);                   // image row of this lane group's eight k
-        bf8v fa[KS][2];
-#pragma unroll
-        for (int r = 0; r < KS; r++) {
-          const int hr = h - (r - PAD);                       // the dY row that meets X row h under filter row r
-          const bool inside = hr >= 0 && hr < 8;
-          const int hc = inside ? hr : h;
-#pragma unroll
-          for (int i = 0; i < 2; i++) {
-            const s8v v = *reinterpret_cast<const s8v*>(st + ig_kc_off(wq * 32 + i * 16 + (lane & 15), hc));
-            fa[r][i] = inside ? __builtin_bit_cast(bf8v, v) : zero8;
-          }
-        }
-#pragma unroll
-        for (int s_ = 0; s_ < KS; s_++) {
-          const s8v v = *reinterpret_cast<const s8v*>(xl + s_ * WG_XCOPY + (h + 1) * 16);   // X row h itself (rows sit one slot down: the zero row above the image)
-          const bf8v fb = __builtin_bit_cast(bf8v, v);
-#pragma unroll
-          for (int r = 0; r < KS; r++)
-#pragma unroll
-            for (int i = 0; i < 2; i++) acc[r * KS + s_][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[r][i], fb, acc[r * KS + s_][i], 0, 0, 0);
-        }
-      }
-      return;
-    }
-#pragma unroll
-    for (int ks = 0; ks < 2; ks++) {
-      bf8v fa[2];
-#pragma unroll
-      for (int i = 0; i < 2; i++) fa[i] = ig_frag_rows(st, wq * 32 + i * 16, ks, lane);
-      const int h = 4 * ks + (lane >> 4);
-#pragma unroll
-      for (int t = 0; t < RS; t++) {
-        const int r = t / KS, s = t % KS;
-        s8v v = *reinterpret_cast<const s8v*>(xl + s * WG_XCOPY + (h + r + (1 - PAD)) * 16);
-        const bf8v fb = __builtin_bit_cast(bf8v, v);
-#pragma unroll
-        for (int i = 0; i < 2; i++) acc[t][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb, acc[t][i], 0, 0, 0);
-      }
-    }
-  };
   auto lds_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); };
-  // images at or beyond nend load as zeros (an odd image count: the missing partner contributes nothing)
   uint4 rb[PAIR ? 2 : 1][2];                                 // PAIR: the sibling's dY packets of the pair in flight
   // LDS-DMA of a [128 co][64 px] dY tile (global_load_lds_dwordx4: no staging registers, no ds_write): the destination is lane-linear, so the
   // tile's XOR swizzle sits on the SOURCE address - position p of the image holds chunk (p & 7) ^ (row & 7) of row p >> 3, as ig_kc_off() reads it.
@@ -1788,52 +1710,33 @@ __global__ __launch_bounds__(512) void ig_wgrad8h_kernel(const bf16_t* __restric
       }
     }
   };
-  auto load_pair = [&](uint4 (&ra_)[2][2], uint4 (&rx_)[2], int n) {
-    if constexpr (W16) {
-#pragma unroll
-      for (int im = 0; im < 2; im++) {
-        const int nn = min(n + im, nend - 1);
-        load_dy(ra_[im], nn);
-        if constexpr (PAIR) load_dy2(rb[im], nn);
-      }
-      rx_[0] = load_x2(n);
-      return;
-    }
+  auto load_pair = [&](uint4 (&ra_)[2][2], uint4& rx_, int n) {
 #pragma unroll
     for (int im = 0; im < 2; im++) {
-      if (n + im < nend) { load_dy(ra_[im], n + im); rx_[im] = load_x(n + im); if constexpr (PAIR) load_dy2(rb[im], n + im); }
-      else {
-        ra_[im][0] = ra_[im][1] = make_uint4(0, 0, 0, 0); rx_[im] = make_uint4(0, 0, 0, 0);
-        if constexpr (PAIR) rb[im][0] = rb[im][1] = make_uint4(0, 0, 0, 0);
-      }
+      const int nn = min(n + im, nend - 1);
+      load_dy(ra_[im], nn);
+      if constexpr (PAIR) load_dy2(rb[im], nn);
     }
+    rx_ = load_x(n);
   };
-  auto store_pair = [&](const uint4 (&ra_)[2][2], const uint4 (&rx_)[2], char* stage, int n) {
-    if constexpr (W16) {
-#pragma unroll
-      for (int im = 0; im < 2; im++) {
-        const bool live = n + im < nend;                    // (uniform) the missing partner of an odd image count: zeros
-        // (component selects: a ?: between two uint4 objects selects ADDRESSES and sends the register arrays to scratch memory)
-        auto keep = [live](const uint4& v) { return make_uint4(live ? v.x : 0u, live ? v.y : 0u, live ? v.z : 0u, live ? v.w : 0u); };
-        const uint4 t[2] = {keep(ra_[im][0]), keep(ra_[im][1])};
-        store_dy(t, stage + im * STG);
-        if constexpr (PAIR) { const uint4 t2[2] = {keep(rb[im][0]), keep(rb[im][1])}; store_dy(t2, stage + im * STG + IG_WTILE); }
-      }
-      store_x2(stage, rx_[0]);
-      return;
-    }
+  auto store_pair = [&](const uint4 (&ra_)[2][2], const uint4& rx_, char* stage, int n) {
 #pragma unroll
     for (int im = 0; im < 2; im++) {
-      store_dy(ra_[im], stage + im * STG); store_x(stage + im * STG, rx_[im]);
-      if constexpr (PAIR) store_dy(rb[im], stage + im * STG + IG_WTILE);
+      const bool live = n + im < nend;                      // (uniform) the missing partner of an odd image count: zeros
+      // (component selects: a ?: between two uint4 objects selects ADDRESSES and sends the register arrays to scratch memory)
+      auto keep = [live](const uint4& v) { return make_uint4(live ? v.x : 0u, live ? v.y : 0u, live ? v.z : 0u, live ? v.w : 0u); };
+      const uint4 t[2] = {keep(ra_[im][0]), keep(ra_[im][1])};
+      store_dy(t, stage + im * STG);
+      if constexpr (PAIR) { const uint4 t2[2] = {keep(rb[im][0]), keep(rb[im][1])}; store_dy(t2, stage + im * STG + IG_WTILE); }
     }
+    store_x(stage, rx_);
   };
-  uint4 ra[2][2], rx[2];
-  if constexpr (W16 && DMA) {
+  uint4 ra[2][2], rx;                                         // (DMA: ra stays unused - only x passes through registers)
+  if constexpr (DMA) {
     if (nbeg < nend) {
       dma_pair(smem, nbeg);
-      store_x2(smem, load_x2(nbeg));
-      if (nbeg + 2 < nend) rx[0] = load_x2(nbeg + 2);
+      store_x(smem, load_x(nbeg));
+      if (nbeg + 2 < nend) rx = load_x(nbeg + 2);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the DMA's arrival is counted by vmcnt (the x request behind it is waited for too, once)
   } else if (nbeg < nend) {
@@ -1843,10 +1746,9 @@ __global__ __launch_bounds__(512) void ig_wgrad8h_kernel(const bf16_t* __restric
   }
   __syncthreads();
   int cur = 0;
-  // (round 5) the second wave of every SIMD (waves 4 - 7) multiplies the pair's first image BEFORE it stores / requests the next pairs: while one
-  // wave of a SIMD is busy with LDS stores and load issue the other one has MFMAs to issue (LAMP_WGRAD_STAGGER=0 via `stream_out` bit 1: off)
-  const bool late = (wid >> 2) != 0 && !(stream_out & 2) && images_per_split >= 8;     // (with one or two pairs per workgroup the order only delays: B = 256 +2 us)
-  const bool prio = (stream_out & 4) != 0;
+  // the second wave of every SIMD (waves 4 - 7) multiplies the pair's first image BEFORE it stores / requests the next pairs: while one wave of a
+  // SIMD is busy with LDS stores and load issue the other one has MFMAs to issue (EXPERIMENTS 45; in lockstep +4 us per launch on the final form)
+  const bool late = (wid >> 2) != 0 && images_per_split >= 8;     // (with one or two pairs per workgroup the order only delays: B = 256 +2 us)
 #ifdef LAMP_WG8H_STAMPS
   unsigned int stamp_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, stamp_last = 0;
   const unsigned int stamp_begin = (unsigned int)__builtin_amdgcn_s_memtime();
@@ -1855,7 +1757,7 @@ __global__ __launch_bounds__(512) void ig_wgrad8h_kernel(const bf16_t* __restric
 #else
 #define WG8H_STAMP(k) do { } while (0)
 #endif
-  // W16: the pair's four k-steps as a pipeline - the fragments of k-step j + 1 are requested before the MFMAs of k-step j are issued (two sets of
+  // The pair's four k-steps as a pipeline - the fragments of k-step j + 1 are requested before the MFMAs of k-step j are issued (two sets of
   // 20 / 24 registers), so one LDS latency per pair is exposed instead of four.  In-kernel clocks of the unpipelined loop: a wave alone on its SIMD's
   // matrix pipe needed 1110 ticks for the 36 MFMAs of an image (~440 ticks of issue) - two exposed fragment reads per image.
   struct Frag { bf8v fa[KS]; unsigned int xc[2][4]; bf8v d2; };
@@ -1907,52 +1809,35 @@ __global__ __launch_bounds__(512) void ig_wgrad8h_kernel(const bf16_t* __restric
   for (int n = nbeg; n < nend; n += 2, cur ^= 1) {
     char* st = smem + cur * (2 * STG);
     WG8H_STAMP(0);
-    if constexpr (W16) {
-      Frag f0, f1;
-      if (late) {
-        if (prio) __builtin_amdgcn_s_setprio(2);
-        rd(f0, st, 0); rd(f1, st, 1); WG8H_SB(); mul(f0); WG8H_SB(); rd(f0, st + STG, 0); WG8H_SB(); mul(f1); WG8H_SB();
-        if (prio) __builtin_amdgcn_s_setprio(0);
-      }
-      WG8H_STAMP(1);
-      if constexpr (DMA) {
-        // x of pair n + 2 from its registers (requested one pair ago), the request of x for pair n + 4, then pair n + 2's dY tiles by DMA - in
-        // this order: hipcc puts a vmcnt(0) of its own in front of the x request (it counts nothing in flight there), which behind the DMAs
-        // would wait for them.  Everything requested here is waited for once, in front of the pair's barrier, a pair of images later.
-        char* nx = smem + (cur ^ 1) * (2 * STG);                // nobody reads that stage since the last barrier
-        if (n + 2 < nend) store_x2(nx, rx[0]);
-        WG8H_STAMP(2);
-        if (n + 4 < nend) rx[0] = load_x2(n + 4);
-        if (n + 2 < nend) dma_pair(nx, n + 2);
-      } else {
-        if (n + 2 < nend) store_pair(ra, rx, smem + (cur ^ 1) * (2 * STG), n + 2);      // nobody reads that stage since the last barrier
-        WG8H_STAMP(2);
-        if (n + 4 < nend) load_pair(ra, rx, n + 4);
-      }
-      WG8H_STAMP(3);
-      if (prio) __builtin_amdgcn_s_setprio(2);
-      if (!late) { rd(f0, st, 0); rd(f1, st, 1); WG8H_SB(); mul(f0); WG8H_SB(); rd(f0, st + STG, 0); WG8H_SB(); mul(f1); WG8H_SB(); }
-      WG8H_STAMP(4);
-      rd(f1, st + STG, 1); WG8H_SB(); mul(f0); WG8H_SB(); mul(f1);
-      if (prio) __builtin_amdgcn_s_setprio(0);
-      WG8H_STAMP(5);
-      if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      lds_barrier();
-      WG8H_STAMP(6);
-      continue;
+    Frag f0, f1;
+    if (late) {
+      __builtin_amdgcn_s_setprio(2);                         // the wave that multiplies goes first: the SIMD's other wave is storing / requesting (EXPERIMENTS 53)
+      rd(f0, st, 0); rd(f1, st, 1); WG8H_SB(); mul(f0); WG8H_SB(); rd(f0, st + STG, 0); WG8H_SB(); mul(f1); WG8H_SB();
+      __builtin_amdgcn_s_setprio(0);
     }
-    if (late) { if (prio) __builtin_amdgcn_s_setprio(2); compute(st); if (prio) __builtin_amdgcn_s_setprio(0); }
     WG8H_STAMP(1);
-    if (n + 2 < nend) store_pair(ra, rx, smem + (cur ^ 1) * (2 * STG), n + 2);      // nobody reads that stage since the last barrier
-    WG8H_STAMP(2);
-    if (n + 4 < nend) load_pair(ra, rx, n + 4);
+    if constexpr (DMA) {
+      // x of pair n + 2 from its registers (requested one pair ago), the request of x for pair n + 4, then pair n + 2's dY tiles by DMA - in
+      // this order: hipcc puts a vmcnt(0) of its own in front of the x request (it counts nothing in flight there), which behind the DMAs
+      // would wait for them.  Everything requested here is waited for once, in front of the pair's barrier, a pair of images later.
+      char* nx = smem + (cur ^ 1) * (2 * STG);                // nobody reads that stage since the last barrier
+      if (n + 2 < nend) store_x(nx, rx);
+      WG8H_STAMP(2);
+      if (n + 4 < nend) rx = load_x(n + 4);
+      if (n + 2 < nend) dma_pair(nx, n + 2);
+    } else {
+      if (n + 2 < nend) store_pair(ra, rx, smem + (cur ^ 1) * (2 * STG), n + 2);      // nobody reads that stage since the last barrier
+      WG8H_STAMP(2);
+      if (n + 4 < nend) load_pair(ra, rx, n + 4);
+    }
     WG8H_STAMP(3);
-    if (prio) __builtin_amdgcn_s_setprio(2);
-    if (!late) compute(st);
+    __builtin_amdgcn_s_setprio(2);
+    if (!late) { rd(f0, st, 0); rd(f1, st, 1); WG8H_SB(); mul(f0); WG8H_SB(); rd(f0, st + STG, 0); WG8H_SB(); mul(f1); WG8H_SB(); }
     WG8H_STAMP(4);
-    compute(st + STG);
-    if (prio) __builtin_amdgcn_s_setprio(0);
+    rd(f1, st + STG, 1); WG8H_SB(); mul(f0); WG8H_SB(); mul(f1);
+    __builtin_amdgcn_s_setprio(0);
     WG8H_STAMP(5);
+    if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     lds_barrier();
     WG8H_STAMP(6);
   }
@@ -1964,52 +1849,26 @@ __global__ __launch_bounds__(512) void ig_wgrad8h_kernel(const bf16_t* __restric
     o[7] = (unsigned int)__builtin_amdgcn_s_memtime() - stamp_begin;
   }
 #endif
-  if constexpr (W16) {
-    // acc[t][i] = [16 ci of half i (rows: 4 consecutive per lane)][16 co (lane & 15)]; columns ci >= CI of a row are padding the reduction never reads
-    const int co = wid * 16 + (lane & 15);
-    if constexpr (PAIR) {
-      float* out2 = partial2 + (int64_t)split * IG_M * CIP;
-#pragma unroll
-      for (int i = 0; i < 2; i++) {
-        const int ci = ci0 + i * 16 + (lane >> 4) * 4;
-        if (co < CO2 && ci < CI) __builtin_nontemporal_store(acc2[i], reinterpret_cast<f4v*>(&out2[co * CIP + ci]));
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < RS; t++) {
-      float* out = partial + (int64_t)(split * RS + t) * IG_M * CIP;
-#pragma unroll
-      for (int i = 0; i < 2; i++) {
-        const int ci = ci0 + i * 16 + (lane >> 4) * 4;
-        if (co < CO && ci < CI) __builtin_nontemporal_store(acc[t][i], reinterpret_cast<f4v*>(&out[co * CIP + ci]));
-      }
-    }
-    return;
-  }
+  // acc[t][i] = [16 ci of half i (rows: 4 consecutive per lane)][16 co (lane & 15)]: partial[split * RS + t][128][CIP], PAIR: partial2[split][128][CIP].
+  // Rows co >= CO and columns ci >= CI are padding the reduction never reads.  Streaming stores: the partial sums of a step (113 MB) that nobody
+  // reads before the end of backprop must not push the activations out of L2 / Infinity Cache
+  const int co = wid * 16 + (lane & 15);
   if constexpr (PAIR) {
-    // the sibling's block: partial2[split][128][CIP]
     float* out2 = partial2 + (int64_t)split * IG_M * CIP;
 #pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int rr = 0; rr < 4; rr++) {
-        const int co = wq * 32 + i * 16 + (lane >> 4) * 4 + rr, ci = ci0 + wc * 16 + (lane & 15);
-        if (co < CO2 && ci < CI) __builtin_nontemporal_store(acc2[i][rr], &out2[co * CIP + ci]);
-      }
+    for (int i = 0; i < 2; i++) {
+      const int ci = ci0 + i * 16 + (lane >> 4) * 4;
+      if (co < CO2 && ci < CI) __builtin_nontemporal_store(acc2[i], reinterpret_cast<f4v*>(&out2[co * CIP + ci]));
+    }
   }
-  // partial[(split * RS + t)][128][CIP]
 #pragma unroll
   for (int t = 0; t < RS; t++) {
     float* out = partial + (int64_t)(split * RS + t) * IG_M * CIP;
 #pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int rr = 0; rr < 4; rr++) {
-        const int co = wq * 32 + i * 16 + (lane >> 4) * 4 + rr, ci = ci0 + wc * 16 + (lane & 15);
-        // padding rows / columns: never read by the reduction (100 of 128: 39 % of the tile).  Streaming stores: 113 MB of partial sums per
-        // step that nobody reads before the end of backprop must not push the activations out of L2 / Infinity Cache
-        if (co < CO && ci < CI) __builtin_nontemporal_store(acc[t][i][rr], &out[co * CIP + ci]);
-      }
+    for (int i = 0; i < 2; i++) {
+      const int ci = ci0 + i * 16 + (lane >> 4) * 4;
+      if (co < CO && ci < CI) __builtin_nontemporal_store(acc[t][i], reinterpret_cast<f4v*>(&out[co * CIP + ci]));
+    }
   }
 }
 // (the reduction of the v2 partial sums lives in wgrad_reduce.h: it runs batched with the other layers' reductions)
@@ -2363,7 +2222,7 @@ bool igemm_conv_dgrad_pair(const Tensor* dy, const Tensor* w, const ConvGeom& g,
 // materialises relu(bn(x)) and convolves that)
 static bool ig_fwd_folds_affine(const ConvGeom& g, int dtype) { return ig_qualifies(g, dtype) && ig_plan(g, false, IgRequest{}).folds_affine; }
 // the weight gradient of a geometry that qualifies runs in the eight-wave kernel (ig_wgrad8h_kernel; else the four-wave one, ig_wgrad8v2_kernel)
-static bool wgrad_takes_eight_wave(const ConvGeom& g) { return sw().wgrad_wide && g.kh == 3 && g.Cin > WG_CI && g.Cout > 64; }
+static bool wgrad_takes_eight_wave(const ConvGeom& g) { return g.kh == 3 && g.Cin > WG_CI && g.Cout > 64; }
 // (only the eight-wave kernel rebuilds relu(bn(x)) while staging)
 static bool ig_wgrad_folds_affine(const ConvGeom& g, int dtype) { return ig_qualifies(g, dtype) && wgrad_takes_eight_wave(g); }
 // both directions apply the batch-norm table while staging: only then does folding the batch norm into this convolution save a pass
@@ -2422,10 +2281,9 @@ static WgradReduceArgs wgrad_reduce_args(int CO, int CI, int CIP, int COP, int R
 // into one of its inputs (queued after the launch), a stream / device synchronisation, the end of a graph capture.  LAMP_WGRAD_GROUP=0: every layer at once.
 static bool wg8h_group_defer(const Tensor* dy, const Tensor* x, Tensor* dw, const ConvGeom& g, hipStream_t st, const Tensor* affine) {
   const bool on = sw().wgrad_group;
-  const int shift_dy = (int)sw().wgrad_shift_dy;
   // large batches only (a workgroup still walks >= 16 images with half the workgroups), deferred reductions on, tensors the library owns (the
   // deferral is honoured by every access through Tensor::raw / data: a caller's own memory can change without the library seeing it)
-  if (!on || shift_dy < 2 || !wgrad_reduce_deferred() || g.N < 8 * (int64_t)num_cus()) return false;
+  if (!on || !wgrad_reduce_deferred() || g.N < 8 * (int64_t)num_cus()) return false;
   if (!dy->st->owned || !x->st->owned || !dw->st->owned || (affine && !affine->st->owned)) return false;
   wgrad_park(Wg8hProblem{dy, x, dw, g, affine}, st);
   return true;
@@ -2461,8 +2319,6 @@ void wg8h_launch(const Wg8hProblem& pa, const Wg8hProblem* pb, hipStream_t st, c
       return;
     }
   }
-  const int shift_dy = (int)sw().wgrad_shift_dy;   // 0: off, 1: dY rows, 2: + X columns in registers
-  LAMP_CHECK(!(pair || pb) || shift_dy >= 2, "internal: the weight-gradient pair / group needs the register-shifted X fragments");
   Hold partial2;
   if (pair) { int64_t ps2[1] = {(int64_t)A.nsplit * IG_M * A.CIP}; partial2 = Hold(new_tensor(ps2, 1, kF32, pa.x->device())); }
   const size_t lds = pair ? 4 * (size_t)(2 * IG_WTILE + WG_XCOPY + 512) : 4 * (size_t)WG_STAGE;
@@ -2481,27 +2337,14 @@ void wg8h_launch(const Wg8hProblem& pa, const Wg8hProblem* pb, hipStream_t st, c
       sp.affine = pb->affine ? reinterpret_cast<const float4*>(pb->affine->ptr<float>()) : (const float4*)nullptr;
       sp.wgs0 = A.wgs;
     }
-    const bool wg_stagger = sw().wgrad_stagger;
-    const bool wg_prio = sw().wgrad_prio;
-    // LAMP_WG8H_DMA=0 (run time): the dY tiles through registers and ds_write instead of LDS-DMA - the same arithmetic in the same order, kept
-    // as the fallback and the bitwise A/B of the hand-counted vmcnt waits (tests/test_ops_gpu.py)
-    const bool wg_dma = sw().wg8h_dma;
-    const int grid = A.wgs + (pb ? B.wgs : 0);
-#define IG_LAUNCH_WG8H(M_, P_)                                                                                                              \
-  do {                                                                                                                                      \
-    if (M_ == 2 && !wg_dma) { IG_LAUNCH_WG8H_(M_, P_, false); } else { IG_LAUNCH_WG8H_(M_, P_, true); }                                       \
-  } while (0)
-#define IG_LAUNCH_WG8H_(M_, P_, D_)                                                                                                         \
-  do {                                                                                                                                      \
-    allow_big_lds((const void*)ig_wgrad8h_kernel<M_, P_, D_>);                                                                             \
-    hipLaunchKernelGGL((ig_wgrad8h_kernel<M_, P_, D_>), dim3(grid), dim3(512), lds, st, pa.dy->ptr<bf16_t>(), pa.x->ptr<bf16_t>(),          \
-                       A.partial->ptr<float>(), (int)pa.g.N, (int)pa.g.Cout, (int)pa.g.Cin, A.CIP, A.ips, A.ntile, affp,                    \
-                       (wgrad_reduce_deferred() ? 1 : 0) | (wg_stagger ? 0 : 2) | (wg_prio ? 4 : 0), dy2p, p2p, co2, sp);                   \
-  } while (0)
-    if (pair) IG_LAUNCH_WG8H(2, true);
-    else if (shift_dy >= 2) IG_LAUNCH_WG8H(2, false); else if (shift_dy == 1) IG_LAUNCH_WG8H(1, false); else IG_LAUNCH_WG8H(0, false);
-#undef IG_LAUNCH_WG8H
-#undef IG_LAUNCH_WG8H_
+    // LAMP_WG8H_DMA=0: the dY tiles through registers and ds_write instead of LDS-DMA - the same arithmetic in the same order, kept as the
+    // bitwise reference of the hand-counted vmcnt waits (tests/test_ops_gpu.py)
+    const bool dma = sw().wg8h_dma;
+    const auto kfn = pair ? (dma ? ig_wgrad8h_kernel<true, true> : ig_wgrad8h_kernel<true, false>)
+                          : (dma ? ig_wgrad8h_kernel<false, true> : ig_wgrad8h_kernel<false, false>);
+    allow_big_lds((const void*)kfn);
+    hipLaunchKernelGGL(kfn, dim3(A.wgs + (pb ? B.wgs : 0)), dim3(512), lds, st, pa.dy->ptr<bf16_t>(), pa.x->ptr<bf16_t>(), A.partial->ptr<float>(),
+                       (int)pa.g.N, (int)pa.g.Cout, (int)pa.g.Cin, A.CIP, A.ips, A.ntile, affp, dy2p, p2p, co2, sp);
     LAMP_LAUNCH_CHECK();
   }
   auto enqueue = [&](const Wg8hProblem& p, Plan& q) {
@@ -2534,10 +2377,8 @@ static bool igemm_conv_wgrad_impl(const Tensor* dy, const Tensor* x, Tensor* dw,
     const int CIP = g.Cin <= 16 ? 16 : (all_ci ? 4 : ntile) * WG_CI;   // columns of a partial-sum tile (see tile_active in the kernel)
     const bool narrow = g.Cout <= 64 || g.Cin <= 16;               // the NARROW instantiation (branches in the MFMA chain) only where it pays
     const int COP = narrow ? (int)((g.Cout + 15) / 16) * 16 : IG_M;  // rows
-    const int wgs_per_cu = (int)sw().wgrad_wgs_per_cu;
-    // one workgroup per CU: half the partial-sum traffic of two, same speed
-    const int narrow_per_cu = (int)sw().wgrad_narrow_per_cu;   // measured: 2 and 3 are 1 % slower on the step
-    const WgradSplit split = wgrad_split(g.N, num_cus() * (narrow ? narrow_per_cu : wgs_per_cu), ntile);
+    // one workgroup per CU: half the partial-sum traffic of two, same speed (the narrow instantiation: 2 and 3 per CU are 1 % slower on the step)
+    const WgradSplit split = wgrad_split(g.N, num_cus(), ntile);
     const int ips = split.ips, nsplit = split.nsplit;
     int64_t ps[1] = {(int64_t)nsplit * RS * COP * CIP};
     Hold partial(new_tensor(ps, 1, kF32, x->device()));
@@ -2551,8 +2392,7 @@ static bool igemm_conv_wgrad_impl(const Tensor* dy, const Tensor* x, Tensor* dw,
       const double sec_fl = pair ? conv_flops(*second->g) : 0.0;
       const double sec_by = pair ? conv_bytes(*second->g, 2) - (double)g.N * g.Cin * 64 * 2 : 0.0;
       KernelTimer kt("conv_wgrad_igemm", conv_flops(g) + sec_fl, conv_bytes(g, 2) + sec_by, st);
-      const bool ci16_on = sw().wgrad_ci16;
-      const bool ci16 = ci16_on && KS == 3 && CIP == 16;           // (then `narrow` holds: Cin <= 16)
+      const bool ci16 = KS == 3 && CIP == 16;                      // (then `narrow` holds: Cin <= 16)
       const void* kfn = ci16    ? (pair ? (const void*)ig_wgrad8v2_kernel<3, true, 1, true, true> : (const void*)ig_wgrad8v2_kernel<3, true, 1, false, true>)
                       : pair    ? (narrow ? (const void*)ig_wgrad8v2_kernel<3, true, 1, true> : (const void*)ig_wgrad8v2_kernel<3, false, 1, true>)
                       : KS == 3 ? (narrow ? (const void*)ig_wgrad8v2_kernel<3, true, 1> : (const void*)ig_wgrad8v2_kernel<3, false, 1>)
@@ -2581,8 +2421,7 @@ bool igemm_conv_wgrad(const Tensor* dy, const Tensor* x, Tensor* dw, const ConvG
 // the LDS the shifted X copies no longer need): the values of the two separate launches up to the order the image ranges are summed in for dw1;
 // false = nothing launched
 bool igemm_conv_wgrad_pair(const Tensor* dy, const Tensor* dy1, const Tensor* x, Tensor* dw, Tensor* dw1, const ConvGeom& g, const ConvGeom& g1, hipStream_t st) {
-  // (the switch alone, not wgrad_takes_eight_wave: with it on, BOTH weight-gradient kernels take a pair - the comment below)
-  if (!sw().conv_wgrad_pair || !sw().wgrad_wide || sw().wgrad_shift_dy < 2) return false;
+  if (!sw().conv_wgrad_pair) return false;
   if (!ig_qualifies(g, x->dtype) || !ig_qualifies(g1, x->dtype) || g.kh != 3 || g1.kh != 1) return false;
   if (g.Cin != g1.Cin || g.N != g1.N) return false;
   // (more than 32 input and 64 output channels: the eight-wave kernel; else the four-wave kernel, one Cin slice per workgroup)

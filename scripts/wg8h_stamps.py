@@ -25,7 +25,7 @@ rc = dll.lamp_debug_wg8h_stamps(buf, n)
 a = np.frombuffer(buf, dtype=np.uint32).reshape(256, 8, 8).astype(np.float64)
 names = ["loop", "late C0", "store", "load issue", "early C0", "C1", "barrier", "kernel"]
 pairs = 16
-print("rc", rc, "cycles per PAIR of images (mean over 256 workgroups); prio", os.environ.get("LAMP_WGRAD_PRIO", "1"), "stagger", os.environ.get("LAMP_WGRAD_STAGGER", "1"))
+print("rc", rc, "cycles per PAIR of images (mean over 256 workgroups)")
 for grp, sl in (("waves 0-3 (early)", slice(0, 4)), ("waves 4-7 (late) ", slice(4, 8))):
     m = a[:, sl, :].mean(axis=(0, 1))
     print(grp, " ".join(f"{names[k]} {m[k] / (pairs if k not in (0, 7) else 1):.0f}" for k in range(8)), f"| loop per pair {m[0] / pairs:.0f}")

@@ -1538,12 +1538,14 @@ def test_weight_gradients_of_a_block_s_two_first_convolutions(gpu, case):
     assert_close(pb, rb.double(), tol, "1x1 against the oracle")
 
 
-@pytest.mark.parametrize("min_ips", ["2", "3"])
+@pytest.mark.parametrize("min_ips", ["2", "3", "8"])
 def test_eight_wave_weight_gradient_dma_and_register_forms_agree_bit_for_bit(gpu, min_ips):
     """`ig_wgrad8h_kernel` brings its dY tiles in by LDS-DMA through inline asm with hand-counted `s_waitcnt vmcnt` (correct only while
     hipcc keeps its own waits where they are).  The register form of the same kernel (`LAMP_WG8H_DMA=0`, a run-time switch and the fallback) does
     the same arithmetic in the same order, so over odd batches, image ranges of one to three images, Cout < 128 and Cin off the 32-channel grid
-    - alone and with the shortcut's gradient riding along - the two must agree BIT FOR BIT.  One child process per form (the switch is read once)."""
+    - alone and with the shortcut's gradient riding along - the two must agree BIT FOR BIT.  One child process per form (the switch is read once).
+    `min_ips` 8: from eight images per workgroup on, waves 4 - 7 multiply a pair's first image before they store / request (the kernel's `late`); the
+    batches of 9, 64, 131 and 259 images then walk ranges of 8 with last ranges of 1, 3 and 3 - the staggered order with a ragged last pair."""
     import subprocess
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
