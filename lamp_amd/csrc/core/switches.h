@@ -65,8 +65,8 @@ constexpr int64_t SW_NO_CLAMP = INT64_MIN;
   X(ncv_pitch, "LAMP_NCV_PITCH", BOOL, 1, 0, "narrow kernels widen the LDS row pitch to a bank-conflict-free one")                        \
   X(ncv_two_shift, "LAMP_NCV_TWO_SHIFT", BOOL, 1, 0, "narrow kernels: two output phases per MFMA where the columns allow it")             \
   X(ncv_per_cu, "LAMP_NCV_PER_CU", INT, 4, 1, "narrow kernels: most workgroups per CU")                                                   \
-  X(pack_cache, "LAMP_PACK_CACHE", BOOL, 1, 0, "packed filter images are cached per parameter and storage version")                       \
-  X(pack_after_step, "LAMP_PACK_AFTER_STEP", BOOL, 1, 0, "the optimiser repacks every cached filter image in one launch (0: lazily at first use)") \
+  X(pack_cache, "LAMP_PACK_CACHE", BOOL, 1, 0, "packed filter images are cached per parameter and storage version (all four packing backends: core/pack_cache.h)") \
+  X(pack_after_step, "LAMP_PACK_AFTER_STEP", BOOL, 1, 0, "the optimiser repacks every cached filter image of all four backends in place (0: lazily at first use)") \
   /* bf16 implicit GEMM, forward and input gradient (kernels/conv_igemm.hip: ig_form) */                                                  \
   X(ig_small_d, "LAMP_IG_SMALL_D", BOOL, 1, 0, "the eight-image kernel for at most 64 output channels too")                               \
   X(ig_w8, "LAMP_IG_W8", BOOL, 1, 0, "two-image 128-row kernel: eight waves per image pair at one workgroup per CU or fewer (0: four)")  \

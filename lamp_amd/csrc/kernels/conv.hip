@@ -13,7 +13,9 @@
 // in conv_igemm.hip and are selected by conv_dispatch when the geometry qualifies.
 #include "device_utils.h"
 #include "../core/strided.h"
+#include "../core/switches.h"
 #include "conv_geom.h"
+#include "conv_backends.h"
 
 namespace lamp {
 
@@ -287,38 +289,15 @@ template <class T> static void launch_wgrad(const Tensor* dy, const Tensor* x, T
   LAMP_LAUNCH_CHECK();
 }
 
-// implemented in conv_igemm.hip; return true when they handled the request
-bool igemm_conv_fwd(const Tensor* x, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, hipStream_t st);
-bool igemm_conv_fwd_pair(const Tensor* x, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, const Tensor* w1, const Tensor* bias1,
-                         Tensor* y1, const ConvGeom& g1, hipStream_t st);
-// addend (optional): dx = round(round(dgrad) + addend) when the kernel chosen has that epilogue; *addend_fused reports whether it was used
-bool igemm_conv_dgrad(const Tensor* dy, const Tensor* w, Tensor* dx, const ConvGeom& g, hipStream_t st, const Tensor* addend = nullptr,
-                      bool* addend_fused = nullptr);
-bool igemm_conv_wgrad(const Tensor* dy, const Tensor* x, Tensor* dw, const ConvGeom& g, hipStream_t st, const Tensor* affine = nullptr);
-bool igemm_conv_folds_affine(const ConvGeom& g, int dtype);
-bool igemm_conv_fwd_affine(const Tensor* x, const Tensor* affine, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, hipStream_t st);
-// implemented in conv_igemm_f32.hip (the same layers in f32, on the f32 matrix instructions)
-bool igemm32_conv_fwd(const Tensor* x, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, hipStream_t st);
-bool igemm32_conv_dgrad(const Tensor* dy, const Tensor* w, Tensor* dx, const ConvGeom& g, hipStream_t st, const Tensor* addend = nullptr,
-                        bool* addend_fused = nullptr);
-bool igemm32_conv_wgrad(const Tensor* dy, const Tensor* x, Tensor* dw, const ConvGeom& g, hipStream_t st);
-// implemented in conv_small.hip (narrow layers: image-per-workgroup LDS kernels)
-bool narrow_conv_fwd(const Tensor* x, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, hipStream_t st);
-bool narrow_conv_fwd_pair(const Tensor* x, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, const Tensor* w1, const Tensor* bias1,
-                          Tensor* y1, const ConvGeom& g1, hipStream_t st);
-bool narrow_conv_dgrad(const Tensor* dy, const Tensor* w, Tensor* dx, const ConvGeom& g, hipStream_t st, const Tensor* addend = nullptr,
-                       bool* addend_fused = nullptr);
-bool narrow_conv_dgrad_pair(const Tensor* dy, const Tensor* w, const ConvGeom& g, const Tensor* dy1, const Tensor* w1, const ConvGeom& g1, Tensor* dx,
-                            hipStream_t st, const Tensor* addend, bool* addend_fused);
-bool igemm_conv_dgrad_pair(const Tensor* dy, const Tensor* w, const ConvGeom& g, const Tensor* dy1, const Tensor* w1, const ConvGeom& g1, Tensor* dx,
-                           hipStream_t st, const Tensor* addend, bool* addend_fused);
-bool narrow_conv_wgrad(const Tensor* dy, const Tensor* x, Tensor* dw, const ConvGeom& g, hipStream_t st);
-bool narrow_conv_wgrad_pair(const Tensor* dy, const Tensor* dy1, const Tensor* x, Tensor* dw, Tensor* dw1, const ConvGeom& g, const ConvGeom& g1, hipStream_t st);
-bool igemm_conv_wgrad_pair(const Tensor* dy, const Tensor* dy1, const Tensor* x, Tensor* dw, Tensor* dw1, const ConvGeom& g, const ConvGeom& g1, hipStream_t st);
-bool small_conv_fwd(const Tensor* x, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, hipStream_t st);
-bool small_conv_dgrad(const Tensor* dy, const Tensor* w, Tensor* dx, const ConvGeom& g, hipStream_t st, const Tensor* addend = nullptr,
-                      bool* addend_fused = nullptr);
-bool small_conv_wgrad(const Tensor* dy, const Tensor* x, Tensor* dw, const ConvGeom& g, hipStream_t st);
+// The optimisers' hook: the packed filter images of the parameters just written on this stream follow the update in place, in one launch
+// per backend (the narrow images ride in the implicit-GEMM one) - the next step's convolutions, and a HIP graph captured earlier, find
+// them fresh.  Values are exactly those a lazy pack at first use would produce.  LAMP_PACK_AFTER_STEP=0 restores the lazy packs.
+void conv_repack_cached(lamp_tensor* const* params, int n, hipStream_t st) {
+  if (!sw().pack_after_step) return;
+  igemm_repack_cached(params, n, st);
+  igemm32_repack_cached(params, n, st);
+  small_repack_cached(params, n, st);
+}
 
 Tensor* reduce_dims(const Tensor* a, const int64_t* dims, int ndims, bool keepdim, int op);
 

@@ -1,0 +1,58 @@
+// Host entry points of the convolution backends that conv_dispatch (conv.hip) tries in turn.  The bool ones return true when they
+// handled the request and false with nothing launched.
+#pragma once
+#include "../core/tensor.h"
+#include "conv_geom.h"
+
+namespace lamp {
+struct NcvPackMany;   // conv_narrow_pack.h
+
+// ---- conv_igemm.hip: bf16 implicit GEMM on the matrix cores, the wide 3x3 / 1x1 layers on 8 x 8 maps
+bool igemm_conv_fwd(const Tensor* x, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, hipStream_t st);
+bool igemm_conv_fwd_pair(const Tensor* x, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, const Tensor* w1, const Tensor* bias1,
+                         Tensor* y1, const ConvGeom& g1, hipStream_t st);
+// addend (optional): dx = round(round(dgrad) + addend) when the kernel chosen has that epilogue; *addend_fused reports whether it was used
+bool igemm_conv_dgrad(const Tensor* dy, const Tensor* w, Tensor* dx, const ConvGeom& g, hipStream_t st, const Tensor* addend = nullptr,
+                      bool* addend_fused = nullptr);
+bool igemm_conv_dgrad_pair(const Tensor* dy, const Tensor* w, const ConvGeom& g, const Tensor* dy1, const Tensor* w1, const ConvGeom& g1, Tensor* dx,
+                           hipStream_t st, const Tensor* addend, bool* addend_fused);
+bool igemm_conv_wgrad(const Tensor* dy, const Tensor* x, Tensor* dw, const ConvGeom& g, hipStream_t st, const Tensor* affine = nullptr);
+bool igemm_conv_wgrad_pair(const Tensor* dy, const Tensor* dy1, const Tensor* x, Tensor* dw, Tensor* dw1, const ConvGeom& g, const ConvGeom& g1, hipStream_t st);
+bool igemm_conv_folds_affine(const ConvGeom& g, int dtype);
+bool igemm_conv_fwd_affine(const Tensor* x, const Tensor* affine, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, hipStream_t st);
+
+// ---- conv_igemm_f32.hip: the same layers in f32 / f64, on the f32 / f64 matrix instructions
+bool igemm32_conv_fwd(const Tensor* x, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, hipStream_t st);
+bool igemm32_conv_dgrad(const Tensor* dy, const Tensor* w, Tensor* dx, const ConvGeom& g, hipStream_t st, const Tensor* addend = nullptr,
+                        bool* addend_fused = nullptr);
+bool igemm32_conv_wgrad(const Tensor* dy, const Tensor* x, Tensor* dw, const ConvGeom& g, hipStream_t st);
+
+// ---- conv_narrow.hip: bf16 layers of at most 16 channels on the matrix cores
+bool narrow_conv_fwd(const Tensor* x, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, hipStream_t st);
+bool narrow_conv_fwd_pair(const Tensor* x, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, const Tensor* w1, const Tensor* bias1,
+                          Tensor* y1, const ConvGeom& g1, hipStream_t st);
+bool narrow_conv_dgrad(const Tensor* dy, const Tensor* w, Tensor* dx, const ConvGeom& g, hipStream_t st, const Tensor* addend = nullptr,
+                       bool* addend_fused = nullptr);
+bool narrow_conv_dgrad_pair(const Tensor* dy, const Tensor* w, const ConvGeom& g, const Tensor* dy1, const Tensor* w1, const ConvGeom& g1, Tensor* dx,
+                            hipStream_t st, const Tensor* addend, bool* addend_fused);
+bool narrow_conv_wgrad(const Tensor* dy, const Tensor* x, Tensor* dw, const ConvGeom& g, hipStream_t st);
+bool narrow_conv_wgrad_pair(const Tensor* dy, const Tensor* dy1, const Tensor* x, Tensor* dw, Tensor* dw1, const ConvGeom& g, const ConvGeom& g1, hipStream_t st);
+
+// ---- conv_small.hip: narrow layers, image-per-workgroup LDS kernels (bf16 / f32 / f64)
+bool small_conv_fwd(const Tensor* x, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, hipStream_t st);
+bool small_conv_dgrad(const Tensor* dy, const Tensor* w, Tensor* dx, const ConvGeom& g, hipStream_t st, const Tensor* addend = nullptr,
+                      bool* addend_fused = nullptr);
+bool small_conv_wgrad(const Tensor* dy, const Tensor* x, Tensor* dw, const ConvGeom& g, hipStream_t st);
+
+// ---- the optimisers' hook (optim.hip calls it right after it has written the parameters; conv.hip): every packed image of these parameters
+// that is cached on this stream is packed again, in place, and its entry moved to the new storage version (core/pack_cache.h)
+void conv_repack_cached(lamp_tensor* const* params, int n, hipStream_t st);
+// ... its per-backend parts; igemm's takes the narrow images' last batch along in its launch: with `fill`, narrow's hands that batch of at most
+// NCV_PACK_MAX images to the caller (*fill, *fill_cnt) instead of launching it
+void igemm_repack_cached(lamp_tensor* const* params, int n, hipStream_t st);
+void igemm32_repack_cached(lamp_tensor* const* params, int n, hipStream_t st);
+void small_repack_cached(lamp_tensor* const* params, int n, hipStream_t st);
+void narrow_repack_cached(lamp_tensor* const* params, int n, hipStream_t st, NcvPackMany* fill, int* fill_cnt);
+void narrow_pack_launch(const NcvPackMany& a, int cnt, hipStream_t st);
+
+}  // namespace lamp

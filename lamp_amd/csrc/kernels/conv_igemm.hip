@@ -32,11 +32,10 @@
 //   * ig_wgrad8v2_kernel: four waves, workgroup = (32-channel slice of Cin, image range), all taps in registers - narrow layers and 1x1s;
 //   * ig_wgrad8h_kernel: eight waves, two per SIMD, the same decomposition - 3x3 layers with more than 32 input and 64 output
 //     channels; takes a sibling 1x1's weight gradient or a second layer into the same launch.
-#include <map>
-#include <mutex>
-#include <tuple>
 #include "device_utils.h"
 #include "conv_geom.h"
+#include "conv_backends.h"
+#include "../core/pack_cache.h"
 #include "wgrad_reduce.h"
 #include <thread>
 #include "conv_narrow_pack.h"
@@ -1886,24 +1885,10 @@ static bool ig_qualifies(const ConvGeom& g, int dtype) {
 }
 static int pad_k(int64_t c) { return c <= 64 ? 64 : 128; }
 
-// Both packed layouts of a weight tensor (fprop and dgrad) are produced by ONE launch and cached per (weight storage, view,
-// stream) while the storage's version is unchanged: every kernel that writes a tensor obtains a mutable pointer through
-// Tensor::data()/ptr<T>(), which bumps the version (core/tensor.h), so "same version" proves "same contents".  In a training
-// step the weights change once (the optimiser), so each convolution packs once per step instead of once per fprop and once
-// per dgrad; with frozen weights (evaluation, gradient accumulation) nothing is repacked at all.  Storages that wrap caller
-// memory (lamp_tensor_from_blob) are never cached.  LAMP_PACK_CACHE=0 disables the cache.
-namespace {
-struct PackKey {
-  uint64_t uid; int64_t offset; int KS, Cout, Cin; hipStream_t st;
-  bool operator<(const PackKey& o) const { return std::tie(uid, offset, KS, Cout, Cin, st) < std::tie(o.uid, o.offset, o.KS, o.Cout, o.Cin, o.st); }
-};
-struct PackVal { uint64_t version; Tensor* packed; uint64_t tick; bool pinned = false; };   // pinned: a captured HIP graph reads this image's address
-std::mutex g_pack_mu;
-std::map<PackKey, PackVal> g_pack_cache;
-uint64_t g_pack_tick = 0;
-}  // namespace
+// Both packed layouts of a weight tensor (fprop and dgrad) are produced by ONE launch and cached (core/pack_cache.h): each convolution
+// packs once per step instead of once per fprop and once per dgrad.
+static PackCache g_ig_packs;
 
-static int pad_k(int64_t c);
 // returns a +1 handle on the buffer [fprop image | dgrad image]; *dgrad_offset = element offset of the second image
 // (tail_offset, optional: element offsets of the fprop / dgrad K-tail images, -1 where the filter has none - ig_tail_ok)
 static Tensor* packed_weights(const Tensor* w, const ConvGeom& g, int KS, hipStream_t st, int64_t* dgrad_offset, int64_t* tail_offset = nullptr) {
@@ -1913,94 +1898,50 @@ static Tensor* packed_weights(const Tensor* w, const ConvGeom& g, int KS, hipStr
   const int64_t ntf = ig_tail_ok((int)g.Cin, KS) ? IG_TAIL_ELEMS : 0, ntd = ig_tail_ok((int)g.Cout, KS) ? IG_TAIL_ELEMS : 0;
   *dgrad_offset = nf;
   if (tail_offset) { tail_offset[0] = ntf ? nf + nd : -1; tail_offset[1] = ntd ? nf + nd + ntf : -1; }
-  const bool cache_on = sw().pack_cache;
-  const bool cacheable = cache_on && w->st->owned && !w->st->scratch;
-  const PackKey key{w->st->uid, w->offset, KS, (int)g.Cout, (int)g.Cin, st};
-  const uint64_t ver = w->st->version.load(std::memory_order_relaxed);
-  if (cacheable) {
-    std::lock_guard<std::mutex> lk(g_pack_mu);
-    auto it = g_pack_cache.find(key);
-    if (it != g_pack_cache.end() && it->second.version == ver) {
-      it->second.tick = ++g_pack_tick;
-      if (allocator_capturing()) it->second.pinned = true;   // the graph being captured records this address: never evict the entry
-      return retain(it->second.packed);
-    }
-  }
+  const bool cacheable = PackCache::cacheable(w);
+  const PackKey key = PackKey::filter(w, KS, (int)g.Cout, (int)g.Cin, st);
+  const uint64_t ver = PackCache::version_of(w);
+  if (cacheable) if (Tensor* hit = g_ig_packs.find(key, ver)) return hit;
   int64_t ps[1] = {nf + nd + ntf + ntd};
   Hold wp(new_tensor(ps, 1, kBF16, w->device()));
   hipLaunchKernelGGL(ig_pack_weights_kernel, dim3(grid_for(ps[0], 256)), dim3(256), 0, st, w->ptr<bf16_t>(), wp->ptr<bf16_t>(), (int)g.Cout,
                      (int)g.Cin, KS, KPf, KPd);
   LAMP_LAUNCH_CHECK();
-  if (cacheable) {
-    std::lock_guard<std::mutex> lk(g_pack_mu);
-    auto it = g_pack_cache.find(key);
-    if (it != g_pack_cache.end()) { release(it->second.packed); g_pack_cache.erase(it); }
-    if (g_pack_cache.size() >= 256) {           // evict the least recently used entry that no captured graph reads
-      auto victim = g_pack_cache.end();
-      for (auto i = g_pack_cache.begin(); i != g_pack_cache.end(); ++i)
-        if (!i->second.pinned && (victim == g_pack_cache.end() || i->second.tick < victim->second.tick)) victim = i;
-      if (victim != g_pack_cache.end()) { release(victim->second.packed); g_pack_cache.erase(victim); }
-    }
-    g_pack_cache[key] = PackVal{ver, retain(wp.get()), ++g_pack_tick, allocator_capturing()};
-  }
+  if (cacheable) g_ig_packs.insert(key, ver, 0, wp.get());
   return wp.take();
 }
 
-// Called by the optimisers right after they have written the parameters: every parameter whose packed images are cached (i.e. that an
-// implicit-GEMM convolution used before, on this stream) is packed again now, all of them in one launch, and the cache entries are
-// moved to the new storage version - the next step's convolutions find them fresh.  Values are exactly those a lazy pack at first use
-// would produce (same kernel body, same weights).  LAMP_PACK_AFTER_STEP=0 restores the lazy packs.
-void narrow_repack_cached(lamp_tensor* const* params, int n, hipStream_t st, NcvPackMany* fill, int* fill_cnt);   // conv_narrow.hip
-void narrow_pack_launch(const NcvPackMany& a, int cnt, hipStream_t st);
-// (round 5: ... and the narrow convolutions' fragment images ride in the last of these launches - the step had two pack launches of 4 - 6 us)
+// The optimisers' hook (conv_repack_cached): one launch per IG_PACK_MAX cached images, and the narrow convolutions' fragment images ride in
+// the last of these launches (round 5: the step had two pack launches of 4 - 6 us)
 void igemm_repack_cached(lamp_tensor* const* params, int n, hipStream_t st) {
-  const bool on = sw().pack_after_step;
-  if (!on) return;
   NcvPackMany nb;
   int ncnt = 0;
   narrow_repack_cached(params, n, st, &nb, &ncnt);
-  struct NarrowLeft { const NcvPackMany& b; int& c; hipStream_t s; ~NarrowLeft() { if (c > 0) narrow_pack_launch(b, c, s); } } narrow_left{nb, ncnt, st};
   PackMany a;
-  int cnt = 0, maxtotal = 0;
-  std::vector<std::pair<PackKey, uint64_t>> done;       // (entry, storage version its image now corresponds to)
-  std::lock_guard<std::mutex> lk(g_pack_mu);
-  auto flush = [&] {                                    // one launch per IG_PACK_MAX images (the loop used to STOP there, and a
-    if (cnt == 0) return;                               // replayed graph that had captured a cache hit kept reading the stale image)
-    hipLaunchKernelGGL(ig_pack_weights_many_kernel, dim3((unsigned)std::min(512, (maxtotal + 255) / 256), (unsigned)cnt), dim3(256), 0, st, a);
-    LAMP_LAUNCH_CHECK();
-    cnt = 0; maxtotal = 0;
-  };
-  for (int i = 0; i < n; i++) {
-    if (cnt == IG_PACK_MAX) flush();
-    const Tensor* w = params[i];
-    if (!w || !w->is_device() || w->dtype != kBF16 || w->ndim != 4 || !w->st->owned || !w->is_contiguous()) continue;
-    for (auto& kv : g_pack_cache) {
-      if (kv.first.uid != w->st->uid || kv.first.offset != w->offset || kv.first.st != st) continue;
-      if (kv.first.Cout != (int)w->sizes[0] || kv.first.Cin != (int)w->sizes[1] || kv.first.KS != (int)w->sizes[2]) continue;
-      const int KS = kv.first.KS, RS = KS * KS, KPf = pad_k(kv.first.Cin), KPd = pad_k(kv.first.Cout);
-      const int total = RS * IG_M * (KPf + KPd) + (ig_tail_ok(kv.first.Cin, KS) ? IG_TAIL_ELEMS : 0) + (ig_tail_ok(kv.first.Cout, KS) ? IG_TAIL_ELEMS : 0);
-      if (kv.second.packed->numel() != total) continue;
-      a.w[cnt] = w->ptr<bf16_t>(); a.Cout[cnt] = kv.first.Cout; a.Cin[cnt] = kv.first.Cin; a.KS[cnt] = KS; a.KPf[cnt] = KPf; a.KPd[cnt] = KPd;
-      // IN PLACE: the entry belongs to this stream, so every convolution that read the old image is ordered before this launch - and a
-      // HIP graph captured earlier keeps reading the same address (bench.py replays forward + backprop around the eager optimiser)
-      a.wp[cnt] = static_cast<bf16_t*>(kv.second.packed->raw());
-      done.push_back({kv.first, w->st->version.load(std::memory_order_relaxed)});
-      maxtotal = std::max(maxtotal, total);
-      cnt++;
-      break;
-    }
-  }
+  int maxtotal = 0;
   static_assert(NCV_NKMAX * 64 <= 4 * 256, "a narrow image is four blocks of the pack kernel");
-  if (cnt > 0 && ncnt > 0 && 4 * ncnt <= std::min(512, (maxtotal + 255) / 256)) {      // the last batch takes the narrow images along
-    hipLaunchKernelGGL(ig_ncv_pack_many_kernel, dim3((unsigned)std::min(512, (maxtotal + 255) / 256), (unsigned)(cnt + 1)), dim3(256), 0, st, a, nb, cnt, ncnt);
-    LAMP_LAUNCH_CHECK();
-    cnt = 0; ncnt = 0;
-  }
-  flush();
-  for (auto& d : done) {
-    auto it = g_pack_cache.find(d.first);
-    if (it != g_pack_cache.end()) { it->second.version = d.second; it->second.tick = ++g_pack_tick; }
-  }
+  g_ig_packs.repack(params, n, st, kBF16, IG_PACK_MAX,
+      [&](int slot, const Tensor* w, const PackKey& k, Tensor* packed) {
+        const int KS = k.tag[0], Cout = k.tag[1], Cin = k.tag[2];
+        const int total = KS * KS * IG_M * (pad_k(Cin) + pad_k(Cout)) + (ig_tail_ok(Cin, KS) ? IG_TAIL_ELEMS : 0) + (ig_tail_ok(Cout, KS) ? IG_TAIL_ELEMS : 0);
+        if (packed->numel() != total) return false;
+        a.w[slot] = w->ptr<bf16_t>(); a.Cout[slot] = Cout; a.Cin[slot] = Cin; a.KS[slot] = KS; a.KPf[slot] = pad_k(Cin); a.KPd[slot] = pad_k(Cout);
+        a.wp[slot] = static_cast<bf16_t*>(packed->raw());           // in place
+        maxtotal = std::max(maxtotal, total);
+        return true;
+      },
+      [&](int cnt, bool last) {
+        const unsigned gx = (unsigned)std::min(512, (maxtotal + 255) / 256);
+        if (last && ncnt > 0 && 4 * ncnt <= (int)gx) {                 // the last batch takes the narrow images along
+          hipLaunchKernelGGL(ig_ncv_pack_many_kernel, dim3(gx, (unsigned)(cnt + 1)), dim3(256), 0, st, a, nb, cnt, ncnt);
+          ncnt = 0;
+        } else {
+          hipLaunchKernelGGL(ig_pack_weights_many_kernel, dim3(gx, (unsigned)cnt), dim3(256), 0, st, a);
+        }
+        LAMP_LAUNCH_CHECK();
+        maxtotal = 0;
+      });
+  if (ncnt > 0) narrow_pack_launch(nb, ncnt, st);                     // (no implicit-GEMM batch to ride in)
 }
 
 // The kernel form a geometry takes:

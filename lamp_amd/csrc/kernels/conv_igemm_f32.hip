@@ -26,12 +26,11 @@
 //    the 34 X values its k-slots can meet under any tap (X[ci][16q - 9 .. 16q + 24]) ONCE; every MFMA then takes its operands straight
 //    from those registers.  Taps whose column falls outside the image for a whole k-step are skipped (132 instead of 144 MFMAs per image).
 //    The partial sums per image range are reduced by the batched kernel of wgrad_reduce.hip (f32) or by a small kernel here (f64).
-#include <map>
-#include <mutex>
-#include <tuple>
 #include <type_traits>
 #include "device_utils.h"
 #include "conv_geom.h"
+#include "conv_backends.h"
+#include "../core/pack_cache.h"
 #include "wgrad_reduce.h"
 #include "../core/switches.h"
 
@@ -491,25 +490,22 @@ static bool ig32_qualifies(const ConvGeom& g, int dtype) {
 }
 static int pad16(int64_t c) { return (int)((c + 15) / 16) * 16; }
 
-// packed images [fprop | dgrad], cached per (weight storage, view, stream) while the storage's version is unchanged and re-packed in
-// place by the optimiser (see conv_igemm.hip: the same discipline, a separate cache because the element type differs)
-namespace {
-struct PackKey32 {
-  uint64_t uid; int64_t offset; int KS, Cout, Cin, dtype; hipStream_t st;
-  bool operator<(const PackKey32& o) const { return std::tie(uid, offset, KS, Cout, Cin, dtype, st) < std::tie(o.uid, o.offset, o.KS, o.Cout, o.Cin, o.dtype, o.st); }
-};
-struct PackVal32 { uint64_t version; Tensor* packed; uint64_t tick;  bool pinned = false; };
-std::mutex g_pack32_mu;
-std::map<PackKey32, PackVal32> g_pack32_cache;
-uint64_t g_pack32_tick = 0;
-}  // namespace
+// packed images [fprop | dgrad], cached and re-packed in place by the optimiser's hook (core/pack_cache.h)
+static PackCache g_ig32_packs;
 
-template <class T> static void launch_pack32(const T* w, T* wp, int Cout, int Cin, int KS, hipStream_t st) {
-  PackManyT<T> a;
-  a.w[0] = w; a.wp[0] = wp; a.Cout[0] = Cout; a.Cin[0] = Cin; a.KS[0] = KS; a.KPf[0] = pad16(Cin); a.KPd[0] = pad16(Cout);
-  const int total = KS * KS * F_ROWS * (a.KPf[0] + a.KPd[0]);
-  hipLaunchKernelGGL((ig32_pack_weights_many_kernel<T>), dim3((unsigned)std::min(512, (total + 255) / 256), 1u), dim3(256), 0, st, a);
+template <class T> static void launch_pack32(const PackManyT<T>& a, int cnt, int maxtotal, hipStream_t st) {
+  hipLaunchKernelGGL((ig32_pack_weights_many_kernel<T>), dim3((unsigned)std::min(512, (maxtotal + 255) / 256), (unsigned)cnt), dim3(256), 0, st, a);
   LAMP_LAUNCH_CHECK();
+}
+// slot of the pack kernel's argument block; returns the image's element count
+template <class T> static int fill_pack32(PackManyT<T>& a, int slot, const T* w, T* wp, int Cout, int Cin, int KS) {
+  a.w[slot] = w; a.wp[slot] = wp; a.Cout[slot] = Cout; a.Cin[slot] = Cin; a.KS[slot] = KS; a.KPf[slot] = pad16(Cin); a.KPd[slot] = pad16(Cout);
+  return KS * KS * F_ROWS * (a.KPf[slot] + a.KPd[slot]);
+}
+template <class T> static void pack32_one(const Tensor* w, Tensor* wp, int Cout, int Cin, int KS, hipStream_t st) {
+  PackManyT<T> a;
+  const int total = fill_pack32<T>(a, 0, w->ptr<T>(), wp->ptr<T>(), Cout, Cin, KS);
+  launch_pack32<T>(a, 1, total, st);
 }
 
 static Tensor* packed_weights32(const Tensor* w, const ConvGeom& g, int KS, hipStream_t st, int64_t* dgrad_offset) {
@@ -517,77 +513,31 @@ static Tensor* packed_weights32(const Tensor* w, const ConvGeom& g, int KS, hipS
   const int KPf = pad16(g.Cin), KPd = pad16(g.Cout);
   const int64_t nf = (int64_t)RS * F_ROWS * KPf, nd = (int64_t)RS * F_ROWS * KPd;
   *dgrad_offset = nf;
-  const bool cache_on = sw().pack_cache;
-  const bool cacheable = cache_on && w->st->owned && !w->st->scratch;
-  const PackKey32 key{w->st->uid, w->offset, KS, (int)g.Cout, (int)g.Cin, w->dtype, st};
-  const uint64_t ver = w->st->version.load(std::memory_order_relaxed);
-  if (cacheable) {
-    std::lock_guard<std::mutex> lk(g_pack32_mu);
-    auto it = g_pack32_cache.find(key);
-    if (it != g_pack32_cache.end() && it->second.version == ver) {
-      it->second.tick = ++g_pack32_tick;
-      if (allocator_capturing()) it->second.pinned = true;
-      return retain(it->second.packed);
-    }
-  }
+  const bool cacheable = PackCache::cacheable(w);
+  const PackKey key = PackKey::filter(w, KS, (int)g.Cout, (int)g.Cin, st);
+  const uint64_t ver = PackCache::version_of(w);
+  if (cacheable) if (Tensor* hit = g_ig32_packs.find(key, ver)) return hit;
   int64_t ps[1] = {nf + nd};
   Hold wp(new_tensor(ps, 1, w->dtype, w->device()));
-  if (w->dtype == kF32) launch_pack32<float>(w->ptr<float>(), wp->ptr<float>(), (int)g.Cout, (int)g.Cin, KS, st);
-  else launch_pack32<double>(w->ptr<double>(), wp->ptr<double>(), (int)g.Cout, (int)g.Cin, KS, st);
-  if (cacheable) {
-    std::lock_guard<std::mutex> lk(g_pack32_mu);
-    auto it = g_pack32_cache.find(key);
-    if (it != g_pack32_cache.end()) { release(it->second.packed); g_pack32_cache.erase(it); }
-    if (g_pack32_cache.size() >= 256) {         // least recently used entry that no captured graph reads
-      auto victim = g_pack32_cache.end();
-      for (auto i = g_pack32_cache.begin(); i != g_pack32_cache.end(); ++i)
-        if (!i->second.pinned && (victim == g_pack32_cache.end() || i->second.tick < victim->second.tick)) victim = i;
-      if (victim != g_pack32_cache.end()) { release(victim->second.packed); g_pack32_cache.erase(victim); }
-    }
-    g_pack32_cache[key] = PackVal32{ver, retain(wp.get()), ++g_pack32_tick, allocator_capturing()};
-  }
+  w->dtype == kF32 ? pack32_one<float>(w, wp.get(), (int)g.Cout, (int)g.Cin, KS, st) : pack32_one<double>(w, wp.get(), (int)g.Cout, (int)g.Cin, KS, st);
+  if (cacheable) g_ig32_packs.insert(key, ver, 0, wp.get());
   return wp.take();
 }
 
-// the optimisers' hook (optim.hip): re-pack, in place and in one launch per element type, every f32 / f64 weight whose packed images are
-// cached on this stream (the caller holds g_pack32_mu)
+// the optimisers' hook (conv_repack_cached): one launch per element type and F_PACK_MAX cached images
 template <class T> static void repack_cached_t(lamp_tensor* const* params, int n, hipStream_t st, int dtype) {
   PackManyT<T> a;
-  int cnt = 0, maxtotal = 0;
-  std::vector<std::pair<PackKey32, uint64_t>> done;
-  auto flush = [&] {                                    // one launch per F_PACK_MAX images; the loop goes on (it used to stop)
-    if (cnt == 0) return;
-    hipLaunchKernelGGL((ig32_pack_weights_many_kernel<T>), dim3((unsigned)std::min(512, (maxtotal + 255) / 256), (unsigned)cnt), dim3(256), 0, st, a);
-    LAMP_LAUNCH_CHECK();
-    cnt = 0; maxtotal = 0;
-  };
-  for (int i = 0; i < n; i++) {
-    if (cnt == F_PACK_MAX) flush();
-    const Tensor* w = params[i];
-    if (!w || !w->is_device() || w->dtype != dtype || w->ndim != 4 || !w->st->owned || !w->is_contiguous()) continue;
-    for (auto& kv : g_pack32_cache) {
-      if (kv.first.uid != w->st->uid || kv.first.offset != w->offset || kv.first.st != st || kv.first.dtype != dtype) continue;
-      if (kv.first.Cout != (int)w->sizes[0] || kv.first.Cin != (int)w->sizes[1] || kv.first.KS != (int)w->sizes[2]) continue;
-      const int KS = kv.first.KS, RS = KS * KS, KPf = pad16(kv.first.Cin), KPd = pad16(kv.first.Cout);
-      const int total = RS * F_ROWS * (KPf + KPd);
-      if (kv.second.packed->numel() != total) continue;
-      a.w[cnt] = w->ptr<T>(); a.Cout[cnt] = kv.first.Cout; a.Cin[cnt] = kv.first.Cin; a.KS[cnt] = KS; a.KPf[cnt] = KPf; a.KPd[cnt] = KPd;
-      a.wp[cnt] = static_cast<T*>(kv.second.packed->raw());
-      done.push_back({kv.first, w->st->version.load(std::memory_order_relaxed)});
-      maxtotal = std::max(maxtotal, total);
-      cnt++;
-      break;
-    }
-  }
-  flush();
-  for (auto& d : done) {
-    auto it = g_pack32_cache.find(d.first);
-    if (it != g_pack32_cache.end()) { it->second.version = d.second; it->second.tick = ++g_pack32_tick; }
-  }
+  int maxtotal = 0;
+  g_ig32_packs.repack(params, n, st, dtype, F_PACK_MAX,
+      [&](int slot, const Tensor* w, const PackKey& k, Tensor* packed) {
+        const int total = fill_pack32<T>(a, slot, w->ptr<T>(), static_cast<T*>(packed->raw()), k.tag[1], k.tag[2], k.tag[0]);
+        if (packed->numel() != total) return false;
+        maxtotal = std::max(maxtotal, total);
+        return true;
+      },
+      [&](int cnt, bool) { launch_pack32<T>(a, cnt, maxtotal, st); maxtotal = 0; });
 }
 void igemm32_repack_cached(lamp_tensor* const* params, int n, hipStream_t st) {
-  std::lock_guard<std::mutex> lk(g_pack32_mu);
-  if (g_pack32_cache.empty()) return;
   repack_cached_t<float>(params, n, st, kF32);
   repack_cached_t<double>(params, n, st, kF64);
 }

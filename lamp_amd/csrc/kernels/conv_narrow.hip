@@ -22,11 +22,10 @@
 // Accumulation is fp32 in a fixed order: results are bitwise reproducible.
 #include "device_utils.h"
 #include "conv_geom.h"
+#include "conv_backends.h"
+#include "../core/pack_cache.h"
 #include "wgrad_reduce.h"
-#include <map>
 #include <type_traits>
-#include <mutex>
-#include <tuple>
 #include <vector>
 #include "conv_narrow_pack.h"
 #include "../core/switches.h"
@@ -809,77 +808,40 @@ static void ncv_launch(const bf16_t* src, const nv_bf8* wpk, const bf16_t* bias,
   hipLaunchKernelGGL((ncv_fwd_kernel<NK>), dim3(blocks), dim3(256), lds, st, src, wpk, bias, dst, q);
 }
 
-// ---- packed weight-fragment images, cached per (storage uid, view, geometry, direction, stream) and storage version: the same scheme
-// as the implicit-GEMM images (conv_igemm.hip, "packed-weight cache"); LAMP_PACK_CACHE=0 disables it.
-namespace {
-struct NcvPackKey {
-  uint64_t uid; int64_t offset; int Cout, Cin, kh, kw, dgrad, ns, sw; hipStream_t st;
-  uint64_t uid2; int64_t offset2; int Cout2;     // the sibling 1x1 filter packed into the same image (0 / 0 / 0: none)
-  bool operator<(const NcvPackKey& o) const {
-    return std::tie(uid, offset, Cout, Cin, kh, kw, dgrad, ns, sw, st, uid2, offset2, Cout2) <
-           std::tie(o.uid, o.offset, o.Cout, o.Cin, o.kh, o.kw, o.dgrad, o.ns, o.sw, o.st, o.uid2, o.offset2, o.Cout2);
-  }
-};
-// version2: the sibling's storage version.  No data pointers are kept: the re-pack hook resolves both filters among the parameters it is handed
-struct NcvPackVal { uint64_t version; Tensor* packed; uint64_t tick; bool pinned = false; uint64_t version2 = 0; };
-std::mutex g_ncv_mu;
-std::map<NcvPackKey, NcvPackVal> g_ncv_cache;
-uint64_t g_ncv_tick = 0;
+// ---- packed weight-fragment images, one per (filter [and sibling], geometry, direction, stream): cached and re-packed in place by the
+// optimiser's hook (core/pack_cache.h).  An entry keeps no data pointers: the hook resolves both filters among the parameters it is handed.
+static PackCache g_ncv_packs;
 constexpr int64_t NCV_PACK_ELEMS = (int64_t)NCV_NKMAX * 64 * 8;
-}  // namespace
+// the key's geometry tag
+enum { NCV_T_COUT, NCV_T_CIN, NCV_T_KH, NCV_T_KW, NCV_T_DGRAD, NCV_T_NS, NCV_T_SW, NCV_T_COUT2 };    // NS: ns + 16 * nke
 
-static void ncv_pack_launch(const NcvPackMany& a, int cnt, hipStream_t st) {
+void narrow_pack_launch(const NcvPackMany& a, int cnt, hipStream_t st) {
   hipLaunchKernelGGL(ncv_pack_kernel, dim3((NCV_NKMAX * 64 + 255) / 256, (unsigned)cnt), dim3(256), 0, st, a);
   LAMP_LAUNCH_CHECK();
 }
 
-// returns a +1 handle on the fragment image of `w` for this direction
+// returns a +1 handle on the fragment image of `w` (and its sibling w2) for this direction
 static Tensor* ncv_packed_weights(const Tensor* w, const NcvW& wq, hipStream_t st, const Tensor* w2 = nullptr) {
-  const bool cache_on = sw().pack_cache;
-  const bool cacheable = cache_on && w->st->owned && !w->st->scratch && (!w2 || (w2->st->owned && !w2->st->scratch));
-  const NcvPackKey key{w->st->uid, w->offset, wq.Cout, wq.Cin, wq.kh, wq.kw, wq.dgrad, wq.ns + 16 * wq.nke, wq.sw, st,
-                       w2 ? w2->st->uid : 0, w2 ? w2->offset : 0, w2 ? wq.Cout2 : 0};
-  const uint64_t ver = w->st->version.load(std::memory_order_relaxed);
-  const uint64_t ver2 = w2 ? w2->st->version.load(std::memory_order_relaxed) : 0;
-  if (cacheable) {
-    std::lock_guard<std::mutex> lk(g_ncv_mu);
-    auto it = g_ncv_cache.find(key);
-    if (it != g_ncv_cache.end() && it->second.version == ver && it->second.version2 == ver2) {
-      it->second.tick = ++g_ncv_tick;
-      if (allocator_capturing()) it->second.pinned = true;       // a graph being captured records this address: never evict the entry
-      return retain(it->second.packed);
-    }
-  }
+  const bool cacheable = PackCache::cacheable(w, w2);
+  const PackKey key{w->st->uid, w->offset, {wq.Cout, wq.Cin, wq.kh, wq.kw, wq.dgrad, wq.ns + 16 * wq.nke, wq.sw, w2 ? wq.Cout2 : 0}, st,
+                    w2 ? w2->st->uid : 0, w2 ? w2->offset : 0};
+  const uint64_t ver = PackCache::version_of(w), ver2 = PackCache::version_of(w2);
+  if (cacheable) if (Tensor* hit = g_ncv_packs.find(key, ver, ver2)) return hit;
   int64_t ps[1] = {NCV_PACK_ELEMS};
   Hold wp(new_tensor(ps, 1, kBF16, w->device()));
   NcvPackMany a;
   a.w[0] = wq; a.dst[0] = reinterpret_cast<nv_bf8*>(wp->ptr<bf16_t>());
-  ncv_pack_launch(a, 1, st);
-  if (cacheable) {
-    std::lock_guard<std::mutex> lk(g_ncv_mu);
-    auto it = g_ncv_cache.find(key);
-    if (it != g_ncv_cache.end()) { release(it->second.packed); g_ncv_cache.erase(it); }
-    if (g_ncv_cache.size() >= 256) {           // evict the least recently used entry that no captured graph reads
-      auto victim = g_ncv_cache.end();
-      for (auto i = g_ncv_cache.begin(); i != g_ncv_cache.end(); ++i)
-        if (!i->second.pinned && (victim == g_ncv_cache.end() || i->second.tick < victim->second.tick)) victim = i;
-      if (victim != g_ncv_cache.end()) { release(victim->second.packed); g_ncv_cache.erase(victim); }
-    }
-    g_ncv_cache[key] = NcvPackVal{ver, retain(wp.get()), ++g_ncv_tick, allocator_capturing(), ver2};
-  }
+  narrow_pack_launch(a, 1, st);
+  if (cacheable) g_ncv_packs.insert(key, ver, ver2, wp.get());
   return wp.take();
 }
 
-// Called by the optimisers right after they have written the parameters (next to igemm_repack_cached): every cached fragment image of
-// these parameters on this stream is packed again IN PLACE (a captured HIP graph keeps the address), all of them in one launch.
-// `fill` (optional): instead of launching, hand the LAST batch of at most NCV_PACK_MAX images to the caller (*fill, *fill_cnt) - the optimiser's hook
-// in conv_igemm.hip packs them in the launch that packs the implicit-GEMM images; earlier full batches are still launched here
+// The narrow half of the optimisers' hook (called by igemm_repack_cached): every cached fragment image of these parameters on this stream
+// is packed again IN PLACE (a captured HIP graph keeps the address), NCV_PACK_MAX per launch.
+// `fill` (optional): instead of launching, hand the LAST batch of at most NCV_PACK_MAX images to the caller (*fill, *fill_cnt), which packs them
+// in the launch that packs the implicit-GEMM images; earlier full batches are still launched here
 void narrow_repack_cached(lamp_tensor* const* params, int n, hipStream_t st, NcvPackMany* fill, int* fill_cnt) {
   if (fill_cnt) *fill_cnt = 0;
-  const bool on = sw().pack_after_step;
-  if (!on) return;
-  std::lock_guard<std::mutex> lk(g_ncv_mu);
-  if (g_ncv_cache.empty()) return;
   // the narrow filters among the parameters just written: an image is packed again ONLY from tensors the caller holds right now (ADVICE r5:
   // the entry used to keep raw data pointers of both filters of a pair and read the absent one's after its storage could be gone)
   std::vector<const Tensor*> cand;
@@ -898,39 +860,30 @@ void narrow_repack_cached(lamp_tensor* const* params, int n, hipStream_t st, Ncv
   };
   NcvPackMany a;
   int cnt = 0;
-  auto flush = [&] {
-    if (cnt == 0) return;
-    ncv_pack_launch(a, cnt, st);
-    cnt = 0;
-  };
-  for (auto it = g_ncv_cache.begin(); it != g_ncv_cache.end();) {
-    const NcvPackKey& k = it->first;
-    NcvPackVal& v = it->second;
-    if (k.st != st) { ++it; continue; }
-    const Tensor* w1 = find(k.uid, k.offset, k.Cout, k.Cin, k.kh, k.kw);
-    const Tensor* w2 = k.Cout2 > 0 ? find(k.uid2, k.offset2, k.Cout2, k.Cin, 1, 1) : nullptr;
-    if (!w1 && !w2) { ++it; continue; }                          // none of this call's parameters
-    if (!w1 || (k.Cout2 > 0 && !w2)) {
-      // a pair image with only ONE of its filters among the parameters (the other was a temporary, or its layer was rebuilt): it cannot be
-      // brought up to date here.  Drop it - the next convolution packs a fresh image from the tensors it is given - unless a captured graph
-      // reads this address; that entry stays, stale by its versions, exactly as when a parameter is written outside the optimiser.
-      if (!v.pinned) { release(v.packed); it = g_ncv_cache.erase(it); }
-      else ++it;
-      continue;
-    }
-    if (cnt == NCV_PACK_MAX) flush();
-    a.w[cnt] = NcvW{w1->ptr<bf16_t>(), k.Cout, k.Cin, k.kh, k.kw, k.dgrad, k.ns & 15, k.sw, w2 ? w2->ptr<bf16_t>() : nullptr, k.Cout2, k.ns >> 4};   // (key: ns + 16 nke)
-    a.dst[cnt] = static_cast<nv_bf8*>(v.packed->raw());
-    v.version = w1->st->version.load(std::memory_order_relaxed);
-    v.version2 = w2 ? w2->st->version.load(std::memory_order_relaxed) : 0;
-    v.tick = ++g_ncv_tick;
-    cnt++;
-    ++it;
-  }
-  if (fill && cnt > 0) { *fill = a; *fill_cnt = cnt; }
-  else flush();
+  g_ncv_packs.walk(st,
+      [&](const PackKey& k, PackEntry& v) {
+        const int* t = k.tag.data();
+        const Tensor* w1 = find(k.uid, k.offset, t[NCV_T_COUT], t[NCV_T_CIN], t[NCV_T_KH], t[NCV_T_KW]);
+        const Tensor* w2 = t[NCV_T_COUT2] > 0 ? find(k.uid2, k.offset2, t[NCV_T_COUT2], t[NCV_T_CIN], 1, 1) : nullptr;
+        if (!w1 && !w2) return true;                                 // none of this call's parameters
+        // a pair image with only ONE of its filters among the parameters (the other was a temporary, or its layer was rebuilt): it cannot be
+        // brought up to date here.  Drop it - the next convolution packs a fresh image from the tensors it is given - unless a captured graph
+        // reads this address; that entry stays, stale by its versions, exactly as when a parameter is written outside the optimiser.
+        if (!w1 || (t[NCV_T_COUT2] > 0 && !w2)) return false;
+        if (cnt == NCV_PACK_MAX) { narrow_pack_launch(a, cnt, st); cnt = 0; }
+        a.w[cnt] = NcvW{w1->ptr<bf16_t>(), t[NCV_T_COUT], t[NCV_T_CIN], t[NCV_T_KH], t[NCV_T_KW], t[NCV_T_DGRAD], t[NCV_T_NS] & 15, t[NCV_T_SW],
+                        w2 ? w2->ptr<bf16_t>() : nullptr, t[NCV_T_COUT2], t[NCV_T_NS] >> 4};
+        a.dst[cnt] = static_cast<nv_bf8*>(v.packed->raw());
+        g_ncv_packs.touch(v, PackCache::version_of(w1), PackCache::version_of(w2));
+        cnt++;
+        return true;
+      },
+      [&] {
+        if (cnt == 0) return;
+        if (fill) { *fill = a; *fill_cnt = cnt; }
+        else narrow_pack_launch(a, cnt, st);
+      });
 }
-void narrow_pack_launch(const NcvPackMany& a, int cnt, hipStream_t st) { ncv_pack_launch(a, cnt, st); }
 
 // sibling (fprop, optional): a 1x1 convolution of the same input, same stride and output map, whose Cout2 channels fit beside w's in the
 // MFMA's 16 columns: both outputs from one launch of the aligned kernel (false, nothing launched, when that kernel does not take the pair)

@@ -6,12 +6,11 @@
 // read through the scalar cache (wave-uniform indices -> s_load, used as SGPR operands of v_fmac).
 //   fprop : y[n, :, ho, wo]  = b + sum_{ci,r,s} x[n, ci, ho*sh - p + r, wo*sw - p + s] * w[:, ci, r, s]
 //   dgrad : dx[n, :, h, w]   = sum_{co,r,s}   dy[n, co, (h + p - r)/sh, (w + p - s)/sw] * w[co, :, r, s]
-#include <map>
 #include <vector>
-#include <mutex>
-#include <tuple>
 #include "device_utils.h"
 #include "conv_geom.h"
+#include "conv_backends.h"
+#include "../core/pack_cache.h"
 #include "wgrad_reduce.h"
 #include "../core/switches.h"
 
@@ -298,91 +297,42 @@ __global__ void cs2_pack_kernel(Cs2PackMany a) {
 }
 static int cs2_cb_of(int64_t ch) { return ch == 6 ? 6 : (ch <= 8 ? 8 : 16); }
 
-// the packed images are kept per (weight view, stream) while the weight's storage is unchanged: the backward pass of a step finds what its
-// forward pass packed (13 -> 6 pack launches per ResNet step)
-namespace {
-struct Cs2PackKey {
-  uint64_t uid; int64_t offset; int KS, Cout, Cin, dtype; hipStream_t st;
-  bool operator<(const Cs2PackKey& o) const { return std::tie(uid, offset, KS, Cout, Cin, dtype, st) < std::tie(o.uid, o.offset, o.KS, o.Cout, o.Cin, o.dtype, o.st); }
-};
-struct Cs2PackVal { uint64_t version; Tensor* packed; uint64_t tick;  bool pinned = false; };
-std::mutex g_cs2_mu;
-std::map<Cs2PackKey, Cs2PackVal> g_cs2_cache;
-uint64_t g_cs2_tick = 0;
-}  // namespace
+// the packed images are cached and re-packed in place by the optimiser's hook (core/pack_cache.h): the backward pass of a step finds what
+// its forward pass packed (13 -> 6 pack launches per ResNet step)
+static PackCache g_cs2_packs;
+static void cs2_fill_pack(Cs2PackMany& pm, int slot, const void* w, void* wf, int Cout, int Cin, int KS) {
+  pm.w[slot] = w; pm.wf[slot] = wf; pm.Cout[slot] = Cout; pm.Cin[slot] = Cin; pm.KS[slot] = KS; pm.CBf[slot] = cs2_cb_of(Cout); pm.CBd[slot] = cs2_cb_of(Cin);
+}
 template <class T, class A> static Tensor* cs2_packed(const Tensor* w, const ConvGeom& g, hipStream_t st, int64_t* dgrad_offset) {
   const int KS = g.kh, CBf = cs2_cb_of(g.Cout), CBd = cs2_cb_of(g.Cin);
   const int64_t nf = g.Cin * KS * KS * CBf, nd = g.Cout * KS * KS * CBd;
   *dgrad_offset = nf;
-  const bool cacheable = w->st->owned && !w->st->scratch;
-  const Cs2PackKey key{w->st->uid, w->offset, KS, (int)g.Cout, (int)g.Cin, w->dtype, st};
-  const uint64_t ver = w->st->version.load(std::memory_order_relaxed);
-  if (cacheable) {
-    std::lock_guard<std::mutex> lk(g_cs2_mu);
-    auto it = g_cs2_cache.find(key);
-    if (it != g_cs2_cache.end() && it->second.version == ver) {
-      it->second.tick = ++g_cs2_tick;
-      if (allocator_capturing()) it->second.pinned = true;
-      return retain(it->second.packed);
-    }
-  }
+  const bool cacheable = PackCache::cacheable(w);
+  const PackKey key = PackKey::filter(w, KS, (int)g.Cout, (int)g.Cin, st);
+  const uint64_t ver = PackCache::version_of(w);
+  if (cacheable) if (Tensor* hit = g_cs2_packs.find(key, ver)) return hit;
   int64_t ps[1] = {nf + nd};
   Hold wf(new_tensor(ps, 1, std::is_same<A, float>::value ? kF32 : kF64, w->device()));
   Cs2PackMany pm;
-  pm.w[0] = w->raw(); pm.wf[0] = wf->raw(); pm.Cout[0] = (int)g.Cout; pm.Cin[0] = (int)g.Cin; pm.KS[0] = KS; pm.CBf[0] = CBf; pm.CBd[0] = CBd;
+  cs2_fill_pack(pm, 0, w->raw(), wf->raw(), (int)g.Cout, (int)g.Cin, KS);
   hipLaunchKernelGGL((cs2_pack_kernel<T, A>), dim3((unsigned)std::min<int64_t>(64, (nf + nd + 255) / 256), 1u), dim3(256), 0, st, pm);
   LAMP_LAUNCH_CHECK();
-  if (cacheable) {
-    std::lock_guard<std::mutex> lk(g_cs2_mu);
-    auto it = g_cs2_cache.find(key);
-    if (it != g_cs2_cache.end()) { release(it->second.packed); g_cs2_cache.erase(it); }
-    if (g_cs2_cache.size() >= 64) {             // least recently used entry that no captured graph reads
-      auto victim = g_cs2_cache.end();
-      for (auto i = g_cs2_cache.begin(); i != g_cs2_cache.end(); ++i)
-        if (!i->second.pinned && (victim == g_cs2_cache.end() || i->second.tick < victim->second.tick)) victim = i;
-      if (victim != g_cs2_cache.end()) { release(victim->second.packed); g_cs2_cache.erase(victim); }
-    }
-    g_cs2_cache[key] = Cs2PackVal{ver, retain(wf.get()), ++g_cs2_tick, allocator_capturing()};
-  }
+  if (cacheable) g_cs2_packs.insert(key, ver, 0, wf.get());
   return wf.take();
 }
 
-// the optimisers' hook (optim.hip): every cached pair of images whose weight was just updated is re-packed in place, one launch per element
-// type - a replayed graph (whose capture found the images in the cache and recorded no pack launch) keeps reading current weights
+// the optimisers' hook (conv_repack_cached): one launch per element type and CS2_PACK_MAX cached images - a replayed graph (whose capture
+// found the images in the cache and recorded no pack launch) keeps reading current weights
 template <class T, class A> static void cs2_repack_t(lamp_tensor* const* params, int n, hipStream_t st, int dtype) {
   Cs2PackMany pm;
-  int cnt = 0;
-  std::vector<std::pair<Cs2PackKey, uint64_t>> done;
-  auto flush = [&] {                                    // one launch per CS2_PACK_MAX images; the loop goes on (it used to stop)
-    if (cnt == 0) return;
-    hipLaunchKernelGGL((cs2_pack_kernel<T, A>), dim3(16u, (unsigned)cnt), dim3(256), 0, st, pm);
-    LAMP_LAUNCH_CHECK();
-    cnt = 0;
-  };
-  for (int i = 0; i < n; i++) {
-    if (cnt == CS2_PACK_MAX) flush();
-    const Tensor* w = params[i];
-    if (!w || !w->is_device() || w->dtype != dtype || w->ndim != 4 || !w->st->owned || !w->is_contiguous()) continue;
-    for (auto& kv : g_cs2_cache) {
-      const Cs2PackKey& k = kv.first;
-      if (k.uid != w->st->uid || k.offset != w->offset || k.st != st || k.dtype != dtype) continue;
-      if (k.Cout != (int)w->sizes[0] || k.Cin != (int)w->sizes[1] || k.KS != (int)w->sizes[2]) continue;
-      pm.w[cnt] = w->raw(); pm.wf[cnt] = kv.second.packed->raw(); pm.Cout[cnt] = k.Cout; pm.Cin[cnt] = k.Cin; pm.KS[cnt] = k.KS;
-      pm.CBf[cnt] = cs2_cb_of(k.Cout); pm.CBd[cnt] = cs2_cb_of(k.Cin);
-      done.push_back({k, w->st->version.load(std::memory_order_relaxed)});
-      cnt++;
-      break;
-    }
-  }
-  flush();
-  for (auto& d : done) {
-    auto it = g_cs2_cache.find(d.first);
-    if (it != g_cs2_cache.end()) { it->second.version = d.second; it->second.tick = ++g_cs2_tick; }
-  }
+  g_cs2_packs.repack(params, n, st, dtype, CS2_PACK_MAX,
+      [&](int slot, const Tensor* w, const PackKey& k, Tensor* packed) { cs2_fill_pack(pm, slot, w->raw(), packed->raw(), k.tag[1], k.tag[2], k.tag[0]); return true; },
+      [&](int cnt, bool) {
+        hipLaunchKernelGGL((cs2_pack_kernel<T, A>), dim3(16u, (unsigned)cnt), dim3(256), 0, st, pm);
+        LAMP_LAUNCH_CHECK();
+      });
 }
 void small_repack_cached(lamp_tensor* const* params, int n, hipStream_t st) {
-  std::lock_guard<std::mutex> lk(g_cs2_mu);
-  if (g_cs2_cache.empty()) return;
   cs2_repack_t<float, float>(params, n, st, kF32);
   cs2_repack_t<double, double>(params, n, st, kF64);
 }

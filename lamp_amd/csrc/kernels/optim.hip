@@ -10,12 +10,9 @@
 // parameter tensors, i.e. ~300 tiny launches become one.
 #include "device_utils.h"
 #include "../core/strided.h"
+#include "conv_backends.h"
 
 namespace lamp {
-
-void igemm_repack_cached(lamp_tensor* const* params, int n, hipStream_t st);   // conv_igemm.hip
-void igemm32_repack_cached(lamp_tensor* const* params, int n, hipStream_t st); // conv_igemm_f32.hip
-void small_repack_cached(lamp_tensor* const* params, int n, hipStream_t st);   // conv_small.hip
 
 constexpr int MT_MAX = 40;       // tensors per launch (the descriptor is a by-value kernel argument: 3.4 KB of the 4 KB limit; the ResNet has 37)
 constexpr int MT_CHUNK = 1024;   // elements per workgroup (4096: the ResNet's 392 k parameters made ~130 workgroups for 256 CUs - 15 us per AdamW launch)
@@ -365,9 +362,7 @@ int lamp_adamw_step_(lamp_tensor* const* params, lamp_tensor* const* grads, lamp
       LAMP_LAUNCH_CHECK();
     }
   }
-  igemm_repack_cached(params, n, st);     // the convolution weights' packed images follow the update in one launch (conv_igemm.hip; the narrow ones ride along)
-  igemm32_repack_cached(params, n, st);
-  small_repack_cached(params, n, st);
+  conv_repack_cached(params, n, st);      // the convolution weights' packed images follow the update (conv.hip)
   LAMP_API_END
 }
 
@@ -393,9 +388,7 @@ int lamp_sgdw_step_(lamp_tensor* const* params, lamp_tensor* const* grads, lamp_
       },
       [&](MultiArgs& a, int blk) { hipLaunchKernelGGL((sgdw_kernel<T>), dim3(blk), dim3(256), 0, st, a); }));
   LAMP_LAUNCH_CHECK();
-  igemm_repack_cached(params, n, st);
-  igemm32_repack_cached(params, n, st);
-  small_repack_cached(params, n, st);
+  conv_repack_cached(params, n, st);
   LAMP_API_END
 }
 

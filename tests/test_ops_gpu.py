@@ -14,7 +14,7 @@ import torch
 
 from lamp_amd import sten as S
 from lamp_amd._capi import lib, i64_array, handle_array
-from tests.util import DTYPES, FWD_TOL, assert_close, closed_form, to_sten, to_torch
+from tests.util import DTYPES, FWD_TOL, TORCH2LAMP, assert_close, closed_form, to_sten, to_torch
 
 pytestmark = pytest.mark.gpu
 aten = torch.ops.aten
@@ -971,13 +971,41 @@ def test_allocation_registry(gpu):
     assert S.live_tensor_count() == n0
 
 
-@pytest.mark.parametrize("cin,cout,hw,stride", [(128, 128, 8, 1), (6, 6, 16, 1), (6, 16, 16, 2), (3, 6, 32, 1)])
-def test_igemm_pack_cache_sees_every_weight_write(gpu, cin, cout, hw, stride):
-    """The implicit-GEMM and the narrow convolutions cache their packed weights (fprop and dgrad images) per storage version.
-    Every way of changing the weights must invalidate them: in-place arithmetic, copy_, a write through a view, a host upload,
-    the optimiser (which re-packs the cached images itself, in place)."""
+_F32, _F64, _BF16 = torch.float32, torch.float64, torch.bfloat16
+# (cin, cout, map, stride, dtype) -> the backend whose packed-filter cache the convolution goes through (core/pack_cache.h has the four users)
+_PACK_CACHE_FP_CASES = [(32, 32, 8, 1, _F32), (32, 32, 8, 1, _F64),        # f32 / f64 implicit GEMM
+                        (6, 6, 16, 1, _F32), (6, 6, 16, 1, _F64), (6, 16, 16, 2, _F32), (6, 16, 16, 2, _F64)]      # cs2
+
+
+def _pack_counts():
+    """{entries, pinned, hits, packs, repacked} of the packed-filter caches, summed over the four backends (a debug export, not in the header)"""
+    buf = (C.c_uint64 * 5)()
+    lib.lamp_debug_pack_cache_counts(buf)
+    return dict(zip(("entries", "pinned", "hits", "packs", "repacked"), (int(v) for v in buf)))
+
+
+def _conv_fwd(X, W, Bt, stride, pad):
+    o = C.c_void_p()
+    lib.lamp_convolution(C.byref(o), X, W, Bt, i64_array([stride, stride]), i64_array([pad, pad]), i64_array([1, 1]), 2, 0, i64_array([0, 0]), 1)
+    return S.STen(o)
+
+
+def _conv_dgrad(GY, X, W, stride, pad):
+    out3 = _out3()
+    lib.lamp_convolution_backward(out3, GY, X, W, i64_array([stride, stride]), i64_array([pad, pad]), i64_array([1, 1]), 2, 0, i64_array([0, 0]), 1, _mask3(1, 0, 0))
+    return S.STen(out3[0])
+
+
+@pytest.mark.parametrize("cin,cout,hw,stride,dt", [(128, 128, 8, 1, _BF16), (6, 6, 16, 1, _BF16), (6, 16, 16, 2, _BF16), (3, 6, 32, 1, _BF16)] + _PACK_CACHE_FP_CASES,
+                         ids=["128-128-8-1", "6-6-16-1", "6-16-16-2", "3-6-32-1"] +
+                             [f"{c[0]}-{c[1]}-{c[2]}-{c[3]}-{'f32' if c[4] == _F32 else 'f64'}" for c in _PACK_CACHE_FP_CASES])
+def test_igemm_pack_cache_sees_every_weight_write(gpu, cin, cout, hw, stride, dt):
+    """The implicit-GEMM (bf16, f32 / f64), the narrow and the small convolutions cache their packed weights (fprop and dgrad images) per
+    storage version.  Every way of changing the weights must invalidate them: in-place arithmetic, copy_, a write through a view, a host
+    upload, the optimiser (which re-packs the cached images itself, in place)."""
     from lamp_amd import nn as NN
-    dt = torch.bfloat16
+    tol = 1.6e-2 if dt == _BF16 else FWD_TOL[dt]
+    rt = torch.float32 if dt == _BF16 else dt             # the input gradient's reference is computed in this type
     k = 5 if cin == 3 else 3
     pad = k // 2
     x = closed_form((4, cin, hw, hw), 3, 2.0, dt)
@@ -1002,9 +1030,9 @@ def test_igemm_pack_cache_sees_every_weight_write(gpu, cin, cout, hw, stride):
 
     def check(w_now, what):
         ref = aten.convolution(x, w_now, b, [stride, stride], [pad, pad], [1, 1], False, [0, 0], 1)
-        assert_close(conv(W), ref.double(), 1.6e-2, what)
-        gx = aten.convolution_backward(gy.float(), x.float(), w_now.float(), [0], [stride, stride], [pad, pad], [1, 1], False, [0, 0], 1, [True, False, False])[0]
-        assert_close(dgrad(W), gx.double(), 1.6e-2, what + " (dgrad)")
+        assert_close(conv(W), ref.double(), tol, what)
+        gx = aten.convolution_backward(gy.to(rt), x.to(rt), w_now.to(rt), [0], [stride, stride], [pad, pad], [1, 1], False, [0, 0], 1, [True, False, False])[0]
+        assert_close(dgrad(W), gx.double(), tol, what + " (dgrad)")
 
     check(w0, "first call")
     check(w0, "cached call")
@@ -1019,14 +1047,130 @@ def test_igemm_pack_cache_sees_every_weight_write(gpu, cin, cout, hw, stride):
     w3 = closed_form((cout, cin, k, k), 9, 1.0, dt)
     W2 = to_sten(w3)                                        # a different tensor with different contents
     ref3 = aten.convolution(x, w3, b, [stride, stride], [pad, pad], [1, 1], False, [0, 0], 1)
-    assert_close(conv(W2), ref3.double(), 1.6e-2, "another weight tensor")
+    assert_close(conv(W2), ref3.double(), tol, "another weight tensor")
     # the optimiser: one SGD step changes W, the next convolution must use the new values
-    g = S.STen.ones([cout, cin, k, k], S.BF16, 0)
+    g = S.STen.ones([cout, cin, k, k], TORCH2LAMP[dt], 0)
     opt = NN.SGDW([W], 0.5, 0.0)
     opt.step([g], 1.0)
     check(to_torch(W).to(dt), "after the optimiser step")
     opt.step([g], 1.0)
     check(to_torch(W).to(dt), "after a second optimiser step (images re-packed in place)")
+
+
+def _is_narrow(cin, cout, dt):
+    return dt == _BF16 and cin <= 16 and cout <= 16
+
+
+@pytest.mark.parametrize("cin,cout,hw,dt", [(128, 128, 8, _BF16), (6, 6, 16, _BF16), (32, 32, 8, _F32), (6, 6, 16, _F32)],
+                         ids=["igemm-bf16", "narrow-bf16", "igemm-f32", "cs2-f32"])
+def test_pack_cache_hits_are_hits(gpu, cin, cout, hw, dt):
+    """A cache hit and a fresh pack give the same values; the caches' counters tell them apart.  One geometry per backend: the first forward
+    packs, the second forward and the input gradient are hits (the implicit-GEMM and cs2 images hold both layouts, one pack; the narrow
+    backend keeps ONE FRAGMENT IMAGE PER DIRECTION - its key carries the direction - so there the first input gradient is that image's one
+    pack and the second a hit), a write to the weight costs one pack, the optimiser re-packs in its hook and the next calls are hits."""
+    from lamp_amd import nn as NN
+    tol = 1.6e-2 if dt == _BF16 else FWD_TOL[dt]
+    rt = torch.float32 if dt == _BF16 else dt
+    x, w0, b = closed_form((4, cin, hw, hw), 3, 2.0, dt), closed_form((cout, cin, 3, 3), 17, 1.0, dt), torch.zeros(cout, dtype=dt)
+    gy = closed_form((4, cout, hw, hw), 23, 1.0, dt)
+    X, W, Bt, GY = to_sten(x), to_sten(w0), to_sten(b), to_sten(gy)
+
+    def fwd(what, hits, packs):
+        c0 = _pack_counts()
+        y = to_torch(_conv_fwd(X, W, Bt, 1, 1))
+        c1 = _pack_counts()
+        assert (c1["hits"] - c0["hits"], c1["packs"] - c0["packs"]) == (hits, packs), f"{what}: (hits, packs) moved by {c1['hits'] - c0['hits'], c1['packs'] - c0['packs']}"
+        assert_close(y, aten.convolution(x, to_torch(W).to(dt), b, [1, 1], [1, 1], [1, 1], False, [0, 0], 1).double(), tol, what)
+
+    def bwd(what, hits, packs):
+        c0 = _pack_counts()
+        gx = to_torch(_conv_dgrad(GY, X, W, 1, 1))
+        c1 = _pack_counts()
+        assert (c1["hits"] - c0["hits"], c1["packs"] - c0["packs"]) == (hits, packs), f"{what}: (hits, packs) moved by {c1['hits'] - c0['hits'], c1['packs'] - c0['packs']}"
+        ref = aten.convolution_backward(gy.to(rt), x.to(rt), to_torch(W).to(rt), [0], [1, 1], [1, 1], [1, 1], False, [0, 0], 1, [True, False, False])[0]
+        assert_close(gx, ref.double(), tol, what)
+
+    fwd("first forward", 0, 1)
+    fwd("second forward", 1, 0)
+    if _is_narrow(cin, cout, dt):
+        bwd("first input gradient (the narrow backend's image of the other direction)", 0, 1)
+    bwd("input gradient", 1, 0)
+    lib.lamp_mul_scalar_(W, 0.5)
+    fwd("after mul_scalar_", 0, 1)
+    g = S.STen.ones([cout, cin, 3, 3], TORCH2LAMP[dt], 0)
+    c0 = _pack_counts()
+    NN.SGDW([W], 0.5, 0.0).step([g], 1.0)
+    assert _pack_counts()["repacked"] - c0["repacked"] >= 1, "the optimiser's hook re-packed nothing"
+    fwd("after the optimiser step", 1, 0)
+    bwd("input gradient after the optimiser step", 1, 0)
+
+
+@pytest.mark.parametrize("cin,hw,N,dt", [(8, 8, 2, _BF16), (32, 8, 2, _F32), (6, 4, 2, _F32), (6, 16, 2, _BF16)],
+                         ids=["igemm-bf16", "igemm-f32", "cs2-f32", "narrow-bf16"])
+def test_optimiser_repacks_past_a_full_batch_of_images(gpu, cin, hw, N, dt):
+    """ADVICE r4, for every backend: the hook packs 16 images per launch, and its loop once STOPPED at the first full batch - the seventeenth
+    filter's image stayed stale, and a replayed graph kept reading it.  17 filters of the backend's smallest shape, all cached, ONE
+    optimiser step over all of them: every convolution equals ATen on the new weights, from a cache hit - all 17 re-packed by the hook."""
+    from lamp_amd import nn as NN
+    tol = 1.6e-2 if dt == _BF16 else FWD_TOL[dt]
+    nf = 17
+    x, b = closed_form((N, cin, hw, hw), 3, 2.0, dt), torch.zeros(cin, dtype=dt)
+    X, Bt = to_sten(x), to_sten(b)
+    Ws = [to_sten(closed_form((cin, cin, 3, 3), 17 + 5 * i, 1.0, dt)) for i in range(nf)]
+
+    def check(what):
+        for i, W in enumerate(Ws):
+            ref = aten.convolution(x, to_torch(W).to(dt), b, [1, 1], [1, 1], [1, 1], False, [0, 0], 1)
+            assert_close(to_torch(_conv_fwd(X, W, Bt, 1, 1)), ref.double(), tol, f"{what}, filter {i}")
+
+    c0 = _pack_counts()
+    check("first call")
+    c1 = _pack_counts()
+    assert c1["packs"] - c0["packs"] == nf
+    g = S.STen.ones([cin, cin, 3, 3], TORCH2LAMP[dt], 0)
+    NN.SGDW(Ws, 0.5, 0.0).step([g] * nf, 1.0)
+    c2 = _pack_counts()
+    assert c2["repacked"] - c1["repacked"] == nf, f"the hook re-packed {c2['repacked'] - c1['repacked']} of {nf} images"
+    check("after one optimiser step over all of them")
+    c3 = _pack_counts()
+    assert (c3["packs"] - c2["packs"], c3["hits"] - c2["hits"]) == (0, nf), "an image was packed lazily: the hook had left it stale"
+
+
+def test_replayed_f32_convolutions_follow_the_optimiser(gpu):
+    """The f32 caches under a HIP graph (the bf16 ones have the ResNet replay tests): a forward of one implicit-GEMM and one cs2 convolution
+    is captured after a warm-up call, so the capture finds both images in the caches and records no pack launch; the weights are stepped
+    eagerly; the replay must compute with the stepped weights - the hook re-packed in place, the pinned entries kept their address."""
+    from lamp_amd import nn as NN
+    dt = _F32
+    cases = [(32, 8), (6, 16)]
+    xs = [closed_form((4, c, hw, hw), 3, 2.0, dt) for c, hw in cases]
+    Xs = [to_sten(x) for x in xs]
+    Ws = [to_sten(closed_form((c, c, 3, 3), 17, 1.0, dt)) for c, _ in cases]
+    Bs = [to_sten(torch.zeros(c, dtype=dt)) for c, _ in cases]
+    gs = [S.STen.ones([c, c, 3, 3], S.F32, 0) for c, _ in cases]
+    st = C.c_void_p(); lib.lamp_stream_get_from_pool(0, 0, C.byref(st)); lib.lamp_stream_set_current(st)
+    try:
+        for X, W, Bt in zip(Xs, Ws, Bs):
+            _conv_fwd(X, W, Bt, 1, 1)                          # warm-up on this stream: the images are cached per stream
+        lib.lamp_device_synchronize()
+        c0 = _pack_counts()
+        lib.lamp_graph_begin_capture()
+        Ys = [_conv_fwd(X, W, Bt, 1, 1) for X, W, Bt in zip(Xs, Ws, Bs)]
+        g = C.c_void_p(); lib.lamp_graph_end_capture(C.byref(g))
+        c1 = _pack_counts()
+        assert (c1["packs"] - c0["packs"], c1["hits"] - c0["hits"]) == (0, 2), "the capture recorded a pack launch"
+        assert c1["pinned"] >= 2
+        NN.SGDW(Ws, 0.5, 0.0).step(gs, 1.0)
+        lib.lamp_graph_launch(g)
+        lib.lamp_device_synchronize()
+        for x, W, Y, (c, hw) in zip(xs, Ws, Ys, cases):
+            ref = aten.convolution(x, to_torch(W), torch.zeros(c, dtype=dt), [1, 1], [1, 1], [1, 1], False, [0, 0], 1)
+            assert_close(to_torch(Y), ref.double(), FWD_TOL[dt], f"replayed {c} -> {c} convolution on the stepped weights")
+        assert _pack_counts()["pinned"] >= 2
+        lib.lamp_graph_release(g)
+    finally:
+        d = C.c_void_p(); lib.lamp_stream_get_default(0, C.byref(d)); lib.lamp_stream_set_current(d)
+        lib.lamp_stream_release(st); lib.lamp_stream_release(d)
 
 
 @pytest.mark.parametrize("cin,cout,N,H,stride", [(6, 6, 16, 32, 2), (128, 100, 1024, 8, 1)])
