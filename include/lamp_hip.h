@@ -418,6 +418,31 @@ int lamp_rnn_cell_forward(const lamp_tensor* gates, lamp_tensor* h_out);
 int lamp_rnn_cell_backward(lamp_tensor* dgates, const lamp_tensor* h, const lamp_tensor* dout_or_null, const lamp_tensor* dh_or_null);
 
 /* ------------------------------------------------------------------------------------------
+ * graph   (lamp-core/src/main/scala/lamp/nn/graph/GCN.scala; f32 / f64, GPU tensors)
+ * GCN.gcnAggregation (GCN.scala:127-145) is degrees * ((A + A' + I) mm (x * degrees)) over a sparse COO tensor
+ * (computeSparseAdjacency, GCN.scala:30-114).  This library has no sparse tensor: the adjacency is a CSR of A + A' with
+ * multiplicity (duplicate pairs and a pair given in both directions count as often as they occur, as the reference's COO
+ * addition does), the self loop is implicit, and the product is one gather-only kernel without atomics.
+ * ------------------------------------------------------------------------------------------ */
+/* GCN.scala:30-114.  edgeI, edgeJ: int64 [E], an asymmetric edge list without self loops.  rowptr int64 [N + 1], col int64 [2E]:
+ * the 2E directed entries (i, j) and (j, i) stably sorted by row, so the order inside a row, and with it the summation order of
+ * lamp_gcn_aggregate, depends on the input alone.  dinv [N] in `dtype`: (occurrences of the node in edgeI ++ edgeJ + 1)^-1/2
+ * (GCN.scala:52-63).  The range of both index vectors is reduced first: an endpoint outside [0, numNodes) is an error, nothing
+ * dereferences it.  E = 0 is valid (rowptr all zero, dinv all one).  Two host synchronisations (range, bincount): once per graph,
+ * not inside a captured step. */
+int lamp_gcn_adjacency(lamp_tensor** rowptr, lamp_tensor** col, lamp_tensor** dinv, const lamp_tensor* edgeI, const lamp_tensor* edgeJ,
+                       int64_t numNodes, int dtype);
+/* GCN.scala:137-145: out[i, :] = dinv[i] * (dinv[i] * x[i, :] + sum over p in [rowptr[i], rowptr[i + 1]) of dinv[col[p]] * x[col[p], :]),
+ * summed in that order in x's type (f32 in f32, f64 in f64).  x is [N, D]; unit column stride with any row pitch is read in place,
+ * every other layout is made contiguous first.  16-byte packets where D, the row pitch and the addresses allow them, 8-byte or
+ * scalar accesses otherwise (an odd D leaves the rows of the contiguous result unaligned, so it takes the scalar form throughout).
+ * The operator is symmetric: the gradient with respect to x is the same call on the incoming gradient.  (rowptr, col, dinv) must be
+ * what lamp_gcn_adjacency returned for a graph of N nodes: their contents are not checked again. */
+int lamp_gcn_aggregate(lamp_tensor** out, const lamp_tensor* x, const lamp_tensor* rowptr, const lamp_tensor* col, const lamp_tensor* dinv);
+/* a row of more neighbours than this is split across the waves of its workgroup (partial sums added in wave order) */
+int lamp_gcn_long_row(int64_t* out);
+
+/* ------------------------------------------------------------------------------------------
  * convolution / pooling   (ATen.convolution, convolution_backward(output_mask[3]),
  * avg_pool2d(+_backward), max_pool2d_with_indices(+_backward): ops.scala:1547-1651,
  * 1721-1825).  NCHW / NCL contiguous, groups supported, transposed supported.

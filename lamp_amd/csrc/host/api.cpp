@@ -110,6 +110,7 @@ int lamp_op_apply(lamp_var** out, const char* name, lamp_var* const* vars, int n
   else if (n == "ScatterAdd") r = F::scatter_add(V(0), V(1), I(0), I(1));              // i = [dim, maxIndex]
   else if (n == "IndexAdd") r = F::index_add(V(0), V(1), I(0), I(1));
   else if (n == "IndexAddToTarget") r = F::index_add_to_target(V(0), V(1), V(2), I(0)); // (target, src, index)
+  else if (n == "GcnAggregation") r = F::gcn_aggregation(V(0), T(0), T(1), T(2));            // tensors = [rowptr, col, dinv]
   else if (n == "RepeatInterleave") r = F::repeat_interleave(V(0), V(1), I(0));
   else if (n == "ExpandAs") r = F::expand_as(V(0), T(0));
   else if (n == "Expand") r = F::expand(V(0), IV(0, ni));

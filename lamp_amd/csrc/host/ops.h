@@ -112,6 +112,8 @@ Var cross(const Var& a, const Var& b, int64_t dim);
 Var argmax(const Var& a, int64_t dim, bool keepDim);      // not differentiable: backprop through it raises, as in the reference
 Var one_hot(const Var& a, int64_t numClasses);            // not differentiable
 Var eq_where(const Var& a, int64_t b);
+// GCN.gcnAggregation (nn/graph/GCN.scala:137-145) over the CSR of lamp_gcn_adjacency: one kernel forward, the same kernel backward
+Var gcn_aggregation(const Var& nodeFeatures, const Ten& rowptr, const Ten& col, const Ten& dinv);
 
 }  // namespace F
 }  // namespace host

@@ -207,6 +207,20 @@ Var eq_where(const Var& a, int64_t b) {                               // no para
   return make_result(op, Ten(v));
 }
 
+// ---- graph (nn/graph/GCN.scala:137-145) -------------------------------------------------------------------------------------------------
+// GcnAggregation: degrees * ((A + A' + I) mm (x * degrees)) in one kernel over the CSR of lamp_gcn_adjacency.  The operator is
+// symmetric, so the closure is the same call on p: out += aggregate(p).  No intermediate is recorded.
+Var gcn_aggregation(const Var& nodeFeatures, const Ten& rowptr, const Ten& col, const Ten& dinv) {
+  auto op = new_op("GcnAggregation");
+  auto aggregate = [rowptr, col, dinv](const Ten& t) {
+    lamp_tensor* o = nullptr;
+    HCALL(lamp_gcn_aggregate(&o, t.h(), rowptr.h(), col.h(), dinv.h()));
+    return Ten(o);
+  };
+  op->params.push_back({nodeFeatures, [aggregate](const Ten& p, Variable& out) { out.accumulate(aggregate(p), true); }});
+  return make_result(op, aggregate(nodeFeatures->value));
+}
+
 // ---- element-wise (ops.scala:841-916, 2287-2340) -------------------------------------------------------------------------------------
 Var tan(const Var& a) {                                               // Tan: tmp = value^2 ; tmp += ones(1) ; out.addcmulSelf(p, tmp, 1)
   auto op = new_op("Tan");

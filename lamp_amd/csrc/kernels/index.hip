@@ -650,6 +650,7 @@ int lamp_index_add_(lamp_tensor* self, int64_t dim, const lamp_tensor* index, co
   Hold sc(contiguous(source)), ic(contiguous(index));
   const int64_t total = outer * J * inner;
   if (total) {
+    KernelTimer kt("index_add", (double)total, (double)total * 3 * self->itemsize() + (double)J * 8, current_stream(self->device()));
     LAMP_DISPATCH_ALL(self->dtype, T, hipLaunchKernelGGL((index_add_kernel<T>), dim3(grid_for(total, 256)), dim3(256), 0,
                                                          current_stream(self->device()), self->ptr<T>(), ic->ptr<int64_t>(), sc->ptr<T>(), outer, D, inner, J));
     LAMP_LAUNCH_CHECK();
