@@ -586,49 +586,162 @@ __global__ __launch_bounds__(256) void bn_bwd_apply2_kernel(const T* __restrict_
 // ---- batch-norm backward in ONE pass over (dy, x) ------------------------------------------------------------------------------
 // The two kernels above read dy and x (and the addend) twice: once for the channel sums, once for dx.  A bf16 activation of the
 // ResNet step is at most 33.5 MB, and the register files of the chip hold 128 MB: here workgroup (c, s) - 512 threads, slice s of
-// channel c's 16-byte packets - loads its packets ONCE, keeps the (masked) gradient and x in registers (NP packets of each per
-// thread), publishes its partial sums, waits for the S - 1 other workgroups of its channel, sums the S partials in a fixed order
-// (every workgroup of the channel gets the same bits; nothing is atomically accumulated) and writes dx (and the addend's gradient)
-// from the registers.  HBM traffic 5 -> 3 passes (7 -> 5 with an addend), one launch instead of two.
-// Waiting is safe because workgroups are handed out in launch order and a channel's S workgroups are consecutive (b = c * S + s):
+// channel c's 16-byte packets (8 bf16, 4 floats or 2 doubles) - loads its packets ONCE, keeps the (masked) gradient and x in
+// registers (NP packets of each per thread), publishes its partial sums, waits for the S - 1 other workgroups of its channel, sums
+// the S partials in a fixed order (every workgroup of the channel gets the same bits; nothing is atomically accumulated) and writes
+// dx (and the addend's gradient) from the registers.  HBM traffic 5 -> 3 passes (7 -> 5 with an addend), one launch instead of two.
+// Sums in the accumulation type of the two-kernel form (f32 / f64).
+// Waiting is safe because workgroups are handed out in launch order and a channel's S workgroups are consecutive (b = cl * S + s):
 // the oldest incomplete channel always gets the next free slots.  Two SUCH kernels running at once on one device (different
 // streams) could in principle starve each other, so the host orders them by an event when the stream changes; a wait that is
-// never satisfied (~seconds) traps instead of hanging the device.
-// slots[c * S + s] = workgroup (c, s)'s (s1, s2), all-ones between launches; depart[c] counts the workgroups that have read the channel's
-// slots, zero between launches: the last one to leave resets both.
-// DUAL (lamp_native_batch_norm2_add_relu_backward): the addend is itself a batch norm's output, round(bn2(x2)), which the forward never
-// wrote: `addend` points at x2, the mask is recomputed from (x, x2), a third sum (sum g (x2 - mean2)) travels through a second slot, and
-// instead of the masked gradient the kernel writes the SECOND batch norm's input gradient (x2 is read once more for that - by then it
-// comes from the Infinity Cache) and its dweight / dbias: one launch and 6 passes instead of two launches and 8.
-struct BnFusedDual { const bf16_t* mean2; const bf16_t* invstd2; const bf16_t* w2; const bf16_t* b2; bf16_t* dweight2; bf16_t* dbias2; unsigned long long* slots2; };
-template <int NP, bool RELU, bool ADD, bool DUAL = false, bool PLANES = false>  // compile-time: run-time branches in the element loop let the compiler sink the sums
-__global__ __launch_bounds__(512) void bn_bwd_fused_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, const bf16_t* __restrict__ mean,
-                                                           const bf16_t* __restrict__ invstd, const bf16_t* __restrict__ w, const bf16_t* __restrict__ b,
-                                                           unsigned long long* slots, unsigned* depart, bf16_t* dweight, bf16_t* dbias, bf16_t* __restrict__ dx,
-                                                           int64_t N, int C, int HW, int S, double inv_m, int relu,
-                                                           const bf16_t* __restrict__ addend, bf16_t* __restrict__ dadd, int vshift, int* assert_word,
-                                                           BnFusedDual dual, int dy_sc) {
+// never satisfied reports a device-side assertion instead of hanging the device.
+// An f32 activation of the step is 67 MB - more than 256 co-resident workgroups hold (33.5 MB per operand) - so the host launches the
+// channels of f32 / f64 in CHUNKS that are each fully co-resident (64 channels x 4 slices for 128 x 2048 x 8 x 8 in f32): c0 is the
+// chunk's first channel, cl = c - c0 the channel inside the launch; slots and counters are indexed by cl.  bf16 is one chunk.
+// DUAL (bf16, lamp_native_batch_norm2_add_relu_backward): the addend is itself a batch norm's output, round(bn2(x2)), which the forward
+// never wrote: `addend` points at x2, the mask is recomputed from (x, x2), a third sum (sum g (x2 - mean2)) travels through the second
+// slot array, and instead of the masked gradient the kernel writes the SECOND batch norm's input gradient (x2 is read once more for that -
+// by then it comes from the Infinity Cache) and its dweight / dbias: one launch and 6 passes instead of two launches and 8.
+//
+// The exchange (bn_publish, bn_poll, bn_collect).  slots[cl * S + s] holds workgroup (cl, s)'s sums, all-ones between launches;
+// depart[cl] counts the workgroups that have read the channel's slots, zero between launches: the last one to leave resets both.
+// No fences (a release / acquire pair at agent scope writes back and invalidates the XCD's whole L2: the step got 35 % slower) and no
+// counter on the critical path: a workgroup publishes its sums by 8-byte relaxed agent-scope atomic stores into its slot, and everybody
+// polls the S slots (agent-scope atomic loads bypass the per-XCD L2) until none holds the all-ones pattern - two memory round trips in
+// all.  Slot encodings: two f32 sums share one slot (s1 low, s2 high); an f64 sum fills a slot, so s2 goes to the second slot array;
+// DUAL's third f32 sum goes there too (upper word 0: never the all-ones pattern).  A sum whose own bits are all ones (a NaN) is
+// published as the quiet NaN.  The second array's slot is stored FIRST and the reader polls both: two independent relaxed stores are not
+// ordered for the reader.
+__device__ __forceinline__ unsigned bn_slot_bits(float v) {
+  const unsigned b = __float_as_uint(v);
+  return b == 0xffffffffu ? 0x7fc00000u : b;                // a NaN either way; the all-ones pattern means "not written yet"
+}
+__device__ __forceinline__ unsigned long long bn_slot_bits(double v) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  return b == ~0ull ? 0x7ff8000000000000ull : b;
+}
+// lane 0 of workgroup (cl, s): v[0 .. NS) into slot (and slot2), the two arrays' entries of this workgroup
+template <class A, int NS>
+__device__ __forceinline__ void bn_publish(unsigned long long* slot, unsigned long long* slot2, const A (&v)[NS]) {
+  if constexpr (sizeof(A) == 8) {
+    __hip_atomic_store(slot2, bn_slot_bits(v[1]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(slot, bn_slot_bits(v[0]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else {
+    if constexpr (NS == 3) __hip_atomic_store(slot2, (unsigned long long)__float_as_uint(v[2]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(slot, (unsigned long long)bn_slot_bits(v[0]) | ((unsigned long long)bn_slot_bits(v[1]) << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+// The wait ends when the channel's other workgroups have run, and they run as soon as compute units are free: workgroups are handed
+// out in launch order, so a foreign kernel that holds CUs (an RCCL collective waiting for a slow peer) only delays this one.  No trap
+// (a straggling rank must not abort the process): after two minutes of the 100 MHz clock the lane reports a device-side assertion -
+// raised by the host's next wait - and goes on, so the slots still return to rest.
+__device__ __forceinline__ unsigned long long bn_poll(unsigned long long* slot, unsigned& spins, unsigned long long& t0, bool& gave_up, int* assert_word) {
+  unsigned long long v;
+  while ((v = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == ~0ull && !gave_up) {
+    __builtin_amdgcn_s_sleep(2);
+    if ((++spins & 0xfffu) == 0) {
+      const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+      if (t0 == 0) t0 = now;
+      else if (now - t0 > 12000000000ull) { gave_up = true; if (assert_word) *assert_word = kAssertBnExchangeTimeout; }
+    }
+  }
+  return v;
+}
+// wave 0 of every workgroup of the channel: v = the sums of the channel's S slots in a fixed order (lane k, stride 64, then wave_sum);
+// every slot of the channel has then been read by this workgroup, and the last one to say so puts the slots back to rest
+template <class A, int NS>
+__device__ __forceinline__ void bn_collect(unsigned long long* slot, unsigned long long* slot2, unsigned* depart, int S, int lane, int* assert_word, A (&v)[NS]) {
+  constexpr bool TWO = NS == 3 || sizeof(A) == 8;           // the second slot array is in use
+#pragma unroll
+  for (int i = 0; i < NS; i++) v[i] = A(0);
+  unsigned spins = 0;
+  unsigned long long t0 = 0;
+  bool gave_up = false;
+  for (int k = lane; k < S; k += 64) {
+    const unsigned long long w = bn_poll(slot + k, spins, t0, gave_up, assert_word);
+    if constexpr (sizeof(A) == 8) {
+      const unsigned long long w2 = bn_poll(slot2 + k, spins, t0, gave_up, assert_word);
+      v[0] += (A)__longlong_as_double((long long)w); v[1] += (A)__longlong_as_double((long long)w2);
+    } else {
+      v[0] += (A)__uint_as_float((unsigned)w); v[1] += (A)__uint_as_float((unsigned)(w >> 32));
+      if constexpr (NS == 3) v[2] += (A)__uint_as_float((unsigned)bn_poll(slot2 + k, spins, t0, gave_up, assert_word));
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NS; i++) v[i] = wave_sum(v[i]);
+  if (lane == 0) {
+    const unsigned left = __hip_atomic_fetch_add(depart, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (left == (unsigned)S - 1) {
+      for (int k = 0; k < S; k++) __hip_atomic_store(slot + k, ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (TWO) for (int k = 0; k < S; k++) __hip_atomic_store(slot2 + k, ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(depart, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+__device__ __forceinline__ float bn_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }   // explicit: every instantiation rounds alike
+__device__ __forceinline__ double bn_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+// The arithmetic on one 16-byte packet: element q as the accumulation type, element q set to zero in place (where the mask says so), element q of a result
+// (q ascending), and the bracket of dx = (g - mean(g) - (x - mean) k) invstd w.  f32 / f64: the expression of bn_bwd_apply2_kernel.
+template <class T> struct BnPacket {
+  using A = acc_t<T>;
+  static constexpr int W = 16 / (int)sizeof(T);
+  static __device__ __forceinline__ A get(const uint4& p, int q) { return load_as<A>(reinterpret_cast<const T*>(&p)[q]); }
+  static __device__ __forceinline__ void zero_if(uint4& p, int q, bool off) { if (off) reinterpret_cast<T*>(&p)[q] = store_as<T>(A(0)); }
+  static __device__ __forceinline__ void put(uint4& p, int q, A v) { reinterpret_cast<T*>(&p)[q] = store_as<T>(v); }
+  static __device__ __forceinline__ A centred(A g, A gm, A x, A mu, A kk) { return g - gm - (x - mu) * kk; }
+};
+// bf16: shifts and masks on the 32-bit words (element 2 j in the low half of word j), and one explicit fma in dx
+template <> struct BnPacket<bf16_t> {
+  using A = float;
+  static constexpr int W = 8;
+  static __device__ __forceinline__ float get(const uint4& p, int q) {
+    const unsigned w = (&p.x)[q >> 1];
+    return __uint_as_float((q & 1) ? (w & 0xffff0000u) : (w << 16));
+  }
+  static __device__ __forceinline__ void zero_if(uint4& p, int q, bool off) { (&p.x)[q >> 1] &= !off ? ~0u : (q & 1) ? 0x0000ffffu : 0xffff0000u; }
+  static __device__ __forceinline__ void put(uint4& p, int q, float v) {
+    unsigned& w = (&p.x)[q >> 1];
+    const unsigned b = bf16_t(v).bits;
+    w = (q & 1) ? (w | (b << 16)) : b;
+  }
+  static __device__ __forceinline__ float centred(float g, float gm, float x, float mu, float kk) { return __builtin_fmaf(-(x - mu), kk, g - gm); }
+};
+
+template <class T> struct BnFusedDual { const T* mean2; const T* invstd2; const T* w2; const T* b2; T* dweight2; T* dbias2; };
+// (NP <= 2: every instantiation fits four workgroups per CU, 8 waves per SIMD - held there, the bf16 dual form at NP = 2 sits on the 64-register edge)
+template <class T, int NP, bool RELU, bool ADD, bool DUAL, bool PLANES>  // compile-time: run-time branches in the element loop let the compiler sink the sums
+__global__ __launch_bounds__(512, NP <= 2 ? 8 : 2) void bn_bwd_fused_kernel(const T* __restrict__ dy, const T* __restrict__ x, const T* __restrict__ mean, const T* __restrict__ invstd,
+                                                           const T* __restrict__ w, const T* __restrict__ b, unsigned long long* slots, unsigned long long* slots2,
+                                                           unsigned* depart, T* dweight, T* dbias, T* __restrict__ dx, int64_t N, int C, int HW, int S, double inv_m,
+                                                           const T* __restrict__ addend, T* __restrict__ dadd, int vshift, int* assert_word, int c0,
+                                                           BnFusedDual<T> dual, int dy_sc) {
   // PLANES: dy holds one value per PLANE, class-major - (n, c) at dy[c * dy_sc + n] - for 8 x 8 maps: the gradient arrives as a view expanded
   // over the map (the pooled LogSoftMax's input gradient, lamp_nll_loss_forward_pooled_gradient_); a packet is that value eight times, and the
   // [N, C, H, W] tensor does not exist.  A wave's 64 packets are the eight planes n8 .. n8 + 7 of channel c, whose values are 16 consecutive
   // bytes at a wave-uniform address: ONE scalar load per round (inline asm: the sixteen of a thread are all in flight together and waited for
   // once, behind the vector loads of x - as an ordinary load hipcc sank each into the lane-select branches with a wait of its own)
-  __shared__ float sm[3][8];
-  __shared__ float stat[3];
-  const int c = blockIdx.x / S, s = blockIdx.x - c * S;
+  static_assert(!(DUAL || PLANES) || std::is_same<T, bf16_t>::value, "the dual and plane forms exist in bf16");
+  using P = BnPacket<T>;
+  using A = typename P::A;
+  constexpr int W = P::W;
+  constexpr int NS = DUAL ? 3 : 2;                          // sums: g, g (x - mean), DUAL: g (x2 - mean2)
+  __shared__ A sm[NS][8];
+  __shared__ A stat[NS];
+  const int cl = blockIdx.x / S, s = blockIdx.x - cl * S, c = c0 + cl;      // cl: channel inside this launch's chunk
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int vpp = HW >> 3;
+  const int vpp = HW >> (W == 8 ? 3 : W == 4 ? 2 : 1);       // HW / W
   const int64_t total = N * vpp;                            // packets of this channel
-  const float mu = (float)mean[c], is = (float)invstd[c];
-  const float wc = w ? (float)w[c] : 1.f;
-  const float scale = is * wc, bb = (RELU && b) ? (float)b[c] : 0.f;
-  const float mu2 = DUAL ? (float)dual.mean2[c] : 0.f, is2 = DUAL ? (float)dual.invstd2[c] : 0.f;
-  const float wc2 = (DUAL && dual.w2) ? (float)dual.w2[c] : 1.f;
-  const float scale2 = is2 * wc2, bb2 = (DUAL && dual.b2) ? (float)dual.b2[c] : 0.f;
+  const A mu = load_as<A>(mean[c]), is = load_as<A>(invstd[c]);
+  const A wc = w ? load_as<A>(w[c]) : A(1);
+  const A scale = is * wc, bb = (RELU && b) ? load_as<A>(b[c]) : A(0);
+  const A mu2 = DUAL ? load_as<A>(dual.mean2[c]) : A(0), is2 = DUAL ? load_as<A>(dual.invstd2[c]) : A(0);
+  const A wc2 = (DUAL && dual.w2) ? load_as<A>(dual.w2[c]) : A(1);
+  const A scale2 = is2 * wc2, bb2 = (DUAL && dual.b2) ? load_as<A>(dual.b2[c]) : A(0);
   uint4 gv[NP], xv[NP];
   typedef unsigned int bn_u4s __attribute__((ext_vector_type(4)));
   bn_u4s pq[PLANES ? NP : 1];                               // PLANES: the eight plane values of each round, in scalar registers
-  int base[NP];                                             // packet (16-byte) index into the tensors, -1: none (host: numel < 2^34)
+  int base[NP];                                             // packet (16-byte) index into the tensors, -1: none (host: packets < 2^31)
   const uint4* dy4 = reinterpret_cast<const uint4*>(dy);
   const uint4* x4 = reinterpret_cast<const uint4*>(x);
   const uint4* ad4 = reinterpret_cast<const uint4*>(addend);
@@ -665,7 +778,7 @@ __global__ __launch_bounds__(512) void bn_bwd_fused_kernel(const bf16_t* __restr
 #pragma unroll
   for (int k = 0; k < NP; k++)
     if (base[k] < 0) gv[k] = make_uint4(0, 0, 0, 0);        // contributes nothing to the sums, never stored
-  float s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  A s1 = 0, s2 = 0, s3 = 0;
   constexpr int HALF = NP > 4 ? 4 : NP;                     // the addend is only needed for the mask: loaded in groups of <= 4 packets
 #pragma unroll
   for (int h = 0; h < NP; h += HALF) {
@@ -676,30 +789,24 @@ __global__ __launch_bounds__(512) void bn_bwd_fused_kernel(const bf16_t* __restr
     }
 #pragma unroll
     for (int k = 0; k < HALF; k++) {
-      unsigned* g32 = &gv[h + k].x;
-      const unsigned* x32 = &xv[h + k].x;
-      const unsigned* a32 = &av[k].x;
 #pragma unroll
-      for (int q = 0; q < 4; q++) {
-        unsigned gw = g32[q];
-#pragma unroll
-        for (int e = 0; e < 2; e++) {
-          const float xx = __uint_as_float(e ? (x32[q] & 0xffff0000u) : (x32[q] << 16));
-          float gg = __uint_as_float(e ? (gw & 0xffff0000u) : (gw << 16));
-          float x2v = 0.f;
-          if (RELU) {
-            bf16_t pre(bn_affine<float>(xx, mu, scale, bb));
-            if (ADD) {
-              float av_ = __uint_as_float(e ? (a32[q] & 0xffff0000u) : (a32[q] << 16));
-              if (DUAL) { x2v = av_; av_ = (float)bf16_t(bn_affine<float>(av_, mu2, scale2, bb2)); }   // the left branch's output as its kernel rounds it
-              pre = bf16_t((float)pre + av_);
-            }
-            if ((float)pre < 0.f) { gg = 0.f; gw &= e ? 0x0000ffffu : 0xffff0000u; }
+      for (int q = 0; q < W; q++) {
+        const A xx = P::get(xv[h + k], q);
+        A gg = P::get(gv[h + k], q);
+        A x2v = 0;
+        if (RELU) {
+          T pre = store_as<T>(bn_affine<A>(xx, mu, scale, bb));
+          if (ADD) {
+            A av_ = P::get(av[k], q);
+            if (DUAL) { x2v = av_; av_ = load_as<A>(store_as<T>(bn_affine<A>(av_, mu2, scale2, bb2))); }   // the left branch's output as its kernel rounds it
+            pre = store_as<T>((A)(load_as<A>(pre) + av_));
           }
-          s1 += gg; s2 = __builtin_fmaf(gg, xx - mu, s2);   // explicit: every instantiation rounds alike
-          if (DUAL) s3 = __builtin_fmaf(gg, x2v - mu2, s3);
+          const bool off = load_as<A>(pre) < A(0);
+          if (off) gg = A(0);
+          P::zero_if(gv[h + k], q, off);                    // gv: dy or 0, what dx and the addend's gradient are computed from
         }
-        g32[q] = gw;                                        // dy or 0: what dx and the addend's gradient are computed from
+        s1 += gg; s2 = bn_fma(gg, xx - mu, s2);
+        if (DUAL) s3 = bn_fma(gg, x2v - mu2, s3);
       }
       // the sums are one serial chain: without this the scheduler unpacks every packet ahead of it and keeps ~128 more values live
       __builtin_amdgcn_sched_barrier(0);
@@ -714,88 +821,39 @@ __global__ __launch_bounds__(512) void bn_bwd_fused_kernel(const bf16_t* __restr
   }
   s1 = wave_sum(s1); s2 = wave_sum(s2);
   if (DUAL) s3 = wave_sum(s3);
-  if (lane == 0) { sm[0][wid] = s1; sm[1][wid] = s2; if (DUAL) sm[2][wid] = s3; }
+  if (lane == 0) { sm[0][wid] = s1; sm[1][wid] = s2; if (DUAL) sm[NS - 1][wid] = s3; }
   __syncthreads();
   if (wid == 0) {
-    // Exchange of the partial sums between the S workgroups of the channel.  No fences (a release / acquire pair at agent scope writes
-    // back and invalidates the XCD's whole L2: the step got 35 % slower) and no counter on the critical path: a workgroup publishes
-    // (s1, s2) as ONE 8-byte agent-scope atomic store into its slot, and everybody polls the S slots (agent-scope atomic loads bypass
-    // the per-XCD L2) until none holds the all-ones pattern the slots rest at between launches - two memory round trips in all.
-    float a = 0.f, bs = 0.f, cs = 0.f;
+    A tot[NS];
 #pragma unroll
-    for (int k = 0; k < 8; k++) { a += sm[0][k]; bs += sm[1][k]; if (DUAL) cs += sm[2][k]; }
+    for (int i = 0; i < NS; i++) {
+      tot[i] = 0;
+#pragma unroll
+      for (int k = 0; k < 8; k++) tot[i] += sm[i][k];
+    }
     if (S > 1) {
-      unsigned long long* slot = slots + (int64_t)c * S;
-      unsigned long long* slot2 = DUAL ? dual.slots2 + (int64_t)c * S : nullptr;
-      if (lane == 0) {
-        unsigned lo = __float_as_uint(a), hi = __float_as_uint(bs);
-        if (lo == 0xffffffffu) lo = 0x7fc00000u;            // a NaN either way; the all-ones pattern means "not written yet"
-        if (hi == 0xffffffffu) hi = 0x7fc00000u;
-        // DUAL: the third sum first (upper word 0: never the all-ones pattern); whoever then sees the first slot written ...
-        if (DUAL) __hip_atomic_store(slot2 + s, (unsigned long long)__float_as_uint(cs), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(slot + s, (unsigned long long)lo | ((unsigned long long)hi << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      a = 0.f; bs = 0.f; cs = 0.f;
-      // The wait ends when the channel's other workgroups have run, and they run as soon as compute units are free: workgroups are
-      // handed out in launch order, so a foreign kernel that holds CUs (an RCCL collective waiting for a slow peer) only delays this
-      // one.  No trap (a straggling rank must not abort the process): after two minutes of the 100 MHz clock the lane
-      // reports a device-side assertion - raised by the host's next wait - and goes on, so the slots still return to rest.
-      unsigned spins = 0;
-      unsigned long long t0 = 0;
-      bool gave_up = false;
-      for (int k = lane; k < S; k += 64) {
-        unsigned long long v;
-        while ((v = __hip_atomic_load(slot + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == ~0ull && !gave_up) {
-          __builtin_amdgcn_s_sleep(2);
-          if ((++spins & 0xfffu) == 0) {
-            const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-            if (t0 == 0) t0 = now;
-            else if (now - t0 > 12000000000ull) { gave_up = true; if (assert_word) *assert_word = kAssertBnExchangeTimeout; }
-          }
-        }
-        a += __uint_as_float((unsigned)v); bs += __uint_as_float((unsigned)(v >> 32));
-        if (DUAL) {
-          // ... polls the second one by itself (two independent relaxed stores are not ordered for the reader)
-          unsigned long long v2;
-          while ((v2 = __hip_atomic_load(slot2 + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == ~0ull && !gave_up) {
-            __builtin_amdgcn_s_sleep(2);
-            if ((++spins & 0xfffu) == 0) {
-              const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-              if (t0 == 0) t0 = now;
-              else if (now - t0 > 12000000000ull) { gave_up = true; if (assert_word) *assert_word = kAssertBnExchangeTimeout; }
-            }
-          }
-          cs += __uint_as_float((unsigned)v2);
-        }
-      }
-      a = wave_sum(a); bs = wave_sum(bs);
-      if (DUAL) cs = wave_sum(cs);
-      // every slot of the channel has been read by this workgroup; the last one to say so puts the slots back to rest
-      if (lane == 0) {
-        const unsigned left = __hip_atomic_fetch_add(depart + c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (left == (unsigned)S - 1) {
-          for (int k = 0; k < S; k++) __hip_atomic_store(slot + k, ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (DUAL) for (int k = 0; k < S; k++) __hip_atomic_store(slot2 + k, ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(depart + c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
+      unsigned long long* slot = slots + (int64_t)cl * S;
+      unsigned long long* slot2 = slots2 + (int64_t)cl * S;
+      if (lane == 0) bn_publish<A, NS>(slot + s, slot2 + s, tot);
+      bn_collect<A, NS>(slot, slot2, depart + cl, S, lane, assert_word, tot);
     }
     if (lane == 0) {
-      stat[0] = a; stat[1] = bs; if (DUAL) stat[2] = cs;
+#pragma unroll
+      for (int i = 0; i < NS; i++) stat[i] = tot[i];
       if (s == 0) {
-        if (dweight) dweight[c] = bf16_t(bs * is);
-        if (dbias) dbias[c] = bf16_t(a);
-        if (DUAL) {
-          if (dual.dweight2) dual.dweight2[c] = bf16_t(cs * is2);
-          if (dual.dbias2) dual.dbias2[c] = bf16_t(a);
+        if (dweight) dweight[c] = store_as<T>((A)(tot[1] * is));
+        if (dbias) dbias[c] = store_as<T>(tot[0]);
+        if constexpr (DUAL) {
+          if (dual.dweight2) dual.dweight2[c] = store_as<T>((A)(tot[NS - 1] * is2));
+          if (dual.dbias2) dual.dbias2[c] = store_as<T>(tot[0]);
         }
       }
     }
   }
   __syncthreads();
   if (!dx && !dadd) return;
-  const float kk = stat[1] * is * is * (float)inv_m, gm = stat[0] * (float)inv_m;
-  const float kk2 = DUAL ? stat[2] * is2 * is2 * (float)inv_m : 0.f;
+  const A kk = stat[1] * is * is * (A)inv_m, gm = stat[0] * (A)inv_m;
+  const A kk2 = DUAL ? stat[NS - 1] * is2 * is2 * (A)inv_m : A(0);
   if (DUAL && dadd) {
     // the second batch norm's input gradient: dx2 = (g - mean(g) - (x2 - mean2) k2) invstd2 w2 from the masked gradient in registers and
     // x2 read once more (groups of <= 4 packets, as the mask's reads above)
@@ -808,16 +866,8 @@ __global__ __launch_bounds__(512) void bn_bwd_fused_kernel(const bf16_t* __restr
       for (int k = 0; k < HALF; k++) {
         if (base[h + k] < 0) continue;
         uint4 r;
-        unsigned* r32 = &r.x;
-        const unsigned* g32 = &gv[h + k].x;
-        const unsigned* x32 = &av[k].x;
 #pragma unroll
-        for (int q = 0; q < 4; q++) {
-          const float g0 = __uint_as_float(g32[q] << 16), g1 = __uint_as_float(g32[q] & 0xffff0000u);
-          const float x0 = __uint_as_float(x32[q] << 16), x1 = __uint_as_float(x32[q] & 0xffff0000u);
-          const bf16_t lo(__builtin_fmaf(-(x0 - mu2), kk2, g0 - gm) * is2 * wc2), hi(__builtin_fmaf(-(x1 - mu2), kk2, g1 - gm) * is2 * wc2);
-          r32[q] = (unsigned)lo.bits | ((unsigned)hi.bits << 16);
-        }
+        for (int q = 0; q < W; q++) P::put(r, q, P::centred(P::get(gv[h + k], q), gm, P::get(av[k], q), mu2, kk2) * is2 * wc2);
         reinterpret_cast<uint4*>(dadd)[base[h + k]] = r;
       }
     }
@@ -828,182 +878,8 @@ __global__ __launch_bounds__(512) void bn_bwd_fused_kernel(const bf16_t* __restr
     if (!DUAL && dadd) reinterpret_cast<uint4*>(dadd)[base[k]] = gv[k];
     if (dx) {
       uint4 r;
-      unsigned* r32 = &r.x;
-      const unsigned* g32 = &gv[k].x;
-      const unsigned* x32 = &xv[k].x;
 #pragma unroll
-      for (int q = 0; q < 4; q++) {
-        const float g0 = __uint_as_float(g32[q] << 16), g1 = __uint_as_float(g32[q] & 0xffff0000u);
-        const float x0 = __uint_as_float(x32[q] << 16), x1 = __uint_as_float(x32[q] & 0xffff0000u);
-        const bf16_t lo(__builtin_fmaf(-(x0 - mu), kk, g0 - gm) * is * wc), hi(__builtin_fmaf(-(x1 - mu), kk, g1 - gm) * is * wc);
-        r32[q] = (unsigned)lo.bits | ((unsigned)hi.bits << 16);
-      }
-      reinterpret_cast<uint4*>(dx)[base[k]] = r;
-    }
-  }
-}
-
-// ---- the one-pass backward in f32 and f64 (round 5): the precisions the reference's CIFAR example runs in ---------------
-// (example-cifar100 cifar100.scala:127-129; op ops.scala:2037-2140).  The same protocol as bn_bwd_fused_kernel on 16-byte packets of 4 floats /
-// 2 doubles: workgroup (c, s) keeps its NP packets of (masked) dy and of x in registers, publishes its two partial sums, polls the S slots
-// of its channel, sums them in a fixed order and writes dx (and the addend's gradient) from the registers: 5 -> 3 passes (7 -> 5 with an
-// addend), one launch instead of two.  Sums in the accumulation type of the two-kernel form (f32 / f64).  An f32 activation of the step is
-// 67 MB - more than 256 co-resident workgroups hold (33.5 MB per operand) - so the host launches the channels in CHUNKS that are each fully
-// co-resident (64 channels x 4 slices for 128 x 2048 x 8 x 8 in f32): c0 is the chunk's first channel, slots are indexed inside the chunk.
-// f64 sums need 16 bytes: the second sum travels through a second slot array (each slot is written by one 8-byte atomic store; the reader
-// polls both, as the dual bf16 form does).
-template <class A> __device__ __forceinline__ unsigned long long bn_slot_bits(A v);
-template <> __device__ __forceinline__ unsigned long long bn_slot_bits<double>(double v) {
-  unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  return b == ~0ull ? 0x7ff8000000000000ull : b;            // a NaN either way; the all-ones pattern means "not written yet"
-}
-template <class T, int NP, bool RELU, bool ADD>
-__global__ __launch_bounds__(512) void bn_bwd_fused_fp_kernel(const T* __restrict__ dy, const T* __restrict__ x, const T* __restrict__ mean, const T* __restrict__ invstd,
-                                                              const T* __restrict__ w, const T* __restrict__ b, unsigned long long* slots, unsigned long long* slots2,
-                                                              unsigned* depart, T* dweight, T* dbias, T* __restrict__ dx, int64_t N, int C, int HW, int S, double inv_m,
-                                                              const T* __restrict__ addend, T* __restrict__ dadd, int vshift, int* assert_word, int c0) {
-  using A = acc_t<T>;
-  constexpr int W = 16 / (int)sizeof(T);
-  constexpr bool F64 = sizeof(A) == 8;
-  __shared__ A sm[2][8];
-  __shared__ A stat[2];
-  const int cl = blockIdx.x / S, s = blockIdx.x - cl * S, c = c0 + cl;      // cl: channel inside this launch's chunk
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int vpp = HW / W;
-  const int64_t total = N * vpp;                            // packets of this channel
-  const A mu = load_as<A>(mean[c]), is = load_as<A>(invstd[c]);
-  const A wc = w ? load_as<A>(w[c]) : A(1);
-  const A scale = is * wc, bb = (RELU && b) ? load_as<A>(b[c]) : A(0);
-  uint4 gv[NP], xv[NP];
-  int base[NP];                                             // packet (16-byte) index into the tensors, -1: none (host: packets < 2^31)
-  const uint4* dy4 = reinterpret_cast<const uint4*>(dy);
-  const uint4* x4 = reinterpret_cast<const uint4*>(x);
-  const uint4* ad4 = reinterpret_cast<const uint4*>(addend);
-#pragma unroll
-  for (int k = 0; k < NP; k++) {
-    const unsigned i = (unsigned)(k * S + s) * 512u + (unsigned)tid;
-    const bool valid = i < (unsigned)total;
-    const unsigned ii = valid ? i : 0u;
-    const unsigned n = vshift >= 0 ? (ii >> vshift) : (ii / (unsigned)vpp);
-    const int idx = (int)((n * (unsigned)C + (unsigned)c) * (unsigned)vpp + (ii - n * (unsigned)vpp));
-    base[k] = valid ? idx : -1;
-    gv[k] = nt_load16(dy4 + idx);                           // the gradient's last reader
-    xv[k] = x4[idx];
-  }
-#pragma unroll
-  for (int k = 0; k < NP; k++)
-    if (base[k] < 0) gv[k] = make_uint4(0, 0, 0, 0);        // contributes nothing to the sums, never stored
-  A s1 = 0, s2 = 0;
-  constexpr int GRP = NP > 4 ? 4 : NP;                      // the addend is only needed for the mask: loaded in groups of <= 4 packets
-#pragma unroll
-  for (int h = 0; h < NP; h += GRP) {
-    uint4 av[GRP];
-    if (ADD) {
-#pragma unroll
-      for (int k = 0; k < GRP; k++) av[k] = ad4[base[h + k] >= 0 ? base[h + k] : c * vpp];
-    }
-#pragma unroll
-    for (int k = 0; k < GRP; k++) {
-      T* gp = reinterpret_cast<T*>(&gv[h + k]);
-      const T* xp = reinterpret_cast<const T*>(&xv[h + k]);
-      const T* ap = reinterpret_cast<const T*>(&av[k]);
-#pragma unroll
-      for (int q = 0; q < W; q++) {
-        const A xx = load_as<A>(xp[q]);
-        A gg = load_as<A>(gp[q]);
-        if (RELU) {
-          T pre = store_as<T>(bn_affine<A>(xx, mu, scale, bb));
-          if (ADD) pre = store_as<T>((A)(load_as<A>(pre) + load_as<A>(ap[q])));
-          if (load_as<A>(pre) < A(0)) { gg = A(0); gp[q] = store_as<T>(A(0)); }
-        }
-        s1 += gg;
-        if (F64) s2 = (A)__builtin_fma((double)gg, (double)(xx - mu), (double)s2); else s2 = (A)__builtin_fmaf((float)gg, (float)(xx - mu), (float)s2);
-      }
-      __builtin_amdgcn_sched_barrier(0);                    // the sums are one serial chain (as in the bf16 kernel)
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < NP; k++) {
-    asm volatile("" : "+v"(gv[k].x), "+v"(gv[k].y), "+v"(gv[k].z), "+v"(gv[k].w));
-    asm volatile("" : "+v"(xv[k].x), "+v"(xv[k].y), "+v"(xv[k].z), "+v"(xv[k].w));
-  }
-  s1 = wave_sum(s1); s2 = wave_sum(s2);
-  if (lane == 0) { sm[0][wid] = s1; sm[1][wid] = s2; }
-  __syncthreads();
-  if (wid == 0) {
-    A a = 0, bs = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) { a += sm[0][k]; bs += sm[1][k]; }
-    if (S > 1) {
-      unsigned long long* slot = slots + (int64_t)cl * S;
-      unsigned long long* slot2 = slots2 + (int64_t)cl * S;
-      if (lane == 0) {
-        if (F64) {
-          __hip_atomic_store(slot2 + s, bn_slot_bits<double>((double)bs), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(slot + s, bn_slot_bits<double>((double)a), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-          unsigned lo = __float_as_uint((float)a), hi = __float_as_uint((float)bs);
-          if (lo == 0xffffffffu) lo = 0x7fc00000u;
-          if (hi == 0xffffffffu) hi = 0x7fc00000u;
-          __hip_atomic_store(slot + s, (unsigned long long)lo | ((unsigned long long)hi << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-      a = 0; bs = 0;
-      unsigned spins = 0;
-      unsigned long long t0 = 0;
-      bool gave_up = false;
-      auto poll = [&](unsigned long long* p) {
-        unsigned long long v;
-        while ((v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == ~0ull && !gave_up) {
-          __builtin_amdgcn_s_sleep(2);
-          if ((++spins & 0xfffu) == 0) {
-            const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-            if (t0 == 0) t0 = now;
-            else if (now - t0 > 12000000000ull) { gave_up = true; if (assert_word) *assert_word = kAssertBnExchangeTimeout; }
-          }
-        }
-        return v;
-      };
-      for (int k = lane; k < S; k += 64) {
-        const unsigned long long v = poll(slot + k);
-        if (F64) {
-          const unsigned long long v2 = poll(slot2 + k);    // (two independent relaxed stores are not ordered for the reader)
-          a += (A)__longlong_as_double((long long)v); bs += (A)__longlong_as_double((long long)v2);
-        } else { a += (A)__uint_as_float((unsigned)v); bs += (A)__uint_as_float((unsigned)(v >> 32)); }
-      }
-      a = wave_sum(a); bs = wave_sum(bs);
-      if (lane == 0) {
-        const unsigned left = __hip_atomic_fetch_add(depart + cl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (left == (unsigned)S - 1) {
-          for (int k = 0; k < S; k++) __hip_atomic_store(slot + k, ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (F64) for (int k = 0; k < S; k++) __hip_atomic_store(slot2 + k, ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(depart + cl, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-    }
-    if (lane == 0) {
-      stat[0] = a; stat[1] = bs;
-      if (s == 0) {
-        if (dweight) dweight[c] = store_as<T>((A)(bs * is));
-        if (dbias) dbias[c] = store_as<T>(a);
-      }
-    }
-  }
-  __syncthreads();
-  if (!dx && !dadd) return;
-  // dx = (g - mean(g) - (x - mean) k) invstd w, k = sum(g (x - mean)) invstd^2 / m: the expression of bn_bwd_apply2_kernel
-  const A kk = stat[1] * is * is * (A)inv_m, gm = stat[0] * (A)inv_m;
-#pragma unroll
-  for (int k = 0; k < NP; k++) {
-    if (base[k] < 0) continue;
-    if (dadd) reinterpret_cast<uint4*>(dadd)[base[k]] = gv[k];
-    if (dx) {
-      uint4 r;
-      T* rp = reinterpret_cast<T*>(&r);
-      const T* gp = reinterpret_cast<const T*>(&gv[k]);
-      const T* xp = reinterpret_cast<const T*>(&xv[k]);
-#pragma unroll
-      for (int q = 0; q < W; q++) rp[q] = store_as<T>((A)((load_as<A>(gp[q]) - gm - (load_as<A>(xp[q]) - mu) * kk) * is * wc));
+      for (int q = 0; q < W; q++) P::put(r, q, P::centred(P::get(gv[k], q), gm, P::get(xv[k], q), mu, kk) * is * wc);
       reinterpret_cast<uint4*>(dx)[base[k]] = r;
     }
   }
@@ -1236,16 +1112,21 @@ static int pick_split(int64_t outputs_blocks, int64_t N) {
   s = std::min<int64_t>(s, 256);
   return (int)std::max<int64_t>(s, 1);
 }
-// The one-pass backward (bn_bwd_fused_kernel).  Returns false when the geometry does not qualify (the caller runs the two kernels).
+// The one-pass backward (bn_bwd_fused_kernel).
 static std::atomic<int> g_bn_bwd_mode{-1};
 struct BnFusedState { unsigned* sync = nullptr; hipStream_t last = nullptr; bool has_last = false; hipEvent_t ev = nullptr; };
-constexpr int BN_FUSED_MAXC = 4096;                         // depart[BN_FUSED_MAXC] (4-byte counters), then slots[BN_FUSED_SLOTS] (8 bytes each)
+constexpr int BN_FUSED_MAXC = 4096;                         // depart[BN_FUSED_MAXC] (4-byte counters), then two arrays of BN_FUSED_SLOTS slots (8 bytes each)
 constexpr int BN_FUSED_SLOTS = 4096;
+struct BnFusedSync { unsigned* depart = nullptr; unsigned long long* slots = nullptr; unsigned long long* slots2 = nullptr; };
 // the second batch norm of the dual form (bn_bwd_fused_kernel<.., DUAL>): `addc` is then ITS input x2 and `dadd` receives ITS input gradient
 struct BnDualHost { const Tensor* mean2; const Tensor* invstd2; const Tensor* w2; const Tensor* b2; Tensor* dw2; Tensor* db2; };
-// the per-device counters / slots of the waiting kernels, created on first use; orders this launch behind the previous waiting kernel of
-// another stream (two of them must not overlap).  nullptr: the buffer cannot be created from this thread (the tensor's device is not current).
-static unsigned* bn_fused_sync_state(int device, hipStream_t st) {
+// The per-device counters / slots of the waiting kernels, created on first use.  One set per device and workgroups that wait for each
+// other: two of these kernels must not overlap.  Same stream: ordered anyway.  Another stream: this launch waits for everything queued
+// there so far.  (A graph replayed on one stream while another thread runs eagerly on a second one is not covered: LAMP_BN_FUSED_BWD=0
+// for such a program.)  The buffer is set once, on a stream of its own and waited for: st may be capturing, and the counters must be
+// zero in memory before the first launch really runs.  depart == nullptr: the buffer cannot be created from this thread (the tensor's
+// device is not current; callers run with it current).
+static BnFusedSync bn_fused_sync_state(int device, hipStream_t st) {
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   (void)hipStreamIsCapturing(st, &cap);
   const bool capturing = cap == hipStreamCaptureStatusActive;
@@ -1254,7 +1135,7 @@ static unsigned* bn_fused_sync_state(int device, hipStream_t st) {
   std::lock_guard<std::mutex> lk(mu);
   BnFusedState& stt = states[device];
   if (!stt.sync) {
-    if (current_device() != device) return nullptr;
+    if (current_device() != device) return BnFusedSync();
     HIP_CHECK(hipMalloc((void**)&stt.sync, BN_FUSED_MAXC * sizeof(unsigned) + 2 * BN_FUSED_SLOTS * sizeof(unsigned long long)));
     hipStream_t side = nullptr;
     HIP_CHECK(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
@@ -1271,152 +1152,124 @@ static unsigned* bn_fused_sync_state(int device, hipStream_t st) {
     }
     stt.last = st; stt.has_last = true;
   }
-  return stt.sync;
+  BnFusedSync r;
+  r.depart = stt.sync;
+  r.slots = reinterpret_cast<unsigned long long*>(stt.sync + BN_FUSED_MAXC);
+  r.slots2 = r.slots + BN_FUSED_SLOTS;
+  return r;
 }
-// f32 / f64 (bn_bwd_fused_fp_kernel): the channels are launched in chunks whose workgroups are all co-resident
-template <class T>
-static bool bn_bwd_fused_fp_launch(const Tensor* gc, const Tensor* xc, const Tensor* mean_t, const Tensor* invstd_t, const Tensor* weight, const Tensor* bias,
-                                   Tensor* dw, Tensor* db, Tensor* dx, Tensor* dadd, const Tensor* addc, const BnGeom& g, int relu, hipStream_t st) {
-  const bool env_on = sw().bn_fused_bwd;
-  const bool fp_on = sw().bn_fused_fp;
+// Whether the one-pass form is wanted at all: the forced mode (lamp_set_bn_backward_mode) or the switches.  Not on a device that is also
+// running kernels this library does not schedule (the overlapped RCCL all-reduce of the eager data-parallel step): the waiting workgroups
+// would sit on their CUs until the foreign kernel lets the rest of their channel in - two kernels then
+static bool bn_fused_gate(int device, bool is_fp) {
   const int mode = g_bn_bwd_mode.load(std::memory_order_relaxed);
-  const bool on = mode < 0 ? (env_on && fp_on) : mode >= 1;
-  if (on && mode != 2 && device_shared(xc->device()) > 0) return false;
-  constexpr int W = 16 / (int)sizeof(T);
-  if (!on || g.HW % W != 0) return false;
-  const int64_t packets = g.N * (g.HW / W);                 // per channel
-  if (packets <= 0 || packets >= (int64_t)1 << 30 || xc->numel() / W >= (int64_t)1 << 31) return false;
-  if (addc && !relu) return false;
-  const int cus = num_cus();
+  const bool on = mode < 0 ? (sw().bn_fused_bwd && (!is_fp || sw().bn_fused_fp)) : mode >= 1;
+  return on && !(mode != 2 && device_shared(device) > 0);
+}
+// s slices per channel when wgs_per_cu workgroups per CU are aimed at, and the packets per thread NP (at most 16) that gives
+struct BnFusedSlices { int64_t s; int NP; };
+static BnFusedSlices bn_fused_slices(int64_t packets, int64_t C, int cus, int wgs_per_cu) {
   auto per_thread = [&](int64_t s) { return (packets + s * 512 - 1) / (s * 512); };
-  int64_t s = std::max<int64_t>(1, (int64_t)cus / g.C);
+  int64_t s = std::max<int64_t>(1, (int64_t)cus * wgs_per_cu / C);
   s = std::min<int64_t>(s, (packets + 511) / 512);
   if (per_thread(s) > 16) s = (packets + 16 * 512 - 1) / (16 * 512);
   const int ppt = (int)per_thread(s);
-  const int NP = ppt <= 1 ? 1 : ppt <= 2 ? 2 : ppt <= 4 ? 4 : ppt <= 8 ? 8 : 16;
-  const int np_mask = (int)sw().bn_fused_np_mask;   // as the bf16 form: the large activations
-  if (!(np_mask & NP)) return false;
-#define BN_FP_K(NPv) (addc ? (const void*)bn_bwd_fused_fp_kernel<T, NPv, true, true> : relu ? (const void*)bn_bwd_fused_fp_kernel<T, NPv, true, false> \
-                           : (const void*)bn_bwd_fused_fp_kernel<T, NPv, false, false>)
-  const void* kfn = NP == 1 ? BN_FP_K(1) : NP == 2 ? BN_FP_K(2) : NP == 4 ? BN_FP_K(4) : NP == 8 ? BN_FP_K(8) : BN_FP_K(16);
-#undef BN_FP_K
-  const int64_t resident = std::min<int64_t>(BN_FUSED_SLOTS, (int64_t)cus * std::max(1, kernel_occupancy(kfn, 512, 0)));
-  if (s > resident) return false;                           // one channel's slices alone do not fit the chip
-  const int64_t chunk = std::min<int64_t>(std::min<int64_t>(g.C, resident / s), BN_FUSED_MAXC);
-  unsigned* sync = bn_fused_sync_state(xc->device(), st);
-  if (!sync) return false;
-  unsigned* departp = sync;
-  unsigned long long* slotp = reinterpret_cast<unsigned long long*>(sync + BN_FUSED_MAXC);
-  unsigned long long* slot2p = slotp + BN_FUSED_SLOTS;
-  const double passes = (dx ? 3.0 : 2.0) + (addc ? 1.0 : 0.0) + (dadd ? 1.0 : 0.0);
-  KernelTimer kt("bn_bwd_fused", 0, passes * (double)xc->numel() * sizeof(T), st);
-  const T* dyp = gc->ptr<T>(); const T* xp = xc->ptr<T>();
-  const T* mp = mean_t->ptr<T>(); const T* ip = invstd_t->ptr<T>();
-  const T* wp = weight ? weight->ptr<T>() : (const T*)nullptr;
-  const T* bp = bias ? bias->ptr<T>() : (const T*)nullptr;
-  T* dwp = dw ? dw->ptr<T>() : (T*)nullptr; T* dbp = db ? db->ptr<T>() : (T*)nullptr;
-  T* dxp = dx ? dx->ptr<T>() : (T*)nullptr;
-  int64_t a_N = g.N; int a_C = (int)g.C, a_HW = (int)g.HW, a_S = (int)s;
-  double inv_m = 1.0 / (double)(g.N * g.HW);
-  const int vppi = (int)(g.HW / W);
-  int a_vshift = -1;
-  for (int b = 0; b < 31; b++) if (vppi == (1 << b)) a_vshift = b;
-  const T* adp = addc ? addc->ptr<T>() : (const T*)nullptr;
-  T* dap = dadd ? dadd->ptr<T>() : (T*)nullptr;
-  int* awp = device_assert_word(xc->device());
-  for (int64_t c0 = 0; c0 < g.C; c0 += chunk) {
-    int a_c0 = (int)c0;
-    const int64_t nc = std::min<int64_t>(chunk, g.C - c0);
-    void* args[] = {(void*)&dyp, (void*)&xp, (void*)&mp, (void*)&ip, (void*)&wp, (void*)&bp, (void*)&slotp, (void*)&slot2p, (void*)&departp, (void*)&dwp, (void*)&dbp,
-                    (void*)&dxp, (void*)&a_N, (void*)&a_C, (void*)&a_HW, (void*)&a_S, (void*)&inv_m, (void*)&adp, (void*)&dap, (void*)&a_vshift, (void*)&awp, (void*)&a_c0};
-    HIP_CHECK(hipLaunchKernel(kfn, dim3((unsigned)(nc * s)), dim3(512), args, 0, st));
+  return {s, ppt <= 1 ? 1 : ppt <= 2 ? 2 : ppt <= 4 ? 4 : ppt <= 8 ? 8 : 16};
+}
+// packets per image row a power of two: a shift instead of a division (-1: none)
+static int bn_fused_vshift(int64_t vpp) {
+  for (int b = 0; b < 31; b++) if (vpp == ((int64_t)1 << b)) return b;
+  return -1;
+}
+template <class T>
+static const void* bn_fused_kernel_for(int NP, bool relu, bool add, bool dual, bool planes) {
+#define BN_FUSED_K(NPv, R, AD, D, P) ((const void*)bn_bwd_fused_kernel<T, NPv, R, AD, D, P>)
+#define BN_FUSED_NP(R, AD, D, P) (NP == 1 ? BN_FUSED_K(1, R, AD, D, P) : NP == 2 ? BN_FUSED_K(2, R, AD, D, P) : NP == 4 ? BN_FUSED_K(4, R, AD, D, P) \
+                                  : NP == 8 ? BN_FUSED_K(8, R, AD, D, P) : BN_FUSED_K(16, R, AD, D, P))
+  if constexpr (std::is_same<T, bf16_t>::value) {
+    if (dual) return planes ? BN_FUSED_NP(true, true, true, true) : BN_FUSED_NP(true, true, true, false);
   }
-  return true;
+  return add ? BN_FUSED_NP(true, true, false, false) : relu ? BN_FUSED_NP(true, false, false, false) : BN_FUSED_NP(false, false, false, false);
+#undef BN_FUSED_NP
+#undef BN_FUSED_K
 }
 // gplanes (instead of gc): the gradient as one value per plane (see plane_broadcast_base)
 struct BnPlaneGrad { const bf16_t* p = nullptr; int sn = 0, sc = 0; };
+// Returns false when the geometry does not qualify (the caller runs the two kernels).  dualh and gplanes: bf16 only.
+template <class T>
 static bool bn_bwd_fused_launch(const Tensor* gc, const Tensor* xc, const Tensor* mean_t, const Tensor* invstd_t, const Tensor* weight, const Tensor* bias,
                                 Tensor* dw, Tensor* db, Tensor* dx, Tensor* dadd, const Tensor* addc, const BnGeom& g, int relu, hipStream_t st,
                                 const BnDualHost* dualh = nullptr, BnPlaneGrad gplanes = BnPlaneGrad()) {
-  const bool env_on = sw().bn_fused_bwd;
-  const int mode = g_bn_bwd_mode.load(std::memory_order_relaxed);
-  const bool on = mode < 0 ? env_on : mode >= 1;
-  // a device that is also running kernels this library does not schedule (the overlapped RCCL all-reduce of the eager data-parallel
-  // step): the waiting workgroups would sit on their CUs until the foreign kernel lets the rest of their channel in - two kernels then
-  if (on && mode != 2 && device_shared(xc->device()) > 0) return false;
-  if (!on || g.C > BN_FUSED_MAXC || g.HW % 8 != 0 || xc->numel() >= (int64_t)1 << 34) return false;
-  const int64_t packets = g.N * (g.HW / 8);                 // per channel
-  if (packets <= 0 || packets >= (int64_t)1 << 30) return false;
+  constexpr bool BF16 = std::is_same<T, bf16_t>::value;
+  constexpr int W = 16 / (int)sizeof(T);
+  if (!bn_fused_gate(xc->device(), !BF16) || g.HW % W != 0) return false;
+  const int64_t packets = g.N * (g.HW / W);                 // per channel
+  if (packets <= 0 || packets >= (int64_t)1 << 30 || xc->numel() / W >= (int64_t)1 << 31) return false;
   if (addc && !relu) return false;
-  const int cus = num_cus();
-  const int per_cu = (int)sw().bn_fused_per_cu;   // measured: 2 is slower
-  auto per_thread = [&](int64_t s) { return (packets + s * 512 - 1) / (s * 512); };
   // the scalar-load form of a plane gradient: 8 x 8 maps, class-major values in whole 16-byte groups (a wave's 64 packets are eight whole planes), the
   // dual form (the only consumer of the loss tail's gradient in Cnn.resnet); anything else gets the materialised tensor from the caller
   const bool planes = gplanes.p != nullptr;
   if (planes && !(dualh && g.HW == 64 && gplanes.sn == 1 && g.N % 8 == 0 && gplanes.sc % 8 == 0 && ((uintptr_t)gplanes.p & 15) == 0)) return false;
+  const int cus = num_cus();
+  // Which sizes take this path (bit = packets per thread).  Default: 8 and 16, i.e. activations of some 10 MB and more.  Below that the
+  // exchange between the workgroups (two memory round trips, ~3 us) costs what the second pass over an L2 / MALL-resident tensor
+  // costs: the ResNet step's six small layers were 4 us SLOWER in total with it, the six large ones 50 us faster.
+  const int np_mask = (int)sw().bn_fused_np_mask;
+  // every workgroup of a launch co-resident: nobody waits for a workgroup that has no slot yet
+  auto resident = [&](const void* k) { return std::min<int64_t>(BN_FUSED_SLOTS, (int64_t)cus * std::max(1, kernel_occupancy(k, 512, 0))); };
   const void* kfn = nullptr;
-  int64_t S = 0;
-  for (int wgs = per_cu; wgs >= 1 && !kfn; wgs--) {        // workgroups per CU aimed at: more, smaller ones first
-    int64_t s = std::max<int64_t>(1, (int64_t)cus * wgs / g.C);
-    s = std::min<int64_t>(s, (packets + 511) / 512);
-    if (per_thread(s) > 16) s = (packets + 16 * 512 - 1) / (16 * 512);
-    const int ppt = (int)per_thread(s);
-    const int NP = ppt <= 1 ? 1 : ppt <= 2 ? 2 : ppt <= 4 ? 4 : ppt <= 8 ? 8 : 16;
-    // Which sizes take this path (bit = packets per thread).  Default: 8 and 16, i.e. activations of some 10 MB and more.  Below that the
-    // exchange between the workgroups (two memory round trips, ~3 us) costs what the second pass over an L2 / MALL-resident tensor
-    // costs: the ResNet step's six small layers were 4 us SLOWER in total with it, the six large ones 50 us faster.
-    // The dual form replaces FOUR kernels (two reductions, two applies) and two passes more: taken at every size.
-    const int np_mask = (int)sw().bn_fused_np_mask;
+  int64_t S = 0, chunk = g.C;                               // slices per channel, channels per launch
+  if constexpr (BF16) {
+    if (g.C > BN_FUSED_MAXC) return false;
     // Activations of at most 4 MiB (the B <= 256 steps): both kernels of the two-pass form sit at the launch floor there, and one launch with an
     // exchange beats two (A/B: B = 256 0.5433 -> 0.5359 ms per step, B = 32 0.4671 -> 0.4545; the 4 MiB layer itself 0.5137 -> 0.5115); above
     // (B = 2048's small maps, 4 - 8 MB) it is even.
-    const int64_t small_bytes = sw().bn_fused_small_bytes;
-    if (!dualh && !(np_mask & NP) && !(xc->numel() * 2 < small_bytes)) continue;
-#define BN_FUSED_K(NPv) (dualh ? (planes ? (const void*)bn_bwd_fused_kernel<NPv, true, true, true, true> : (const void*)bn_bwd_fused_kernel<NPv, true, true, true>) \
-                               : addc ? (const void*)bn_bwd_fused_kernel<NPv, true, true> \
-                               : relu ? (const void*)bn_bwd_fused_kernel<NPv, true, false> : (const void*)bn_bwd_fused_kernel<NPv, false, false>)
-    const void* k = NP == 1 ? BN_FUSED_K(1) : NP == 2 ? BN_FUSED_K(2) : NP == 4 ? BN_FUSED_K(4) : NP == 8 ? BN_FUSED_K(8) : BN_FUSED_K(16);
-#undef BN_FUSED_K
-    // every workgroup co-resident: nobody waits for a workgroup that has no slot yet
-    if (g.C * s <= std::min<int64_t>(BN_FUSED_SLOTS, (int64_t)cus * std::max(1, kernel_occupancy(k, 512, 0)))) { kfn = k; S = s; }
+    // The dual form replaces FOUR kernels (two reductions, two applies) and two passes more: taken at every size.
+    const bool any_size = dualh || xc->numel() * 2 < sw().bn_fused_small_bytes;
+    for (int wgs = (int)sw().bn_fused_per_cu; wgs >= 1 && !kfn; wgs--) {   // workgroups per CU aimed at: more, smaller ones first (measured: 2 is slower)
+      const BnFusedSlices sl = bn_fused_slices(packets, g.C, cus, wgs);
+      if (!any_size && !(np_mask & sl.NP)) continue;
+      const void* k = bn_fused_kernel_for<T>(sl.NP, relu, addc, dualh, planes);
+      if (g.C * sl.s <= resident(k)) { kfn = k; S = sl.s; }   // the whole tensor in one launch
+    }
+    if (!kfn) return false;
+  } else {
+    // f32 / f64: the channels are launched in chunks whose workgroups are all co-resident
+    const BnFusedSlices sl = bn_fused_slices(packets, g.C, cus, 1);
+    if (!(np_mask & sl.NP)) return false;
+    kfn = bn_fused_kernel_for<T>(sl.NP, relu, addc, false, false);
+    const int64_t r = resident(kfn);
+    if (sl.s > r) return false;                             // one channel's slices alone do not fit the chip
+    S = sl.s;
+    chunk = std::min<int64_t>(std::min<int64_t>(g.C, r / S), BN_FUSED_MAXC);
   }
-  if (!kfn) return false;
-  // one counter set per device and workgroups that wait for each other: two of these kernels must not overlap.  Same stream: ordered anyway.
-  // Another stream: this launch waits for everything queued there so far.  (A graph replayed on one stream while another thread runs eagerly
-  // on a second one is not covered: LAMP_BN_FUSED_BWD=0 for such a program.)  The buffer is zeroed once, on a stream of its own and waited
-  // for: st may be capturing, and the counters must be zero in memory before the first launch really runs.
-  unsigned* sync = bn_fused_sync_state(xc->device(), st);
-  if (!sync) return false;                                  // (callers run with the tensor's device current; the buffer must live there)
-  unsigned* departp = sync;
-  unsigned long long* slotp = reinterpret_cast<unsigned long long*>(sync + BN_FUSED_MAXC);
-  const double passes = (dx ? 3.0 : 2.0) + (addc ? 1.0 : 0.0) + (dadd ? 1.0 : 0.0) - (gplanes.p ? 1.0 : 0.0);   // (the dual form's second read of x2 is served by the caches)
-  KernelTimer kt("bn_bwd_fused", 0, passes * (double)xc->numel() * 2.0, st);
-  const bf16_t* dyp = gplanes.p ? gplanes.p : gc->ptr<bf16_t>(); const bf16_t* xp = xc->ptr<bf16_t>();
-  const bf16_t* mp = mean_t->ptr<bf16_t>(); const bf16_t* ip = invstd_t->ptr<bf16_t>();
-  const bf16_t* wp = weight ? weight->ptr<bf16_t>() : (const bf16_t*)nullptr;
-  const bf16_t* bp = bias ? bias->ptr<bf16_t>() : (const bf16_t*)nullptr;
-  bf16_t* dwp = dw ? dw->ptr<bf16_t>() : (bf16_t*)nullptr; bf16_t* dbp = db ? db->ptr<bf16_t>() : (bf16_t*)nullptr;
-  bf16_t* dxp = dx ? dx->ptr<bf16_t>() : (bf16_t*)nullptr;
-  int64_t a_N = g.N; int a_C = (int)g.C, a_HW = (int)g.HW, a_S = (int)S, a_relu = relu, a_sc = gplanes.sc;
+  BnFusedSync sync = bn_fused_sync_state(xc->device(), st);
+  if (!sync.depart) return false;
+  const double passes = (dx ? 3.0 : 2.0) + (addc ? 1.0 : 0.0) + (dadd ? 1.0 : 0.0) - (planes ? 1.0 : 0.0);   // (the dual form's second read of x2 is served by the caches)
+  KernelTimer kt("bn_bwd_fused", 0, passes * (double)xc->numel() * sizeof(T), st);
+  auto in = [](const Tensor* t) { return t ? t->ptr<T>() : (const T*)nullptr; };
+  auto out = [](Tensor* t) { return t ? t->ptr<T>() : (T*)nullptr; };
+  const T* dyp = in(gc); const T* xp = in(xc); const T* mp = in(mean_t); const T* ip = in(invstd_t); const T* wp = in(weight); const T* bp = in(bias);
+  const T* adp = in(addc);
+  T* dwp = out(dw); T* dbp = out(db); T* dxp = out(dx); T* dap = out(dadd);
+  BnFusedDual<T> dual{};
+  int a_sc = 0;
+  if constexpr (BF16) {
+    if (planes) { dyp = gplanes.p; a_sc = gplanes.sc; }
+    if (dualh) dual = BnFusedDual<T>{in(dualh->mean2), in(dualh->invstd2), in(dualh->w2), in(dualh->b2), out(dualh->dw2), out(dualh->db2)};
+  }
+  int64_t a_N = g.N; int a_C = (int)g.C, a_HW = (int)g.HW, a_S = (int)S;
   double inv_m = 1.0 / (double)(g.N * g.HW);
-  const int vppi = (int)(g.HW / 8);
-  int a_vshift = -1;                                        // packets per image row a power of two: a shift instead of a division
-  for (int b = 0; b < 31; b++) if (vppi == (1 << b)) a_vshift = b;
-  const bf16_t* adp = addc ? addc->ptr<bf16_t>() : (const bf16_t*)nullptr;
-  bf16_t* dap = dadd ? dadd->ptr<bf16_t>() : (bf16_t*)nullptr;
+  int a_vshift = bn_fused_vshift(g.HW / W);
   int* awp = device_assert_word(xc->device());
-  BnFusedDual dual{};
-  if (dualh) {
-    dual.mean2 = dualh->mean2->ptr<bf16_t>(); dual.invstd2 = dualh->invstd2->ptr<bf16_t>();
-    dual.w2 = dualh->w2 ? dualh->w2->ptr<bf16_t>() : (const bf16_t*)nullptr; dual.b2 = dualh->b2 ? dualh->b2->ptr<bf16_t>() : (const bf16_t*)nullptr;
-    dual.dweight2 = dualh->dw2 ? dualh->dw2->ptr<bf16_t>() : (bf16_t*)nullptr; dual.dbias2 = dualh->db2 ? dualh->db2->ptr<bf16_t>() : (bf16_t*)nullptr;
-    dual.slots2 = slotp + BN_FUSED_SLOTS;
+  for (int64_t c0 = 0; c0 < g.C; c0 += chunk) {
+    int a_c0 = (int)c0;
+    const int64_t nc = std::min<int64_t>(chunk, g.C - c0);
+    void* args[] = {(void*)&dyp, (void*)&xp, (void*)&mp, (void*)&ip, (void*)&wp, (void*)&bp, (void*)&sync.slots, (void*)&sync.slots2, (void*)&sync.depart, (void*)&dwp,
+                    (void*)&dbp, (void*)&dxp, (void*)&a_N, (void*)&a_C, (void*)&a_HW, (void*)&a_S, (void*)&inv_m, (void*)&adp, (void*)&dap, (void*)&a_vshift, (void*)&awp,
+                    (void*)&a_c0, (void*)&dual, (void*)&a_sc};
+    HIP_CHECK(hipLaunchKernel(kfn, dim3((unsigned)(nc * S)), dim3(512), args, 0, st));
   }
-  void* args[] = {(void*)&dyp, (void*)&xp, (void*)&mp, (void*)&ip, (void*)&wp, (void*)&bp, (void*)&slotp, (void*)&departp, (void*)&dwp, (void*)&dbp, (void*)&dxp,
-                  (void*)&a_N, (void*)&a_C, (void*)&a_HW, (void*)&a_S, (void*)&inv_m, (void*)&a_relu, (void*)&adp, (void*)&dap, (void*)&a_vshift, (void*)&awp,
-                  (void*)&dual, (void*)&a_sc};
-  HIP_CHECK(hipLaunchKernel(kfn, dim3((unsigned)(g.C * S)), dim3(512), args, 0, st));
   return true;
 }
 // A gradient that is constant over every plane, handed over as a view expanded over the map (strides [sn, sc, 0, 0]) of one value per (n, c):
@@ -1672,12 +1525,9 @@ static int bn_backward_impl(lamp_tensor* out3[3], const lamp_tensor* grad_out, c
                                                           (uintptr_t)(AD ? AD->data() : nullptr) | (uintptr_t)(dadd.get() ? dadd->data() : nullptr)) & 15) == 0;
     const bool col = g.HW < 64;
     bool fused_done = false;
-    if constexpr (std::is_same<T, bf16_t>::value) {
+    if constexpr (!std::is_same<T, f16_t>::value) {         // (f16 has the two kernels only)
       if (training && vec && !col && total > 0 && (dx.get() || dadd.get()))
-        fused_done = bn_bwd_fused_launch(G, X, mean_t, invstd_t, weight, bias, dw.get(), db.get(), dx.get(), dadd.get(), AD, g, relu, st);
-    } else if constexpr (std::is_same<T, float>::value || std::is_same<T, double>::value) {
-      if (training && vec && !col && total > 0 && (dx.get() || dadd.get()))
-        fused_done = bn_bwd_fused_fp_launch<T>(G, X, mean_t, invstd_t, weight, bias, dw.get(), db.get(), dx.get(), dadd.get(), AD, g, relu, st);
+        fused_done = bn_bwd_fused_launch<T>(G, X, mean_t, invstd_t, weight, bias, dw.get(), db.get(), dx.get(), dadd.get(), AD, g, relu, st);
     }
     if (!fused_done) {
     const int64_t blocks = col ? (g.C + 255) / 256 : g.C;
@@ -1823,11 +1673,11 @@ int lamp_native_batch_norm2_add_relu_backward(lamp_tensor* out6[6], const lamp_t
     const bool aligned = g.HW % 8 == 0 && (((uintptr_t)xc->raw() | (uintptr_t)(gc.get() ? gc->raw() : nullptr) | (uintptr_t)x2c->raw() |
                                             (uintptr_t)(dx.get() ? dx->data() : nullptr) | (uintptr_t)(dx2.get() ? dx2->data() : nullptr)) & 15) == 0;
     BnDualHost dh{save_mean2, save_invstd2, weight2, bias2, dw2.get(), db2.get()};
-    bool done = aligned && bn_bwd_fused_launch(gc.get(), xc.get(), save_mean, save_invstd, weight, bias, dw.get(), db.get(), dx.get(), dx2.get(), x2c.get(), g, 1, st, &dh, gplanes);
+    bool done = aligned && bn_bwd_fused_launch<bf16_t>(gc.get(), xc.get(), save_mean, save_invstd, weight, bias, dw.get(), db.get(), dx.get(), dx2.get(), x2c.get(), g, 1, st, &dh, gplanes);
     if (!done && !gc.get()) {                               // the plane form did not take it: the same kernel on the materialised gradient
       gc = Hold(contiguous(grad_out));
       done = (((uintptr_t)gc->raw()) & 15) == 0 && g.HW % 8 == 0 &&
-             bn_bwd_fused_launch(gc.get(), xc.get(), save_mean, save_invstd, weight, bias, dw.get(), db.get(), dx.get(), dx2.get(), x2c.get(), g, 1, st, &dh);
+             bn_bwd_fused_launch<bf16_t>(gc.get(), xc.get(), save_mean, save_invstd, weight, bias, dw.get(), db.get(), dx.get(), dx2.get(), x2c.get(), g, 1, st, &dh);
     }
     if (done) {
       out6[0] = dx.take(); out6[1] = dw.take(); out6[2] = db.take(); out6[3] = dx2.take(); out6[4] = dw2.take(); out6[5] = db2.take();

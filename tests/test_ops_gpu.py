@@ -499,8 +499,8 @@ BN_ONE_PASS_CASES = [(2048, 128, 8, 2), (2048, 128, 8, 1), (2048, 100, 8, 0), (2
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32, torch.float64])
 @pytest.mark.parametrize("case", BN_ONE_PASS_CASES)
 def test_batch_norm_backward_in_one_pass(gpu, case, dt):
-    """Training-mode batch-norm backward reads dy and x ONCE (bn_bwd_fused_kernel, and since round 5 bn_bwd_fused_fp_kernel for f32 / f64 - the
-    precisions the reference's example runs in - whose channels are launched in co-resident chunks): the workgroups of a channel keep their
+    """Training-mode batch-norm backward reads dy and x ONCE (bn_bwd_fused_kernel: bf16, and f32 / f64 - the precisions the reference's
+    example runs in - whose channels are launched in co-resident chunks): the workgroups of a channel keep their
     slice in registers while they wait for each other's partial sums.  Checked against ATen (f32 arithmetic on the bf16 inputs; f64 for the
     wide types), at the ResNet step's shapes and at ragged ones; repeated launches (the wait counters reset themselves) and launches that
     alternate between two streams give bitwise the same tensors."""
@@ -2221,7 +2221,7 @@ def test_one_pass_batch_norm_backward_under_cu_pressure(gpu, held, dt):
     backward on the compute stream.  The kernel has to finish (workgroups are handed out in launch order, so the channels complete
     one after the other as CUs free up) with bitwise the results it gives on an idle device, which in turn agree with the two-kernel
     form; marked shared through lamp_device_shared_hint the host takes the two kernels by itself.  f32 / f64 (round 5): the chunked launches
-    of bn_bwd_fused_fp_kernel size their chunks for an idle chip - under pressure a chunk is NOT fully co-resident and completes channel
+    of bn_bwd_fused_kernel size their chunks for an idle chip - under pressure a chunk is NOT fully co-resident and completes channel
     by channel all the same."""
     maps = [(2048, 6, 32, 1), (2048, 16, 16, 2), (2048, 128, 8, 2), (2048, 128, 8, 1), (2048, 100, 8, 0), (2048, 16, 16, 1)]
     hi = C.c_void_p(); lib.lamp_stream_get_from_pool(1, 0, C.byref(hi))
