@@ -344,7 +344,19 @@ __global__ void repeat_interleave_tensor_kernel(const T* __restrict__ a, T* __re
 //   final : one candidate per lane, bitonic sort by (value, index), lanes 0..k-1 write the result.
 // Ordering is lexicographic (value, index) as in the k-pass kernel below, so ties resolve identically.  A row with more than 64
 // candidates (massive ties) is handled by the k-pass kernel's rounds inside the same wavefront.
+// NaN: < and == alone are no order once a value is NaN, so the scan only notes that the row holds one (a compare per element) and such
+// a row takes the rounds, which like the k-pass kernel order with tk_lt / tk_eq: numbers by <, every NaN equal to every other NaN and,
+// as in ATen, greater than any number.  The kernels order the negated values for `largest`, where the greatest comes first:
+// nan_first = largest puts NaN before every number there.  Rows without NaN never reach a comparison that differs; a row with a NaN
+// costs k further passes over the row (its sorted lane minima and tau are computed and discarded), which is accepted for a rare case.
 template <class A> __device__ __forceinline__ bool tk_before(A v, int i, A w, int j) { return j < 0 || (i >= 0 && (v < w || (v == w && i < j))); }
+template <class A> __device__ __forceinline__ bool tk_lt(A v, A w, bool nan_first) {
+  return v < w || (nan_first ? (v != v && w == w) : (w != w && v == v));
+}
+template <class A> __device__ __forceinline__ bool tk_eq(A v, A w) { return v == w || (v != v && w != w); }
+template <class A> __device__ __forceinline__ bool tk_before(A v, int i, A w, int j, bool nan_first) {
+  return j < 0 || (i >= 0 && (tk_lt(v, w, nan_first) || (tk_eq(v, w) && i < j)));
+}
 template <class A> __device__ __forceinline__ void tk_sort64(A& v, int& i, int lane) {
 #pragma unroll
   for (int k2 = 2; k2 <= 64; k2 <<= 1) {
@@ -370,8 +382,10 @@ __global__ __launch_bounds__(256) void topk_wave_kernel(const T* __restrict__ a,
   const T* row = a + r0 * D;
   // pass 1: lane minima (index -1 = nothing seen).  Four consecutive elements per lane and load (16-byte loads for f32),
   // several loads in flight: with one scalar load per iteration the scan is latency bound (0.3 TB/s measured)
+  const bool nf = largest != 0;
   A mv = A(0);
   int mi = -1;
+  bool nan = false;
   const bool vec4 = (D % 4 == 0) && ((uintptr_t)row % (4 * sizeof(T)) == 0);
   if (vec4) {
 #pragma unroll 4
@@ -381,6 +395,7 @@ __global__ __launch_bounds__(256) void topk_wave_kernel(const T* __restrict__ a,
       for (int e = 0; e < 4; e++) {
         A v = load_as<A>(pk.v[e]);
         if (largest) v = -v;
+        nan |= v != v;
         if (tk_before(v, (int)d + e, mv, mi)) { mv = v; mi = (int)d + e; }
       }
     }
@@ -388,16 +403,18 @@ __global__ __launch_bounds__(256) void topk_wave_kernel(const T* __restrict__ a,
     for (int64_t d = lane; d < D; d += 64) {
       A v = load_as<A>(row[d]);
       if (largest) v = -v;
+      nan |= v != v;
       if (tk_before(v, (int)d, mv, mi)) { mv = v; mi = (int)d; }
     }
   }
+  const bool row_nan = __ballot(nan) != 0;
   A sv = mv; int si = mi;
   tk_sort64(sv, si, lane);
   const A tau = __shfl(sv, k - 1, 64);
   const int tau_i = __shfl(si, k - 1, 64);
   int count = 0;
   bool overflow = false;
-  if (tau_i >= 0) {   // at least k lanes saw an element: compact everything <= tau
+  if (tau_i >= 0 && !row_nan) {   // at least k lanes saw an element: compact everything <= tau
     if (vec4) {
       for (int64_t d0 = 0; d0 < D && !overflow; d0 += 256) {
         const int64_t d = d0 + (int64_t)lane * 4;
@@ -431,7 +448,7 @@ __global__ __launch_bounds__(256) void topk_wave_kernel(const T* __restrict__ a,
       }
     }
   } else {
-    overflow = true;   // fewer than k lanes have elements (D < 64 * ... small rows): take the exact slow path
+    overflow = true;   // fewer than k lanes have elements (D < 64 * ... small rows), or a NaN in the row: take the exact slow path
   }
   if (!overflow) {
     A v = lane < count ? cv[wid][lane] : A(0);
@@ -452,13 +469,13 @@ __global__ __launch_bounds__(256) void topk_wave_kernel(const T* __restrict__ a,
     for (int64_t d = lane; d < D; d += 64) {
       A v = load_as<A>(row[d]);
       if (largest) v = -v;
-      const bool after = (li < 0) || (v > lv) || (v == lv && (int)d > li);
-      if (after && tk_before(v, (int)d, bv, bi)) { bv = v; bi = (int)d; }
+      const bool after = (li < 0) || tk_lt(lv, v, nf) || (tk_eq(v, lv) && (int)d > li);
+      if (after && tk_before(v, (int)d, bv, bi, nf)) { bv = v; bi = (int)d; }
     }
     for (int off = 32; off > 0; off >>= 1) {
       const A ov = __shfl_xor(bv, off, 64);
       const int oi = __shfl_xor(bi, off, 64);
-      if (tk_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+      if (tk_before(ov, oi, bv, bi, nf)) { bv = ov; bi = oi; }
     }
     lv = bv; li = bi;
     if (lane == 0) {
@@ -478,6 +495,7 @@ __global__ __launch_bounds__(256) void topk_kernel(const T* __restrict__ a, T* _
   __shared__ A last_v;
   __shared__ int64_t last_i;
   const T* row = a + (int64_t)blockIdx.x * D;
+  const bool nf = largest != 0;
   if (threadIdx.x == 0) { last_v = 0; last_i = -1; }
   __syncthreads();
   for (int64_t r = 0; r < k; r++) {
@@ -490,16 +508,16 @@ __global__ __launch_bounds__(256) void topk_kernel(const T* __restrict__ a, T* _
     for (int64_t d = threadIdx.x; d < D; d += blockDim.x) {
       A v = load_as<A>(row[d]);
       if (largest) v = -v;
-      const bool after = (li < 0) || (v > lv) || (v == lv && d > li);
+      const bool after = (li < 0) || tk_lt(lv, v, nf) || (tk_eq(v, lv) && d > li);
       if (!after) continue;
-      if (!has || v < bv || (v == bv && d < bi)) { has = true; bv = v; bi = d; }
+      if (!has || tk_lt(v, bv, nf) || (tk_eq(v, bv) && d < bi)) { has = true; bv = v; bi = d; }
     }
     // wave + block reduction on (bv, bi)
     for (int off = 32; off > 0; off >>= 1) {
       const A ov = __shfl_xor(bv, off, 64);
       const int64_t oi = __shfl_xor(bi, off, 64);
       const int oh = __shfl_xor((int)has, off, 64);
-      if (oh && (!has || ov < bv || (ov == bv && oi < bi))) { has = true; bv = ov; bi = oi; }
+      if (oh && (!has || tk_lt(ov, bv, nf) || (tk_eq(ov, bv) && oi < bi))) { has = true; bv = ov; bi = oi; }
     }
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     __syncthreads();
@@ -508,7 +526,7 @@ __global__ __launch_bounds__(256) void topk_kernel(const T* __restrict__ a, T* _
     if (threadIdx.x == 0) {
       A fv = 0; int64_t fi = -1;
       for (int w = 0; w < (int)(blockDim.x >> 6); w++)
-        if (si[w] >= 0 && (fi < 0 || sv[w] < fv || (sv[w] == fv && si[w] < fi))) { fv = sv[w]; fi = si[w]; }
+        if (si[w] >= 0 && (fi < 0 || tk_lt(sv[w], fv, nf) || (tk_eq(sv[w], fv) && si[w] < fi))) { fv = sv[w]; fi = si[w]; }
       last_v = fv; last_i = fi;
       vals[(int64_t)blockIdx.x * k + r] = store_as<T>(largest ? -fv : fv);
       idxs[(int64_t)blockIdx.x * k + r] = fi;
@@ -623,7 +641,9 @@ int lamp_index_select(lamp_tensor** out, const lamp_tensor* a, int64_t dim, cons
   if (total) {
     const int64_t row_bytes = inner * (int64_t)a->itemsize();
     const void* ap = static_cast<const Tensor*>(ac.get())->raw();
-    if (outer == 1 && row_bytes % 16 == 0 && row_bytes / 16 < (1 << 30) && (((uintptr_t)ap | (uintptr_t)r->raw()) & 15) == 0) {
+    const bool rows_vec = outer == 1 && row_bytes % 16 == 0 && row_bytes / 16 < (1 << 30) && (((uintptr_t)ap | (uintptr_t)r->raw()) & 15) == 0;
+    KernelTimer kt(rows_vec ? "index_select_rows_vec" : "index_select", (double)total, 2.0 * total * a->itemsize() + (double)J * 8, current_stream(a->device()));
+    if (rows_vec) {
       const int ppr = (int)(row_bytes / 16);
       hipLaunchKernelGGL(index_select_rows_vec_kernel, dim3(grid_for(J * ppr, 256)), dim3(256), 0, current_stream(a->device()), (const uint4*)ap,
                          static_cast<const Tensor*>(ic.get())->ptr<int64_t>(), (uint4*)r->data(), D, ppr, J);
@@ -1097,7 +1117,9 @@ int lamp_topk(lamp_tensor** values, lamp_tensor** indices, const lamp_tensor* a,
   oshape.back() = k;
   Hold v(new_tensor(oshape, a->dtype, a->device())), ix(new_tensor(oshape, kI64, a->device()));
   if (rows && k) {
-    if (k <= 64 && D < (int64_t)1 << 31) {
+    const bool wave = k <= 64 && D < (int64_t)1 << 31;
+    KernelTimer kt(wave ? "topk_wave" : "topk_rounds", (double)rows * D, ((double)rows * D + (double)rows * k) * a->itemsize() + (double)rows * k * 8, current_stream(a->device()));
+    if (wave) {
       LAMP_DISPATCH_FLOAT(a->dtype, T, hipLaunchKernelGGL((topk_wave_kernel<T>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, current_stream(a->device()),
                                                           ac->ptr<T>(), v->ptr<T>(), ix->ptr<int64_t>(), rows, D, (int)k, largest));
     } else {
@@ -1158,6 +1180,7 @@ int lamp_embedding_backward(lamp_tensor** out, const lamp_tensor* grad, const la
   LAMP_CHECK(gc->numel() == N * E, "embedding_backward: grad " << grad->describe() << " does not match indices " << indices->describe());
   const bool floating = grad->dtype == kF32 || grad->dtype == kF64 || grad->dtype == kBF16;
   if (floating && num_weights > 0 && E > 0 && num_weights <= 65535 * 16 && (double)num_weights * (double)N <= (double)(1ll << 28)) {
+    KernelTimer kt("embedding_bwd_scan", (double)N * E, ((double)N + num_weights) * E * grad->itemsize() + (double)num_weights * N * 8, current_stream(grad->device()));
     LAMP_DISPATCH_FLOAT(grad->dtype, T, hipLaunchKernelGGL((embedding_backward_scan_kernel<T>), dim3((unsigned)num_weights, (unsigned)((E + 255) / 256)),
                                                            dim3(256), 0, current_stream(grad->device()), gc->ptr<T>(), ic->ptr<int64_t>(), r->ptr<T>(), N, E,
                                                            padding_idx));

@@ -255,6 +255,7 @@ int lamp_avg_pool2d(lamp_tensor** out, const lamp_tensor* x, int64_t kernel, int
   const bool global = (g.k == g.H && g.k == g.W && g.p == 0 && g.Ho == 1 && g.Wo == 1);
   if (total && global) {
     const int lpp = (((uintptr_t)xc->data() & 15) == 0) ? global_pool_lanes(xc.get(), (int)(g.H * g.W)) : 0;
+    KernelTimer kt(lpp ? "avg_pool_global_vec" : "avg_pool_global", (double)x->numel(), (double)(x->numel() + total) * x->itemsize(), current_stream(x->device()));
     if (lpp) {
       LAMP_DISPATCH_FLOAT(x->dtype, T, hipLaunchKernelGGL((avg_pool_global_fwd_vec_kernel<T>), dim3((unsigned)((g.NC * lpp + 255) / 256)), dim3(256), 0,
                                                           current_stream(x->device()), xc->ptr<T>(), y->ptr<T>(), g.NC, (int)(g.H * g.W), lpp));
@@ -264,6 +265,7 @@ int lamp_avg_pool2d(lamp_tensor** out, const lamp_tensor* x, int64_t kernel, int
     }
     LAMP_LAUNCH_CHECK();
   } else if (total) {
+    KernelTimer kt("avg_pool", (double)total * g.k * g.k, (double)(x->numel() + total) * x->itemsize(), current_stream(x->device()));
     LAMP_DISPATCH_FLOAT(x->dtype, T, hipLaunchKernelGGL((avg_pool_fwd_kernel<T>), dim3(grid_for(total, 256)), dim3(256), 0,
                                                         current_stream(x->device()), xc->ptr<T>(), y->ptr<T>(), g));
     LAMP_LAUNCH_CHECK();
@@ -283,6 +285,7 @@ int lamp_avg_pool2d_backward(lamp_tensor** out, const lamp_tensor* grad_out, con
   const bool global = (g.k == g.H && g.k == g.W && g.p == 0 && g.Ho == 1 && g.Wo == 1);
   if (total && global) {
     const int lpp = (((uintptr_t)dx->data() & 15) == 0) ? global_pool_lanes(dx.get(), (int)(g.H * g.W)) : 0;
+    KernelTimer kt(lpp ? "avg_pool_global_vec_bwd" : "avg_pool_global_bwd", (double)total, (double)(total + gc->numel()) * x->itemsize(), current_stream(x->device()));
     if (lpp) {
       const int64_t packets = g.NC * lpp;
       LAMP_DISPATCH_FLOAT(x->dtype, T, hipLaunchKernelGGL((avg_pool_global_bwd_vec_kernel<T>), dim3(grid_for(packets, 256)), dim3(256), 0,
@@ -293,6 +296,7 @@ int lamp_avg_pool2d_backward(lamp_tensor** out, const lamp_tensor* grad_out, con
     }
     LAMP_LAUNCH_CHECK();
   } else if (total) {
+    KernelTimer kt("avg_pool_bwd", (double)total, (double)(total + gc->numel()) * x->itemsize(), current_stream(x->device()));
     LAMP_DISPATCH_FLOAT(x->dtype, T, hipLaunchKernelGGL((avg_pool_bwd_kernel<T>), dim3(grid_for(total, 256)), dim3(256), 0,
                                                         current_stream(x->device()), gc->ptr<T>(), dx->ptr<T>(), g));
     LAMP_LAUNCH_CHECK();
@@ -310,6 +314,7 @@ int lamp_max_pool2d_with_indices(lamp_tensor** out, lamp_tensor** indices, const
   Hold y(new_tensor(os, x->dtype, x->device())), idx(new_tensor(os, kI64, x->device()));
   const int64_t total = y->numel();
   if (total) {
+    KernelTimer kt("max_pool", (double)total * g.k * g.k, (double)(x->numel() + total) * x->itemsize() + (double)total * 8, current_stream(x->device()));
     LAMP_DISPATCH_FLOAT(x->dtype, T, hipLaunchKernelGGL((max_pool_fwd_kernel<T>), dim3(grid_for(total, 256)), dim3(256), 0,
                                                         current_stream(x->device()), xc->ptr<T>(), y->ptr<T>(), idx->ptr<int64_t>(), g));
     LAMP_LAUNCH_CHECK();
@@ -329,6 +334,7 @@ int lamp_max_pool2d_with_indices_backward(lamp_tensor** out, const lamp_tensor* 
   Hold dx(new_tensor(x->shape(), x->dtype, x->device()));
   const int64_t total = dx->numel();
   if (total) {
+    KernelTimer kt("max_pool_bwd", (double)total, (double)(total + gc->numel()) * x->itemsize() + (double)gc->numel() * 8, current_stream(x->device()));
     LAMP_DISPATCH_FLOAT(x->dtype, T, hipLaunchKernelGGL((max_pool_bwd_kernel<T>), dim3(grid_for(total, 256)), dim3(256), 0,
                                                         current_stream(x->device()), gc->ptr<T>(), ic->ptr<int64_t>(), dx->ptr<T>(), g));
     LAMP_LAUNCH_CHECK();
@@ -347,6 +353,7 @@ int lamp_max_pool1d_with_indices(lamp_tensor** out, lamp_tensor** indices, const
   Hold y(new_tensor(os, 3, x->dtype, x->device())), idx(new_tensor(os, 3, kI64, x->device()));
   const int64_t total = y->numel();
   if (total) {
+    KernelTimer kt("max_pool1d", (double)total * g.k, (double)(x->numel() + total) * x->itemsize() + (double)total * 8, current_stream(x->device()));
     LAMP_DISPATCH_FLOAT(x->dtype, T, hipLaunchKernelGGL((max_pool1d_fwd_kernel<T>), dim3(grid_for(total, 256)), dim3(256), 0, current_stream(x->device()),
                                                         xc->ptr<T>(), y->ptr<T>(), idx->ptr<int64_t>(), g));
     LAMP_LAUNCH_CHECK();
@@ -366,6 +373,7 @@ int lamp_max_pool1d_with_indices_backward(lamp_tensor** out, const lamp_tensor* 
   Hold dx(new_tensor(x->shape(), x->dtype, x->device()));
   const int64_t total = dx->numel();
   if (total) {
+    KernelTimer kt("max_pool1d_bwd", (double)total, (double)(total + gc->numel()) * x->itemsize() + (double)gc->numel() * 8, current_stream(x->device()));
     LAMP_DISPATCH_FLOAT(x->dtype, T, hipLaunchKernelGGL((max_pool1d_bwd_kernel<T>), dim3(grid_for(total, 256)), dim3(256), 0, current_stream(x->device()),
                                                         gc->ptr<T>(), ic->ptr<int64_t>(), dx->ptr<T>(), g));
     LAMP_LAUNCH_CHECK();

@@ -252,6 +252,7 @@ static void reduce_typed(const Tensor* ac, Tensor* out, const DimPlan& p, double
       for (int d = 0; d < kMaxDims; d++) { a.sizes[d] = d < (int)sz.size() ? sz[d] : 1; a.strides[0][d] = d < (int)stv.size() ? stv[d] : 0; }
       return a;
     };
+    KernelTimer kt("reduce_generic", (double)nout * p.nred, ((double)nout * p.nred + nout) * sizeof(T), st);
     hipLaunchKernelGGL((reduce_generic_kernel<T, OP>), dim3(grid_for(nout, 256)), dim3(256), 0, st, ac->ptr<T>(), out->ptr<T>(),
                        nout, p.nred, mk(ksz, kst), mk(rsz, rst), scale, do_sqrt);
     LAMP_LAUNCH_CHECK();
@@ -275,22 +276,28 @@ static void reduce_typed(const Tensor* ac, Tensor* out, const DimPlan& p, double
   Hold partial(new_tensor(psz, 1, std::is_same<A, double>::value ? kF64 : (std::is_same<A, float>::value ? kF32 : kI64), ac->device()));
   constexpr int WV = 16 / sizeof(T);
   const bool column_vec = column && sizeof(T) <= 8 && g.K1 % WV == 0 && ((uintptr_t)ac->data() & 15) == 0 && g.K0 <= 65535 && g.R1 >= 64;
-  if (column_vec) {
-    const int64_t bx = (g.K1 / WV + 31) / 32;
-    dim3 grid((unsigned)bx, (unsigned)nsplit, (unsigned)g.K0);
-    hipLaunchKernelGGL((reduce_column_vec_kernel<T, OP>), grid, dim3(256), 0, st, ac->ptr<T>(), partial->ptr<A>(), g);
-  } else if (column) {
-    dim3 grid((unsigned)((nout + 255) / 256), (unsigned)nsplit);
-    hipLaunchKernelGGL((reduce_column_kernel<T, OP>), grid, dim3(256), 0, st, ac->ptr<T>(), partial->ptr<A>(), g);
-  } else {
-    LAMP_CHECK(nout < (1ll << 31), "too many outputs for the block reduction");
-    dim3 grid((unsigned)nout, (unsigned)nsplit);
-    int64_t per = (g.R1 * g.R2 + nsplit - 1) / nsplit;
-    int block = per >= 256 ? 256 : (per > 64 ? 128 : 64);
-    hipLaunchKernelGGL((reduce_block_kernel<T, OP>), grid, dim3(block), 0, st, ac->ptr<T>(), partial->ptr<A>(), g);
+  {
+    KernelTimer kt(column_vec ? "reduce_column_vec" : (column ? "reduce_column" : "reduce_block"), (double)nout * p.nred,
+                   (double)nout * p.nred * sizeof(T) + (double)nsplit * nout * sizeof(A), st);
+    if (column_vec) {
+      const int64_t bx = (g.K1 / WV + 31) / 32;
+      dim3 grid((unsigned)bx, (unsigned)nsplit, (unsigned)g.K0);
+      hipLaunchKernelGGL((reduce_column_vec_kernel<T, OP>), grid, dim3(256), 0, st, ac->ptr<T>(), partial->ptr<A>(), g);
+    } else if (column) {
+      dim3 grid((unsigned)((nout + 255) / 256), (unsigned)nsplit);
+      hipLaunchKernelGGL((reduce_column_kernel<T, OP>), grid, dim3(256), 0, st, ac->ptr<T>(), partial->ptr<A>(), g);
+    } else {
+      LAMP_CHECK(nout < (1ll << 31), "too many outputs for the block reduction");
+      dim3 grid((unsigned)nout, (unsigned)nsplit);
+      int64_t per = (g.R1 * g.R2 + nsplit - 1) / nsplit;
+      int block = per >= 256 ? 256 : (per > 64 ? 128 : 64);
+      hipLaunchKernelGGL((reduce_block_kernel<T, OP>), grid, dim3(block), 0, st, ac->ptr<T>(), partial->ptr<A>(), g);
+    }
+    LAMP_LAUNCH_CHECK();
   }
-  LAMP_LAUNCH_CHECK();
-  if (nsplit >= 16 && nout < 65536)
+  const bool wide = nsplit >= 16 && nout < 65536;
+  KernelTimer kt(wide ? "reduce_finalize_wide" : "reduce_finalize", (double)nsplit * nout, (double)nsplit * nout * sizeof(A) + (double)nout * sizeof(T), st);
+  if (wide)
     hipLaunchKernelGGL((reduce_finalize_wide_kernel<T, OP>), dim3((unsigned)((nout + 15) / 16)), dim3(256), 0, st, partial->ptr<A>(), out->ptr<T>(),
                        nout, nsplit, scale, do_sqrt);
   else
