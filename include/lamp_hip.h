@@ -486,6 +486,17 @@ int lamp_convolution_pair(lamp_tensor* out2[2], const lamp_tensor* x, const lamp
                           const int64_t* stride_a, const int64_t* padding_a, const int64_t* dilation_a, const lamp_tensor* w_b,
                           const lamp_tensor* bias_b_or_null, const int64_t* stride_b, const int64_t* padding_b,
                           const int64_t* dilation_b, int nspatial, int64_t groups);
+/* A convolution and the lamp_convolution_pair behind it: out3 = {s, a, b} with s = convolution(x, w, bias, geometry), {a, b} =
+ * lamp_convolution_pair(s, ...) - the stem of Cnn.resnet and the two branches of its first residual block (example-cifar100 cnn.scala:95-109: no
+ * batch norm in between).  Values, and the batch-norm statistics hand-off of a and b, are those of the two calls; where a kernel keeps s in
+ * LDS for the pair (bf16, stride-1 first convolution of at most 8 output channels such as the 3 -> 6 5x5 on 32x32 maps, stride-2 3x3 + 1x1
+ * behind it) they are one launch and s is written but not read back. */
+int lamp_convolution_chain_pair(lamp_tensor* out3[3], const lamp_tensor* x, const lamp_tensor* w, const lamp_tensor* bias_or_null,
+                                const int64_t* stride, const int64_t* padding, const int64_t* dilation, const lamp_tensor* w_a,
+                                const lamp_tensor* bias_a_or_null, const int64_t* stride_a, const int64_t* padding_a,
+                                const int64_t* dilation_a, const lamp_tensor* w_b, const lamp_tensor* bias_b_or_null,
+                                const int64_t* stride_b, const int64_t* padding_b, const int64_t* dilation_b, int nspatial,
+                                int64_t groups);
 int lamp_avg_pool2d(lamp_tensor** out, const lamp_tensor* x, int64_t kernel, int64_t stride, int64_t padding,
                     int ceil_mode, int count_include_pad);
 int lamp_avg_pool2d_backward(lamp_tensor** out, const lamp_tensor* grad_out, const lamp_tensor* x, int64_t kernel,

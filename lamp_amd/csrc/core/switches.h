@@ -17,6 +17,7 @@ constexpr int64_t SW_NO_CLAMP = INT64_MIN;
 #define LAMP_SWITCHES_ONCE(X)                                                                                                             \
   /* model level (host/nn.cpp, host/ops.cpp, host/transformer.cpp, host/data.cpp) */                                                      \
   X(conv_sibling, "LAMP_CONV_SIBLING", BOOL, 1, 0, "a residual block's 3x3 and its sibling 1x1 of the same input as one forward launch") \
+  X(conv_chain, "LAMP_CONV_CHAIN", BOOL, 1, 0, "a convolution directly in front of a residual block and the block's 3x3 + 1x1 as one forward call (0: two)") \
   X(fuse_bn_pair, "LAMP_FUSE_BN_PAIR", BOOL, 1, 0, "relu(bn(right) + bn(left)) at a block's end as one op (0: the chain)")                \
   X(fuse_pool_logsoftmax, "LAMP_FUSE_POOL_LOGSOFTMAX", BOOL, 1, 0, "average pool -> flatten -> log-softmax tail as one node")             \
   X(fuse_block_tail, "LAMP_FUSE_BLOCK_TAIL", BOOL, 1, 0, "the last residual block and the pooled log-softmax tail as one node")          \

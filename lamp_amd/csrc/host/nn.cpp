@@ -63,7 +63,29 @@ bool BatchNorm::can_fuse_add_relu(const Var& x) const { return training && can_f
 Var BatchNorm::forward_add_relu(const Var& x, const Var& addend) {
   return F::batch_norm_add_relu_2d(x, addend, weight, bias, runningMean->value, runningVar->value, training, momentum, eps);
 }
-Var Residual::forward_relu(const Var& x, int64_t pool_tail) {
+// Sequential::forward's look-ahead (see there): a Conv2D that stands directly in front of a residual block and has NOT been applied yet - the
+// block's forward_relu applies it, together with its own two convolutions where that is one call.  Per thread: one model may run on several.
+namespace {
+struct ChainHead { Residual* block = nullptr; Conv2D* conv = nullptr; const Variable* input = nullptr; };
+thread_local ChainHead tls_chain_head;
+// the residual block that `m` applies to its input first, reached through forward_relu, with both branches starting in a Conv2D (else nullptr)
+Residual* chain_target(Module* m) {
+  auto* seq = dynamic_cast<Sequential*>(m);
+  if (!seq || seq->mods.empty()) return nullptr;
+  auto* res = dynamic_cast<Residual*>(seq->mods[0].get());
+  if (!res) return chain_target(seq->mods[0].get());
+  auto* fn = seq->mods.size() > 1 ? dynamic_cast<Fun*>(seq->mods[1].get()) : nullptr;
+  auto* rs = dynamic_cast<Sequential*>(res->right.get());
+  auto* ls = res->left ? dynamic_cast<Sequential*>(res->left.get()) : nullptr;
+  const bool convs = rs && ls && !rs->mods.empty() && !ls->mods.empty() && dynamic_cast<Conv2D*>(rs->mods[0].get()) && dynamic_cast<Conv2D*>(ls->mods[0].get());
+  return (fn && fn->tag == "relu" && convs) ? res : nullptr;
+}
+}  // namespace
+Var Residual::forward_relu(const Var& x_in, int64_t pool_tail) {
+  Var x = x_in;
+  Conv2D* stem = nullptr;                          // the convolution in front of this block, still to be applied to x
+  if (tls_chain_head.block == this && tls_chain_head.input == x_in.get()) stem = tls_chain_head.conv;
+  if (tls_chain_head.block == this) tls_chain_head = ChainHead();
   // (the tail behind the block's output y, where the one-node form does not apply)
   auto tail = [&](const Var& y) -> Var {
     if (!pool_tail) return y;
@@ -72,6 +94,7 @@ Var Residual::forward_relu(const Var& x, int64_t pool_tail) {
   };
   auto* seq = dynamic_cast<Sequential*>(right.get());
   BatchNorm* bn = (seq && !seq->mods.empty()) ? dynamic_cast<BatchNorm*>(seq->mods.back().get()) : nullptr;
+  if (stem && !bn) { x = stem->forward(x); stem = nullptr; }
   if (bn) {
     // right branch up to (not including) its last batch norm, with the usual BatchNorm -> relu rewrite inside
     Sequential head(std::vector<Mod>(seq->mods.begin(), seq->mods.end() - 1));
@@ -83,9 +106,17 @@ Var Residual::forward_relu(const Var& x, int64_t pool_tail) {
     auto* c3 = head.mods.empty() ? nullptr : dynamic_cast<Conv2D*>(head.mods[0].get());
     auto* c1 = (lbn && lseq->mods.size() == 2) ? dynamic_cast<Conv2D*>(lseq->mods[0].get()) : nullptr;
     Var v, lconv;                                  // lconv: the left branch's convolution output when it came with the right one
-    if (pair_on && c3 && c1 && c3->groups == c1->groups && x->value.h()->is_device()) {
-      auto pr = F::convolution_pair(x, c3->weights, c3->bias, {c3->stride, c3->stride}, {c3->padding, c3->padding}, {c3->dilation, c3->dilation},
-                                    c1->weights, c1->bias, {c1->stride, c1->stride}, {c1->padding, c1->padding}, {c1->dilation, c1->dilation}, c3->groups);
+    const bool pair = pair_on && c3 && c1 && c3->groups == c1->groups && x->value.h()->is_device();
+    // ... and with the convolution in front of the block (the stem of Cnn.resnet, cnn.scala:95: no batch norm between it and this block) the
+    // three are one call - one launch where a kernel keeps the stem's output in LDS for the pair (LAMP_CONV_CHAIN=0: stem, then pair)
+    if (stem && !(pair && stem->groups == c3->groups)) { x = stem->forward(x); stem = nullptr; }
+    if (pair) {
+      auto pr = stem ? F::convolution_chain_pair(x, stem->weights, stem->bias, {stem->stride, stem->stride}, {stem->padding, stem->padding},
+                                                 {stem->dilation, stem->dilation}, c3->weights, c3->bias, {c3->stride, c3->stride}, {c3->padding, c3->padding},
+                                                 {c3->dilation, c3->dilation}, c1->weights, c1->bias, {c1->stride, c1->stride}, {c1->padding, c1->padding},
+                                                 {c1->dilation, c1->dilation}, c3->groups)
+                     : F::convolution_pair(x, c3->weights, c3->bias, {c3->stride, c3->stride}, {c3->padding, c3->padding}, {c3->dilation, c3->dilation},
+                                           c1->weights, c1->bias, {c1->stride, c1->stride}, {c1->padding, c1->padding}, {c1->dilation, c1->dilation}, c3->groups);
       Sequential rest(std::vector<Mod>(head.mods.begin() + 1, head.mods.end()));
       v = rest.forward(pr.first);
       lconv = pr.second;
@@ -150,6 +181,18 @@ Var Sequential::forward_pool_tail(const Var& x, int64_t pool, bool probe) {
 Var Sequential::forward(const Var& x) {
   Var v = x;
   for (size_t i = 0; i < mods.size(); i++) {
+    if (i + 1 < mods.size() && v->value.h()->is_device()) {
+      // Conv2D directly in front of a module that starts with a residual block whose two branches start in a Conv2D (Cnn.resnet: the stem and
+      // the Sequential of the four blocks, cnn.scala:95-118): the convolution is handed down to the block's forward_relu, which runs it with
+      // its own two as one call (LAMP_CONV_CHAIN=0: off).  Same nodes, same values.
+      const bool chain_on = sw().conv_chain && sw().conv_sibling;
+      auto* conv = chain_on ? dynamic_cast<Conv2D*>(mods[i].get()) : nullptr;
+      Residual* block = conv ? chain_target(mods[i + 1].get()) : nullptr;
+      if (block) {
+        tls_chain_head.block = block; tls_chain_head.conv = conv; tls_chain_head.input = v.get();
+        continue;                                  // (v is still the convolution's input)
+      }
+    }
     if (i + 3 < mods.size() && v->value.h()->is_device()) {
       // module -> Fun(avgpool2d, stride 1) -> Fun(flatten the last three dims) -> Fun(logsoftmax over dim 1) where the module ends in a residual
       // block under a relu (Cnn.resnet: the Sequential of the four blocks, cnn.scala:118-136): the last block and the tail as one node - the
@@ -207,6 +250,7 @@ Var Sequential::forward(const Var& x) {
     }
     v = mods[i]->forward(v);
   }
+  LAMP_CHECK(!tls_chain_head.block, "Sequential: a convolution handed to the residual block behind it was not applied");
   return v;
 }
 Mod LayerNorm::make(const std::vector<int64_t>& shape, int dtype, int device, bool scale, bool bias) {

@@ -856,6 +856,10 @@ Var convolution(const Var& input, const Var& weight, const Var& bias, const std:
                 const std::vector<int64_t>& outputPadding, int64_t groups) {
   return convolution_node(input, weight, bias, stride, padding, dilation, transposed, outputPadding, groups, nullptr);
 }
+static std::pair<Var, Var> convolution_pair_nodes(const Var& input, const Var& weight_a, const Var& bias_a, const std::vector<int64_t>& stride_a,
+                                                  const std::vector<int64_t>& padding_a, const std::vector<int64_t>& dilation_a, const Var& weight_b,
+                                                  const Var& bias_b, const std::vector<int64_t>& stride_b, const std::vector<int64_t>& padding_b,
+                                                  const std::vector<int64_t>& dilation_b, int64_t groups, const Ten& ya, const Ten& yb);
 // Two Convolution nodes on ONE input (the two branches of Residual, cnn.scala:16-20) whose forward values come from one call: the graph, the
 // closures and every value are those of two `convolution` calls
 std::pair<Var, Var> convolution_pair(const Var& input, const Var& weight_a, const Var& bias_a, const std::vector<int64_t>& stride_a,
@@ -867,7 +871,15 @@ std::pair<Var, Var> convolution_pair(const Var& input, const Var& weight_a, cons
   lamp_tensor* o2[2] = {nullptr, nullptr};
   HCALL(lamp_convolution_pair(o2, input->value.h(), weight_a->value.h(), bias_a->value.h(), stride_a.data(), padding_a.data(), dilation_a.data(),
                               weight_b->value.h(), bias_b->value.h(), stride_b.data(), padding_b.data(), dilation_b.data(), ns, groups));
-  const Ten ya(o2[0]), yb(o2[1]);
+  return convolution_pair_nodes(input, weight_a, bias_a, stride_a, padding_a, dilation_a, weight_b, bias_b, stride_b, padding_b, dilation_b, groups, Ten(o2[0]),
+                                Ten(o2[1]));
+}
+// the two nodes of convolution_pair around forward values ya, yb that a call has already produced
+static std::pair<Var, Var> convolution_pair_nodes(const Var& input, const Var& weight_a, const Var& bias_a, const std::vector<int64_t>& stride_a,
+                                                  const std::vector<int64_t>& padding_a, const std::vector<int64_t>& dilation_a, const Var& weight_b,
+                                                  const Var& bias_b, const std::vector<int64_t>& stride_b, const std::vector<int64_t>& padding_b,
+                                                  const std::vector<int64_t>& dilation_b, int64_t groups, const Ten& ya, const Ten& yb) {
+  const int ns = (int)stride_a.size();
   const std::vector<int64_t> zero(ns, 0);
   auto pg = std::make_shared<ConvPairGrad>();
   pg->side[0] = {weight_a->value, stride_a, padding_a, dilation_a, Ten()};
@@ -876,6 +888,26 @@ std::pair<Var, Var> convolution_pair(const Var& input, const Var& weight_a, cons
   Var a = convolution_node(input, weight_a, bias_a, stride_a, padding_a, dilation_a, false, zero, groups, &ya, pg, 0);
   Var b = convolution_node(input, weight_b, bias_b, stride_b, padding_b, dilation_b, false, zero, groups, &yb, pg, 1);
   return {a, b};
+}
+// convolution(x, w) directly in front of convolution_pair (the stem of Cnn.resnet and the first residual block, cnn.scala:95-109): the three
+// forward values come from one call, which is one launch where a kernel keeps the first output in LDS for the pair.  The graph is the one of
+// `convolution` followed by `convolution_pair`: same nodes, same closures, same values.
+std::pair<Var, Var> convolution_chain_pair(const Var& input, const Var& weight, const Var& bias, const std::vector<int64_t>& stride,
+                                           const std::vector<int64_t>& padding, const std::vector<int64_t>& dilation, const Var& weight_a,
+                                           const Var& bias_a, const std::vector<int64_t>& stride_a, const std::vector<int64_t>& padding_a,
+                                           const std::vector<int64_t>& dilation_a, const Var& weight_b, const Var& bias_b,
+                                           const std::vector<int64_t>& stride_b, const std::vector<int64_t>& padding_b,
+                                           const std::vector<int64_t>& dilation_b, int64_t groups) {
+  const int ns = (int)stride.size();
+  LAMP_CHECK(ns == (int)stride_a.size() && ns == (int)stride_b.size(), "convolution_chain_pair: the convolutions have different numbers of spatial dimensions");
+  lamp_tensor* o3[3] = {nullptr, nullptr, nullptr};
+  HCALL(lamp_convolution_chain_pair(o3, input->value.h(), weight->value.h(), bias->value.h(), stride.data(), padding.data(), dilation.data(),
+                                    weight_a->value.h(), bias_a->value.h(), stride_a.data(), padding_a.data(), dilation_a.data(), weight_b->value.h(),
+                                    bias_b->value.h(), stride_b.data(), padding_b.data(), dilation_b.data(), ns, groups));
+  const Ten s(o3[0]), ya(o3[1]), yb(o3[2]);
+  const std::vector<int64_t> zero(ns, 0);
+  const Var sv = convolution_node(input, weight, bias, stride, padding, dilation, false, zero, groups, &s);
+  return convolution_pair_nodes(sv, weight_a, bias_a, stride_a, padding_a, dilation_a, weight_b, bias_b, stride_b, padding_b, dilation_b, groups, ya, yb);
 }
 Var avg_pool2d(const Var& input, int64_t k, int64_t stride, int64_t padding) {
   LAMP_CHECK(input->value.ndim() == 4, "Input dimensions must be 4");

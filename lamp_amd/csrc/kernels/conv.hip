@@ -402,6 +402,47 @@ int lamp_convolution_pair(lamp_tensor* out2[2], const lamp_tensor* x, const lamp
   LAMP_API_END
 }
 
+int lamp_convolution_chain_pair(lamp_tensor* out3[3], const lamp_tensor* x, const lamp_tensor* w, const lamp_tensor* bias, const int64_t* stride,
+                                const int64_t* padding, const int64_t* dilation, const lamp_tensor* w_a, const lamp_tensor* bias_a, const int64_t* stride_a,
+                                const int64_t* padding_a, const int64_t* dilation_a, const lamp_tensor* w_b, const lamp_tensor* bias_b,
+                                const int64_t* stride_b, const int64_t* padding_b, const int64_t* dilation_b, int nspatial, int64_t groups) {
+  LAMP_API_BEGIN
+  out3[0] = out3[1] = out3[2] = nullptr;
+  check_device_tensor(x, "input"); check_device_tensor(w, "weight"); check_device_tensor(w_a, "weight a"); check_device_tensor(w_b, "weight b");
+  const int64_t zero2[2] = {0, 0};
+  bool fused = false;
+  auto bias_ok = [&](const lamp_tensor* b, int64_t c) { return !b || (b->is_device() && b->numel() == c && b->dtype == x->dtype); };
+  if (nspatial == 2 && x->ndim == 4 && x->dtype == kBF16 && w->dtype == kBF16 && w_a->dtype == kBF16 && w_b->dtype == kBF16 && w_a->ndim == 4 && w_b->ndim == 4 &&
+      w_a->sizes[1] * groups == w->sizes[0] && w_b->sizes[1] * groups == w->sizes[0]) {
+    ConvGeom g0 = make_geom(x, w, stride, padding, dilation, nspatial, 0, zero2, groups);
+    if (g0.Ho > 0 && g0.Wo > 0) {
+      Hold s(new_tensor({g0.N, g0.Cout, g0.Ho, g0.Wo}, x->dtype, x->device()));
+      ConvGeom ga = make_geom(s.get(), w_a, stride_a, padding_a, dilation_a, nspatial, 0, zero2, groups);
+      ConvGeom gb = make_geom(s.get(), w_b, stride_b, padding_b, dilation_b, nspatial, 0, zero2, groups);
+      if (bias_ok(bias, g0.Cout) && bias_ok(bias_a, ga.Cout) && bias_ok(bias_b, gb.Cout) && ga.Ho == gb.Ho && ga.Wo == gb.Wo && ga.Ho > 0 && ga.Wo > 0) {
+        Hold xc(contiguous(x)), w0(contiguous_filter(w)), wa(contiguous_filter(w_a)), wb(contiguous_filter(w_b));
+        Hold b0(bias ? contiguous(bias) : nullptr), ba(bias_a ? contiguous(bias_a) : nullptr), bb(bias_b ? contiguous(bias_b) : nullptr);
+        Hold ya(new_tensor({ga.N, ga.Cout, ga.Ho, ga.Wo}, x->dtype, x->device())), yb(new_tensor({gb.N, gb.Cout, gb.Ho, gb.Wo}, x->dtype, x->device()));
+        hipStream_t st = current_stream(x->device());
+        if (narrow_conv_chain_pair(xc.get(), w0.get(), b0.get(), s.get(), g0, wa.get(), ba.get(), ya.get(), ga, wb.get(), bb.get(), yb.get(), gb, st)) {
+          out3[0] = s.take(); out3[1] = ya.take(); out3[2] = yb.take();
+          fused = true;
+        }
+      }
+    }
+  }
+  if (!fused) {                                       // the two calls (each validates its own arguments)
+    lamp_tensor* s = nullptr;
+    if (lamp_convolution(&s, x, w, bias, stride, padding, dilation, nspatial, 0, zero2, groups) != 0) throw Error(lamp_last_error());
+    Hold hs(s);
+    lamp_tensor* o2[2] = {nullptr, nullptr};
+    if (lamp_convolution_pair(o2, s, w_a, bias_a, stride_a, padding_a, dilation_a, w_b, bias_b, stride_b, padding_b, dilation_b, nspatial, groups) != 0)
+      throw Error(lamp_last_error());
+    out3[0] = hs.take(); out3[1] = o2[0]; out3[2] = o2[1];
+  }
+  LAMP_API_END
+}
+
 int lamp_convolution_backward(lamp_tensor* out3[3], const lamp_tensor* grad_out, const lamp_tensor* x, const lamp_tensor* w,
                               const int64_t* stride, const int64_t* padding, const int64_t* dilation, int nspatial, int transposed,
                               const int64_t* output_padding, int64_t groups, const uint8_t mask[3]) {

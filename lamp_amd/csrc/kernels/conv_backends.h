@@ -31,6 +31,9 @@ bool igemm32_conv_wgrad(const Tensor* dy, const Tensor* x, Tensor* dw, const Con
 bool narrow_conv_fwd(const Tensor* x, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, hipStream_t st);
 bool narrow_conv_fwd_pair(const Tensor* x, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, const Tensor* w1, const Tensor* bias1,
                           Tensor* y1, const ConvGeom& g1, hipStream_t st);
+// s = conv(x, w0) (stride 1), y = conv3x3(s, w), y1 = conv1x1(s, w1) from one launch (false: nothing launched)
+bool narrow_conv_chain_pair(const Tensor* x, const Tensor* w0, const Tensor* bias0, Tensor* s, const ConvGeom& g0, const Tensor* w, const Tensor* bias,
+                            Tensor* y, const ConvGeom& g, const Tensor* w1, const Tensor* bias1, Tensor* y1, const ConvGeom& g1, hipStream_t st);
 bool narrow_conv_dgrad(const Tensor* dy, const Tensor* w, Tensor* dx, const ConvGeom& g, hipStream_t st, const Tensor* addend = nullptr,
                        bool* addend_fused = nullptr);
 bool narrow_conv_dgrad_pair(const Tensor* dy, const Tensor* w, const ConvGeom& g, const Tensor* dy1, const Tensor* w1, const ConvGeom& g1, Tensor* dx,

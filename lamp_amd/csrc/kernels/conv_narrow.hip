@@ -61,13 +61,21 @@ __global__ __launch_bounds__(256) void ncv_pack_kernel(NcvPackMany a) { ncv_pack
 // written to the LDS image [C][Hs][Ws] at (top + a*dil, left + b*dil) once the previous image's reads are done.  A thread handles
 // the same packets of every image, so their LDS destinations are computed once (ncv_stage_plan): -1 = no packet.
 constexpr int NCV_PF = 4;
-struct NcvPre { uint4 v[NCV_PF]; };
-struct NcvPlan { int dst[NCV_PF]; int src[NCV_PF]; };      // src: element offset in the image's source tensor, + (1 << 30) for the second one
-__device__ __forceinline__ NcvPlan ncv_stage_plan(const NcvGeom& q, int tid, int nthreads) {
-  NcvPlan pl;
+// (compile-time loop: the index reaches the body as a constant, so register arrays indexed by it never turn into scratch memory)
+template <int I0, int I1, class F> __device__ __forceinline__ void ncv_static_for(F&& f) {
+  if constexpr (I0 < I1) { f(std::integral_constant<int, I0>{}); ncv_static_for<I0 + 1, I1>(f); }
+}
+// (NPF: packets per thread; ncv_chain_kernel, whose first image is small and whose registers are scarce, holds 2)
+template <int NPF> struct NcvPreT { uint4 v[NPF]; };
+template <int NPF> struct NcvPlanT { int dst[NPF]; int src[NPF]; };      // src: element offset in the image's source tensor, + (1 << 30) for the second one
+typedef NcvPreT<NCV_PF> NcvPre;
+typedef NcvPlanT<NCV_PF> NcvPlan;
+template <int NPF = NCV_PF>
+__device__ __forceinline__ NcvPlanT<NPF> ncv_stage_plan(const NcvGeom& q, int tid, int nthreads) {
+  NcvPlanT<NPF> pl;
   const int rc = q.W >> 3, total = q.C * q.H * rc, first = q.C1 * q.H * rc;
 #pragma unroll
-  for (int k = 0; k < NCV_PF; k++) {
+  for (int k = 0; k < NPF; k++) {
     const int i = tid + k * nthreads;
     const int b = i % rc, a = (i / rc) % q.H, c = i / (rc * q.H);
     pl.dst[k] = (q.pf && i < total) ? (c * q.Hs + q.top + a * q.dil) * q.Ws + q.left + b * 8 * q.dil : -1;
@@ -75,23 +83,27 @@ __device__ __forceinline__ NcvPlan ncv_stage_plan(const NcvGeom& q, int tid, int
   }
   return pl;
 }
-__device__ __forceinline__ void ncv_stage_load(NcvPre& r, const NcvPlan& pl, const bf16_t* __restrict__ sp, const bf16_t* __restrict__ sp2) {
-#pragma unroll
-  for (int k = 0; k < NCV_PF; k++)
+template <int NPF>
+__device__ __forceinline__ void ncv_stage_load(NcvPreT<NPF>& r, const NcvPlanT<NPF>& pl, const bf16_t* __restrict__ sp, const bf16_t* __restrict__ sp2) {
+  ncv_static_for<0, NPF>([&](auto kc) {
+    constexpr int k = decltype(kc)::value;
     if (pl.dst[k] >= 0) r.v[k] = *reinterpret_cast<const uint4*>(((pl.src[k] >> 30) ? sp2 : sp) + (pl.src[k] & ((1 << 30) - 1)));
+  });
 }
-__device__ __forceinline__ void ncv_stage_store(unsigned short* xs, const NcvPre& r, const NcvPlan& pl, int dil) {
-#pragma unroll
-  for (int k = 0; k < NCV_PF; k++) {
-    if (pl.dst[k] < 0) continue;
-    if (dil == 1) *reinterpret_cast<uint4*>(xs + pl.dst[k]) = r.v[k];
+template <int NPF>
+__device__ __forceinline__ void ncv_stage_store(unsigned short* xs, const NcvPreT<NPF>& r, const NcvPlanT<NPF>& pl, int dil) {
+  ncv_static_for<0, NPF>([&](auto kc) {
+    constexpr int k = decltype(kc)::value;
+    if (pl.dst[k] < 0) return;
+    // (member-wise: a whole-struct copy is a memcpy, and a register array that only memcpys touch - dil a compile-time 1 - stays in scratch memory)
+    if (dil == 1) *reinterpret_cast<uint4*>(xs + pl.dst[k]) = make_uint4(r.v[k].x, r.v[k].y, r.v[k].z, r.v[k].w);
     else {
       unsigned short* d = xs + pl.dst[k];
       const unsigned int u[4] = {r.v[k].x, r.v[k].y, r.v[k].z, r.v[k].w};
 #pragma unroll
       for (int j = 0; j < 4; j++) { d[(2 * j) * dil] = (unsigned short)(u[j] & 0xffffu); d[(2 * j + 1) * dil] = (unsigned short)(u[j] >> 16); }
     }
-  }
+  });
 }
 
 __device__ __forceinline__ void ncv_stage(unsigned short* xs, const bf16_t* __restrict__ sp, const NcvGeom& q, int tid, int nthreads) {
@@ -188,9 +200,6 @@ __device__ unsigned long long ncv_stamps[1024 * 8];
 //   NS = shifts per MFMA (see NcvW): NS = 2 halves the P window phases an MFMA has to be issued for.
 //   ADD: dst = round(round(conv) + add) - a separate instantiation (dgrad only: SW = 1) because the addend's registers cost the plain
 //   kernels a wave of occupancy
-template <int I0, int I1, class F> __device__ __forceinline__ void ncv_static_for(F&& f) {
-  if constexpr (I0 < I1) { f(std::integral_constant<int, I0>{}); ncv_static_for<I0 + 1, I1>(f); }
-}
 struct NcvWf { float n, mean, m2; };
 __device__ __forceinline__ NcvWf ncv_wf_merge(const NcvWf& a, const NcvWf& b) {   // Chan's merge; either side may be empty
   NcvWf r;
@@ -216,34 +225,13 @@ __device__ __forceinline__ NcvWf ncv_wf_merge(const NcvWf& a, const NcvWf& b) { 
 //   rows of one parity (rows blk * 2 TR + 2 tr + par): it runs the NK / 2 k-steps of its class instead of all NK - the other half multiplied
 //   structural zeros (EXPERIMENTS 66: the two such launches of the step spent 12 and 9 us in their k-loops).  Same products, same order per
 //   output element as far as non-zero terms go; the skipped terms were exact zeros.
-template <int NK, int SW, int PH0, int NS, bool ADD, bool STATS, bool PAR = false>
-__global__ __launch_bounds__(256, (STATS && NK <= 5) ? 3 : 1) void ncv_fwd2_kernel(const bf16_t* __restrict__ src, const nv_bf8* __restrict__ wpk, const bf16_t* __restrict__ bias,
-                                                       bf16_t* dst, NcvGeom q, const bf16_t* add, bf16_t* dst2, const bf16_t* __restrict__ bias2, int co_a,
-                                                       float* __restrict__ stats, float* __restrict__ stats2, int stats_per_wg,
-                                                       const bf16_t* __restrict__ src2) {
-  // src2 (dgrad of a pair): the second source of the staged image, channels [q.C1, q.C)
-  // co_a: output columns [0, co_a) belong to dst, [co_a, q.CO) to dst2 (the sibling 1x1 of NcvW; co_a = q.CO and dst2 = nullptr otherwise)
-  __shared__ float sst[STATS ? 2 : 1][4][16][3];           // [image parity][wave][MFMA column]: the waves' triples of one image
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  unsigned short* xs = reinterpret_cast<unsigned short*>(smem);
-  NCV_STAMP_AT(0);
-  constexpr int P = 8 / SW;
-  constexpr int ND = P / NS;                               // accumulators (MFMAs per k-step) of a super-tile
-  constexpr int NSEG = (PH0 + (ND - 1) * NS * SW + 7) < 16 ? 2 : 3;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, nthreads = blockDim.x, nwaves = nthreads >> 6;
-  const int co = NS == 2 ? (lane & 7) : (lane & 15);
-  const int ncg = q.Wo / P, TR = 16 / ncg;
-  // The first image's packets are requested before anything else: a workgroup lives for two or three images, and in-kernel stamps
-  // (scripts/ncv_stamp_probe.py) showed 3800 - 6300 of its 11 - 20 k cycles between "weights in registers" and "first image in LDS" -
-  // the HBM round trip of that first load, started only after the weights had arrived and the LDS was zeroed.
-  const int64_t img_in = (int64_t)q.C1 * q.H * q.W, img_in2 = (int64_t)(q.C - q.C1) * q.H * q.W;
-  NcvPre pre;
-  const NcvPlan plan = ncv_stage_plan(q, tid, nthreads);
-  if (q.pf && (int)blockIdx.x < q.N) ncv_stage_load(pre, plan, src + blockIdx.x * img_in, src2 + blockIdx.x * img_in2);
-  nv_bf8 wfr[NK];
-  int koff[NK];
-#pragma unroll
-  for (int ks = 0; ks < NK; ks++) {
+// The pieces of the aligned-window kernel as device functions: ncv_fwd2_kernel runs them for one convolution (or a 3x3 with its sibling 1x1),
+// ncv_chain_kernel runs them twice per image, the second time over the first one's output in LDS.
+//   this lane's k-steps: B fragments (in registers for the whole kernel) and the byte offset of their (channel, filter row) in the LDS image
+template <int NK, bool PAR>
+__device__ __forceinline__ void ncv_frag_setup(const NcvGeom& q, const nv_bf8* __restrict__ wpk, int lane, nv_bf8 (&wfr)[NK], int (&koff)[NK]) {
+  ncv_static_for<0, NK>([&](auto ksc) {
+    constexpr int ks = decltype(ksc)::value;
     wfr[ks] = wpk[ks * 64 + lane];
     int pair = ks * 4 + (lane >> 4);
     const int pairs1 = q.C1 * q.kh;
@@ -261,53 +249,224 @@ __global__ __launch_bounds__(256, (STATS && NK <= 5) ? 3 : 1) void ncv_fwd2_kern
       }
     }
     koff[ks] = (c * q.Hs + r) * q.Ws * 2;
+  });
+}
+//   sum y (every row of st1 alike) and sum y^2 (diagonal of st2: row j of column j = lane & 15 is register j & 3 of lane group j >> 2) of a
+//   wave's `tiles` super-tiles
+struct NcvStatAcc { nv_f4 st1, st2; int tiles; };
+__device__ __forceinline__ void ncv_stats_take(NcvStatAcc& s, unsigned a, unsigned b, unsigned c, unsigned d) {
+  typedef unsigned int nv_u4 __attribute__((ext_vector_type(4)));
+  const unsigned ones2 = 0x3f803f80u;                      // two bf16 ones
+  const nv_bf8 ones = __builtin_bit_cast(nv_bf8, nv_u4{ones2, ones2, ones2, ones2});
+  const nv_bf8 y = __builtin_bit_cast(nv_bf8, nv_u4{a, b, c, d});
+  s.st1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, y, s.st1, 0, 0, 0);
+  s.st2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(y, y, s.st2, 0, 0, 0);
+}
+//   ... -> sst[wave][column] = (count, sum y, sum y^2); VPT = output values per column and super-tile
+template <int VPT>
+__device__ __forceinline__ void ncv_stats_leave(NcvStatAcc& s, float (*sst)[16][3], int lane, int wid) {
+  const int j = lane & 15, r = j & 3;
+  const float sq = r == 0 ? s.st2[0] : r == 1 ? s.st2[1] : r == 2 ? s.st2[2] : s.st2[3];
+  if ((lane >> 4) == (j >> 2)) { sst[wid][j][0] = (float)(s.tiles * VPT); sst[wid][j][1] = s.st1[0]; sst[wid][j][2] = sq; }
+  s.st1 = nv_f4{0.f, 0.f, 0.f, 0.f}; s.st2 = nv_f4{0.f, 0.f, 0.f, 0.f}; s.tiles = 0;
+}
+//   the waves' sums of one part (left in sst before the barrier the caller has just passed) -> stats[channel][part] = (count, mean, M2),
+//   added in wave order; NS = 2: channel co sits in columns co and co + 8
+template <int NS>
+__device__ __forceinline__ void ncv_stats_flush(float (*sst)[16][3], int lane, int wid, int nwaves, int CO, int co_a, float* __restrict__ stats,
+                                                float* __restrict__ stats2, int part, int nparts) {
+  if (wid == 0 && lane < (NS == 2 ? 8 : 16) && lane < CO) {
+    float cnt = 0.f, sy = 0.f, sq = 0.f;
+    for (int h = 0; h < NS; h++)
+      for (int k = 0; k < nwaves; k++) { cnt += sst[k][lane + 8 * h][0]; sy += sst[k][lane + 8 * h][1]; sq += sst[k][lane + 8 * h][2]; }
+    const float mean = sy / cnt;                         // (cnt > 0: every image has at least one super-tile)
+    float* o = lane < co_a ? stats + ((int64_t)lane * nparts + part) * 3 : stats2 + ((int64_t)(lane - co_a) * nparts + part) * 3;
+    o[0] = cnt; o[1] = mean; o[2] = fmaxf(sq - sy * mean, 0.f);
   }
+}
+//   The super-tiles of ONE staged image (this wave's share): window reads, MFMAs, epilogue, stores to this lane's output plane yc.
+//   smem: the LDS image; ap (ADD): this lane's plane of the addend; sa (STATS): the wave's running sums.
+//   MIRROR (stride 1, plain tiles): every 16-byte packet stored to yc also goes to row (h, column cg * 8) of the lane's channel plane mc (row
+//   pitch mws elements) of a second LDS image - the staged input of the convolution that reads this output next (ncv_chain_kernel)
+template <int NK, int SW, int PH0, int NS, bool ADD, bool STATS, bool PAR, bool MIRROR>
+__device__ __forceinline__ void ncv_super_tiles(const char* smem, const NcvGeom& q, const nv_bf8 (&wfr)[NK], const int (&koff)[NK], int a_off, float bv, int co,
+                                                bf16_t* yc, const bf16_t* ap, NcvStatAcc& sa, unsigned short* mc, int mws, int lane, int wid, int nwaves) {
+  constexpr int P = 8 / SW;
+  constexpr int ND = P / NS;                               // accumulators (MFMAs per k-step) of a super-tile
+  constexpr int NSEG = (PH0 + (ND - 1) * NS * SW + 7) < 16 ? 2 : 3;
+  static_assert(!MIRROR || (P == 8 && !PAR), "the LDS copy takes whole 16-byte packets of plain tiles");
+  const int ncg = q.Wo / P, TR = 16 / ncg;
+  const int nsuper = q.Ho / TR;
+  for (int st = wid; st < nsuper; st += nwaves) {
+    // rows of the super-tile: h0 + RS * tr (PAR: super-tiles 2 b and 2 b + 1 share the 2 TR rows of block b, one parity each)
+    constexpr int RS = PAR ? 2 : 1;
+    const int h0 = PAR ? (st >> 1) * (2 * TR) + (st & 1) : st * TR;
+    const char* base = smem + a_off + h0 * q.sh * q.Ws * 2;
+    nv_f4 acc[ND];
+#pragma unroll
+    for (int d = 0; d < ND; d++) acc[d] = nv_f4{0.f, 0.f, 0.f, 0.f};
+#ifdef NCV_SKIP                      // diagnostic builds only (scripts/build_variant.sh): 1 = no k-loop, 2 = no output stores, 4 = no image staging
+    if (NCV_SKIP & 1) { acc[0][0] = (float)lane; }
+    else
+#endif
+    {
+    auto kstep = [&](auto ksc) {
+      constexpr int ks = decltype(ksc)::value;
+      unsigned int sg[NSEG * 4 + 1];
+#pragma unroll
+      for (int e = 0; e < NSEG; e++) {
+        const uint4 v = *reinterpret_cast<const uint4*>(base + koff[ks] + e * 16);
+        sg[e * 4 + 0] = v.x; sg[e * 4 + 1] = v.y; sg[e * 4 + 2] = v.z; sg[e * 4 + 3] = v.w;
+      }
+      sg[NSEG * 4] = 0;
+#pragma unroll
+      for (int d = 0; d < ND; d++) {
+        const int o = PH0 + d * NS * SW;                 // compile-time after unrolling: window origin of phase d * NS
+        const int dq = o >> 1;
+        unsigned int f[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) f[j] = (o & 1) ? __builtin_amdgcn_alignbit(sg[dq + j + 1], sg[dq + j], 16) : sg[dq + j];
+        typedef unsigned int u4v __attribute__((ext_vector_type(4)));
+        const u4v fv = {f[0], f[1], f[2], f[3]};
+        acc[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(nv_bf8, fv), wfr[ks], acc[d], 0, 0, 0);
+      }
+    };
+    if constexpr (PAR) {
+      // rows h0 + 2 tr of the dilated image hold values iff (row + r - top) is even: the class of k-steps whose r has the parity of (h0 + top)
+      if (((h0 + q.top) & 1) == 0) ncv_static_for<0, NK / 2>(kstep);          // r in {0, 2}
+      else ncv_static_for<NK / 2, NK>(kstep);                                  // r = 1 (and the second source's centre row)
+    } else ncv_static_for<0, NK>(kstep);
+    }
+    // ap != nullptr: dst = round(round(conv) + add) (see ig_conv8d_kernel); the rows this lane stores.  Requested after the MFMAs:
+    // held across them they cost 12 - 20 registers and a wave of occupancy
+    constexpr int NROW = NS == 1 ? 4 : 2;
+    const int row0 = (lane >> 4) * 4 + (NS == 1 ? 0 : ((lane >> 3) & 1) * 2);
+    uint4 addv[NROW];
+    if (ADD && co < q.CO) {
+#pragma unroll
+      for (int k = 0; k < NROW; k++) {
+        const int i = row0 + k, tr = i / ncg, cg = i - tr * ncg;
+        const bf16_t* a = ap + (h0 + RS * tr) * q.Wo + cg * P;
+        if (P == 8) addv[k] = *reinterpret_cast<const uint4*>(a);
+        else { const uint2 t = *reinterpret_cast<const uint2*>(a); addv[k] = make_uint4(t.x, t.y, 0, 0); }
+      }
+    }
+    if (STATS) sa.tiles++;
+    if (NS == 1) {
+      unsigned int prev[P / 2];                          // P = 4: two rows make one fragment
+#pragma unroll
+      for (int rr = 0; rr < 4; rr++) {
+        const int i = (lane >> 4) * 4 + rr;
+        const int tr = i / ncg, cg = i - tr * ncg;
+        bf16_t* o = yc + (h0 + RS * tr) * q.Wo + cg * P;
+        unsigned int pk[P / 2];
+#pragma unroll
+        for (int d = 0; d < P; d += 2) {
+          const bf16_t lo(acc[d % ND][rr] + bv), hi(acc[(d + 1) % ND][rr] + bv);
+          pk[d >> 1] = (unsigned)lo.bits | ((unsigned)hi.bits << 16);
+        }
+        if (ADD) {
+#pragma unroll
+          for (int j = 0; j < P / 2; j++) pk[j] = add_bf16x2(pk[j], (&addv[rr % NROW].x)[j]);
+        }
+        if (STATS) {                                     // (every lane: the columns beyond CO carry zeros)
+          if (P == 8) ncv_stats_take(sa, pk[0], pk[1], pk[2 % (P / 2)], pk[3 % (P / 2)]);
+          else if (rr & 1) ncv_stats_take(sa, prev[0], prev[1], pk[0], pk[1]);
+          else { prev[0] = pk[0]; prev[1] = pk[1]; }
+        }
+        if (co < q.CO NCV_STORE_COND) {
+          if (P == 8) *reinterpret_cast<uint4*>(o) = make_uint4(pk[0], pk[1], pk[2 % (P / 2)], pk[3 % (P / 2)]);
+          else *reinterpret_cast<uint2*>(o) = make_uint2(pk[0], pk[1]);
+          if constexpr (MIRROR) *reinterpret_cast<uint4*>(mc + (h0 + tr) * mws + cg * 8) = make_uint4(pk[0], pk[1], pk[2 % (P / 2)], pk[3 % (P / 2)]);
+        }
+      }
+    } else {
+      // lane (s, co, g) holds phases 2d + s of rows 4g .. 4g+3; its partner lane ^ 8 holds the other parity.  The s = 0 lane
+      // completes rows 4g, 4g+1 and the s = 1 lane rows 4g+2, 4g+3: each sends the two rows it does not store.
+      const int sft = (lane >> 3) & 1;
+      unsigned int keep[2][ND], got[2][ND];
+#pragma unroll
+      for (int h = 0; h < 2; h++)
+#pragma unroll
+        for (int d = 0; d < ND; d++) {
+          const bf16_t mine(acc[d][sft * 2 + h] + bv), theirs(acc[d][(1 - sft) * 2 + h] + bv);    // rows this lane stores / sends
+          keep[h][d] = mine.bits;
+          got[h][d] = (unsigned)__shfl_xor((int)theirs.bits, 8, 64);
+        }
+      unsigned int prev[ND];
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        const int i = (lane >> 4) * 4 + sft * 2 + h;
+        const int tr = i / ncg, cg = i - tr * ncg;
+        bf16_t* o = yc + (h0 + RS * tr) * q.Wo + cg * P;
+        unsigned int pk[ND];
+#pragma unroll
+        for (int d = 0; d < ND; d++) {
+          const unsigned int even = sft ? got[h][d] : keep[h][d], odd = sft ? keep[h][d] : got[h][d];
+          pk[d] = even | (odd << 16);
+        }
+        if (ADD) {
+#pragma unroll
+          for (int d = 0; d < ND; d++) pk[d] = add_bf16x2(pk[d], (&addv[h % NROW].x)[d]);
+        }
+        if (STATS) {
+          if (P == 8) ncv_stats_take(sa, pk[0], pk[1], pk[2 % ND], pk[3 % ND]);
+          else if (h) ncv_stats_take(sa, prev[0], prev[1], pk[0], pk[1]);
+          else { prev[0] = pk[0]; prev[1] = pk[1]; }
+        }
+        if (co < q.CO NCV_STORE_COND) {
+          if (P == 8) *reinterpret_cast<uint4*>(o) = make_uint4(pk[0], pk[1], pk[2 % ND], pk[3 % ND]);
+          else *reinterpret_cast<uint2*>(o) = make_uint2(pk[0], pk[1]);
+          if constexpr (MIRROR) *reinterpret_cast<uint4*>(mc + (h0 + tr) * mws + cg * 8) = make_uint4(pk[0], pk[1], pk[2 % ND], pk[3 % ND]);
+        }
+      }
+    }
+  }
+}
+
+template <int NK, int SW, int PH0, int NS, bool ADD, bool STATS, bool PAR = false>
+__global__ __launch_bounds__(256, (STATS && NK <= 5) ? 3 : 1) void ncv_fwd2_kernel(const bf16_t* __restrict__ src, const nv_bf8* __restrict__ wpk, const bf16_t* __restrict__ bias,
+                                                       bf16_t* dst, NcvGeom q, const bf16_t* add, bf16_t* dst2, const bf16_t* __restrict__ bias2, int co_a,
+                                                       float* __restrict__ stats, float* __restrict__ stats2, int stats_per_wg,
+                                                       const bf16_t* __restrict__ src2) {
+  // src2 (dgrad of a pair): the second source of the staged image, channels [q.C1, q.C)
+  // co_a: output columns [0, co_a) belong to dst, [co_a, q.CO) to dst2 (the sibling 1x1 of NcvW; co_a = q.CO and dst2 = nullptr otherwise)
+  __shared__ float sst[STATS ? 2 : 1][4][16][3];           // [image parity][wave][MFMA column]: the waves' triples of one image
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned short* xs = reinterpret_cast<unsigned short*>(smem);
+  NCV_STAMP_AT(0);
+  constexpr int P = 8 / SW;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, nthreads = blockDim.x, nwaves = nthreads >> 6;
+  const int co = NS == 2 ? (lane & 7) : (lane & 15);
+  const int ncg = q.Wo / P;
+  // The first image's packets are requested before anything else: a workgroup lives for two or three images, and in-kernel stamps
+  // (scripts/ncv_stamp_probe.py) showed 3800 - 6300 of its 11 - 20 k cycles between "weights in registers" and "first image in LDS" -
+  // the HBM round trip of that first load, started only after the weights had arrived and the LDS was zeroed.
+  const int64_t img_in = (int64_t)q.C1 * q.H * q.W, img_in2 = (int64_t)(q.C - q.C1) * q.H * q.W;
+  NcvPre pre;
+  const NcvPlan plan = ncv_stage_plan(q, tid, nthreads);
+  if (q.pf && (int)blockIdx.x < q.N) ncv_stage_load(pre, plan, src + blockIdx.x * img_in, src2 + blockIdx.x * img_in2);
+  nv_bf8 wfr[NK];
+  int koff[NK];
+  ncv_frag_setup<NK, PAR>(q, wpk, lane, wfr, koff);
   const float bv = co < co_a ? (bias ? (float)bias[co] : 0.f) : ((bias2 && co < q.CO) ? (float)bias2[co - co_a] : 0.f);
 #ifdef NCV_STAMP
   __builtin_amdgcn_s_waitcnt(0);
   NCV_STAMP_AT(1);
 #endif
-  const int HoWo = q.Ho * q.Wo, nsuper = q.Ho / TR;
+  const int HoWo = q.Ho * q.Wo;
   const int img_elems = q.C * q.Hs * q.Ws;
   for (int o = tid * 8; o < img_elems; o += nthreads * 8) *reinterpret_cast<uint4*>(xs + o) = make_uint4(0, 0, 0, 0);
   // A-side lane -> (row within the super-tile, column group)
   const int a_tr = (lane & 15) / ncg, a_cg = (lane & 15) - a_tr * ncg;
   const int a_off = ((PAR ? 2 : 1) * a_tr * q.sh * q.Ws + a_cg * 8 + (q.wx - PH0)) * 2;      // PAR: a tile's rows are two apart
-  // the waves' sums of one part (left in sst[par] before the barrier the caller has just passed) -> stats[channel][part] = (count, mean, M2),
-  // added in wave order; NS = 2: channel co sits in columns co and co + 8
-  auto stats_flush = [&](int part, int nparts, int par) {
-    if (wid == 0 && lane < (NS == 2 ? 8 : 16) && lane < q.CO) {
-      float cnt = 0.f, sy = 0.f, sq = 0.f;
-      for (int h = 0; h < NS; h++)
-        for (int k = 0; k < nwaves; k++) { cnt += sst[par][k][lane + 8 * h][0]; sy += sst[par][k][lane + 8 * h][1]; sq += sst[par][k][lane + 8 * h][2]; }
-      const float mean = sy / cnt;                         // (cnt > 0: every image has at least one super-tile)
-      float* o = lane < co_a ? stats + ((int64_t)lane * nparts + part) * 3 : stats2 + ((int64_t)(lane - co_a) * nparts + part) * 3;
-      o[0] = cnt; o[1] = mean; o[2] = fmaxf(sq - sy * mean, 0.f);
-    }
-  };
-  // sum y (every row of st1 alike) and sum y^2 (diagonal of st2: row j of column j = lane & 15 is register j & 3 of lane group j >> 2) of this
-  // wave's `tiles` super-tiles -> sst[par][wave][column] = (count, sum y, sum y^2)
-  nv_f4 st1 = nv_f4{0.f, 0.f, 0.f, 0.f}, st2 = nv_f4{0.f, 0.f, 0.f, 0.f};
-  int tiles = 0;
-  auto stats_leave = [&](int par) {
-    const int j = lane & 15, r = j & 3;
-    const float sq = r == 0 ? st2[0] : r == 1 ? st2[1] : r == 2 ? st2[2] : st2[3];
-    if ((lane >> 4) == (j >> 2)) { sst[par][wid][j][0] = (float)(tiles * (16 * P / NS)); sst[par][wid][j][1] = st1[0]; sst[par][wid][j][2] = sq; }
-    st1 = nv_f4{0.f, 0.f, 0.f, 0.f}; st2 = nv_f4{0.f, 0.f, 0.f, 0.f}; tiles = 0;
-  };
-  const unsigned ones2 = 0x3f803f80u;                      // two bf16 ones
-  typedef unsigned int nv_u4 __attribute__((ext_vector_type(4)));
-  const nv_bf8 ones = __builtin_bit_cast(nv_bf8, nv_u4{ones2, ones2, ones2, ones2});
-  auto stats_take = [&](unsigned a, unsigned b, unsigned c, unsigned d) {
-    const nv_bf8 y = __builtin_bit_cast(nv_bf8, nv_u4{a, b, c, d});
-    st1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, y, st1, 0, 0, 0);
-    st2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(y, y, st2, 0, 0, 0);
-  };
+  constexpr int VPT = 16 * P / NS;
+  NcvStatAcc sa{nv_f4{0.f, 0.f, 0.f, 0.f}, nv_f4{0.f, 0.f, 0.f, 0.f}, 0};
   int it = 0;
   for (int n = blockIdx.x; n < q.N; n += gridDim.x, it++) {
     __syncthreads();                                     // zero fill / the previous image's reads are done
     NCV_STAMP_ONCE(2);
-    if (STATS && !stats_per_wg && it > 0) stats_flush(n - (int)gridDim.x, q.N, (it - 1) & 1);
+    if (STATS && !stats_per_wg && it > 0) ncv_stats_flush<NS>(sst[(it - 1) & 1], lane, wid, nwaves, q.CO, co_a, stats, stats2, n - (int)gridDim.x, q.N);
 #if defined(NCV_SKIP) && (NCV_SKIP & 4)
     if (n < 0)
 #endif
@@ -324,144 +483,92 @@ __global__ __launch_bounds__(256, (STATS && NK <= 5) ? 3 : 1) void ncv_fwd2_kern
       ncv_stage_load(pre, plan, src + (n + (int)gridDim.x) * img_in, src2 + (n + (int)gridDim.x) * img_in2);
     // this lane's output plane: channel co of dst, or channel co - co_a of the sibling's tensor
     bf16_t* yc = co < co_a ? dst + ((int64_t)n * co_a + co) * HoWo : dst2 + ((int64_t)n * (q.CO - co_a) + (co - co_a)) * HoWo;
-    for (int st = wid; st < nsuper; st += nwaves) {
-      // rows of the super-tile: h0 + RS * tr (PAR: super-tiles 2 b and 2 b + 1 share the 2 TR rows of block b, one parity each)
-      constexpr int RS = PAR ? 2 : 1;
-      const int h0 = PAR ? (st >> 1) * (2 * TR) + (st & 1) : st * TR;
-      const char* base = smem + a_off + h0 * q.sh * q.Ws * 2;
-      nv_f4 acc[ND];
-#pragma unroll
-      for (int d = 0; d < ND; d++) acc[d] = nv_f4{0.f, 0.f, 0.f, 0.f};
-#ifdef NCV_SKIP                      // diagnostic builds only (scripts/build_variant.sh): 1 = no k-loop, 2 = no output stores, 4 = no image staging
-      if (NCV_SKIP & 1) { acc[0][0] = (float)lane; }
-      else
-#endif
-      {
-      auto kstep = [&](auto ksc) {
-        constexpr int ks = decltype(ksc)::value;
-        unsigned int sg[NSEG * 4 + 1];
-#pragma unroll
-        for (int e = 0; e < NSEG; e++) {
-          const uint4 v = *reinterpret_cast<const uint4*>(base + koff[ks] + e * 16);
-          sg[e * 4 + 0] = v.x; sg[e * 4 + 1] = v.y; sg[e * 4 + 2] = v.z; sg[e * 4 + 3] = v.w;
-        }
-        sg[NSEG * 4] = 0;
-#pragma unroll
-        for (int d = 0; d < ND; d++) {
-          const int o = PH0 + d * NS * SW;                 // compile-time after unrolling: window origin of phase d * NS
-          const int dq = o >> 1;
-          unsigned int f[4];
-#pragma unroll
-          for (int j = 0; j < 4; j++) f[j] = (o & 1) ? __builtin_amdgcn_alignbit(sg[dq + j + 1], sg[dq + j], 16) : sg[dq + j];
-          typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-          const u4v fv = {f[0], f[1], f[2], f[3]};
-          acc[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(nv_bf8, fv), wfr[ks], acc[d], 0, 0, 0);
-        }
-      };
-      if constexpr (PAR) {
-        // rows h0 + 2 tr of the dilated image hold values iff (row + r - top) is even: the class of k-steps whose r has the parity of (h0 + top)
-        if (((h0 + q.top) & 1) == 0) ncv_static_for<0, NK / 2>(kstep);          // r in {0, 2}
-        else ncv_static_for<NK / 2, NK>(kstep);                                  // r = 1 (and the second source's centre row)
-      } else ncv_static_for<0, NK>(kstep);
-      }
-      // add != nullptr: dst = round(round(conv) + add) (see ig_conv8d_kernel); the rows this lane stores.  Requested after the MFMAs:
-      // held across them they cost 12 - 20 registers and a wave of occupancy
-      constexpr int NROW = NS == 1 ? 4 : 2;
-      const int row0 = (lane >> 4) * 4 + (NS == 1 ? 0 : ((lane >> 3) & 1) * 2);
-      uint4 addv[NROW];
-      if (ADD && co < q.CO) {
-        const bf16_t* ap = add + (int64_t)n * q.CO * HoWo + co * HoWo;
-#pragma unroll
-        for (int k = 0; k < NROW; k++) {
-          const int i = row0 + k, tr = i / ncg, cg = i - tr * ncg;
-          const bf16_t* a = ap + (h0 + RS * tr) * q.Wo + cg * P;
-          if (P == 8) addv[k] = *reinterpret_cast<const uint4*>(a);
-          else { const uint2 t = *reinterpret_cast<const uint2*>(a); addv[k] = make_uint4(t.x, t.y, 0, 0); }
-        }
-      }
-      if (STATS) tiles++;
-      if (NS == 1) {
-        unsigned int prev[P / 2];                          // P = 4: two rows make one fragment
-#pragma unroll
-        for (int rr = 0; rr < 4; rr++) {
-          const int i = (lane >> 4) * 4 + rr;
-          const int tr = i / ncg, cg = i - tr * ncg;
-          bf16_t* o = yc + (h0 + RS * tr) * q.Wo + cg * P;
-          unsigned int pk[P / 2];
-#pragma unroll
-          for (int d = 0; d < P; d += 2) {
-            const bf16_t lo(acc[d % ND][rr] + bv), hi(acc[(d + 1) % ND][rr] + bv);
-            pk[d >> 1] = (unsigned)lo.bits | ((unsigned)hi.bits << 16);
-          }
-          if (ADD) {
-#pragma unroll
-            for (int j = 0; j < P / 2; j++) pk[j] = add_bf16x2(pk[j], (&addv[rr % NROW].x)[j]);
-          }
-          if (STATS) {                                     // (every lane: the columns beyond CO carry zeros)
-            if (P == 8) stats_take(pk[0], pk[1], pk[2 % (P / 2)], pk[3 % (P / 2)]);
-            else if (rr & 1) stats_take(prev[0], prev[1], pk[0], pk[1]);
-            else { prev[0] = pk[0]; prev[1] = pk[1]; }
-          }
-          if (co < q.CO NCV_STORE_COND) {
-            if (P == 8) *reinterpret_cast<uint4*>(o) = make_uint4(pk[0], pk[1], pk[2 % (P / 2)], pk[3 % (P / 2)]);
-            else *reinterpret_cast<uint2*>(o) = make_uint2(pk[0], pk[1]);
-          }
-        }
-      } else {
-        // lane (s, co, g) holds phases 2d + s of rows 4g .. 4g+3; its partner lane ^ 8 holds the other parity.  The s = 0 lane
-        // completes rows 4g, 4g+1 and the s = 1 lane rows 4g+2, 4g+3: each sends the two rows it does not store.
-        const int sft = (lane >> 3) & 1;
-        unsigned int keep[2][ND], got[2][ND];
-#pragma unroll
-        for (int h = 0; h < 2; h++)
-#pragma unroll
-          for (int d = 0; d < ND; d++) {
-            const bf16_t mine(acc[d][sft * 2 + h] + bv), theirs(acc[d][(1 - sft) * 2 + h] + bv);    // rows this lane stores / sends
-            keep[h][d] = mine.bits;
-            got[h][d] = (unsigned)__shfl_xor((int)theirs.bits, 8, 64);
-          }
-        unsigned int prev[ND];
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-          const int i = (lane >> 4) * 4 + sft * 2 + h;
-          const int tr = i / ncg, cg = i - tr * ncg;
-          bf16_t* o = yc + (h0 + RS * tr) * q.Wo + cg * P;
-          unsigned int pk[ND];
-#pragma unroll
-          for (int d = 0; d < ND; d++) {
-            const unsigned int even = sft ? got[h][d] : keep[h][d], odd = sft ? keep[h][d] : got[h][d];
-            pk[d] = even | (odd << 16);
-          }
-          if (ADD) {
-#pragma unroll
-            for (int d = 0; d < ND; d++) pk[d] = add_bf16x2(pk[d], (&addv[h % NROW].x)[d]);
-          }
-          if (STATS) {
-            if (P == 8) stats_take(pk[0], pk[1], pk[2 % ND], pk[3 % ND]);
-            else if (h) stats_take(prev[0], prev[1], pk[0], pk[1]);
-            else { prev[0] = pk[0]; prev[1] = pk[1]; }
-          }
-          if (co < q.CO NCV_STORE_COND) {
-            if (P == 8) *reinterpret_cast<uint4*>(o) = make_uint4(pk[0], pk[1], pk[2 % ND], pk[3 % ND]);
-            else *reinterpret_cast<uint2*>(o) = make_uint2(pk[0], pk[1]);
-          }
-        }
-      }
-    }
-    if (STATS && !stats_per_wg) stats_leave(it & 1);
+    const bf16_t* ap = ADD ? add + (int64_t)n * q.CO * HoWo + co * HoWo : nullptr;
+    ncv_super_tiles<NK, SW, PH0, NS, ADD, STATS, PAR, false>(smem, q, wfr, koff, a_off, bv, co, yc, ap, sa, nullptr, 0, lane, wid, nwaves);
+    if (STATS && !stats_per_wg) ncv_stats_leave<VPT>(sa, sst[it & 1], lane, wid);
     NCV_STAMP_ONCE(4);
   }
   if (STATS && it > 0) {
-    if (stats_per_wg) stats_leave(0);
+    if (stats_per_wg) ncv_stats_leave<VPT>(sa, sst[0], lane, wid);
     __syncthreads();
-    if (stats_per_wg) stats_flush((int)blockIdx.x, (int)gridDim.x, 0);
-    else stats_flush((int)blockIdx.x + (it - 1) * (int)gridDim.x, q.N, (it - 1) & 1);
+    if (stats_per_wg) ncv_stats_flush<NS>(sst[0], lane, wid, nwaves, q.CO, co_a, stats, stats2, (int)blockIdx.x, (int)gridDim.x);
+    else ncv_stats_flush<NS>(sst[(it - 1) & 1], lane, wid, nwaves, q.CO, co_a, stats, stats2, (int)blockIdx.x + (it - 1) * (int)gridDim.x, q.N);
   }
 #ifdef NCV_STAMP
   NCV_STAMP_AT(5);
   __builtin_amdgcn_s_waitcnt(0);
   NCV_STAMP_AT(6);
 #endif
+}
+
+// A stride-1 convolution and the 3x3 + 1x1 pair that reads its output (the stem of Cnn.resnet and the two branches of the first residual block,
+// cnn.scala:95-109: no batch norm between them, so nothing between x and (a, b) needs the whole batch) in ONE launch.  Per image: the first
+// convolution's super-tiles run as in ncv_fwd2_kernel; each rounded 16-byte packet goes to s in global memory (the pair's weight gradient reads
+// it in backward) AND into a second LDS image laid out as the pair's staged input (q1's top / left / pitch); after a barrier the pair's
+// super-tiles run from that image, with the statistics epilogue of a and b.  Same MFMA chains over the same rounded values: s, a, b and the
+// statistics are bitwise those of ncv_fwd2_kernel twice; what goes away is one launch and the 25 MB read of s (B = 2048).
+// The first convolution is the two-shift form (NS = 2), the pair the one-shift form at stride 2: the geometries of the ResNet's entry.
+constexpr int NCV_CHAIN_PF = 2;
+template <int NK0, int PH00, int NK1, int PH01, bool STATS>
+__global__ __launch_bounds__(256, NK1 <= 5 ? 3 : 1) void ncv_chain_kernel(const bf16_t* __restrict__ x, const nv_bf8* __restrict__ wpk0, const bf16_t* __restrict__ bias0,
+                                                                          bf16_t* s, NcvGeom q0, const nv_bf8* __restrict__ wpk1, const bf16_t* __restrict__ bias1,
+                                                                          const bf16_t* __restrict__ bias1b, bf16_t* ya, bf16_t* yb, int co_a, NcvGeom q1,
+                                                                          float* __restrict__ stats, float* __restrict__ stats2, int stats_per_wg) {
+  __shared__ float sst[STATS ? 2 : 1][4][16][3];
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int img0 = q0.C * q0.Hs * q0.Ws, img1 = q1.C * q1.Hs * q1.Ws;         // elements, multiples of 8
+  unsigned short* xs0 = reinterpret_cast<unsigned short*>(smem);
+  unsigned short* xs1 = xs0 + img0;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int co0 = lane & 7, co1 = lane & 15;
+  const int64_t img_in = (int64_t)q0.C * q0.H * q0.W;
+  NcvPreT<NCV_CHAIN_PF> pre;
+  const NcvPlanT<NCV_CHAIN_PF> plan = ncv_stage_plan<NCV_CHAIN_PF>(q0, tid, 256);      // (the launcher fuses only images that fit the prefetch)
+  if ((int)blockIdx.x < q0.N) ncv_stage_load(pre, plan, x + blockIdx.x * img_in, x);
+  // The pair's fragments stay in registers; the first convolution's are read again for every image (the pair's phase alone needs all but five of
+  // the 168 registers that three workgroups per CU leave a thread, and keeping both sets spilled 15 of them)
+  nv_bf8 wfr1[NK1];
+  int koff1[NK1];
+  ncv_frag_setup<NK1, false>(q1, wpk1, lane, wfr1, koff1);
+  const float bv0 = (bias0 && co0 < q0.CO) ? (float)bias0[co0] : 0.f;
+  const float bv1 = co1 < co_a ? (bias1 ? (float)bias1[co1] : 0.f) : ((bias1b && co1 < q1.CO) ? (float)bias1b[co1 - co_a] : 0.f);
+  for (int o = tid * 8; o < img0 + img1; o += 256 * 8) *reinterpret_cast<uint4*>(xs0 + o) = make_uint4(0, 0, 0, 0);
+  const int ncg0 = q0.Wo / 8, ncg1 = q1.Wo / 4;
+  const int a_tr0 = (lane & 15) / ncg0, a_cg0 = (lane & 15) - a_tr0 * ncg0;
+  const int a_off0 = (a_tr0 * q0.sh * q0.Ws + a_cg0 * 8 + (q0.wx - PH00)) * 2;
+  const int a_tr1 = (lane & 15) / ncg1, a_cg1 = (lane & 15) - a_tr1 * ncg1;
+  const int a_off1 = (a_tr1 * q1.sh * q1.Ws + a_cg1 * 8 + (q1.wx - PH01)) * 2;
+  const int HoWo0 = q0.Ho * q0.Wo, HoWo1 = q1.Ho * q1.Wo;
+  // this lane's channel plane of the pair's image: pixel (h, w) of s at (top + h, left + w), as ncv_stage_store places a staged one
+  unsigned short* mc = xs1 + (co0 * q1.Hs + q1.top) * q1.Ws + q1.left;
+  constexpr int VPT = 16 * 4;
+  NcvStatAcc sa{nv_f4{0.f, 0.f, 0.f, 0.f}, nv_f4{0.f, 0.f, 0.f, 0.f}, 0}, none = sa;
+  int it = 0;
+  for (int n = blockIdx.x; n < q0.N; n += gridDim.x, it++) {
+    __syncthreads();                                     // zero fill / the previous image's reads of both LDS images are done
+    if (STATS && !stats_per_wg && it > 0) ncv_stats_flush<1>(sst[(it - 1) & 1], lane, wid, 4, q1.CO, co_a, stats, stats2, n - (int)gridDim.x, q1.N);
+    ncv_stage_store(xs0, pre, plan, 1);
+    __syncthreads();
+    if (n + (int)gridDim.x < q0.N) ncv_stage_load(pre, plan, x + (n + (int)gridDim.x) * img_in, x);      // in flight during both phases' MFMAs
+    nv_bf8 wfr0[NK0];
+    int koff0[NK0];
+    int lane0 = lane;
+    asm volatile("" : "+v"(lane0));                      // (opaque: keeps these loads inside the loop, out of the pair's phase)
+    ncv_frag_setup<NK0, false>(q0, wpk0, lane0, wfr0, koff0);
+    ncv_super_tiles<NK0, 1, PH00, 2, false, false, false, true>(smem, q0, wfr0, koff0, a_off0, bv0, co0, s + ((int64_t)n * q0.CO + co0) * HoWo0, nullptr, none,
+                                                                mc, q1.Ws, lane, wid, 4);
+    __syncthreads();                                     // s of this image is complete in the second LDS image
+    bf16_t* yc = co1 < co_a ? ya + ((int64_t)n * co_a + co1) * HoWo1 : yb + ((int64_t)n * (q1.CO - co_a) + (co1 - co_a)) * HoWo1;
+    ncv_super_tiles<NK1, 2, PH01, 1, false, STATS, false, false>(reinterpret_cast<const char*>(xs1), q1, wfr1, koff1, a_off1, bv1, co1, yc, nullptr, sa, nullptr, 0,
+                                                                 lane, wid, 4);
+    if (STATS && !stats_per_wg) ncv_stats_leave<VPT>(sa, sst[it & 1], lane, wid);
+  }
+  if (STATS && it > 0) {
+    if (stats_per_wg) ncv_stats_leave<VPT>(sa, sst[0], lane, wid);
+    __syncthreads();
+    if (stats_per_wg) ncv_stats_flush<1>(sst[0], lane, wid, 4, q1.CO, co_a, stats, stats2, (int)blockIdx.x, (int)gridDim.x);
+    else ncv_stats_flush<1>(sst[(it - 1) & 1], lane, wid, 4, q1.CO, co_a, stats, stats2, (int)blockIdx.x + (it - 1) * (int)gridDim.x, q1.N);
+  }
 }
 #ifdef NCV_STAMP
 extern "C" int lamp_debug_ncv_stamps(unsigned long long* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(ncv_stamps), sizeof(ncv_stamps)) == hipSuccess ? 0 : 1; }
@@ -891,15 +998,24 @@ struct NcvSibling { const Tensor* w; const Tensor* bias; Tensor* out; };
 // second (dgrad, optional): the output gradient and the filter of a sibling 1x1 convolution of the same input (same stride and output map): both
 // input gradients, summed in f32, from one launch of the aligned kernel (false, nothing launched, when that kernel does not take the pair)
 struct NcvSecondGrad { const Tensor* dy; const Tensor* w; };
-static bool ncv_run(const Tensor* in, const Tensor* w, const Tensor* bias, Tensor* out, const ConvGeom& g, bool dgrad, hipStream_t st,
-                    const Tensor* addend = nullptr, bool* addend_fused = nullptr, const NcvSibling* sib = nullptr,
-                    const NcvSecondGrad* second = nullptr) {
-  if (addend_fused) *addend_fused = false;
-  if (!ncv_common(g, in->dtype)) return false;
-  const int cout2 = sib ? (int)sib->w->sizes[0] : second ? (int)second->w->sizes[0] : 0;
+// What a narrow forward / input-gradient launch looks like for a geometry: the LDS image, the kernel form and its template arguments.
+// sib / second: a sibling 1x1's cout2 output channels (fprop) or its output gradient as extra image channels (dgrad) take part.
+// false: the narrow kernels do not take it.
+struct NcvLaunchPlan {
+  NcvGeom q;
+  bool aligned;          // the aligned-window kernel (ncv_fwd2_kernel); else ncv_fwd_kernel
+  int ncg, ph0;          // aligned: column groups per output row, window phase
+  int NK;                // k-steps of the pairs (an entry of nk_opts); aligned: the kernel's are NK2
+  int nke;               // > 0: parity tiles, nke k-steps per class
+  int NS;                // output phases per MFMA
+  size_t lds;
+  int threads, NK2;      // aligned only
+};
+static bool ncv_plan(const ConvGeom& g, int dtype, bool dgrad, bool sib, bool second, int cout2, NcvLaunchPlan& lp) {
+  if (!ncv_common(g, dtype)) return false;
   if (sib && (dgrad || g.Cout + cout2 > 16)) return false;
   if (second && (!dgrad || sib || cout2 > 16)) return false;
-  NcvGeom q;
+  NcvGeom& q = lp.q;
   q.N = (int)g.N; q.kh = g.kh; q.pf = 0; q.kh_inv = 65536 / g.kh + 1;
   if (!dgrad) {
     if (g.W % 8 != 0) return false;
@@ -960,32 +1076,33 @@ static bool ncv_run(const Tensor* in, const Tensor* w, const Tensor* bias, Tenso
   // two output phases per MFMA where the columns allow it (see NcvW)
   const bool two_shift_on = sw().ncv_two_shift;
   const int NS = (two_shift_on && aligned && q.CO <= 8 && g.kw + q.sw <= 8) ? 2 : 1;
-  const Tensor* wsecond = sib ? sib->w : second ? second->w : nullptr;
-  const NcvW wq{w->ptr<bf16_t>(), (int)g.Cout, (int)g.Cin, g.kh, g.kw, dgrad ? 1 : 0, NS, q.sw, wsecond ? wsecond->ptr<bf16_t>() : (const bf16_t*)nullptr, cout2, nke};
-  Hold wpk_h(ncv_packed_weights(w, wq, st, wsecond));
-  const nv_bf8* wpk = reinterpret_cast<const nv_bf8*>(static_cast<const Tensor*>(wpk_h.get())->ptr<bf16_t>());
-  const int max_per_cu = (int)sw().ncv_per_cu;   // A/B on one device: 4 beats 8 and 2
-  const int lds_per_cu = (int)std::max<size_t>(1, std::min<size_t>(max_per_cu, (size_t)(150 * 1024) / std::max<size_t>(lds, 1)));
-  const bf16_t* bp = bias ? bias->ptr<bf16_t>() : (const bf16_t*)nullptr;
+  lp.aligned = aligned; lp.ncg = ncg; lp.ph0 = ph0; lp.NK = NK; lp.nke = nke; lp.NS = NS; lp.lds = lds; lp.threads = 256; lp.NK2 = NK;
   if (aligned) {
     const int nsuper = q.Ho / (16 / ncg);
-    const int threads = 64 * std::min(4, nsuper);
-    q.pf = (q.W % 8 == 0 && (int64_t)q.C * q.H * q.W <= (int64_t)NCV_PF * threads * 8) ? 1 : 0;
-    if (second && !q.pf) return false;                     // (two sources are staged through the register prefetch only)
-    if (NK > 12 && !second) return false;
+    lp.threads = 64 * std::min(4, nsuper);
+    q.pf = (q.W % 8 == 0 && (int64_t)q.C * q.H * q.W <= (int64_t)NCV_PF * lp.threads * 8) ? 1 : 0;
     // (parity tiles: the kernel's k-steps are the packed image's two halves - 2 nke, whatever the plain form would have taken: 12 k-steps of
     // pairs are 16 there)
-    const int NK2 = nke > 0 ? 2 * nke : NK <= 2 ? 2 : (NK <= 4 ? 4 : (NK <= 5 ? 5 : (NK <= 6 && second ? 6 : (NK <= 8 && second ? 8 : (NK <= 12 ? 12 : 16)))));
-    const void* kfn = nullptr;
-    const bool with_add = addend != nullptr && q.sw == 1;
-    // fprop: per-image batch-norm statistics of the output(s) from the epilogue (LAMP_CONV_BN_STATS=0 turns the hand-off off)
-    const bool bn_stats = sw().conv_bn_stats && sw().ncv_bn_stats;          // (the second: the narrow kernels' alone, A/B)
-    // (a filter whose output's statistics nobody took last time - the stem of Cnn.resnet feeds res1's convolutions directly - stops paying for them)
-    const bool with_stats = bn_stats && !dgrad && !addend && g.N >= 2 && (int64_t)q.Ho * q.Wo >= 64 && (sib || conv_stats_wanted(w->st->uid));
+    lp.NK2 = nke > 0 ? 2 * nke : NK <= 2 ? 2 : (NK <= 4 ? 4 : (NK <= 5 ? 5 : (NK <= 6 && second ? 6 : (NK <= 8 && second ? 8 : (NK <= 12 ? 12 : 16)))));
+  }
+  return true;
+}
+// the packed image's description for a planned launch (second: the sibling's / the second gradient's filter)
+static NcvW ncv_weights_of(const Tensor* w, const ConvGeom& g, bool dgrad, const NcvLaunchPlan& lp, const Tensor* wsecond, int cout2) {
+  return NcvW{w->ptr<bf16_t>(), (int)g.Cout, (int)g.Cin, g.kh, g.kw, dgrad ? 1 : 0, lp.NS, lp.q.sw, wsecond ? wsecond->ptr<bf16_t>() : (const bf16_t*)nullptr, cout2, lp.nke};
+}
+// workgroups per CU the LDS image allows (LAMP_NCV_PER_CU at most: A/B on one device, 4 beats 8 and 2)
+static int ncv_lds_per_cu(size_t lds) {
+  const int max_per_cu = (int)sw().ncv_per_cu;
+  return (int)std::max<size_t>(1, std::min<size_t>(max_per_cu, (size_t)(150 * 1024) / std::max<size_t>(lds, 1)));
+}
+// the instantiation of ncv_fwd2_kernel for (k-steps, phases per MFMA, window phase, stride, addend, statistics, parity tiles)
+static const void* ncv_fwd2_fn(int NK2, int NS, int ph0, int sw, bool with_add, bool with_stats, int nke) {
+  const void* kfn = nullptr;
 #define NCV_F2(NKv, SWv, PHv, ADDv, STv) kfn = NS == 2 ? (const void*)ncv_fwd2_kernel<NKv, SWv, PHv, 2, ADDv, STv> : (const void*)ncv_fwd2_kernel<NKv, SWv, PHv, 1, ADDv, STv>
 #define NCV_F2_PH(NKv, SWv, ADDv, STv) do { if (ph0 == 0) NCV_F2(NKv, SWv, 0, ADDv, STv); else if (ph0 == 6) NCV_F2(NKv, SWv, 6, ADDv, STv); else NCV_F2(NKv, SWv, 7, ADDv, STv); } while (0)
-#define NCV_F2_SW(NKv) do { if (with_stats) { if (q.sw == 1) NCV_F2_PH(NKv, 1, false, true); else NCV_F2_PH(NKv, 2, false, true); }                \
-                            else if (q.sw == 1) { if (with_add) NCV_F2_PH(NKv, 1, true, false); else NCV_F2_PH(NKv, 1, false, false); }                \
+#define NCV_F2_SW(NKv) do { if (with_stats) { if (sw == 1) NCV_F2_PH(NKv, 1, false, true); else NCV_F2_PH(NKv, 2, false, true); }                \
+                            else if (sw == 1) { if (with_add) NCV_F2_PH(NKv, 1, true, false); else NCV_F2_PH(NKv, 1, false, false); }                \
                             else NCV_F2_PH(NKv, 2, false, false); } while (0)
     // (6, 8 and 16 k-steps: the pairs' input gradients only - stride-1 correlations without statistics)
 #define NCV_F2P(NKv, PHv, ADDv) kfn = NS == 2 ? (const void*)ncv_fwd2_kernel<NKv, 1, PHv, 2, ADDv, false, true> : (const void*)ncv_fwd2_kernel<NKv, 1, PHv, 1, ADDv, false, true>
@@ -1007,6 +1124,36 @@ static bool ncv_run(const Tensor* in, const Tensor* w, const Tensor* bias, Tenso
 #undef NCV_F2_SW
 #undef NCV_F2_PH
 #undef NCV_F2
+  return kfn;
+}
+static bool ncv_run(const Tensor* in, const Tensor* w, const Tensor* bias, Tensor* out, const ConvGeom& g, bool dgrad, hipStream_t st,
+                    const Tensor* addend = nullptr, bool* addend_fused = nullptr, const NcvSibling* sib = nullptr,
+                    const NcvSecondGrad* second = nullptr) {
+  if (addend_fused) *addend_fused = false;
+  const int cout2 = sib ? (int)sib->w->sizes[0] : second ? (int)second->w->sizes[0] : 0;
+  NcvLaunchPlan lp;
+  if (!ncv_plan(g, in->dtype, dgrad, sib != nullptr, second != nullptr, cout2, lp)) return false;
+  const NcvGeom& q = lp.q;
+  const bool aligned = lp.aligned;
+  const int ncg = lp.ncg, ph0 = lp.ph0, NK = lp.NK, nke = lp.nke, NS = lp.NS;
+  const size_t lds = lp.lds;
+  const Tensor* wsecond = sib ? sib->w : second ? second->w : nullptr;
+  const NcvW wq = ncv_weights_of(w, g, dgrad, lp, wsecond, cout2);
+  Hold wpk_h(ncv_packed_weights(w, wq, st, wsecond));
+  const nv_bf8* wpk = reinterpret_cast<const nv_bf8*>(static_cast<const Tensor*>(wpk_h.get())->ptr<bf16_t>());
+  const int lds_per_cu = ncv_lds_per_cu(lds);
+  const bf16_t* bp = bias ? bias->ptr<bf16_t>() : (const bf16_t*)nullptr;
+  if (aligned) {
+    const int threads = lp.threads;
+    if (second && !q.pf) return false;                     // (two sources are staged through the register prefetch only)
+    if (NK > 12 && !second) return false;
+    const int NK2 = lp.NK2;
+    const bool with_add = addend != nullptr && q.sw == 1;
+    // fprop: per-image batch-norm statistics of the output(s) from the epilogue (LAMP_CONV_BN_STATS=0 turns the hand-off off)
+    const bool bn_stats = sw().conv_bn_stats && sw().ncv_bn_stats;          // (the second: the narrow kernels' alone, A/B)
+    // (a filter whose output's statistics nobody took last time - the stem of Cnn.resnet feeds res1's convolutions directly - stops paying for them)
+    const bool with_stats = bn_stats && !dgrad && !addend && g.N >= 2 && (int64_t)q.Ho * q.Wo >= 64 && (sib || conv_stats_wanted(w->st->uid));
+    const void* kfn = ncv_fwd2_fn(NK2, NS, ph0, q.sw, with_add, with_stats, nke);
     // persistent grid: as many workgroups as are really co-resident (registers and LDS), each walks a strided range of images
     const int per_cu = std::min(lds_per_cu, kernel_occupancy(kfn, threads, lds));
     const int blocks = (int)std::min<int64_t>(g.N, (int64_t)num_cus() * per_cu);
@@ -1066,18 +1213,97 @@ static bool ncv_run(const Tensor* in, const Tensor* w, const Tensor* bias, Tenso
 bool narrow_conv_fwd(const Tensor* x, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, hipStream_t st) {
   return ncv_run(x, w, bias, y, g, false, st);
 }
-// y = conv3x3(x, w) and y1 = conv1x1(x, w1), same stride and output map (the two branches of lamp's residual block on its input,
-// cnn.scala:16-20), Cout + Cout1 <= 16: one launch, the values of the two separate ones (the second filter is the centre tap of extra
-// output columns); false = nothing launched
-bool narrow_conv_fwd_pair(const Tensor* x, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, const Tensor* w1, const Tensor* bias1,
-                          Tensor* y1, const ConvGeom& g1, hipStream_t st) {
+// the 3x3 pad 1 + 1x1 pad 0 pairs the sibling launch is for (LAMP_CONV_SIBLING=0: none)
+static bool ncv_fwd_pair_shapes(const Tensor* x, const ConvGeom& g, const ConvGeom& g1) {
   const bool on = sw().conv_sibling;
   if (!on || x->dtype != kBF16) return false;
   if (g.kh != 3 || g.kw != 3 || g.ph != 1 || g.pw != 1 || g1.kh != 1 || g1.kw != 1 || g1.ph != 0 || g1.pw != 0) return false;
   if (g.sh != g1.sh || g.sw != g1.sw || g.Ho != g1.Ho || g.Wo != g1.Wo || g.Cin != g1.Cin || g.N != g1.N || g.groups != 1 || g1.groups != 1) return false;
   if (g.dh != 1 || g.dw != 1 || g1.dh != 1 || g1.dw != 1) return false;
+  return true;
+}
+// y = conv3x3(x, w) and y1 = conv1x1(x, w1), same stride and output map (the two branches of lamp's residual block on its input,
+// cnn.scala:16-20), Cout + Cout1 <= 16: one launch, the values of the two separate ones (the second filter is the centre tap of extra
+// output columns); false = nothing launched
+bool narrow_conv_fwd_pair(const Tensor* x, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, const Tensor* w1, const Tensor* bias1,
+                          Tensor* y1, const ConvGeom& g1, hipStream_t st) {
+  if (!ncv_fwd_pair_shapes(x, g, g1)) return false;
   const NcvSibling sb{w1, bias1, y1};
   return ncv_run(x, w, bias, y, g, false, st, nullptr, nullptr, &sb);
+}
+// s = conv(x, w0), y = conv3x3(s, w) and y1 = conv1x1(s, w1): a stride-1 convolution and the pair that reads its output, in one launch of
+// ncv_chain_kernel - bitwise the values, and the statistics hand-off of y and y1, of narrow_conv_fwd followed by narrow_conv_fwd_pair.
+// false = nothing launched: the caller runs those two.  Taken when both are the aligned-window form the chain kernel is built for (the first
+// in the two-shift form with 4 k-steps and window phase 6: up to 8 output channels from up to 3 x 5 (channel, row) pairs of a 5-wide filter;
+// the pair at stride 2 in the one-shift form, 5 or 12 k-steps), one image of each fits the LDS together, and the pair's statistics keep the
+// partition they have in a launch of their own.
+bool narrow_conv_chain_pair(const Tensor* x, const Tensor* w0, const Tensor* bias0, Tensor* s, const ConvGeom& g0, const Tensor* w, const Tensor* bias,
+                            Tensor* y, const ConvGeom& g, const Tensor* w1, const Tensor* bias1, Tensor* y1, const ConvGeom& g1, hipStream_t st) {
+  if (!ncv_fwd_pair_shapes(x, g, g1)) return false;
+  if (g0.groups != 1 || g0.sh != 1 || g0.sw != 1 || g0.N != g.N || g0.Cout != g.Cin || g0.Ho != g.H || g0.Wo != g.W) return false;
+  const int cout2 = (int)w1->sizes[0];
+  NcvLaunchPlan p0, p1;
+  if (!ncv_plan(g0, x->dtype, false, false, false, 0, p0) || !ncv_plan(g, x->dtype, false, true, false, cout2, p1)) return false;
+  if (!p0.aligned || !p1.aligned || p0.threads != 256 || p1.threads != 256) return false;
+  if ((int64_t)p0.q.C * p0.q.H * p0.q.W > (int64_t)NCV_CHAIN_PF * 256 * 8) return false;      // (the chain kernel's register prefetch of x)
+  p0.q.pf = 1;
+  if (p0.NS != 2 || p0.NK2 != 4 || p0.ph0 != 6) return false;
+  if (p1.NS != 1 || p1.q.sw != 2 || p1.ph0 != 7 || !(p1.NK2 == 5 || p1.NK2 == 12)) return false;
+  const size_t lds = p0.lds + p1.lds;
+  if (lds > 150 * 1024) return false;
+  const NcvGeom& q0 = p0.q;
+  const NcvGeom& q1 = p1.q;
+  const bool with_stats = sw().conv_bn_stats && sw().ncv_bn_stats && g.N >= 2 && (int64_t)q1.Ho * q1.Wo >= 64;      // as ncv_run decides for a pair
+  const void* kfn = nullptr;
+  if (p1.NK2 == 5) kfn = with_stats ? (const void*)ncv_chain_kernel<4, 6, 5, 7, true> : (const void*)ncv_chain_kernel<4, 6, 5, 7, false>;
+  else kfn = with_stats ? (const void*)ncv_chain_kernel<4, 6, 12, 7, true> : (const void*)ncv_chain_kernel<4, 6, 12, 7, false>;
+  if (lds > 64 * 1024) allow_big_lds(kfn);
+  // the grid of the pair's own launch decides how its statistics are partitioned (per workgroup when every workgroup walks the same number
+  // of images): this launch takes that grid, or a smaller one where per-image triples are what the pair's launch would have written too
+  const void* kpair = ncv_fwd2_fn(p1.NK2, 1, 7, 2, false, with_stats, 0);
+  const int pair_per_cu = std::min(ncv_lds_per_cu(p1.lds), kernel_occupancy(kpair, 256, p1.lds));
+  const int pair_blocks = (int)std::min<int64_t>(g.N, (int64_t)num_cus() * pair_per_cu);
+  const int per_cu = std::min(pair_per_cu, std::min(ncv_lds_per_cu(lds), kernel_occupancy(kfn, 256, lds)));
+  const int blocks = (int)std::min<int64_t>(g.N, (int64_t)num_cus() * per_cu);
+  const bool pair_per_wg = g.N % pair_blocks == 0;
+  if (with_stats && blocks != pair_blocks && pair_per_wg && g.N > pair_blocks) return false;
+  int stats_per_wg = (blocks == pair_blocks && pair_per_wg) ? 1 : 0;
+  const int parts = stats_per_wg ? blocks : (int)g.N;
+  Hold wpk0_h(ncv_packed_weights(w0, ncv_weights_of(w0, g0, false, p0, nullptr, 0), st));
+  Hold wpk1_h(ncv_packed_weights(w, ncv_weights_of(w, g, false, p1, w1, cout2), st, w1));
+  const nv_bf8* wpk0 = reinterpret_cast<const nv_bf8*>(static_cast<const Tensor*>(wpk0_h.get())->ptr<bf16_t>());
+  const nv_bf8* wpk1 = reinterpret_cast<const nv_bf8*>(static_cast<const Tensor*>(wpk1_h.get())->ptr<bf16_t>());
+  Hold statt, statt2;
+  float* statp = nullptr;
+  float* stat2p = nullptr;
+  if (with_stats) {
+    int64_t ps[1] = {(int64_t)parts * g.Cout * 3}, ps2[1] = {(int64_t)parts * cout2 * 3};
+    statt = Hold(new_tensor(ps, 1, kF32, x->device()));
+    statt2 = Hold(new_tensor(ps2, 1, kF32, x->device()));
+    statp = statt->ptr<float>(); stat2p = statt2->ptr<float>();
+  }
+  {
+    // both convolutions' work and traffic, less the read of s that the LDS image replaces
+    const double fl = conv_flops(g0) + conv_flops(g) + 2.0 * (double)g.N * cout2 * (double)g.Ho * g.Wo * (double)g.Cin;
+    const double by = conv_bytes(g0, 2) + conv_bytes(g, 2) + ((double)g.N * cout2 * g.Ho * g.Wo + (double)cout2 * g.Cin) * 2.0 -
+                      (double)g.N * g.Cin * g.H * g.W * 2.0;
+    KernelTimer kt("conv_fwd_narrow", fl, by, st);
+    const bf16_t* xp = x->ptr<bf16_t>();
+    const bf16_t* b0p = bias0 ? bias0->ptr<bf16_t>() : (const bf16_t*)nullptr;
+    const bf16_t* bp = bias ? bias->ptr<bf16_t>() : (const bf16_t*)nullptr;
+    const bf16_t* b1p = bias1 ? bias1->ptr<bf16_t>() : (const bf16_t*)nullptr;
+    bf16_t* sp = s->ptr<bf16_t>();
+    bf16_t* yp = y->ptr<bf16_t>();
+    bf16_t* y1p = y1->ptr<bf16_t>();
+    int co_a = (int)g.Cout;
+    void* args[] = {(void*)&xp, (void*)&wpk0, (void*)&b0p, (void*)&sp, (void*)&q0, (void*)&wpk1, (void*)&bp, (void*)&b1p, (void*)&yp, (void*)&y1p,
+                    (void*)&co_a, (void*)&q1, (void*)&statp, (void*)&stat2p, (void*)&stats_per_wg};
+    HIP_CHECK(hipLaunchKernel(kfn, dim3(blocks), dim3(256), args, lds, st));
+    LAMP_LAUNCH_CHECK();
+  }
+  if (statt.get()) conv_stats_publish(y, statt.get(), parts, 0);
+  if (statt2.get()) conv_stats_publish(y1, statt2.get(), parts);
+  return true;
 }
 bool narrow_conv_dgrad(const Tensor* dy, const Tensor* w, Tensor* dx, const ConvGeom& g, hipStream_t st, const Tensor* addend, bool* addend_fused) {
   return ncv_run(dy, w, nullptr, dx, g, true, st, addend, addend_fused);
