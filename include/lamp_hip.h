@@ -442,6 +442,40 @@ int lamp_gcn_aggregate(lamp_tensor** out, const lamp_tensor* x, const lamp_tenso
 /* a row of more neighbours than this is split across the waves of its workgroup (partial sums added in wave order) */
 int lamp_gcn_long_row(int64_t* out);
 
+/* GraphAttention.multiheadGraphAttention (GraphAttention.scala:172-197), everything from `activations` to `h`: the softmax of the
+ * scores over the edges that share a destination, and the sum of the source nodes' values under those weights.  The reference writes
+ * it as exp / indexAdd / log / indexSelect / exp / indexSelect / Mult / indexAdd against one global maximum; here the edges are grouped
+ * by endpoint once per graph and three gather-only kernels without atomics do the rest, against each destination's own maximum.
+ * Self loops are edges like any other (the reference needs them present in the edge list). */
+/* index: int64 [E].  rowptr int64 [N + 1], perm int64 [E]: the edge ids stably sorted by index[e], so group n is
+ * perm[rowptr[n] .. rowptr[n + 1]) and the order inside it depends on the edge list alone.  Built as lamp_gcn_adjacency builds its CSR:
+ * the range of `index` is reduced first (an entry outside [0, numNodes) is an error, nothing dereferences it), then a stable argsort, a
+ * bincount and a prefix sum.  E = 0 is valid (rowptr all zero).  Two host synchronisations: once per graph, not inside a captured step. */
+int lamp_graph_edge_csr(lamp_tensor** rowptr, lamp_tensor** perm, const lamp_tensor* index, int64_t numNodes);
+/* score [E, H] (the raw activations), value [N, H, V], edgeI int64 [E] (the source of every edge), (inRowptr, inPerm) =
+ * lamp_graph_edge_csr(edgeJ, N).  Per destination j and head h, over j's incoming edges e in inPerm's order: m = max score[e, h],
+ * s = sum exp(score[e, h] - m), lse[j, h] = m + log s, out[j, h, :] = (sum exp(score[e, h] - m) * value[edgeI[e], h, :]) / s, in the
+ * online form (one pass, one exp per edge and head; sums in score's type).  out is [N, H * V], lse [N, H].  A destination without an
+ * incoming edge gets a zero row and lse = -inf.  Scores must be finite.  16-byte packets where H * V and the addresses allow them, 8-byte
+ * or scalar accesses otherwise; a packet may straddle a head boundary.  Inputs that are not contiguous are made contiguous.  The
+ * grouping must be what lamp_graph_edge_csr returned for edgeJ and a graph of N nodes: its contents are not checked again. */
+int lamp_gat_forward(lamp_tensor** out, lamp_tensor** lse, const lamp_tensor* score, const lamp_tensor* value, const lamp_tensor* edgeI,
+                     const lamp_tensor* inRowptr, const lamp_tensor* inPerm);
+/* the gradients of lamp_gat_forward given dout [N, H * V] and the out and lse it returned.  With a[e, h] the weight of edge e in the
+ * forward pass, exp(score[e, h] - m) / s, and delta[j, h] = <dout[j, h, :], out[j, h, :]> for j = edgeJ[e]:
+ *   dscore[e, h]    = a[e, h] * (<dout[j, h, :], value[edgeI[e], h, :]> - delta[j, h])        (one kernel over the incoming grouping)
+ *   dvalue[i, h, :] = sum over e with edgeI[e] = i, in outPerm's order, of a[e, h] * dout[edgeJ[e], h, :]   (one over the outgoing one)
+ * a is exp(score - lse) in exact arithmetic, but lse = m + log s rounded to the type has lost log2 |m| bits of it (scores near 64 would
+ * cost the weights six bits), so the first kernel takes m and s from the destination's scores again, a pass over [E, H]; lse is
+ * checked for its shape and not read.  (outRowptr, outPerm) = lamp_graph_edge_csr(edgeI, N).  dscore is [E, H], dvalue [N, H, V];
+ * every element is written once.  edgeI and edgeJ must be the vectors the groupings were built from (that is where their range was
+ * checked). */
+int lamp_gat_backward(lamp_tensor** dscore, lamp_tensor** dvalue, const lamp_tensor* dout, const lamp_tensor* out, const lamp_tensor* lse,
+                      const lamp_tensor* score, const lamp_tensor* value, const lamp_tensor* edgeI, const lamp_tensor* edgeJ,
+                      const lamp_tensor* inRowptr, const lamp_tensor* inPerm, const lamp_tensor* outRowptr, const lamp_tensor* outPerm);
+/* a destination (source) of more edges than this is split across the waves of its workgroup (partial results merged in wave order) */
+int lamp_gat_long_row(int64_t* out);
+
 /* ------------------------------------------------------------------------------------------
  * convolution / pooling   (ATen.convolution, convolution_backward(output_mask[3]),
  * avg_pool2d(+_backward), max_pool2d_with_indices(+_backward): ops.scala:1547-1651,

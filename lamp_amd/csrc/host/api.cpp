@@ -111,6 +111,7 @@ int lamp_op_apply(lamp_var** out, const char* name, lamp_var* const* vars, int n
   else if (n == "IndexAdd") r = F::index_add(V(0), V(1), I(0), I(1));
   else if (n == "IndexAddToTarget") r = F::index_add_to_target(V(0), V(1), V(2), I(0)); // (target, src, index)
   else if (n == "GcnAggregation") r = F::gcn_aggregation(V(0), T(0), T(1), T(2));            // tensors = [rowptr, col, dinv]
+  else if (n == "GraphAttentionAggregate") r = F::graph_attention_aggregate(V(0), V(1), T(0), T(1), T(2), T(3), T(4), T(5), I(0));   // (score, value), tensors = [edgeI, edgeJ, inRowptr, inPerm, outRowptr, outPerm], i = [numHeads]
   else if (n == "RepeatInterleave") r = F::repeat_interleave(V(0), V(1), I(0));
   else if (n == "ExpandAs") r = F::expand_as(V(0), T(0));
   else if (n == "Expand") r = F::expand(V(0), IV(0, ni));
@@ -381,7 +382,17 @@ int lamp_optimizer_sgdw(lamp_optimizer** out, lamp_tensor* const* params, int n,
 int lamp_optimizer_step(lamp_optimizer* o, lamp_tensor* const* gradients, int n, double schedule_factor) {
   LAMP_API_BEGIN
   std::vector<Ten> gs;
-  for (int i = 0; i < n; i++) gs.push_back(gradients[i] ? borrow(gradients[i]) : Ten());
+  // the update kernels read dense tensors; a gradient may arrive as a strided view (Transpose's closure hands its input a transposed view
+  // of the incoming derivative, so a parameter that is viewed and transposed before its first use gets one): such a gradient is copied
+  for (int i = 0; i < n; i++) {
+    Ten g = gradients[i] ? borrow(gradients[i]) : Ten();
+    if (g.defined() && !g.h()->is_contiguous()) {
+      lamp_tensor* c = nullptr;
+      HCALL(lamp_contiguous(&c, g.h()));
+      g = Ten(c);
+    }
+    gs.push_back(g);
+  }
   o->o->step(gs, schedule_factor);
   LAMP_API_END
 }

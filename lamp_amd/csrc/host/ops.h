@@ -121,6 +121,10 @@ Var one_hot(const Var& a, int64_t numClasses);            // not differentiable
 Var eq_where(const Var& a, int64_t b);
 // GCN.gcnAggregation (nn/graph/GCN.scala:137-145) over the CSR of lamp_gcn_adjacency: one kernel forward, the same kernel backward
 Var gcn_aggregation(const Var& nodeFeatures, const Ten& rowptr, const Ten& col, const Ten& dinv);
+// GraphAttention.multiheadGraphAttention from `activations` to `h` (nn/graph/GraphAttention.scala:172-197): score [E, H], value [N, H, V] ->
+// [N, H * V] over the two groupings of lamp_graph_edge_csr; one lamp_gat_forward, one lamp_gat_backward for both gradients
+Var graph_attention_aggregate(const Var& score, const Var& value, const Ten& edgeI, const Ten& edgeJ, const Ten& inRowptr, const Ten& inPerm,
+                              const Ten& outRowptr, const Ten& outPerm, int64_t numHeads);
 
 }  // namespace F
 }  // namespace host

@@ -221,6 +221,42 @@ Var gcn_aggregation(const Var& nodeFeatures, const Ten& rowptr, const Ten& col, 
   return make_result(op, aggregate(nodeFeatures->value));
 }
 
+// GraphAttentionAggregate: the softmax of score [E, H] over the edges of a destination and the sum of the sources' value rows [N, H, V]
+// under it, in one lamp_gat_forward.  The node records out and lse; one lamp_gat_backward gives both gradients, whichever closure runs
+// first makes the call and leaves the other gradient for its sibling.
+Var graph_attention_aggregate(const Var& score, const Var& value, const Ten& edgeI, const Ten& edgeJ, const Ten& inRowptr, const Ten& inPerm,
+                              const Ten& outRowptr, const Ten& outPerm, int64_t numHeads) {
+  auto op = new_op("GraphAttentionAggregate");
+  const Ten sv = score->value, vv = value->value;
+  LAMP_CHECK(sv.ndim() == 2 && sv.size(1) == numHeads, "GraphAttentionAggregate: score must be [E, " << numHeads << "], got a tensor of " << sv.ndim()
+                                                            << " dimensions" << (sv.ndim() ? " whose last is " + std::to_string(sv.size(-1)) : std::string()));
+  lamp_tensor *o = nullptr, *l = nullptr;
+  HCALL(lamp_gat_forward(&o, &l, sv.h(), vv.h(), edgeI.h(), inRowptr.h(), inPerm.h()));
+  const Ten out(o), lse(l);
+  struct Cache { Ten g[2]; Ten p; };                       // dscore, dvalue of one backward call, and the p they belong to
+  auto cache = std::make_shared<Cache>();
+  const bool want[2] = {score->needsGrad(), value->needsGrad()};
+  auto back = [=](int which) {
+    return [=](const Ten& p, Variable& v) {
+      if (!(cache->p.defined() && cache->p.h() == p.h() && cache->g[which].defined())) {
+        lamp_tensor *ds = nullptr, *dv = nullptr;
+        HCALL(lamp_gat_backward(&ds, &dv, p.h(), out.h(), lse.h(), sv.h(), vv.h(), edgeI.h(), edgeJ.h(), inRowptr.h(), inPerm.h(), outRowptr.h(), outPerm.h()));
+        cache->g[0] = Ten(ds);
+        cache->g[1] = Ten(dv);
+        if (want[1 - which]) cache->p = p; else cache->g[1 - which] = Ten();
+      }
+      const Ten g = cache->g[which];
+      cache->g[which] = Ten();
+      if (!cache->g[1 - which].defined()) cache->p = Ten();
+      v.accumulate(g, true);
+    };
+  };
+  op->reset = [cache]() { cache->g[0] = cache->g[1] = cache->p = Ten(); };
+  op->params.push_back({score, back(0)});
+  op->params.push_back({value, back(1)});
+  return make_result(op, out);
+}
+
 // ---- element-wise (ops.scala:841-916, 2287-2340) -------------------------------------------------------------------------------------
 Var tan(const Var& a) {                                               // Tan: tmp = value^2 ; tmp += ones(1) ; out.addcmulSelf(p, tmp, 1)
   auto op = new_op("Tan");

@@ -139,13 +139,14 @@ __global__ __launch_bounds__(kGcnWaves * 64) void gcn_aggregate_kernel(T* __rest
   }
 }
 
-// per workgroup the smallest and the largest value of a[0, n) and b[0, n): out[2 * blockIdx.x] = min, out[2 * blockIdx.x + 1] = max
+// per workgroup the smallest and the largest value of a[0, n) and b[0, n) (b == nullptr: of a alone): out[2 * blockIdx.x] = min,
+// out[2 * blockIdx.x + 1] = max
 __global__ __launch_bounds__(256) void gcn_index_range_kernel(const int64_t* __restrict__ a, const int64_t* __restrict__ b, int64_t n,
                                                               int64_t* __restrict__ out) {
   __shared__ int64_t smn[4], smx[4];
   int64_t mn = INT64_MAX, mx = INT64_MIN;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t v = a[i], w = b[i];
+    const int64_t v = a[i], w = b ? b[i] : v;
     mn = min(mn, min(v, w));
     mx = max(mx, max(v, w));
   }
@@ -160,7 +161,8 @@ __global__ __launch_bounds__(256) void gcn_index_range_kernel(const int64_t* __r
   }
 }
 
-// rowptr = exclusive prefix sum of counts ([N + 1], rowptr[N] = total), dinv = (counts + 1)^-1/2.  counts == nullptr: all zero.
+// rowptr = exclusive prefix sum of counts ([N + 1], rowptr[N] = total), dinv = (counts + 1)^-1/2 (dinv == nullptr: the prefix sum
+// alone).  counts == nullptr: all zero.
 // One workgroup: thread t owns a contiguous share of the nodes, the shares' sums are scanned through LDS.
 template <class T>
 __global__ __launch_bounds__(1024) void gcn_rowptr_dinv_kernel(const int64_t* __restrict__ counts, int64_t* __restrict__ rowptr, T* __restrict__ dinv,
@@ -184,9 +186,422 @@ __global__ __launch_bounds__(1024) void gcn_rowptr_dinv_kernel(const int64_t* __
     const int64_t c = counts ? counts[i] : 0;
     rowptr[i] = run;
     run += c;
-    dinv[i] = (T)(1.0 / sqrt((double)(c + 1)));
+    if (dinv) dinv[i] = (T)(1.0 / sqrt((double)(c + 1)));
   }
   if (t == 1023) rowptr[N] = part[1023];
+}
+
+// ---- graph attention (lamp-core/src/main/scala/lamp/nn/graph/GraphAttention.scala:172-197) ---------------------------------------------------
+// Everything from `activations` to `h`: a softmax of score [E, H] over the edges that share a destination, and the sum of the source
+// nodes' value rows [N, H, V] under those weights.  The reference writes it as exp / indexAdd / log / indexSelect / exp / indexSelect /
+// Mult / indexAdd against one global maximum; here the edges are grouped by destination once per graph (lamp_graph_edge_csr: rowptr
+// [N + 1] and the edge ids stably sorted by endpoint) and every kernel is gather-only, without atomics, with a fixed order.
+//
+// gat_forward_kernel and gat_backward_value_kernel have gcn_aggregate_kernel's shape: a wave per row, lanes across the C = H * V columns
+// in packets of VW elements, C tiled in grid.y, edge id and source row read once per 64 edges (one per lane) and passed round with
+// v_readlane, kGatUnroll edges in flight, a row of more than kGatLongRow edges split over the workgroup's waves and merged through LDS
+// by wave 0 in wave order.  A packet of two may straddle a head boundary (V odd): ONE = false keeps a softmax state per element then,
+// ONE = true one per lane; packets of four are used only where V % 4 == 0.  The softmax is the online form with one exp per edge and
+// head: against the row's running maximum m, either the new score is larger (the sums so far are scaled by exp(m - x)) or it is not (it
+// enters as exp(x - m)).
+constexpr int kGatWaves = 16;       // waves (= rows) per workgroup
+constexpr int kGatLongRow = 256;    // a row with more edges is split across the workgroup's waves
+// edges in flight per wave (f64's exp leaves room for fewer)
+template <class T> constexpr int gat_unroll() { return sizeof(T) == 8 ? 2 : 4; }
+
+__device__ __forceinline__ float gat_exp(float x) { return expf(x); }
+__device__ __forceinline__ double gat_exp(double x) { return exp(x); }
+__device__ __forceinline__ float gat_log(float x) { return logf(x); }
+__device__ __forceinline__ double gat_log(double x) { return log(x); }
+template <class T> __device__ __forceinline__ T gat_neg_inf() { return -(T)INFINITY; }
+
+// per lane: the running maximum m and the sum s = sum exp(x - m) of each head its packet touches, and a = sum exp(x - m) * value
+template <class T, int VW, bool ONE> struct GatAcc {
+  static constexpr int NH = ONE ? 1 : VW;
+  T m[NH], s[NH];
+  Vec<T, VW> a;
+  __device__ __forceinline__ void init() {
+#pragma unroll
+    for (int h = 0; h < NH; h++) { m[h] = gat_neg_inf<T>(); s[h] = T(0); }
+    a = gcn_zero<T, VW>();
+  }
+  // one edge: its scores x (finite) for the packet's heads and its value packet v
+  __device__ __forceinline__ void step(const T (&x)[NH], const Vec<T, VW>& v) {
+    T scale[NH], p[NH];
+#pragma unroll
+    for (int h = 0; h < NH; h++) {
+      const bool up = x[h] > m[h];
+      const T t = gat_exp(up ? m[h] - x[h] : x[h] - m[h]);      // m = -inf: exp(-inf) = 0
+      scale[h] = up ? t : T(1);
+      p[h] = up ? T(1) : t;
+      m[h] = up ? x[h] : m[h];
+      s[h] = s[h] * scale[h] + p[h];
+    }
+#pragma unroll
+    for (int j = 0; j < VW; j++) a.v[j] = a.v[j] * scale[ONE ? 0 : j] + p[ONE ? 0 : j] * v.v[j];
+  }
+  // the state (mw, sw, q) of the edges that follow this one's
+  __device__ __forceinline__ void merge(const T (&mw)[NH], const T (&sw)[NH], const Vec<T, VW>& q) {
+    T cr[NH], cw[NH];
+#pragma unroll
+    for (int h = 0; h < NH; h++) {
+      cr[h] = T(1); cw[h] = T(0);
+      if (sw[h] > T(0)) {                                       // an empty share has m = -inf and takes no part
+        const T mn = m[h] > mw[h] ? m[h] : mw[h];
+        cr[h] = gat_exp(m[h] - mn);
+        cw[h] = gat_exp(mw[h] - mn);
+        m[h] = mn;
+        s[h] = s[h] * cr[h] + sw[h] * cw[h];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < VW; j++) a.v[j] = a.v[j] * cr[ONE ? 0 : j] + q.v[j] * cw[ONE ? 0 : j];
+  }
+};
+
+// st takes in the edges perm[b .. e) in that order: score[edge, hh[.]] and value row src[edge], columns c0 .. c0 + VW (vc = value + c0).
+// Lanes with `active` false hold no column: they take part in the index reads and load nothing else.  b and e are wave-uniform.
+template <class T, int VW, bool ONE>
+__device__ __forceinline__ void gat_gather(GatAcc<T, VW, ONE>& st, const T* __restrict__ score, int64_t H, const int (&hh)[ONE ? 1 : VW],
+                                           const T* __restrict__ vc, int64_t ldv, const int64_t* __restrict__ perm, const int64_t* __restrict__ src,
+                                           int64_t b, int64_t e, int lane, bool active) {
+  constexpr int NH = ONE ? 1 : VW, kGatUnroll = gat_unroll<T>();
+  for (int64_t p = b; p < e; p += 64) {
+    const int n = (int)(e - p < 64 ? e - p : 64);
+    int64_t ed = 0, sr = 0;
+    if (lane < n) { ed = perm[p + lane]; sr = src[ed]; }
+    int k = 0;
+    for (; k + kGatUnroll <= n; k += kGatUnroll) {
+      Vec<T, VW> v[kGatUnroll];
+      T x[kGatUnroll][NH];
+#pragma unroll
+      for (int u = 0; u < kGatUnroll; u++) {
+        const int64_t eu = lane_bcast(ed, k + u), su = lane_bcast(sr, k + u);
+#pragma unroll
+        for (int h = 0; h < NH; h++) x[u][h] = active ? score[eu * H + hh[h]] : T(0);
+        v[u] = active ? gcn_load<T, VW>(vc + su * ldv) : gcn_zero<T, VW>();
+      }
+#pragma unroll
+      for (int u = 0; u < kGatUnroll; u++) st.step(x[u], v[u]);
+    }
+    for (; k < n; k++) {
+      const int64_t eu = lane_bcast(ed, k), su = lane_bcast(sr, k);
+      T x[NH];
+#pragma unroll
+      for (int h = 0; h < NH; h++) x[h] = active ? score[eu * H + hh[h]] : T(0);
+      st.step(x, active ? gcn_load<T, VW>(vc + su * ldv) : gcn_zero<T, VW>());
+    }
+  }
+}
+
+// out[r, c0 ..] = a / s, and lse[r, h] = m + log s from the lane that holds head h's first column; a row without an edge: zeros and -inf
+template <class T, int VW, bool ONE>
+__device__ __forceinline__ void gat_finish(const GatAcc<T, VW, ONE>& st, T* __restrict__ out, T* __restrict__ lse, int64_t r, int64_t C, int64_t H, int V,
+                                           int c0, const int (&hh)[ONE ? 1 : VW]) {
+  Vec<T, VW> o;
+#pragma unroll
+  for (int j = 0; j < VW; j++) {
+    const T sj = st.s[ONE ? 0 : j];
+    o.v[j] = sj > T(0) ? st.a.v[j] / sj : T(0);
+    if ((!ONE || j == 0) && (c0 + j) % V == 0) lse[r * H + hh[ONE ? 0 : j]] = sj > T(0) ? st.m[ONE ? 0 : j] + gat_log(sj) : gat_neg_inf<T>();
+  }
+  *reinterpret_cast<Vec<T, VW>*>(out + r * C + c0) = o;
+}
+
+// out [N, C], lse [N, H] from score [E, H], value [N, H, V] (C = H * V, C % VW == 0; ONE: V % VW == 0) over the incoming grouping
+// (rowptr, perm).  grid: (ceil(N / kGatWaves), ceil(C / (64 * VW))), block: kGatWaves * 64.
+template <class T, int VW, bool ONE>
+__global__ __launch_bounds__(kGatWaves * 64) void gat_forward_kernel(T* __restrict__ out, T* __restrict__ lse, const T* __restrict__ score,
+                                                                      const T* __restrict__ value, const int64_t* __restrict__ edgeI,
+                                                                      const int64_t* __restrict__ rowptr, const int64_t* __restrict__ perm, int64_t N,
+                                                                      int64_t H, int V) {
+  constexpr int NH = ONE ? 1 : VW;
+  __shared__ Vec<T, VW> part[kGatWaves][64];
+  __shared__ T pm[kGatWaves][NH][64], ps[kGatWaves][NH][64];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t C = H * V;
+  const int c0 = ((int)blockIdx.y * 64 + lane) * VW;
+  const bool active = c0 < C;
+  int hh[NH];
+#pragma unroll
+  for (int h = 0; h < NH; h++) hh[h] = active ? (c0 + h) / V : 0;
+  const int64_t row0 = (int64_t)blockIdx.x * kGatWaves;
+  const T* vc = value + c0;
+  const int nrows = (int)(N - row0 < kGatWaves ? N - row0 : kGatWaves);
+
+  // k = blockIdx.z - 1.  k = -1: every wave its own row, unless it is a long one; k >= 0: row row0 + k if it is long, by all waves of the
+  // workgroup (that condition is the same in every thread of the workgroup, so the barriers are).  A grid slice per k, so that long rows
+  // that are neighbours (hubs numbered 0, 1, 2, ...) run side by side and not one after the other in their workgroup; the workgroups of the
+  // slices k >= 0 whose row is short, nearly all of them, read two row pointers and leave.
+  for (int k = (int)blockIdx.z - 1; k < (int)blockIdx.z && k < nrows; k++) {   // one turn: a grid slice per k
+    const bool own = k < 0;
+    const int64_t r = own ? (wave < nrows ? row0 + wave : -1) : row0 + k;
+    int64_t b = 0, e = 0;
+    if (r >= 0) { b = rowptr[r]; e = rowptr[r + 1]; }
+    const bool longRow = e - b > kGatLongRow;
+    if (own == longRow) continue;
+    if (!own) {
+      const int64_t chunk = (e - b + kGatWaves - 1) / kGatWaves;
+      b = b + wave * chunk < e ? b + wave * chunk : e;
+      e = b + chunk < e ? b + chunk : e;
+    }
+    GatAcc<T, VW, ONE> st;
+    st.init();
+    gat_gather<T, VW, ONE>(st, score, H, hh, vc, C, perm, edgeI, b, e, lane, active);
+    if (own) {
+      if (active && r >= 0) gat_finish<T, VW, ONE>(st, out, lse, r, C, H, V, c0, hh);
+      continue;
+    }
+    part[wave][lane] = st.a;
+#pragma unroll
+    for (int h = 0; h < NH; h++) { pm[wave][h][lane] = st.m[h]; ps[wave][h][lane] = st.s[h]; }
+    __syncthreads();
+    if (wave == 0 && active) {
+#pragma unroll 1
+      for (int w = 1; w < kGatWaves; w++) {
+        T mw[NH], sw[NH];
+#pragma unroll
+        for (int h = 0; h < NH; h++) { mw[h] = pm[w][h][lane]; sw[h] = ps[w][h][lane]; }
+        st.merge(mw, sw, part[w][lane]);
+      }
+      gat_finish<T, VW, ONE>(st, out, lse, r, C, H, V, c0, hh);
+    }
+    __syncthreads();
+  }
+}
+
+// acc += sum over the edges perm[b .. e), in that order, of a[edge, hh[.]] * x[src[edge], c0 .. c0 + VW) (xc = x + c0)
+template <class T, int VW, bool ONE>
+__device__ __forceinline__ void gat_weighted_gather(Vec<T, VW>& acc, const T* __restrict__ a, int64_t H, const int (&hh)[ONE ? 1 : VW],
+                                                    const T* __restrict__ xc, int64_t ldx, const int64_t* __restrict__ perm,
+                                                    const int64_t* __restrict__ src, int64_t b, int64_t e, int lane, bool active) {
+  constexpr int NH = ONE ? 1 : VW, kGatUnroll = gat_unroll<T>();
+  for (int64_t p = b; p < e; p += 64) {
+    const int n = (int)(e - p < 64 ? e - p : 64);
+    int64_t ed = 0, sr = 0;
+    if (lane < n) { ed = perm[p + lane]; sr = src[ed]; }
+    int k = 0;
+    for (; k + kGatUnroll <= n; k += kGatUnroll) {
+      Vec<T, VW> v[kGatUnroll];
+      T w[kGatUnroll][NH];
+#pragma unroll
+      for (int u = 0; u < kGatUnroll; u++) {
+        const int64_t eu = lane_bcast(ed, k + u), su = lane_bcast(sr, k + u);
+#pragma unroll
+        for (int h = 0; h < NH; h++) w[u][h] = active ? a[eu * H + hh[h]] : T(0);
+        v[u] = active ? gcn_load<T, VW>(xc + su * ldx) : gcn_zero<T, VW>();
+      }
+#pragma unroll
+      for (int u = 0; u < kGatUnroll; u++)
+#pragma unroll
+        for (int j = 0; j < VW; j++) acc.v[j] += w[u][ONE ? 0 : j] * v[u].v[j];
+    }
+    for (; k < n; k++) {
+      const int64_t eu = lane_bcast(ed, k), su = lane_bcast(sr, k);
+      T w[NH];
+#pragma unroll
+      for (int h = 0; h < NH; h++) w[h] = active ? a[eu * H + hh[h]] : T(0);
+      const Vec<T, VW> v = active ? gcn_load<T, VW>(xc + su * ldx) : gcn_zero<T, VW>();
+#pragma unroll
+      for (int j = 0; j < VW; j++) acc.v[j] += w[ONE ? 0 : j] * v.v[j];
+    }
+  }
+}
+
+// dvalue[i, h, :] = sum over the edges e leaving i (the outgoing grouping, in its order) of a[e, h] * dout[edgeJ[e], h, :].  Same grid,
+// same split of a long row; the partial sums are added in wave order.
+template <class T, int VW, bool ONE>
+__global__ __launch_bounds__(kGatWaves * 64) void gat_backward_value_kernel(T* __restrict__ dvalue, const T* __restrict__ a, const T* __restrict__ dout,
+                                                                             const int64_t* __restrict__ edgeJ, const int64_t* __restrict__ rowptr,
+                                                                             const int64_t* __restrict__ perm, int64_t N, int64_t H, int V) {
+  constexpr int NH = ONE ? 1 : VW;
+  __shared__ Vec<T, VW> part[kGatWaves][64];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t C = H * V;
+  const int c0 = ((int)blockIdx.y * 64 + lane) * VW;
+  const bool active = c0 < C;
+  int hh[NH];
+#pragma unroll
+  for (int h = 0; h < NH; h++) hh[h] = active ? (c0 + h) / V : 0;
+  const int64_t row0 = (int64_t)blockIdx.x * kGatWaves;
+  const T* xc = dout + c0;
+  const int nrows = (int)(N - row0 < kGatWaves ? N - row0 : kGatWaves);
+
+  for (int k = (int)blockIdx.z - 1; k < (int)blockIdx.z && k < nrows; k++) {   // one turn: a grid slice per k          // as in gat_forward_kernel
+    const bool own = k < 0;
+    const int64_t r = own ? (wave < nrows ? row0 + wave : -1) : row0 + k;
+    int64_t b = 0, e = 0;
+    if (r >= 0) { b = rowptr[r]; e = rowptr[r + 1]; }
+    const bool longRow = e - b > kGatLongRow;
+    if (own == longRow) continue;
+    if (!own) {
+      const int64_t chunk = (e - b + kGatWaves - 1) / kGatWaves;
+      b = b + wave * chunk < e ? b + wave * chunk : e;
+      e = b + chunk < e ? b + chunk : e;
+    }
+    Vec<T, VW> acc = gcn_zero<T, VW>();
+    gat_weighted_gather<T, VW, ONE>(acc, a, H, hh, xc, C, perm, edgeJ, b, e, lane, active);
+    if (own) {
+      if (active && r >= 0) *reinterpret_cast<Vec<T, VW>*>(dvalue + r * C + c0) = acc;
+      continue;
+    }
+    part[wave][lane] = acc;
+    __syncthreads();
+    if (wave == 0 && active) {
+#pragma unroll 1
+      for (int w = 1; w < kGatWaves; w++) {
+        const Vec<T, VW> q = part[w][lane];
+#pragma unroll
+        for (int j = 0; j < VW; j++) acc.v[j] += q.v[j];
+      }
+      *reinterpret_cast<Vec<T, VW>*>(dvalue + r * C + c0) = acc;
+    }
+    __syncthreads();
+  }
+}
+
+// m = max and s = sum exp(. - m) of score[perm[rb .. re), h]: lanes across the edges, two butterflies, every lane gets both.  The score
+// gradient takes the weights from these and not from lse: m + log s rounded to the type has lost log2 |m| bits of the weight
+// exp(score - m) / s, which the forward pass, working against m, never loses.
+template <class T>
+__device__ __forceinline__ void gat_row_softmax(T& m, T& s, const T* __restrict__ score, const int64_t* __restrict__ perm, int64_t rb, int64_t re, int64_t H,
+                                                int h, int lane) {
+  m = gat_neg_inf<T>();
+  for (int64_t p = rb + lane; p < re; p += 64) {
+    const T x = score[perm[p] * H + h];
+    m = x > m ? x : m;
+  }
+  m = wave_max(m);
+  s = T(0);
+  for (int64_t p = rb + lane; p < re; p += 64) s += gat_exp(score[perm[p] * H + h] - m);
+  s = wave_sum(s);
+}
+
+// The edges perm[b .. e) of destination j, whose edges are perm[rb .. re): a[e, h] = exp(score[e, h] - m) / s with the row's m and s,
+// dscore[e, h] = a * (<dout[j, h, :], value[i, h, :]> - delta), delta[j, h] = <dout[j, h, :], out[j, h, :]>, each written once by one lane.
+// Two forms, chosen per launch:
+//   lph > 0  (V = lph * VW, lph a power of two up to 64): lanes across the C columns in packets, tile after tile; a head's columns sit in
+//            lph neighbouring lanes, its dot product is a butterfly over them, its first lane writes.  gat_unroll value rows in flight.
+//   lph == 0 (any V; VW = 1): head after head, lanes across the head's V columns, the dot product a butterfly over the wave, lane 0 writes.
+// Either order of additions is fixed.
+template <class T, int VW>
+__device__ __forceinline__ void gat_score_edges(T* __restrict__ dscore, T* __restrict__ aout, const T* __restrict__ dout, const T* __restrict__ out,
+                                                const T* __restrict__ score, const T* __restrict__ value, const int64_t* __restrict__ edgeI,
+                                                const int64_t* __restrict__ perm, int64_t j, int64_t rb, int64_t re, int64_t b, int64_t e, int64_t H, int V,
+                                                int lph, int lane) {
+  constexpr int kGatUnroll = sizeof(T) * VW == 16 ? 2 : gat_unroll<T>();     // 16-byte packets: two rows in flight keep the kernel inside 64 VGPRs
+  const int64_t C = H * V;
+  if (b >= e) return;
+  if (lph > 0) {
+    for (int t0 = 0; t0 < C; t0 += 64 * VW) {
+      const int c0 = t0 + lane * VW;
+      const bool active = c0 < C;
+      const int h = active ? c0 / V : 0;
+      const bool writer = active && (lane & (lph - 1)) == 0;
+      const Vec<T, VW> g = active ? gcn_load<T, VW>(dout + j * C + c0) : gcn_zero<T, VW>();
+      const Vec<T, VW> o = active ? gcn_load<T, VW>(out + j * C + c0) : gcn_zero<T, VW>();
+      T delta = T(0);
+#pragma unroll
+      for (int q = 0; q < VW; q++) delta += g.v[q] * o.v[q];
+      for (int off = 1; off < lph; off <<= 1) delta += __shfl_xor(delta, off, 64);
+      T mj = T(0), sj = T(1);                                   // of this lane's head, from the heads of this tile
+      const int hEnd = (int)((t0 + 64 * VW < C ? t0 + 64 * VW : C) / V);
+      for (int ht = t0 / V; ht < hEnd; ht++) {
+        T mt, st;
+        gat_row_softmax<T>(mt, st, score, perm, rb, re, H, ht, lane);
+        if (ht == h) { mj = mt; sj = st; }
+      }
+      const T* vc = value + c0;
+      for (int64_t p = b; p < e; p += 64) {
+        const int n = (int)(e - p < 64 ? e - p : 64);
+        int64_t ed = 0, sr = 0;
+        if (lane < n) { ed = perm[p + lane]; sr = edgeI[ed]; }
+        for (int k = 0; k < n; k += kGatUnroll) {
+          Vec<T, VW> v[kGatUnroll];
+          T x[kGatUnroll];
+#pragma unroll
+          for (int u = 0; u < kGatUnroll; u++) {
+            const int ku = k + u < n ? k + u : n - 1;            // past the end: the last edge again, not written
+            const int64_t eu = lane_bcast(ed, ku), su = lane_bcast(sr, ku);
+            v[u] = active ? gcn_load<T, VW>(vc + su * C) : gcn_zero<T, VW>();
+            x[u] = writer ? score[eu * H + h] : T(0);
+          }
+#pragma unroll
+          for (int u = 0; u < kGatUnroll; u++) {
+            T d = T(0);
+#pragma unroll
+            for (int q = 0; q < VW; q++) d += g.v[q] * v[u].v[q];
+            for (int off = 1; off < lph; off <<= 1) d += __shfl_xor(d, off, 64);
+            if (k + u < n) {
+              const int64_t eu = lane_bcast(ed, k + u);
+              if (writer) {
+                const T a = gat_exp(x[u] - mj) / sj;
+                aout[eu * H + h] = a;
+                dscore[eu * H + h] = a * (d - delta);
+              }
+            }
+          }
+        }
+      }
+    }
+  } else {
+    for (int h = 0; h < H; h++) {
+      const T* gj = dout + j * C + (int64_t)h * V;
+      const T* oj = out + j * C + (int64_t)h * V;
+      T delta = T(0);
+      for (int v = lane; v < V; v += 64) delta += gj[v] * oj[v];
+      delta = wave_sum(delta);
+      T mj, sj;
+      gat_row_softmax<T>(mj, sj, score, perm, rb, re, H, h, lane);
+      for (int64_t p = b; p < e; p += 64) {
+        const int n = (int)(e - p < 64 ? e - p : 64);
+        int64_t ed = 0, sr = 0;
+        if (lane < n) { ed = perm[p + lane]; sr = edgeI[ed]; }
+        for (int k = 0; k < n; k++) {
+          const int64_t eu = lane_bcast(ed, k), su = lane_bcast(sr, k);
+          const T* vi = value + su * C + (int64_t)h * V;
+          T d = T(0);
+          for (int v = lane; v < V; v += 64) d += gj[v] * vi[v];
+          d = wave_sum(d);
+          if (lane == 0) {
+            const T a = gat_exp(score[eu * H + h] - mj) / sj;
+            aout[eu * H + h] = a;
+            dscore[eu * H + h] = a * (d - delta);
+          }
+        }
+      }
+    }
+  }
+}
+
+// grid: (ceil(N / kGatWaves), 1, kGatWaves + 1), block: kGatWaves * 64.  A wave per destination; the edges of a long row are shared out among the workgroup's
+// waves (nothing is summed across edges, so nothing is merged).
+template <class T, int VW>
+__global__ __launch_bounds__(kGatWaves * 64) __attribute__((amdgpu_num_sgpr(96))) void gat_backward_score_kernel(T* __restrict__ dscore, T* __restrict__ aout, const T* __restrict__ dout,
+                                                                             const T* __restrict__ out, const T* __restrict__ score,
+                                                                             const T* __restrict__ value,
+                                                                             const int64_t* __restrict__ edgeI, const int64_t* __restrict__ rowptr,
+                                                                             const int64_t* __restrict__ perm, int64_t N, int64_t H, int V, int lph) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t row0 = (int64_t)blockIdx.x * kGatWaves;
+  const int nrows = (int)(N - row0 < kGatWaves ? N - row0 : kGatWaves);
+  for (int k = (int)blockIdx.z - 1; k < (int)blockIdx.z && k < nrows; k++) {   // one turn: a grid slice per k          // k = -1: every wave its own short row; k >= 0: row row0 + k if it is long, by all waves
+    const bool own = k < 0;
+    const int64_t r = own ? (wave < nrows ? row0 + wave : -1) : row0 + k;
+    if (r < 0) continue;
+    const int64_t rb = rowptr[r], re = rowptr[r + 1];
+    if (own == (re - rb > kGatLongRow)) continue;
+    int64_t b = rb, e = re;
+    if (!own) {
+      const int64_t chunk = (re - rb + kGatWaves - 1) / kGatWaves;
+      b = rb + wave * chunk < re ? rb + wave * chunk : re;
+      e = b + chunk < re ? b + chunk : re;
+    }
+    gat_score_edges<T, VW>(dscore, aout, dout, out, score, value, edgeI, perm, r, rb, re, b, e, H, V, lph, lane);
+  }
 }
 
 template <class T, int V>
@@ -209,6 +624,110 @@ void check_i64_vector(const Tensor* t, const Tensor* first, const char* what) {
   check_device_tensor(t, what);
   check_same_device(t, first);
   LAMP_CHECK(t->dtype == kI64 && t->ndim == 1, what << " must be an int64 vector, got " << t->describe());
+}
+
+// every entry of a (and of b, where given; both int64 [n], contiguous, n > 0) lies in [0, N), or an error: one reduction kernel and one host
+// read, before anything uses an entry as an index
+void check_index_range(const char* tag, const Tensor* a, const Tensor* b, int64_t N, hipStream_t st) {
+  const int64_t n = a->numel();
+  const int nb = grid_for(n, 256, 2);
+  int64_t ms[1] = {2 * (int64_t)nb};
+  Hold mm(new_tensor(ms, 1, kI64, a->device()));
+  {
+    KernelTimer kt(tag, 0, (double)n * (b ? 16 : 8), st);
+    hipLaunchKernelGGL(gcn_index_range_kernel, dim3(nb), dim3(256), 0, st, a->ptr<int64_t>(), b ? b->ptr<int64_t>() : nullptr, n, mm->ptr<int64_t>());
+    LAMP_LAUNCH_CHECK();
+  }
+  std::vector<int64_t> h(2 * (size_t)nb);
+  HIP_CHECK(hipMemcpyAsync(h.data(), mm->ptr<int64_t>(), h.size() * 8, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  int64_t mn = INT64_MAX, mx = INT64_MIN;
+  for (int i = 0; i < nb; i++) { mn = std::min(mn, h[2 * i]); mx = std::max(mx, h[2 * i + 1]); }
+  LAMP_CHECK(mn >= 0 && mx < N, "edge endpoints must lie in [0, " << N << "), got " << mn << " .. " << mx);
+}
+
+// the widest packet (in elements, at most 16 bytes) that C and the base addresses of contiguous [., C] tensors allow
+template <class T> int gat_packet(int64_t C, std::initializer_list<const Tensor*> ts) {
+  for (int v = 16 / (int)sizeof(T); v > 1; v >>= 1) {
+    bool ok = C % v == 0;
+    for (const Tensor* t : ts) ok = ok && ((uintptr_t)t->raw() % (v * sizeof(T))) == 0;
+    if (ok) return v;
+  }
+  return 1;
+}
+struct GatGrid { dim3 grid, block; };
+GatGrid gat_grid(int64_t N, int64_t C, int vw) {
+  const int64_t tiles = (C + 64 * vw - 1) / (64 * vw), groups = (N + kGatWaves - 1) / kGatWaves;
+  LAMP_CHECK(tiles <= 65535 && groups <= INT32_MAX, "a graph of " << N << " nodes with " << C << " columns is too large");
+  return {dim3((unsigned)groups, (unsigned)tiles, kGatWaves + 1), dim3(kGatWaves * 64)};
+}
+// the packet width of gat_forward_kernel / gat_backward_value_kernel: the widest that C and the addresses allow, but four only where it
+// stays inside a head (a softmax state per element costs an exp each)
+template <class T> int gat_gather_packet(int64_t C, int V, std::initializer_list<const Tensor*> ts) {
+  int vw = gat_packet<T>(C, ts);
+  while (vw > 2 && V % vw) vw >>= 1;
+  return vw;
+}
+// F<T, VW, ONE>::launch(args...) for that width: ONE where no packet straddles a head boundary
+template <template <class, int, bool> class F, class T, class... A> void gat_dispatch(int vw, int V, A... a) {
+  if constexpr (sizeof(T) == 4) {
+    if (vw == 4) { F<T, 4, true>::launch(a...); return; }
+  }
+  if (vw == 2) { if (V % 2 == 0) F<T, 2, true>::launch(a...); else F<T, 2, false>::launch(a...); return; }
+  F<T, 1, true>::launch(a...);
+}
+template <class T, int VW, bool ONE> struct GatForward {
+  static void launch(GatGrid g, hipStream_t st, Tensor* out, Tensor* lse, const Tensor* score, const Tensor* value, const Tensor* edgeI, const Tensor* rowptr,
+                     const Tensor* perm, int64_t N, int64_t H, int V) {
+    hipLaunchKernelGGL((gat_forward_kernel<T, VW, ONE>), g.grid, g.block, 0, st, out->ptr<T>(), lse->ptr<T>(), score->ptr<T>(), value->ptr<T>(),
+                       edgeI->ptr<int64_t>(), rowptr->ptr<int64_t>(), perm->ptr<int64_t>(), N, H, V);
+  }
+};
+template <class T, int VW, bool ONE> struct GatBackwardValue {
+  static void launch(GatGrid g, hipStream_t st, Tensor* dvalue, const Tensor* a, const Tensor* dout, const Tensor* edgeJ, const Tensor* rowptr, const Tensor* perm,
+                     int64_t N, int64_t H, int V) {
+    hipLaunchKernelGGL((gat_backward_value_kernel<T, VW, ONE>), g.grid, g.block, 0, st, dvalue->ptr<T>(), a->ptr<T>(), dout->ptr<T>(), edgeJ->ptr<int64_t>(),
+                       rowptr->ptr<int64_t>(), perm->ptr<int64_t>(), N, H, V);
+  }
+};
+template <class T, int VW>
+void gat_backward_score_launch(hipStream_t st, Tensor* dscore, Tensor* a, const Tensor* dout, const Tensor* out, const Tensor* score, const Tensor* value,
+                               const Tensor* edgeI, const Tensor* rowptr, const Tensor* perm, int64_t N, int64_t H, int V, int lph) {
+  const int64_t groups = (N + kGatWaves - 1) / kGatWaves;
+  LAMP_CHECK(groups <= INT32_MAX, "a graph of " << N << " nodes is too large");
+  hipLaunchKernelGGL((gat_backward_score_kernel<T, VW>), dim3((unsigned)groups, 1, kGatWaves + 1), dim3(kGatWaves * 64), 0, st, dscore->ptr<T>(), a->ptr<T>(), dout->ptr<T>(),
+                     out->ptr<T>(), score->ptr<T>(), value->ptr<T>(), edgeI->ptr<int64_t>(), rowptr->ptr<int64_t>(), perm->ptr<int64_t>(), N, H, V, lph);
+}
+// the packet form of gat_backward_score_kernel: V = lph * vw with lph a power of two up to 64; 0 where V has no such split
+int gat_lanes_per_head(int V, int vw) {
+  if (V % vw) return 0;
+  const int lph = V / vw;
+  return lph <= 64 && (lph & (lph - 1)) == 0 ? lph : 0;
+}
+
+// score [E, H], value [N, H, V] of one floating type, the index vectors int64 [E], the grouping's rowptr [N + 1]
+struct GatShape { int64_t E, H, N, V; };
+GatShape gat_check(const Tensor* score, const Tensor* value, std::initializer_list<std::pair<const Tensor*, const char*>> edgeVectors,
+                   std::initializer_list<std::pair<const Tensor*, const char*>> rowptrs) {
+  check_device_tensor(score, "score");
+  check_device_tensor(value, "value");
+  check_same_device(value, score);
+  LAMP_CHECK(score->dtype == kF32 || score->dtype == kF64, "f32 and f64 only, got " << score->describe());
+  LAMP_CHECK(value->dtype == score->dtype, "value " << value->describe() << " is not of score's type " << score->describe());
+  LAMP_CHECK(score->ndim == 2, "score " << score->describe() << " must be [E, H]");
+  LAMP_CHECK(value->ndim == 3 && value->sizes[1] == score->sizes[1],
+             "value " << value->describe() << " must be [N, H, V] with the H = " << score->sizes[1] << " heads of score " << score->describe());
+  const GatShape g{score->sizes[0], score->sizes[1], value->sizes[0], value->sizes[2]};
+  LAMP_CHECK(g.H * g.V <= INT32_MAX / 2, "value " << value->describe() << " has too many columns");
+  for (auto& v : edgeVectors) {
+    check_i64_vector(v.first, score, v.second);
+    LAMP_CHECK(v.first->numel() == g.E, v.second << " " << v.first->describe() << " does not have score's " << g.E << " edges: edgeI and edgeJ differ in length?");
+  }
+  for (auto& v : rowptrs) {
+    check_i64_vector(v.first, score, v.second);
+    LAMP_CHECK(v.first->numel() == g.N + 1, v.second << " " << v.first->describe() << " does not belong to a graph of " << g.N << " nodes");
+  }
+  return g;
 }
 
 }  // namespace
@@ -242,20 +761,7 @@ int lamp_gcn_adjacency(lamp_tensor** rowptr, lamp_tensor** col, lamp_tensor** di
   Hold rp(new_tensor(n1, 1, kI64, dev)), dv(new_tensor(ns, 1, dtype, dev)), cl, counts;
   if (E) {
     // the range of both index vectors, before anything uses one of them as an index
-    const int nb = grid_for(E, 256, 2);
-    int64_t ms[1] = {2 * (int64_t)nb};
-    Hold mm(new_tensor(ms, 1, kI64, dev));
-    {
-      KernelTimer kt("gcn_index_range", 0, (double)E * 16, st);
-      hipLaunchKernelGGL(gcn_index_range_kernel, dim3(nb), dim3(256), 0, st, ei->ptr<int64_t>(), ej->ptr<int64_t>(), E, mm->ptr<int64_t>());
-      LAMP_LAUNCH_CHECK();
-    }
-    std::vector<int64_t> h(2 * (size_t)nb);
-    HIP_CHECK(hipMemcpyAsync(h.data(), mm->ptr<int64_t>(), h.size() * 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    int64_t mn = INT64_MAX, mx = INT64_MIN;
-    for (int i = 0; i < nb; i++) { mn = std::min(mn, h[2 * i]); mx = std::max(mx, h[2 * i + 1]); }
-    LAMP_CHECK(mn >= 0 && mx < N, "edge endpoints must lie in [0, " << N << "), got " << mn << " .. " << mx);
+    check_index_range("gcn_index_range", ei.get(), ej.get(), N, st);
     // the 2E directed entries (row, col) = (i, j) then (j, i), stably sorted by row
     lamp_tensor *ks[2] = {ei.get(), ej.get()}, *vs[2] = {ej.get(), ei.get()}, *t = nullptr;
     LAMP_CHECK(lamp_cat(&t, ks, 2, 0) == 0, lamp_last_error());
@@ -317,6 +823,129 @@ int lamp_gcn_aggregate(lamp_tensor** out, const lamp_tensor* x, const lamp_tenso
     }
   }
   *out = o.take();
+  LAMP_API_END
+}
+
+int lamp_gat_long_row(int64_t* out) {
+  LAMP_API_BEGIN
+  *out = kGatLongRow;
+  LAMP_API_END
+}
+
+int lamp_graph_edge_csr(lamp_tensor** rowptr, lamp_tensor** perm, const lamp_tensor* index, int64_t numNodes) {
+  LAMP_API_BEGIN
+  check_device_tensor(index, "index");
+  check_i64_vector(index, index, "index");
+  LAMP_CHECK(numNodes >= 0, "numNodes = " << numNodes);
+  const int dev = index->device();
+  const int64_t N = numNodes, E = index->numel();
+  LAMP_CHECK(E < ((int64_t)1 << 31), "too many edges: " << E);
+  hipStream_t st = current_stream(dev);
+  Hold ix(contiguous(index));
+  int64_t n1[1] = {N + 1}, es[1] = {E};
+  Hold rp(new_tensor(n1, 1, kI64, dev)), pm, counts;
+  if (E) {
+    check_index_range("graph_index_range", ix.get(), nullptr, N, st);
+    lamp_tensor* t = nullptr;
+    LAMP_CHECK(lamp_argsort(&t, ix.get(), 1, 0, 0) == 0, lamp_last_error());
+    pm = Hold(t);
+    LAMP_CHECK(lamp_bincount(&t, ix.get(), nullptr, N) == 0, lamp_last_error());
+    counts = Hold(t);
+    LAMP_CHECK(counts->numel() == N && pm->numel() == E && pm->dtype == kI64, "internal: counts " << counts->describe() << ", perm " << pm->describe());
+  } else {
+    pm = Hold(new_tensor(es, 1, kI64, dev));
+  }
+  {
+    KernelTimer kt("graph_edge_rowptr", 0, (double)N * 16, st);
+    hipLaunchKernelGGL((gcn_rowptr_dinv_kernel<float>), dim3(1), dim3(1024), 0, st, counts.get() ? counts->ptr<int64_t>() : nullptr, rp->ptr<int64_t>(),
+                       (float*)nullptr, N);
+    LAMP_LAUNCH_CHECK();
+  }
+  *rowptr = rp.take(); *perm = pm.take();
+  LAMP_API_END
+}
+
+int lamp_gat_forward(lamp_tensor** out, lamp_tensor** lse, const lamp_tensor* score, const lamp_tensor* value, const lamp_tensor* edgeI,
+                     const lamp_tensor* inRowptr, const lamp_tensor* inPerm) {
+  LAMP_API_BEGIN
+  const GatShape g = gat_check(score, value, {{edgeI, "edgeI"}, {inPerm, "inPerm"}}, {{inRowptr, "inRowptr"}});
+  const int64_t C = g.H * g.V;
+  Hold sc(contiguous(score)), vc(contiguous(value)), ei(contiguous(edgeI)), rp(contiguous(inRowptr)), pm(contiguous(inPerm));
+  int64_t os[2] = {g.N, C}, ls[2] = {g.N, g.H};
+  Hold o(new_tensor(os, 2, score->dtype, score->device())), l(new_tensor(ls, 2, score->dtype, score->device()));
+  if (g.N * g.H) {
+    LAMP_CHECK(g.V > 0, "value " << value->describe() << " has no columns");
+    hipStream_t st = current_stream(score->device());
+    const double sz = (double)dtype_size(score->dtype), E = (double)g.E, N = (double)g.N;
+    KernelTimer kt("gat_forward", 2.0 * E * C + 4.0 * E * g.H + N * C, (E * C + N * C + E * g.H + N * g.H) * sz + E * 16 + N * 8, st);
+    if (score->dtype == kF32) {
+      const int vw = gat_gather_packet<float>(C, (int)g.V, {o.get(), vc.get()});
+      gat_dispatch<GatForward, float>(vw, (int)g.V, gat_grid(g.N, C, vw), st, o.get(), l.get(), sc.get(), vc.get(), ei.get(), rp.get(), pm.get(), g.N, g.H, (int)g.V);
+    } else {
+      const int vw = gat_gather_packet<double>(C, (int)g.V, {o.get(), vc.get()});
+      gat_dispatch<GatForward, double>(vw, (int)g.V, gat_grid(g.N, C, vw), st, o.get(), l.get(), sc.get(), vc.get(), ei.get(), rp.get(), pm.get(), g.N, g.H, (int)g.V);
+    }
+    LAMP_LAUNCH_CHECK();
+  }
+  *out = o.take(); *lse = l.take();
+  LAMP_API_END
+}
+
+int lamp_gat_backward(lamp_tensor** dscore, lamp_tensor** dvalue, const lamp_tensor* dout, const lamp_tensor* out, const lamp_tensor* lse,
+                      const lamp_tensor* score, const lamp_tensor* value, const lamp_tensor* edgeI, const lamp_tensor* edgeJ, const lamp_tensor* inRowptr,
+                      const lamp_tensor* inPerm, const lamp_tensor* outRowptr, const lamp_tensor* outPerm) {
+  LAMP_API_BEGIN
+  const GatShape g = gat_check(score, value, {{edgeI, "edgeI"}, {edgeJ, "edgeJ"}, {inPerm, "inPerm"}, {outPerm, "outPerm"}},
+                               {{inRowptr, "inRowptr"}, {outRowptr, "outRowptr"}});
+  const int64_t C = g.H * g.V;
+  for (auto& t : {std::make_pair(dout, "dout"), std::make_pair(out, "out"), std::make_pair(lse, "lse")}) {
+    check_device_tensor(t.first, t.second);
+    check_same_device(t.first, score);
+    const int64_t cols = t.first == lse ? g.H : C;
+    LAMP_CHECK(t.first->dtype == score->dtype && t.first->ndim == 2 && t.first->sizes[0] == g.N && t.first->sizes[1] == cols,
+               t.second << " " << t.first->describe() << " must be [" << g.N << ", " << cols << "] of score's type " << score->describe());
+  }
+  Hold go(contiguous(dout)), oc(contiguous(out)), sc(contiguous(score)), vc(contiguous(value)), ei(contiguous(edgeI)),
+      ej(contiguous(edgeJ)), irp(contiguous(inRowptr)), ipm(contiguous(inPerm)), orp(contiguous(outRowptr)), opm(contiguous(outPerm));
+  int64_t ss[2] = {g.E, g.H}, vs[3] = {g.N, g.H, g.V};
+  const int dt = score->dtype, dev = score->device();
+  Hold ds(new_tensor(ss, 2, dt, dev)), a(new_tensor(ss, 2, dt, dev)), dv(new_tensor(vs, 3, dt, dev));
+  if (g.N * g.H) {
+    LAMP_CHECK(g.V > 0, "value " << value->describe() << " has no columns");
+    hipStream_t st = current_stream(dev);
+    const double sz = (double)dtype_size(dt), E = (double)g.E, N = (double)g.N;
+    const int V = (int)g.V;
+    if (g.E) {
+      KernelTimer kt("gat_backward_score", 2.0 * E * C + 2.0 * N * C + 4.0 * E * g.H, (E * C + 2.0 * N * C + 3.0 * E * g.H + N * g.H) * sz + E * 16 + N * 8, st);
+      if (dt == kF32) {
+        int vw = gat_packet<float>(C, {go.get(), oc.get(), vc.get()});
+        while (vw > 1 && !gat_lanes_per_head(V, vw)) vw >>= 1;
+        const int lph = gat_lanes_per_head(V, vw);
+        if (lph && vw == 4) gat_backward_score_launch<float, 4>(st, ds.get(), a.get(), go.get(), oc.get(), sc.get(), vc.get(), ei.get(), irp.get(), ipm.get(), g.N, g.H, V, lph);
+        else if (lph && vw == 2) gat_backward_score_launch<float, 2>(st, ds.get(), a.get(), go.get(), oc.get(), sc.get(), vc.get(), ei.get(), irp.get(), ipm.get(), g.N, g.H, V, lph);
+        else gat_backward_score_launch<float, 1>(st, ds.get(), a.get(), go.get(), oc.get(), sc.get(), vc.get(), ei.get(), irp.get(), ipm.get(), g.N, g.H, V, lph);
+      } else {
+        int vw = gat_packet<double>(C, {go.get(), oc.get(), vc.get()});
+        while (vw > 1 && !gat_lanes_per_head(V, vw)) vw >>= 1;
+        const int lph = gat_lanes_per_head(V, vw);
+        if (lph && vw == 2) gat_backward_score_launch<double, 2>(st, ds.get(), a.get(), go.get(), oc.get(), sc.get(), vc.get(), ei.get(), irp.get(), ipm.get(), g.N, g.H, V, lph);
+        else gat_backward_score_launch<double, 1>(st, ds.get(), a.get(), go.get(), oc.get(), sc.get(), vc.get(), ei.get(), irp.get(), ipm.get(), g.N, g.H, V, lph);
+      }
+      LAMP_LAUNCH_CHECK();
+    }
+    {
+      KernelTimer kt("gat_backward_value", 2.0 * E * C, (E * C + N * C + E * g.H) * sz + E * 16 + N * 8, st);
+      if (dt == kF32) {
+        const int vw = gat_gather_packet<float>(C, V, {dv.get(), go.get()});
+        gat_dispatch<GatBackwardValue, float>(vw, V, gat_grid(g.N, C, vw), st, dv.get(), a.get(), go.get(), ej.get(), orp.get(), opm.get(), g.N, g.H, V);
+      } else {
+        const int vw = gat_gather_packet<double>(C, V, {dv.get(), go.get()});
+        gat_dispatch<GatBackwardValue, double>(vw, V, gat_grid(g.N, C, vw), st, dv.get(), a.get(), go.get(), ej.get(), orp.get(), opm.get(), g.N, g.H, V);
+      }
+      LAMP_LAUNCH_CHECK();
+    }
+  }
+  *dscore = ds.take(); *dvalue = dv.take();
   LAMP_API_END
 }
 

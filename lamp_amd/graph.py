@@ -1,18 +1,25 @@
-"""lamp.nn.graph's GCN path over the C ABI: Graph, GCN, gcn, gcnAggregation, VertexPooling (and nn.ResidualModule, which gcn needs).
+"""lamp.nn.graph's GCN and GraphAttention paths over the C ABI: Graph, GCN, gcn, gcnAggregation, VertexPooling (and nn.ResidualModule,
+which gcn needs), GraphAttention, multiheadGraphAttention.
 
-Reference: lamp-core/src/main/scala/lamp/nn/graph/{Graph,GCN,VertexPooling}.scala.  GCN.computeSparseAdjacency builds a sparse COO
+Reference: lamp-core/src/main/scala/lamp/nn/graph/{Graph,GCN,VertexPooling,GraphAttention}.scala.  GCN.computeSparseAdjacency builds a sparse COO
 tensor and gcnAggregation multiplies it with `mm`; here the adjacency is a CSR (`lamp_gcn_adjacency`) and the product one gather-only
 kernel (`lamp_gcn_aggregate`, the autograd node `GcnAggregation`), forward and backward.  The same mathematics out of IndexSelect,
 IndexAdd and the broadcasting operators (`gcnAggregationComposed`) is the fallback for other types than f32 / f64 and the yardstick
 of scripts/gcn_probe.py; `gcnFused` switches between the two.
+
+GraphAttention.multiheadGraphAttention scores every edge and then takes, per destination, the softmax of the scores and the sum of the
+sources' values under it.  The scoring is a composition of existing nodes; everything after it is one node, `GraphAttentionAggregate`
+(`lamp_gat_forward` / `lamp_gat_backward` over the two groupings of `Graph.edgeCsr()`), or the reference's own chain of exp, indexAdd,
+log, indexSelect and Mult (`graphAttentionAggregateComposed`); `graphAttentionFused` switches between the two.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import List, Optional, Sequence
 
 from ._capi import lib
-from .autograd import Variable, apply_op, const
+from .autograd import Variable, apply_op, const, param
 from . import nn
 from .sten import STen, F32, F64
 
@@ -82,9 +89,39 @@ def gcnAggregation(nodeFeatures: Variable, edgeI, edgeJ: Optional[STen] = None) 
     return apply_op("GcnAggregation", [nodeFeatures], tensors=adj.tensors)
 
 
+class EdgeCsr:
+    """the edge ids grouped by destination (`incoming`: rowptr and perm of edgeJ) and by source (`outgoing`: of edgeI), each group in the
+    order of the edge list (lamp_graph_edge_csr): what lamp_gat_forward and lamp_gat_backward read"""
+
+    def __init__(self, inRowptr: STen, inPerm: STen, outRowptr: STen, outPerm: STen, edgeI: STen, edgeJ: STen, numNodes: int):
+        self.inRowptr, self.inPerm, self.outRowptr, self.outPerm = inRowptr, inPerm, outRowptr, outPerm
+        self.edgeI, self.edgeJ, self.numNodes = edgeI, edgeJ, numNodes
+
+    @property
+    def incoming(self): return [self.inRowptr, self.inPerm]
+
+    @property
+    def outgoing(self): return [self.outRowptr, self.outPerm]
+
+    @property
+    def tensors(self): return [self.edgeI, self.edgeJ, self.inRowptr, self.inPerm, self.outRowptr, self.outPerm]
+
+
+def _edge_csr(index: STen, numNodes: int):
+    r, p = C.c_void_p(), C.c_void_p()
+    lib.lamp_graph_edge_csr(C.byref(r), C.byref(p), index.h, int(numNodes))
+    return STen(r), STen(p)
+
+
+def computeEdgeCsr(edgeI: STen, edgeJ: STen, numNodes: int) -> EdgeCsr:
+    """both groupings of an edge list; an endpoint outside [0, numNodes) raises"""
+    return EdgeCsr(*_edge_csr(edgeJ, numNodes), *_edge_csr(edgeI, numNodes), edgeI, edgeJ, int(numNodes))
+
+
 class Graph:
-    """Graph(nodeFeatures, edgeFeatures, edgeI, edgeJ, vertexPoolingIndices) (Graph.scala).  The adjacency of the edge list is built on
-    first use and shared by every copy(nodeFeatures = ...), so stacked GCN layers over one graph build it once."""
+    """Graph(nodeFeatures, edgeFeatures, edgeI, edgeJ, vertexPoolingIndices) (Graph.scala).  The adjacency of the edge list and its
+    grouping by endpoint are built on first use and shared by every copy(nodeFeatures = ...), so stacked GCN or GraphAttention layers
+    over one graph build them once."""
 
     def __init__(self, nodeFeatures: Variable, edgeFeatures: Optional[Variable], edgeI: STen, edgeJ: STen, vertexPoolingIndices: Optional[STen] = None,
                  _adjacencies: Optional[dict] = None):
@@ -100,6 +137,12 @@ class Graph:
         key = (x.shape[0], x.dtype if dtype is None else dtype)
         if key not in self._adjacencies:
             self._adjacencies[key] = computeAdjacency(self.edgeI, self.edgeJ, key[0], key[1])
+        return self._adjacencies[key]
+
+    def edgeCsr(self) -> EdgeCsr:
+        key = ("edgeCsr", self.nodeFeatures.value.shape[0])
+        if key not in self._adjacencies:
+            self._adjacencies[key] = computeEdgeCsr(self.edgeI, self.edgeJ, key[1])
         return self._adjacencies[key]
 
 
@@ -164,3 +207,139 @@ def VertexPooling(x: Graph, pooling: str) -> Variable:
     v = x.nodeFeatures.value
     ones = const(STen.ones([v.shape[0], 1], v.dtype, v.device))
     return total / ones.indexAdd(const(idx), 0, maxi)
+
+
+# ---- graph attention (GraphAttention.scala) ----------------------------------------------------------------------------------------------------
+_gat_fused = True
+
+
+def graphAttentionFused(on: bool) -> bool:
+    """process-wide: everything after the scores as one GraphAttentionAggregate node over the edge CSR (True, the default) or as the
+    reference's chain of Exp / IndexAdd / Log / IndexSelect / Mult nodes; returns the previous setting."""
+    global _gat_fused
+    prev, _gat_fused = _gat_fused, bool(on)
+    return prev
+
+
+def gatLongRow() -> int:
+    """destinations (sources) of more edges than this are split across the waves of a workgroup (lamp_gat_long_row)"""
+    n = C.c_int64(); lib.lamp_gat_long_row(C.byref(n)); return n.value
+
+
+def graphAttentionAggregateComposed(activations: Variable, nodeValue: Variable, edgeI: STen, edgeJ: STen, numHeads: int) -> Variable:
+    """GraphAttention.scala:172-197 as written: activations [E, H] or [E, H, 1], nodeValue [N, H, V] -> [N, H * V].  The exponentials
+    are taken against one global maximum, and the sums per destination are IndexAdds."""
+    n = nodeValue.shape[0]
+    c = const(activations.value.maxAll())
+    e = (activations - c).exp()
+    lse = e.indexAdd(const(edgeJ), 0, n).log() + c
+    lseBroadCast = lse.indexSelect(0, const(edgeJ))
+    logsoftmax = activations - lseBroadCast
+    a = logsoftmax.exp().view([-1, numHeads, 1])
+    nodeValueScatter = nodeValue.indexSelect(0, const(edgeI))
+    shape = nodeValueScatter.shape
+    return (a * nodeValueScatter).reshape([-1, shape[1] * shape[2]]).indexAdd(const(edgeJ), 0, n)
+
+
+def graphAttentionAggregate(activations: Variable, nodeValue: Variable, edgeI: STen, edgeJ: STen, numHeads: int, csr: Optional[EdgeCsr] = None) -> Variable:
+    """the softmax of activations [E, H] (or [E, H, 1]) over the edges that share a destination and the sum of the sources' rows of
+    nodeValue [N, H, V] under it: [N, H * V].  f32 / f64 with graphAttentionFused(True): one GraphAttentionAggregate node over `csr`
+    (built here if not given); otherwise the composed chain."""
+    dt = nodeValue.value.dtype
+    if not _gat_fused or dt not in (F32, F64):
+        return graphAttentionAggregateComposed(activations, nodeValue, edgeI, edgeJ, numHeads)
+    if csr is None:
+        csr = computeEdgeCsr(edgeI, edgeJ, nodeValue.shape[0])
+    score = activations if len(activations.shape) == 2 else activations.view([-1, numHeads])
+    return apply_op("GraphAttentionAggregate", [score, nodeValue], tensors=[edgeI, edgeJ] + csr.incoming + csr.outgoing, i=[numHeads])
+
+
+def _attention_scores(nodeFeatures, edgeFeatures, edgeI, edgeJ, wNodeKey1, wNodeKey2, wEdgeKey, wNodeValue, wAttention, numHeads):
+    """GraphAttention.scala:132-171: (activations, nodeValue) out of existing nodes"""
+    assert wNodeValue.shape[1] % numHeads == 0, f"wNodeValue and numHeads size do not align {wNodeValue.shape[1]} {numHeads}"
+
+    def mm(a, b):
+        return a.mm(b).view([a.shape[0], numHeads, b.shape[1] // numHeads])
+
+    nodeKey1, nodeKey2, edgeKey, nodeValue = mm(nodeFeatures, wNodeKey1), mm(nodeFeatures, wNodeKey2), mm(edgeFeatures, wEdgeKey), mm(nodeFeatures, wNodeValue)
+    ni, nj = nodeKey1.indexSelect(0, const(edgeI)), nodeKey2.indexSelect(0, const(edgeJ))
+    if wAttention is not None:
+        ninjeij = apply_op("Concatenate", [ni, nj, edgeKey], i=[2])
+        k = ninjeij.shape[2]
+        activations = ninjeij.transpose(0, 1).bmm(wAttention.view([k, numHeads, 1]).transpose(0, 1)).tanh().transpose(0, 1).view([-1, numHeads])
+    else:
+        prod = (ni * nj) * (1.0 / math.sqrt(float(ni.shape[1])))        # the reference scales by shape(1), the number of heads: kept
+        activations = prod.sum([2], True) + edgeKey.reshape([-1, numHeads, 1])
+    return activations, nodeValue
+
+
+def multiheadGraphAttention(nodeFeatures: Variable, edgeFeatures: Variable, edgeI: STen, edgeJ: STen, wNodeKey1: Variable, wNodeKey2: Variable,
+                            wEdgeKey: Variable, wNodeValue: Variable, wAttention: Optional[Variable], numHeads: int, csr: Optional[EdgeCsr] = None) -> Variable:
+    """GraphAttention.multiheadGraphAttention (GraphAttention.scala:119-198): the next node representation [N, H * V], without
+    non-linearity or dropout.  Self edges must be present in the edge list.  With wAttention the score of an edge is tanh of the
+    concatenated keys times wAttention per head, without it the scaled dot product of the node keys plus the edge key."""
+    activations, nodeValue = _attention_scores(nodeFeatures, edgeFeatures, edgeI, edgeJ, wNodeKey1, wNodeKey2, wEdgeKey, wNodeValue, wAttention, numHeads)
+    return graphAttentionAggregate(activations, nodeValue, edgeI, edgeJ, numHeads, csr)
+
+
+def multiheadGraphAttentionComposed(nodeFeatures: Variable, edgeFeatures: Variable, edgeI: STen, edgeJ: STen, wNodeKey1: Variable, wNodeKey2: Variable,
+                                    wEdgeKey: Variable, wNodeValue: Variable, wAttention: Optional[Variable], numHeads: int) -> Variable:
+    """the same with the reference's own chain after the scores, whatever graphAttentionFused says"""
+    activations, nodeValue = _attention_scores(nodeFeatures, edgeFeatures, edgeI, edgeJ, wNodeKey1, wNodeKey2, wEdgeKey, wNodeValue, wAttention, numHeads)
+    return graphAttentionAggregateComposed(activations, nodeValue, edgeI, edgeJ, numHeads)
+
+
+def _init_linear(in_: int, out: int, dtype, device) -> Variable:
+    """nn.initLinear (nn/package.scala:102-109)"""
+    return param(STen.normal(0.0, math.sqrt(2.0 / (out + in_)), [in_, out], dtype, device))
+
+
+class GraphAttention:
+    """GraphAttention (GraphAttention.scala:8-54): forward(graph) = graph.copy(nodeFeatures = [graph.nodeFeatures +] f(attention)) with
+    f = dropout(swish1(.)) if nonLinearity; the residual applies only where the shapes agree.  State: wNodeKey1, wNodeKey2, wEdgeKey,
+    wNodeValue[, wAttention].  The positional constructor takes the weights; GraphAttention.apply(...) initialises them."""
+
+    def __init__(self, wNodeKey1: Variable, wNodeKey2: Variable, wEdgeKey: Variable, wNodeValue: Variable, wAttention: Optional[Variable],
+                 nonLinearity: bool, dropout: float, numHeads: int, training: bool = True):
+        self.wNodeKey1, self.wNodeKey2, self.wEdgeKey, self.wNodeValue, self.wAttention = wNodeKey1, wNodeKey2, wEdgeKey, wNodeValue, wAttention
+        self.nonLinearity, self.dropout, self.numHeads, self.training = bool(nonLinearity), float(dropout), int(numHeads), bool(training)
+
+    @staticmethod
+    def apply(nodeDim: int, edgeDim: int, attentionKeyHiddenDimPerHead: int, attentionNumHeads: int, valueDimPerHead: int, dropout: float = 0.0,
+              dtype=F32, device=0, dotProductAttention: bool = False, nonLinearity: bool = True) -> "GraphAttention":
+        """GraphAttention.apply (GraphAttention.scala:58-106)"""
+        keys = attentionKeyHiddenDimPerHead * attentionNumHeads
+        return GraphAttention(
+            _init_linear(nodeDim, keys, dtype, device), _init_linear(nodeDim, keys, dtype, device),
+            _init_linear(edgeDim, attentionNumHeads if dotProductAttention else keys, dtype, device),
+            _init_linear(nodeDim, valueDimPerHead * attentionNumHeads, dtype, device),
+            None if dotProductAttention else _init_linear(attentionKeyHiddenDimPerHead * 3, attentionNumHeads, dtype, device),
+            nonLinearity, dropout, attentionNumHeads)
+
+    def forward(self, x: Graph) -> Graph:
+        dt = x.nodeFeatures.value.dtype
+        csr = x.edgeCsr() if _gat_fused and dt in (F32, F64) else None
+        activation = multiheadGraphAttention(x.nodeFeatures, x.edgeFeatures, x.edgeI, x.edgeJ, self.wNodeKey1, self.wNodeKey2, self.wEdgeKey,
+                                             self.wNodeValue, self.wAttention, self.numHeads, csr)
+        nxt = (activation * activation.sigmoid()).dropout(self.dropout, self.training) if self.nonLinearity else activation      # swish1, Dropout
+        return x.copy(nodeFeatures=x.nodeFeatures + nxt if nxt.shape == x.nodeFeatures.shape else nxt)
+
+    @property
+    def state(self) -> List[Variable]:
+        return [self.wNodeKey1, self.wNodeKey2, self.wEdgeKey, self.wNodeValue] + ([self.wAttention] if self.wAttention is not None else [])
+
+    @property
+    def parameters(self) -> List[Variable]: return [v for v in self.state if v.needsGrad]
+
+    def zeroGrad(self):
+        for v in self.state:
+            v.zeroGrad()
+
+    def asEval(self): self.training = False; return self
+    def asTraining(self): self.training = True; return self
+
+    def load(self, tensors: Sequence[STen]):
+        st = self.state
+        assert len(st) == len(tensors), f"state has {len(st)} tensors, got {len(tensors)}"
+        for v, t in zip(st, tensors):
+            v.value.copyFrom(t)
