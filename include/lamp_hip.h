@@ -476,6 +476,50 @@ int lamp_gat_backward(lamp_tensor** dscore, lamp_tensor** dvalue, const lamp_ten
 /* a destination (source) of more edges than this is split across the waves of its workgroup (partial results merged in wave order) */
 int lamp_gat_long_row(int64_t* out);
 
+/* MPNN (nn/graph/MPNN.scala): the two data movements of a message-passing layer, each as gather-only kernels without atomics over the
+ * groupings of lamp_graph_edge_csr; every element of every output is written exactly once, no call synchronises with the host.
+ * The reference composes the message out of two IndexSelects and a Concatenate, and MPNN.aggregate out of up to two broadcast Mults, two
+ * IndexAdds and an Add.  In all of them edgeI and edgeJ (int64 [E]) must be the vectors the groupings were built from for a graph of N
+ * nodes: that is where their range was checked, nothing here checks it again. */
+/* rowptr int64 [N + 1] of lamp_graph_edge_csr(index, N) -> out [N] of `dtype` (f32 / f64): what
+ * countOccurences(index, N).pow(p).castToType(dtype) gives (MPNN.scala:75-81, 96-113).  The count is a long tensor there, so its pow is
+ * an f32 tensor whatever dtype is: the factor is computed in f32 (p = -0.5: 1 / sqrt(count), two roundings; p = -1: 1 / count; only
+ * these two exponents occur) and then cast, so an f64 factor is an f32 value widened.  A node without an occurrence gets +inf. */
+int lamp_mpnn_degree_factor(lamp_tensor** out, const lamp_tensor* rowptr, double p, int dtype);
+/* x [N, D], edgeFeatures [E, Fe] of one type (f32 / f64) -> out [E, Fe + 2 D], out[e, :] = [ edgeFeatures[e, :] | x[edgeI[e], :] |
+ * x[edgeJ[e], :] ] in one launch (MPNN.scala:21-25).  A thread per packet over a flat index of edges x packets (at most 2^31 packets,
+ * more is an error).  The packet width is chosen per
+ * segment: the edge segment takes the widest packet (16, 8 bytes or one element) that Fe, the row pitches Fe + 2 D and edgeFeatures'
+ * own, and the addresses allow, the two node segments the widest that D, their column offsets Fe and Fe + D, both pitches and the
+ * addresses allow; an odd row pitch (Fe odd) leaves every segment scalar.  Rows of unit column stride are read in place whatever their
+ * pitch; anything else is copied dense first. */
+int lamp_mpnn_message_forward(lamp_tensor** out, const lamp_tensor* x, const lamp_tensor* edgeFeatures, const lamp_tensor* edgeI,
+                              const lamp_tensor* edgeJ);
+/* the gradients of lamp_mpnn_message_forward given dmsg [E, edgeDim + 2 D]; either output may be NULL, and then its launch is skipped.
+ *   dx[n, :]    = sum over e in outgoing(n), in outPerm's order, of dmsg[e, edgeDim : edgeDim + D]
+ *               + sum over e in incoming(n), in inPerm's order,  of dmsg[e, edgeDim + D : edgeDim + 2 D]     (the two sums added last)
+ *   dedge[e, :] = dmsg[e, 0 : edgeDim]
+ * dx is [numNodes, D], the true gradient of x as the source of both gathers.  A wave per node, columns tiled in the grid; a node of more
+ * than lamp_mpnn_long_row edges (both groupings together) is split over the waves of its workgroup, partial sums added in wave order. */
+int lamp_mpnn_message_backward(lamp_tensor** dx_or_null, lamp_tensor** dedge_or_null, const lamp_tensor* dmsg, int64_t numNodes, int64_t edgeDim,
+                               const lamp_tensor* inRowptr, const lamp_tensor* inPerm, const lamp_tensor* outRowptr, const lamp_tensor* outPerm);
+/* MPNN.aggregate (MPNN.scala:84-126): message [E, M] -> out [N, M] with N = inRowptr's length - 1,
+ *   out[n, :] = sum over e in incoming(n) of t(e)  [ + sum over e in outgoing(n) of t(e)  if aggregateJ ],
+ *   t(e) = (message[e, :] * fI[edgeI[e]]) * fJ[edgeJ[e]], multiplied in that order and not contracted into the sum, so every term has the
+ * bits of the reference's chain and only the order of the additions differs; the two partial sums are added last.  fI, fJ: [N] of
+ * message's type (lamp_mpnn_degree_factor), NULL = that factor is absent (nothing is multiplied by 1).  outRowptr / outPerm may be NULL
+ * unless aggregateJ.  The kernel and the long-row split (by the edges of both groups together) of the message gradient. */
+int lamp_mpnn_aggregate_forward(lamp_tensor** out, const lamp_tensor* message, const lamp_tensor* edgeI, const lamp_tensor* edgeJ,
+                                const lamp_tensor* inRowptr, const lamp_tensor* inPerm, const lamp_tensor* outRowptr_or_null,
+                                const lamp_tensor* outPerm_or_null, const lamp_tensor* fI_or_null, const lamp_tensor* fJ_or_null, int aggregateJ);
+/* dout [N, M] -> dmsg [E, M], per edge, no grouping:
+ *   dmsg[e, :] = ((dout[edgeJ[e], :] [+ dout[edgeI[e], :] if aggregateJ]) * fJ[edgeJ[e]]) * fI[edgeI[e]]
+ * which is what the chain's closures produce, in their order. */
+int lamp_mpnn_aggregate_backward(lamp_tensor** dmsg, const lamp_tensor* dout, const lamp_tensor* edgeI, const lamp_tensor* edgeJ,
+                                 const lamp_tensor* fI_or_null, const lamp_tensor* fJ_or_null, int aggregateJ);
+/* a node of more edges than this is split across the waves of its workgroup (partial sums added in wave order) */
+int lamp_mpnn_long_row(int64_t* out);
+
 /* ------------------------------------------------------------------------------------------
  * convolution / pooling   (ATen.convolution, convolution_backward(output_mask[3]),
  * avg_pool2d(+_backward), max_pool2d_with_indices(+_backward): ops.scala:1547-1651,

@@ -112,6 +112,11 @@ int lamp_op_apply(lamp_var** out, const char* name, lamp_var* const* vars, int n
   else if (n == "IndexAddToTarget") r = F::index_add_to_target(V(0), V(1), V(2), I(0)); // (target, src, index)
   else if (n == "GcnAggregation") r = F::gcn_aggregation(V(0), T(0), T(1), T(2));            // tensors = [rowptr, col, dinv]
   else if (n == "GraphAttentionAggregate") r = F::graph_attention_aggregate(V(0), V(1), T(0), T(1), T(2), T(3), T(4), T(5), I(0));   // (score, value), tensors = [edgeI, edgeJ, inRowptr, inPerm, outRowptr, outPerm], i = [numHeads]
+  else if (n == "MpnnMessage") r = F::mpnn_message(V(0), V(1), T(0), T(1), T(2), T(3), T(4), T(5));   // (nodeFeatures, edgeFeatures), tensors = [edgeI, edgeJ, inRowptr, inPerm, outRowptr, outPerm]
+  else if (n == "MpnnAggregate") {   // (message), tensors = [edgeI, edgeJ, inRowptr, inPerm, outRowptr, outPerm] + [fI if hasFI] + [fJ if hasFJ], i = [aggregateJ, hasFI, hasFJ]
+    const bool hasFI = I(1) != 0, hasFJ = I(2) != 0;
+    r = F::mpnn_aggregate(V(0), T(0), T(1), T(2), T(3), T(4), T(5), hasFI ? T(6) : Ten(), hasFJ ? T(hasFI ? 7 : 6) : Ten(), I(0) != 0);
+  }
   else if (n == "RepeatInterleave") r = F::repeat_interleave(V(0), V(1), I(0));
   else if (n == "ExpandAs") r = F::expand_as(V(0), T(0));
   else if (n == "Expand") r = F::expand(V(0), IV(0, ni));

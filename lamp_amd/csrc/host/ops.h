@@ -125,6 +125,13 @@ Var gcn_aggregation(const Var& nodeFeatures, const Ten& rowptr, const Ten& col, 
 // [N, H * V] over the two groupings of lamp_graph_edge_csr; one lamp_gat_forward, one lamp_gat_backward for both gradients
 Var graph_attention_aggregate(const Var& score, const Var& value, const Ten& edgeI, const Ten& edgeJ, const Ten& inRowptr, const Ten& inPerm,
                               const Ten& outRowptr, const Ten& outPerm, int64_t numHeads);
+// MPNN's message cat(edgeFeatures, nodeFeatures[edgeI], nodeFeatures[edgeJ]) (nn/graph/MPNN.scala:21-25) in one lamp_mpnn_message_forward; the
+// closure on nodeFeatures adds the true gradient (one lamp_mpnn_message_backward over both groupings), the one on edgeFeatures the first columns
+Var mpnn_message(const Var& nodeFeatures, const Var& edgeFeatures, const Ten& edgeI, const Ten& edgeJ, const Ten& inRowptr, const Ten& inPerm,
+                 const Ten& outRowptr, const Ten& outPerm);
+// MPNN.aggregate (nn/graph/MPNN.scala:84-126) over the two groupings; fI / fJ undefined: that degree normalisation is off
+Var mpnn_aggregate(const Var& message, const Ten& edgeI, const Ten& edgeJ, const Ten& inRowptr, const Ten& inPerm, const Ten& outRowptr, const Ten& outPerm,
+                   const Ten& fI, const Ten& fJ, bool aggregateJ);
 
 }  // namespace F
 }  // namespace host

@@ -257,6 +257,55 @@ Var graph_attention_aggregate(const Var& score, const Var& value, const Ten& edg
   return make_result(op, out);
 }
 
+// MpnnMessage: [ edgeFeatures | nodeFeatures[edgeI] | nodeFeatures[edgeJ] ] in one launch.  The reference's chain routes both gathers through
+// IndexSelect, whose closure doubles a gradient its input already holds (`out += out.indexAdd(...)`); nodeFeatures has other consumers in
+// MPNN.forward, so this node's closure adds the true gradient instead: the rows of p summed per node over both groupings.
+Var mpnn_message(const Var& nodeFeatures, const Var& edgeFeatures, const Ten& edgeI, const Ten& edgeJ, const Ten& inRowptr, const Ten& inPerm,
+                 const Ten& outRowptr, const Ten& outPerm) {
+  auto op = new_op("MpnnMessage");
+  const Ten xv = nodeFeatures->value, ev = edgeFeatures->value;
+  LAMP_CHECK(xv.ndim() == 2 && ev.ndim() == 2, "MpnnMessage: nodeFeatures must be [N, D] and edgeFeatures [E, Fe], got tensors of " << xv.ndim() << " and "
+                                                   << ev.ndim() << " dimensions");
+  LAMP_CHECK(xv.dtype() == ev.dtype(), "MpnnMessage: nodeFeatures and edgeFeatures differ in type");
+  const int64_t N = xv.size(0), Fe = ev.size(1);
+  LAMP_CHECK(inRowptr.numel() == N + 1 && outRowptr.numel() == N + 1, "MpnnMessage: the groupings belong to a graph of " << inRowptr.numel() - 1 << " nodes, nodeFeatures has "
+                                                                          << N << " rows");
+  lamp_tensor* o = nullptr;
+  HCALL(lamp_mpnn_message_forward(&o, xv.h(), ev.h(), edgeI.h(), edgeJ.h()));
+  op->params.push_back({nodeFeatures, [=](const Ten& p, Variable& out) {
+    lamp_tensor* dx = nullptr;
+    HCALL(lamp_mpnn_message_backward(&dx, nullptr, p.h(), N, Fe, inRowptr.h(), inPerm.h(), outRowptr.h(), outPerm.h()));
+    out.accumulate(Ten(dx), true);
+  }});
+  op->params.push_back({edgeFeatures, [=](const Ten& p, Variable& out) {
+    lamp_tensor* de = nullptr;
+    HCALL(lamp_mpnn_message_backward(nullptr, &de, p.h(), N, Fe, inRowptr.h(), inPerm.h(), outRowptr.h(), outPerm.h()));
+    out.accumulate(Ten(de), true);
+  }});
+  return make_result(op, Ten(o));
+}
+
+// MpnnAggregate: the messages, scaled by the degree factors of their endpoints, summed per destination (and per source with aggregateJ) in one
+// lamp_mpnn_aggregate_forward; the closure is one lamp_mpnn_aggregate_backward per edge.  Nothing is recorded but the inputs.
+Var mpnn_aggregate(const Var& message, const Ten& edgeI, const Ten& edgeJ, const Ten& inRowptr, const Ten& inPerm, const Ten& outRowptr, const Ten& outPerm,
+                   const Ten& fI, const Ten& fJ, bool aggregateJ) {
+  auto op = new_op("MpnnAggregate");
+  const Ten mv = message->value;
+  LAMP_CHECK(mv.ndim() == 2 && mv.size(0) == edgeI.numel(), "MpnnAggregate: message must be [" << edgeI.numel() << ", M] (a row per edge), got a tensor of " << mv.ndim()
+                                                                << " dimensions" << (mv.ndim() ? " whose first is " + std::to_string(mv.size(0)) : std::string()));
+  for (const Ten* f : {&fI, &fJ})
+    LAMP_CHECK(!f->defined() || f->dtype() == mv.dtype(), "MpnnAggregate: the degree factors are not of message's type");
+  auto h = [](const Ten& t) -> const lamp_tensor* { return t.defined() ? t.h() : nullptr; };
+  lamp_tensor* o = nullptr;
+  HCALL(lamp_mpnn_aggregate_forward(&o, mv.h(), edgeI.h(), edgeJ.h(), inRowptr.h(), inPerm.h(), outRowptr.h(), outPerm.h(), h(fI), h(fJ), aggregateJ ? 1 : 0));
+  op->params.push_back({message, [=](const Ten& p, Variable& out) {
+    lamp_tensor* dm = nullptr;
+    HCALL(lamp_mpnn_aggregate_backward(&dm, p.h(), edgeI.h(), edgeJ.h(), h(fI), h(fJ), aggregateJ ? 1 : 0));
+    out.accumulate(Ten(dm), true);
+  }});
+  return make_result(op, Ten(o));
+}
+
 // ---- element-wise (ops.scala:841-916, 2287-2340) -------------------------------------------------------------------------------------
 Var tan(const Var& a) {                                               // Tan: tmp = value^2 ; tmp += ones(1) ; out.addcmulSelf(p, tmp, 1)
   auto op = new_op("Tan");

@@ -604,6 +604,226 @@ __global__ __launch_bounds__(kGatWaves * 64) __attribute__((amdgpu_num_sgpr(96))
   }
 }
 
+// ---- message passing (lamp-core/src/main/scala/lamp/nn/graph/MPNN.scala) ---------------------------------------------------------------------
+// The two data movements of an MPNN layer.  The message cat(edgeFeatures, x[edgeI], x[edgeJ]) and MPNN.aggregate's backward are per
+// edge: a row has no sum, so these kernels run a thread per packet over a flat index of rows x packets (no idle lane at any width,
+// neighbouring lanes on neighbouring packets).  The message's gradient with respect to x and MPNN.aggregate are
+// sums per node over the groupings of lamp_graph_edge_csr: gat_backward_value_kernel's shape (a wave per node, lanes across the columns
+// in packets, columns tiled in grid.y, edge ids read once per 64 edges and passed round with v_readlane, kMpnnUnroll rows in flight, a
+// node of more than kMpnnLongRow edges split over the workgroup's waves in a grid slice of its own and merged through LDS by wave 0 in
+// wave order).  No atomics, every element written once, nothing synchronises with the host.
+constexpr int kMpnnWaves = 16;      // waves (= nodes) per workgroup of the summing kernels
+constexpr int kMpnnLongRow = 256;   // a node with more edges (both groupings together) is split across the workgroup's waves
+constexpr int kMpnnUnroll = 4;      // edge rows in flight per wave
+constexpr int kMpnnEdgeBlock = 256; // threads per workgroup of the per-edge kernels
+
+// out[n] = (T) f32(count^p), count = rowptr[n + 1] - rowptr[n]: the reference's pow of a long tensor is an f32 tensor, cast afterwards.
+// p = -0.5 (HALF) is 1 / sqrt(count) in two f32 roundings, as ATen's pow computes it; p = -1 is 1 / count.  count = 0 gives +inf.
+template <class T, bool HALF>
+__global__ __launch_bounds__(256) void mpnn_degree_factor_kernel(T* __restrict__ out, const int64_t* __restrict__ rowptr, int64_t N) {
+  const int64_t n = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  const float c = (float)(rowptr[n + 1] - rowptr[n]);
+  // each f32 operation as an f64 one rounded to f32: the same value (a square root or a quotient of f32 operands rounds to f32 alike from 53
+  // bits as from the exact result), whatever the build makes of f32 sqrt and division
+  const float s = HALF ? (float)sqrt((double)c) : c;
+  out[n] = (T)(float)(1.0 / (double)s);
+}
+
+// which row and which packet slot of it a thread of a per-edge kernel holds: a flat index over rows x slots, so no lane idles whatever the
+// number of slots, and neighbouring lanes hold neighbouring packets.  The index is 32 bits wide (one unsigned division per thread; the
+// host refuses more than 2^31 packets); a thread past the last packet gets a row past the last.
+struct MpnnSlot { int64_t row; int slot; };
+__device__ __forceinline__ MpnnSlot mpnn_slot(uint32_t slots) {
+  const uint32_t idx = blockIdx.x * (uint32_t)kMpnnEdgeBlock + threadIdx.x;
+  const uint32_t r = idx / slots;
+  return {(int64_t)r, (int)(idx - r * slots)};
+}
+
+// msg[e, :] = [ edge[e, 0:Fe] | x[edgeI[e], 0:D] | x[edgeJ[e], 0:D] ]: slot s < se is packet s (VE elements) of the edge segment, then sx
+// packets (VX elements) of x[edgeI[e]], then sx of x[edgeJ[e]].  The host chooses VE and VX per segment (mpnn_message_packets).
+template <class T, int VE, int VX>
+__global__ __launch_bounds__(kMpnnEdgeBlock) void mpnn_message_kernel(T* __restrict__ msg, const T* __restrict__ edge, int64_t lde, const T* __restrict__ x,
+                                                                     int64_t ldx, const int64_t* __restrict__ edgeI, const int64_t* __restrict__ edgeJ, int64_t E,
+                                                                     int Fe, int D, uint32_t slots) {
+  const MpnnSlot t = mpnn_slot(slots);
+  const int se = Fe / VE, sx = D / VX;
+  if (t.row >= E || t.slot >= se + 2 * sx) return;
+  T* o = msg + t.row * ((int64_t)Fe + 2 * (int64_t)D);
+  if (t.slot < se) {
+    const int c = t.slot * VE;
+    *reinterpret_cast<Vec<T, VE>*>(o + c) = gcn_load<T, VE>(edge + t.row * lde + c);
+  } else {
+    const bool second = t.slot - se >= sx;
+    const int c = (t.slot - se - (second ? sx : 0)) * VX;
+    const int64_t node = second ? edgeJ[t.row] : edgeI[t.row];
+    *reinterpret_cast<Vec<T, VX>*>(o + Fe + (second ? D : 0) + c) = gcn_load<T, VX>(x + node * ldx + c);
+  }
+}
+
+// dst[e, 0:C] = src[e, 0:C] of rows with the pitches ldd and lds (dedge = dmsg[:, 0:Fe])
+template <class T, int V>
+__global__ __launch_bounds__(kMpnnEdgeBlock) void mpnn_columns_kernel(T* __restrict__ dst, int64_t ldd, const T* __restrict__ src, int64_t lds, int64_t E, int C,
+                                                                     uint32_t slots) {
+  const MpnnSlot t = mpnn_slot(slots);
+  const int c = t.slot * V;
+  if (t.row >= E || c >= C) return;
+  *reinterpret_cast<Vec<T, V>*>(dst + t.row * ldd + c) = gcn_load<T, V>(src + t.row * lds + c);
+}
+
+// dmsg[e, :] = ((dout[edgeJ[e], :] [+ dout[edgeI[e], :] if aggregateJ]) [* fJ[edgeJ[e]]]) [* fI[edgeI[e]]]; a null factor is absent
+template <class T, int V>
+__global__ __launch_bounds__(kMpnnEdgeBlock) void mpnn_aggregate_backward_kernel(T* __restrict__ dmsg, const T* __restrict__ dout, const int64_t* __restrict__ edgeI,
+                                                                                const int64_t* __restrict__ edgeJ, const T* __restrict__ fI,
+                                                                                const T* __restrict__ fJ, int aggregateJ, int64_t E, int M, uint32_t slots) {
+  const MpnnSlot t = mpnn_slot(slots);
+  const int c = t.slot * V;
+  if (t.row >= E || c >= M) return;
+  const int64_t i = edgeI[t.row], j = edgeJ[t.row];
+  Vec<T, V> g = gcn_load<T, V>(dout + j * M + c);
+  if (aggregateJ) {
+    const Vec<T, V> h = gcn_load<T, V>(dout + i * M + c);
+#pragma unroll
+    for (int q = 0; q < V; q++) g.v[q] += h.v[q];
+  }
+  if (fJ) {
+    const T f = fJ[j];
+#pragma unroll
+    for (int q = 0; q < V; q++) g.v[q] *= f;
+  }
+  if (fI) {
+    const T f = fI[i];
+#pragma unroll
+    for (int q = 0; q < V; q++) g.v[q] *= f;
+  }
+  *reinterpret_cast<Vec<T, V>*>(dmsg + t.row * M + c) = g;
+}
+
+// acc += sum over the edges ed = perm[b .. e), in that order, of t(ed) = (row[ed * ld + c0 ..] [* fI[edgeI[ed]]]) [* fJ[edgeJ[ed]]] (rc = row
+// + c0).  The products are rounded before they are added (no contraction into an fma): a term has the bits the chain of Mult nodes gives
+// it.  Lanes with `active` false hold no column: they take part in the index reads and load no row.  b and e are wave-uniform.
+template <class T, int V, bool FI, bool FJ>
+__device__ __forceinline__ void mpnn_gather(Vec<T, V>& acc, const T* __restrict__ rc, int64_t ld, const int64_t* __restrict__ perm,
+                                            const int64_t* __restrict__ edgeI, const int64_t* __restrict__ edgeJ, const T* __restrict__ fI,
+                                            const T* __restrict__ fJ, int64_t b, int64_t e, int lane, bool active) {
+#pragma clang fp contract(off)
+  for (int64_t p = b; p < e; p += 64) {
+    const int n = (int)(e - p < 64 ? e - p : 64);
+    int64_t ed = 0;
+    T fi = T(0), fj = T(0);
+    if (lane < n) {
+      ed = perm[p + lane];
+      if (FI) fi = fI[edgeI[ed]];
+      if (FJ) fj = fJ[edgeJ[ed]];
+    }
+    int k = 0;
+    for (; k + kMpnnUnroll <= n; k += kMpnnUnroll) {
+      Vec<T, V> v[kMpnnUnroll];
+      T a[kMpnnUnroll], c[kMpnnUnroll];
+#pragma unroll
+      for (int u = 0; u < kMpnnUnroll; u++) {
+        const int64_t eu = lane_bcast(ed, k + u);
+        if (FI) a[u] = lane_bcast(fi, k + u);
+        if (FJ) c[u] = lane_bcast(fj, k + u);
+        v[u] = active ? gcn_load<T, V>(rc + eu * ld) : gcn_zero<T, V>();
+      }
+#pragma unroll
+      for (int u = 0; u < kMpnnUnroll; u++)
+#pragma unroll
+        for (int j = 0; j < V; j++) {
+          T t = v[u].v[j];
+          if (FI) t = t * a[u];
+          if (FJ) t = t * c[u];
+          acc.v[j] = acc.v[j] + t;
+        }
+    }
+    for (; k < n; k++) {
+      const int64_t eu = lane_bcast(ed, k);
+      const T a = FI ? lane_bcast(fi, k) : T(0), c = FJ ? lane_bcast(fj, k) : T(0);
+      const Vec<T, V> v = active ? gcn_load<T, V>(rc + eu * ld) : gcn_zero<T, V>();
+#pragma unroll
+      for (int j = 0; j < V; j++) {
+        T t = v.v[j];
+        if (FI) t = t * a;
+        if (FJ) t = t * c;
+        acc.v[j] = acc.v[j] + t;
+      }
+    }
+  }
+}
+
+// out[r, 0:C] from the rows src[ed, off .. off + C) of the edges of node r: the sum over those of grouping 1 (columns off1) and, where
+// rowptr2 is not null, the sum over those of grouping 2 (columns off2), each in its grouping's order, the two added last - as the chains
+// add them (MPNN.aggregate: aggregateI + aggregateJ over incoming and outgoing; the message's gradient with respect to x: the two
+// gathers' gradients, outgoing at Fe and incoming at Fe + D).  A node whose two groups together hold more than kMpnnLongRow edges is
+// split: the waves take contiguous shares of the concatenated sequence, and either sum's partial sums are added in wave order.
+// grid: (ceil(N / kMpnnWaves), ceil(C / (64 * V)), kMpnnWaves + 1), block: kMpnnWaves * 64.
+template <class T, int V, bool FI, bool FJ>
+__global__ __launch_bounds__(kMpnnWaves * 64) void mpnn_node_sum_kernel(T* __restrict__ out, const T* __restrict__ src, int64_t ld, int64_t off1, int64_t off2,
+                                                                        const int64_t* __restrict__ rowptr1, const int64_t* __restrict__ perm1,
+                                                                        const int64_t* __restrict__ rowptr2, const int64_t* __restrict__ perm2,
+                                                                        const int64_t* __restrict__ edgeI, const int64_t* __restrict__ edgeJ,
+                                                                        const T* __restrict__ fI, const T* __restrict__ fJ, int64_t N, int64_t C) {
+  __shared__ Vec<T, V> part[2][kMpnnWaves][64];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t c0 = ((int64_t)blockIdx.y * 64 + lane) * V;
+  const bool active = c0 < C;
+  const int64_t row0 = (int64_t)blockIdx.x * kMpnnWaves;
+  const int nrows = (int)(N - row0 < kMpnnWaves ? N - row0 : kMpnnWaves);
+
+  for (int k = (int)blockIdx.z - 1; k < (int)blockIdx.z && k < nrows; k++) {   // one turn: a grid slice per k, as in gat_forward_kernel
+    const bool own = k < 0;
+    const int64_t r = own ? (wave < nrows ? row0 + wave : -1) : row0 + k;
+    int64_t b1 = 0, n1 = 0, b2 = 0, n2 = 0;
+    if (r >= 0) {
+      b1 = rowptr1[r]; n1 = rowptr1[r + 1] - b1;
+      if (rowptr2) { b2 = rowptr2[r]; n2 = rowptr2[r + 1] - b2; }
+    }
+    const int64_t total = n1 + n2;
+    if (own == (total > kMpnnLongRow)) continue;
+    int64_t lo = 0, hi = total;                 // this wave's share of the n1 + n2 edges
+    if (!own) {
+      const int64_t chunk = (total + kMpnnWaves - 1) / kMpnnWaves;
+      lo = wave * chunk < total ? wave * chunk : total;
+      hi = lo + chunk < total ? lo + chunk : total;
+    }
+    Vec<T, V> acc = gcn_zero<T, V>(), acc2 = gcn_zero<T, V>();
+    if (lo < n1) mpnn_gather<T, V, FI, FJ>(acc, src + off1 + c0, ld, perm1, edgeI, edgeJ, fI, fJ, b1 + lo, b1 + (hi < n1 ? hi : n1), lane, active);
+    if (hi > n1) mpnn_gather<T, V, FI, FJ>(acc2, src + off2 + c0, ld, perm2, edgeI, edgeJ, fI, fJ, b2 + (lo > n1 ? lo - n1 : 0), b2 + hi - n1, lane, active);
+    if (own) {
+      if (active && r >= 0) {
+        if (rowptr2) {
+#pragma unroll
+          for (int j = 0; j < V; j++) acc.v[j] += acc2.v[j];
+        }
+        *reinterpret_cast<Vec<T, V>*>(out + r * C + c0) = acc;
+      }
+      continue;
+    }
+    part[0][wave][lane] = acc;
+    part[1][wave][lane] = acc2;
+    __syncthreads();
+    if (wave == 0 && active) {
+#pragma unroll 1
+      for (int w = 1; w < kMpnnWaves; w++) {
+        const Vec<T, V> q = part[0][w][lane];
+#pragma unroll
+        for (int j = 0; j < V; j++) acc.v[j] += q.v[j];
+        const Vec<T, V> q2 = part[1][w][lane];
+#pragma unroll
+        for (int j = 0; j < V; j++) acc2.v[j] += q2.v[j];
+      }
+      if (rowptr2) {
+#pragma unroll
+        for (int j = 0; j < V; j++) acc.v[j] += acc2.v[j];
+      }
+      *reinterpret_cast<Vec<T, V>*>(out + r * C + c0) = acc;
+    }
+    __syncthreads();
+  }
+}
+
 template <class T, int V>
 void gcn_launch(Tensor* out, const Tensor* x, int64_t ldx, const Tensor* rowptr, const Tensor* col, const Tensor* dinv, int64_t N, int64_t D,
                 hipStream_t st) {
@@ -728,6 +948,123 @@ GatShape gat_check(const Tensor* score, const Tensor* value, std::initializer_li
     LAMP_CHECK(v.first->numel() == g.N + 1, v.second << " " << v.first->describe() << " does not belong to a graph of " << g.N << " nodes");
   }
   return g;
+}
+
+// the widest packet (in elements, at most 16 bytes) that divides every length (widths, column offsets, row pitches) and at which every
+// address is aligned
+template <class T> int mpnn_packet(std::initializer_list<int64_t> lengths, std::initializer_list<const Tensor*> ts) {
+  for (int v = 16 / (int)sizeof(T); v > 1; v >>= 1) {
+    bool ok = true;
+    for (int64_t l : lengths) ok = ok && l % v == 0;
+    for (const Tensor* t : ts) ok = ok && ((uintptr_t)t->raw() % (v * sizeof(T))) == 0;
+    if (ok) return v;
+  }
+  return 1;
+}
+// the grid of a per-edge kernel: rows of `slots` packets (slots >= 1), a thread per packet; see mpnn_slot
+struct MpnnEdgeGrid { dim3 grid; uint32_t slots; };
+MpnnEdgeGrid mpnn_edge_grid(int64_t rows, int64_t slots) {
+  LAMP_CHECK(slots >= 1 && rows * slots <= ((int64_t)1 << 31), rows << " rows of " << slots << " packets are too many");
+  return {dim3((unsigned)((rows * slots + kMpnnEdgeBlock - 1) / kMpnnEdgeBlock)), (uint32_t)slots};
+}
+// a [rows, cols] tensor whose rows are read in place (unit column stride, rows that do not overlap) or a dense copy; -> its row pitch
+Tensor* mpnn_rows(const Tensor* t, int64_t* ld) {
+  const int64_t rows = t->sizes[0], cols = t->sizes[1];
+  const bool in_place = (cols == 1 || t->strides[1] == 1) && (rows == 1 || t->strides[0] >= cols);
+  Tensor* r = in_place ? retain(t) : contiguous(t);
+  *ld = rows == 1 ? cols : r->strides[0];
+  return r;
+}
+void mpnn_check_float(const Tensor* t, const char* what, const Tensor* first) {
+  check_device_tensor(t, what);
+  check_same_device(t, first);
+  LAMP_CHECK(first->dtype == kF32 || first->dtype == kF64, "f32 and f64 only, got " << first->describe());
+  LAMP_CHECK(t->dtype == first->dtype, what << " " << t->describe() << " is not of the type of " << first->describe());
+}
+// a factor vector: null, or [N] of message's type
+void mpnn_check_factor(const Tensor* f, const char* what, const Tensor* first, int64_t N) {
+  if (!f) return;
+  mpnn_check_float(f, what, first);
+  LAMP_CHECK(f->ndim == 1 && f->numel() == N, what << " " << f->describe() << " must be [" << N << "]");
+}
+
+template <class T, int VE, int VX>
+void mpnn_message_launch(MpnnEdgeGrid g, hipStream_t st, Tensor* msg, const Tensor* edge, int64_t lde, const Tensor* x, int64_t ldx, const Tensor* edgeI,
+                         const Tensor* edgeJ, int64_t E, int Fe, int D) {
+  hipLaunchKernelGGL((mpnn_message_kernel<T, VE, VX>), g.grid, dim3(kMpnnEdgeBlock), 0, st, msg->ptr<T>(), edge->ptr<T>(), lde, x->ptr<T>(), ldx,
+                     edgeI->ptr<int64_t>(), edgeJ->ptr<int64_t>(), E, Fe, D, g.slots);
+}
+template <class T, int VE>
+void mpnn_message_launch_x(int vx, MpnnEdgeGrid g, hipStream_t st, Tensor* msg, const Tensor* edge, int64_t lde, const Tensor* x, int64_t ldx,
+                           const Tensor* edgeI, const Tensor* edgeJ, int64_t E, int Fe, int D) {
+  if constexpr (sizeof(T) == 4) {
+    if (vx == 4) { mpnn_message_launch<T, VE, 4>(g, st, msg, edge, lde, x, ldx, edgeI, edgeJ, E, Fe, D); return; }
+  }
+  if (vx == 2) mpnn_message_launch<T, VE, 2>(g, st, msg, edge, lde, x, ldx, edgeI, edgeJ, E, Fe, D);
+  else mpnn_message_launch<T, VE, 1>(g, st, msg, edge, lde, x, ldx, edgeI, edgeJ, E, Fe, D);
+}
+template <class T>
+void mpnn_message_dispatch(hipStream_t st, Tensor* msg, const Tensor* edge, int64_t lde, const Tensor* x, int64_t ldx, const Tensor* edgeI, const Tensor* edgeJ,
+                           int64_t E, int Fe, int D) {
+  // per segment: the edge segment starts every row (pitch Fe + 2 D), the node segments start at Fe and Fe + D
+  const int64_t W = (int64_t)Fe + 2 * (int64_t)D;
+  const int ve = mpnn_packet<T>({Fe, W, lde}, {msg, edge}), vx = mpnn_packet<T>({D, Fe, W, ldx}, {msg, x});
+  const MpnnEdgeGrid g = mpnn_edge_grid(E, Fe / ve + 2 * (int64_t)(D / vx));
+  if constexpr (sizeof(T) == 4) {
+    if (ve == 4) { mpnn_message_launch_x<T, 4>(vx, g, st, msg, edge, lde, x, ldx, edgeI, edgeJ, E, Fe, D); return; }
+  }
+  if (ve == 2) mpnn_message_launch_x<T, 2>(vx, g, st, msg, edge, lde, x, ldx, edgeI, edgeJ, E, Fe, D);
+  else mpnn_message_launch_x<T, 1>(vx, g, st, msg, edge, lde, x, ldx, edgeI, edgeJ, E, Fe, D);
+}
+
+struct MpnnSum {
+  Tensor* out; const Tensor* src; int64_t ld, off1, off2;
+  const Tensor *rowptr1, *perm1, *rowptr2, *perm2, *edgeI, *edgeJ, *fI, *fJ;
+  int64_t N, C;
+};
+template <class T, int V, bool FI, bool FJ> void mpnn_sum_launch(const MpnnSum& a, hipStream_t st) {
+  const int64_t tiles = (a.C + 64 * V - 1) / (64 * V), groups = (a.N + kMpnnWaves - 1) / kMpnnWaves;
+  LAMP_CHECK(tiles <= 65535 && groups <= INT32_MAX, "a graph of " << a.N << " nodes with " << a.C << " columns is too large");
+  auto ip = [](const Tensor* t) { return t ? t->ptr<int64_t>() : nullptr; };
+  hipLaunchKernelGGL((mpnn_node_sum_kernel<T, V, FI, FJ>), dim3((unsigned)groups, (unsigned)tiles, kMpnnWaves + 1), dim3(kMpnnWaves * 64), 0, st,
+                     a.out->ptr<T>(), a.src->ptr<T>(), a.ld, a.off1, a.off2, ip(a.rowptr1), ip(a.perm1), ip(a.rowptr2), ip(a.perm2), ip(a.edgeI), ip(a.edgeJ),
+                     a.fI ? a.fI->ptr<T>() : nullptr, a.fJ ? a.fJ->ptr<T>() : nullptr, a.N, a.C);
+}
+template <class T, bool FI, bool FJ> void mpnn_sum_packet(int v, const MpnnSum& a, hipStream_t st) {
+  if constexpr (sizeof(T) == 4) {
+    if (v == 4) { mpnn_sum_launch<T, 4, FI, FJ>(a, st); return; }
+  }
+  if (v == 2) mpnn_sum_launch<T, 2, FI, FJ>(a, st);
+  else mpnn_sum_launch<T, 1, FI, FJ>(a, st);
+}
+// MPNN.aggregate: a factor that is null is a kernel without that multiplication
+template <class T> void mpnn_aggregate_dispatch(int v, const MpnnSum& a, hipStream_t st) {
+  if (a.fI && a.fJ) mpnn_sum_packet<T, true, true>(v, a, st);
+  else if (a.fI) mpnn_sum_packet<T, true, false>(v, a, st);
+  else if (a.fJ) mpnn_sum_packet<T, false, true>(v, a, st);
+  else mpnn_sum_packet<T, false, false>(v, a, st);
+}
+template <class T>
+void mpnn_columns_dispatch(hipStream_t st, Tensor* dst, int64_t ldd, const Tensor* src, int64_t lds, int64_t E, int C) {
+  const int v = mpnn_packet<T>({C, ldd, lds}, {dst, src});
+  const MpnnEdgeGrid g = mpnn_edge_grid(E, C / v);
+  if constexpr (sizeof(T) == 4) {
+    if (v == 4) { hipLaunchKernelGGL((mpnn_columns_kernel<T, 4>), g.grid, dim3(kMpnnEdgeBlock), 0, st, dst->ptr<T>(), ldd, src->ptr<T>(), lds, E, C, g.slots); return; }
+  }
+  if (v == 2) hipLaunchKernelGGL((mpnn_columns_kernel<T, 2>), g.grid, dim3(kMpnnEdgeBlock), 0, st, dst->ptr<T>(), ldd, src->ptr<T>(), lds, E, C, g.slots);
+  else hipLaunchKernelGGL((mpnn_columns_kernel<T, 1>), g.grid, dim3(kMpnnEdgeBlock), 0, st, dst->ptr<T>(), ldd, src->ptr<T>(), lds, E, C, g.slots);
+}
+template <class T>
+void mpnn_aggregate_backward_dispatch(hipStream_t st, Tensor* dmsg, const Tensor* dout, const Tensor* edgeI, const Tensor* edgeJ, const Tensor* fI, const Tensor* fJ,
+                                      int aggregateJ, int64_t E, int M) {
+  const int v = mpnn_packet<T>({M}, {dmsg, dout});
+  const MpnnEdgeGrid g = mpnn_edge_grid(E, M / v);
+  const T *pi = fI ? fI->ptr<T>() : nullptr, *pj = fJ ? fJ->ptr<T>() : nullptr;
+  if constexpr (sizeof(T) == 4) {
+    if (v == 4) { hipLaunchKernelGGL((mpnn_aggregate_backward_kernel<T, 4>), g.grid, dim3(kMpnnEdgeBlock), 0, st, dmsg->ptr<T>(), dout->ptr<T>(), edgeI->ptr<int64_t>(), edgeJ->ptr<int64_t>(), pi, pj, aggregateJ, E, M, g.slots); return; }
+  }
+  if (v == 2) hipLaunchKernelGGL((mpnn_aggregate_backward_kernel<T, 2>), g.grid, dim3(kMpnnEdgeBlock), 0, st, dmsg->ptr<T>(), dout->ptr<T>(), edgeI->ptr<int64_t>(), edgeJ->ptr<int64_t>(), pi, pj, aggregateJ, E, M, g.slots);
+  else hipLaunchKernelGGL((mpnn_aggregate_backward_kernel<T, 1>), g.grid, dim3(kMpnnEdgeBlock), 0, st, dmsg->ptr<T>(), dout->ptr<T>(), edgeI->ptr<int64_t>(), edgeJ->ptr<int64_t>(), pi, pj, aggregateJ, E, M, g.slots);
 }
 
 }  // namespace
@@ -946,6 +1283,185 @@ int lamp_gat_backward(lamp_tensor** dscore, lamp_tensor** dvalue, const lamp_ten
     }
   }
   *dscore = ds.take(); *dvalue = dv.take();
+  LAMP_API_END
+}
+
+int lamp_mpnn_long_row(int64_t* out) {
+  LAMP_API_BEGIN
+  *out = kMpnnLongRow;
+  LAMP_API_END
+}
+
+int lamp_mpnn_degree_factor(lamp_tensor** out, const lamp_tensor* rowptr, double p, int dtype) {
+  LAMP_API_BEGIN
+  check_device_tensor(rowptr, "rowptr");
+  check_i64_vector(rowptr, rowptr, "rowptr");
+  LAMP_CHECK(rowptr->numel() >= 1, "rowptr " << rowptr->describe() << " must be [N + 1]");
+  LAMP_CHECK(dtype == kF32 || dtype == kF64, "f32 and f64 only, got " << dtype_name(dtype));
+  LAMP_CHECK(p == -0.5 || p == -1.0, "the exponent must be -0.5 or -1, got " << p);
+  const int64_t N = rowptr->numel() - 1;
+  Hold rp(contiguous(rowptr));
+  int64_t ns[1] = {N};
+  Hold o(new_tensor(ns, 1, dtype, rowptr->device()));
+  if (N) {
+    hipStream_t st = current_stream(rowptr->device());
+    KernelTimer kt("mpnn_degree_factor", 2.0 * N, (double)N * (8 + dtype_size(dtype)), st);
+    const dim3 grid((unsigned)((N + 255) / 256));
+    if (dtype == kF32 && p == -0.5) hipLaunchKernelGGL((mpnn_degree_factor_kernel<float, true>), grid, dim3(256), 0, st, o->ptr<float>(), rp->ptr<int64_t>(), N);
+    else if (dtype == kF32) hipLaunchKernelGGL((mpnn_degree_factor_kernel<float, false>), grid, dim3(256), 0, st, o->ptr<float>(), rp->ptr<int64_t>(), N);
+    else if (p == -0.5) hipLaunchKernelGGL((mpnn_degree_factor_kernel<double, true>), grid, dim3(256), 0, st, o->ptr<double>(), rp->ptr<int64_t>(), N);
+    else hipLaunchKernelGGL((mpnn_degree_factor_kernel<double, false>), grid, dim3(256), 0, st, o->ptr<double>(), rp->ptr<int64_t>(), N);
+    LAMP_LAUNCH_CHECK();
+  }
+  *out = o.take();
+  LAMP_API_END
+}
+
+int lamp_mpnn_message_forward(lamp_tensor** out, const lamp_tensor* x, const lamp_tensor* edgeFeatures, const lamp_tensor* edgeI, const lamp_tensor* edgeJ) {
+  LAMP_API_BEGIN
+  check_device_tensor(x, "x");
+  mpnn_check_float(edgeFeatures, "edgeFeatures", x);
+  LAMP_CHECK(x->ndim == 2, "x " << x->describe() << " must be [N, D]");
+  LAMP_CHECK(edgeFeatures->ndim == 2, "edgeFeatures " << edgeFeatures->describe() << " must be [E, Fe]");
+  check_i64_vector(edgeI, x, "edgeI");
+  check_i64_vector(edgeJ, x, "edgeJ");
+  const int64_t E = edgeI->numel(), Fe = edgeFeatures->sizes[1], D = x->sizes[1];
+  LAMP_CHECK(edgeJ->numel() == E, "edgeI " << edgeI->describe() << " and edgeJ " << edgeJ->describe() << " differ in length");
+  LAMP_CHECK(edgeFeatures->sizes[0] == E, "edgeFeatures " << edgeFeatures->describe() << " does not have one row per edge (" << E << " edges)");
+  LAMP_CHECK(E == 0 || x->sizes[0] > 0, "x " << x->describe() << " has no rows");
+  LAMP_CHECK(Fe + 2 * D <= INT32_MAX / 2, "a message of " << Fe + 2 * D << " columns is too wide");
+  int64_t lde = 0, ldx = 0;
+  Hold ec(mpnn_rows(edgeFeatures, &lde)), xc(mpnn_rows(x, &ldx)), ei(contiguous(edgeI)), ej(contiguous(edgeJ));
+  int64_t os[2] = {E, Fe + 2 * D};
+  Hold o(new_tensor(os, 2, x->dtype, x->device()));
+  if (E * (Fe + 2 * D)) {
+    hipStream_t st = current_stream(x->device());
+    KernelTimer kt("mpnn_message", 0, 2.0 * E * (Fe + 2 * D) * dtype_size(x->dtype) + E * 16.0, st);
+    if (x->dtype == kF32) mpnn_message_dispatch<float>(st, o.get(), ec.get(), lde, xc.get(), ldx, ei.get(), ej.get(), E, (int)Fe, (int)D);
+    else mpnn_message_dispatch<double>(st, o.get(), ec.get(), lde, xc.get(), ldx, ei.get(), ej.get(), E, (int)Fe, (int)D);
+    LAMP_LAUNCH_CHECK();
+  }
+  *out = o.take();
+  LAMP_API_END
+}
+
+int lamp_mpnn_message_backward(lamp_tensor** dx_or_null, lamp_tensor** dedge_or_null, const lamp_tensor* dmsg, int64_t numNodes, int64_t edgeDim,
+                               const lamp_tensor* inRowptr, const lamp_tensor* inPerm, const lamp_tensor* outRowptr, const lamp_tensor* outPerm) {
+  LAMP_API_BEGIN
+  check_device_tensor(dmsg, "dmsg");
+  LAMP_CHECK(dmsg->dtype == kF32 || dmsg->dtype == kF64, "f32 and f64 only, got " << dmsg->describe());
+  LAMP_CHECK(dmsg->ndim == 2, "dmsg " << dmsg->describe() << " must be [E, edgeDim + 2 D]");
+  const int64_t E = dmsg->sizes[0], W = dmsg->sizes[1], N = numNodes, Fe = edgeDim;
+  LAMP_CHECK(N >= 0 && Fe >= 0 && W >= Fe && (W - Fe) % 2 == 0, "dmsg " << dmsg->describe() << " is not [E, " << Fe << " + 2 D]");
+  LAMP_CHECK(W <= INT32_MAX / 2, "a message of " << W << " columns is too wide");
+  const int64_t D = (W - Fe) / 2;
+  const int dt = dmsg->dtype, dev = dmsg->device();
+  hipStream_t st = current_stream(dev);
+  const double sz = (double)dtype_size(dt);
+  Hold g(contiguous(dmsg)), dx, de;
+  if (dx_or_null) {
+    for (auto& v : {std::make_pair(inRowptr, "inRowptr"), std::make_pair(outRowptr, "outRowptr")}) {
+      check_i64_vector(v.first, dmsg, v.second);
+      LAMP_CHECK(v.first->numel() == N + 1, v.second << " " << v.first->describe() << " does not belong to a graph of " << N << " nodes");
+    }
+    for (auto& v : {std::make_pair(inPerm, "inPerm"), std::make_pair(outPerm, "outPerm")}) {
+      check_i64_vector(v.first, dmsg, v.second);
+      LAMP_CHECK(v.first->numel() == E, v.second << " " << v.first->describe() << " does not have dmsg's " << E << " edges");
+    }
+    Hold irp(contiguous(inRowptr)), ipm(contiguous(inPerm)), orp(contiguous(outRowptr)), opm(contiguous(outPerm));
+    int64_t xs[2] = {N, D};
+    dx = Hold(new_tensor(xs, 2, dt, dev));
+    if (N * D) {
+      KernelTimer kt("mpnn_message_backward_x", 2.0 * E * D, (2.0 * E * D + (double)N * D) * sz + E * 16.0 + N * 16.0, st);
+      const MpnnSum a{dx.get(), g.get(), W, Fe, Fe + D, orp.get(), opm.get(), irp.get(), ipm.get(), nullptr, nullptr, nullptr, nullptr, N, D};
+      if (dt == kF32) mpnn_sum_packet<float, false, false>(mpnn_packet<float>({D, Fe, W}, {dx.get(), g.get()}), a, st);
+      else mpnn_sum_packet<double, false, false>(mpnn_packet<double>({D, Fe, W}, {dx.get(), g.get()}), a, st);
+      LAMP_LAUNCH_CHECK();
+    }
+  }
+  if (dedge_or_null) {
+    int64_t es[2] = {E, Fe};
+    de = Hold(new_tensor(es, 2, dt, dev));
+    if (E * Fe) {
+      KernelTimer kt("mpnn_message_backward_edge", 0, 2.0 * E * Fe * sz, st);
+      if (dt == kF32) mpnn_columns_dispatch<float>(st, de.get(), Fe, g.get(), W, E, (int)Fe);
+      else mpnn_columns_dispatch<double>(st, de.get(), Fe, g.get(), W, E, (int)Fe);
+      LAMP_LAUNCH_CHECK();
+    }
+  }
+  if (dx_or_null) *dx_or_null = dx.take();
+  if (dedge_or_null) *dedge_or_null = de.take();
+  LAMP_API_END
+}
+
+int lamp_mpnn_aggregate_forward(lamp_tensor** out, const lamp_tensor* message, const lamp_tensor* edgeI, const lamp_tensor* edgeJ,
+                                const lamp_tensor* inRowptr, const lamp_tensor* inPerm, const lamp_tensor* outRowptr_or_null,
+                                const lamp_tensor* outPerm_or_null, const lamp_tensor* fI_or_null, const lamp_tensor* fJ_or_null, int aggregateJ) {
+  LAMP_API_BEGIN
+  check_device_tensor(message, "message");
+  LAMP_CHECK(message->dtype == kF32 || message->dtype == kF64, "f32 and f64 only, got " << message->describe());
+  LAMP_CHECK(message->ndim == 2, "message " << message->describe() << " must be [E, M]");
+  const int64_t E = message->sizes[0], M = message->sizes[1];
+  LAMP_CHECK(M <= INT32_MAX / 2, "message " << message->describe() << " has too many columns");
+  check_i64_vector(inRowptr, message, "inRowptr");
+  LAMP_CHECK(inRowptr->numel() >= 1, "inRowptr " << inRowptr->describe() << " must be [N + 1]");
+  const int64_t N = inRowptr->numel() - 1;
+  LAMP_CHECK(!aggregateJ || (outRowptr_or_null && outPerm_or_null), "aggregateJ needs the outgoing grouping");
+  const Tensor *orp0 = aggregateJ ? outRowptr_or_null : nullptr, *opm0 = aggregateJ ? outPerm_or_null : nullptr;
+  for (auto& v : {std::make_pair(edgeI, "edgeI"), std::make_pair(edgeJ, "edgeJ"), std::make_pair(inPerm, "inPerm"), std::make_pair(opm0 ? opm0 : inPerm, "outPerm")}) {
+    check_i64_vector(v.first, message, v.second);
+    LAMP_CHECK(v.first->numel() == E, v.second << " " << v.first->describe() << " does not have one entry per row of message " << message->describe());
+  }
+  if (orp0) {
+    check_i64_vector(orp0, message, "outRowptr");
+    LAMP_CHECK(orp0->numel() == N + 1, "outRowptr " << orp0->describe() << " does not belong to a graph of " << N << " nodes");
+  }
+  mpnn_check_factor(fI_or_null, "fI", message, N);
+  mpnn_check_factor(fJ_or_null, "fJ", message, N);
+  Hold mc(contiguous(message)), ei(contiguous(edgeI)), ej(contiguous(edgeJ)), irp(contiguous(inRowptr)), ipm(contiguous(inPerm)), orp(orp0 ? contiguous(orp0) : nullptr),
+      opm(opm0 ? contiguous(opm0) : nullptr), fi(fI_or_null ? contiguous(fI_or_null) : nullptr), fj(fJ_or_null ? contiguous(fJ_or_null) : nullptr);
+  int64_t os[2] = {N, M};
+  Hold o(new_tensor(os, 2, message->dtype, message->device()));
+  if (N * M) {
+    hipStream_t st = current_stream(message->device());
+    const double sz = (double)dtype_size(message->dtype), terms = (aggregateJ ? 2.0 : 1.0) * E;
+    KernelTimer kt("mpnn_aggregate", 3.0 * terms * M, (terms * M + (double)N * M) * sz + terms * (24 + 2 * sz) + N * 16.0, st);
+    const MpnnSum a{o.get(), mc.get(), M, 0, 0, irp.get(), ipm.get(), orp.get(), opm.get(), ei.get(), ej.get(), fi.get(), fj.get(), N, M};
+    if (message->dtype == kF32) mpnn_aggregate_dispatch<float>(mpnn_packet<float>({M}, {o.get(), mc.get()}), a, st);
+    else mpnn_aggregate_dispatch<double>(mpnn_packet<double>({M}, {o.get(), mc.get()}), a, st);
+    LAMP_LAUNCH_CHECK();
+  }
+  *out = o.take();
+  LAMP_API_END
+}
+
+int lamp_mpnn_aggregate_backward(lamp_tensor** dmsg, const lamp_tensor* dout, const lamp_tensor* edgeI, const lamp_tensor* edgeJ,
+                                 const lamp_tensor* fI_or_null, const lamp_tensor* fJ_or_null, int aggregateJ) {
+  LAMP_API_BEGIN
+  check_device_tensor(dout, "dout");
+  LAMP_CHECK(dout->dtype == kF32 || dout->dtype == kF64, "f32 and f64 only, got " << dout->describe());
+  LAMP_CHECK(dout->ndim == 2, "dout " << dout->describe() << " must be [N, M]");
+  const int64_t N = dout->sizes[0], M = dout->sizes[1];
+  LAMP_CHECK(M <= INT32_MAX / 2, "dout " << dout->describe() << " has too many columns");
+  check_i64_vector(edgeI, dout, "edgeI");
+  check_i64_vector(edgeJ, dout, "edgeJ");
+  const int64_t E = edgeI->numel();
+  LAMP_CHECK(edgeJ->numel() == E, "edgeI " << edgeI->describe() << " and edgeJ " << edgeJ->describe() << " differ in length");
+  LAMP_CHECK(E == 0 || N > 0, "dout " << dout->describe() << " has no rows");
+  mpnn_check_factor(fI_or_null, "fI", dout, N);
+  mpnn_check_factor(fJ_or_null, "fJ", dout, N);
+  Hold gc(contiguous(dout)), ei(contiguous(edgeI)), ej(contiguous(edgeJ)), fi(fI_or_null ? contiguous(fI_or_null) : nullptr), fj(fJ_or_null ? contiguous(fJ_or_null) : nullptr);
+  int64_t ms[2] = {E, M};
+  Hold o(new_tensor(ms, 2, dout->dtype, dout->device()));
+  if (E * M) {
+    hipStream_t st = current_stream(dout->device());
+    const double sz = (double)dtype_size(dout->dtype);
+    KernelTimer kt("mpnn_aggregate_backward", 3.0 * E * M, ((aggregateJ ? 3.0 : 2.0) * E * M + 2.0 * E) * sz + E * 16.0, st);
+    if (dout->dtype == kF32) mpnn_aggregate_backward_dispatch<float>(st, o.get(), gc.get(), ei.get(), ej.get(), fi.get(), fj.get(), aggregateJ, E, (int)M);
+    else mpnn_aggregate_backward_dispatch<double>(st, o.get(), gc.get(), ei.get(), ej.get(), fi.get(), fj.get(), aggregateJ, E, (int)M);
+    LAMP_LAUNCH_CHECK();
+  }
+  *dmsg = o.take();
   LAMP_API_END
 }
 

@@ -1,5 +1,5 @@
-"""lamp.nn.graph's GCN and GraphAttention paths over the C ABI: Graph, GCN, gcn, gcnAggregation, VertexPooling (and nn.ResidualModule,
-which gcn needs), GraphAttention, multiheadGraphAttention.
+"""lamp.nn.graph over the C ABI: Graph, GCN, gcn, gcnAggregation, VertexPooling (and nn.ResidualModule, which gcn needs), GraphAttention,
+multiheadGraphAttention, MPNN.
 
 Reference: lamp-core/src/main/scala/lamp/nn/graph/{Graph,GCN,VertexPooling,GraphAttention}.scala.  GCN.computeSparseAdjacency builds a sparse COO
 tensor and gcnAggregation multiplies it with `mm`; here the adjacency is a CSR (`lamp_gcn_adjacency`) and the product one gather-only
@@ -11,6 +11,11 @@ GraphAttention.multiheadGraphAttention scores every edge and then takes, per des
 sources' values under it.  The scoring is a composition of existing nodes; everything after it is one node, `GraphAttentionAggregate`
 (`lamp_gat_forward` / `lamp_gat_backward` over the two groupings of `Graph.edgeCsr()`), or the reference's own chain of exp, indexAdd,
 log, indexSelect and Mult (`graphAttentionAggregateComposed`); `graphAttentionFused` switches between the two.
+
+MPNN's two data movements are a node each: `MpnnMessage` writes cat(edgeFeatures, x[edgeI], x[edgeJ]) in one launch and hands x the true
+gradient, `MpnnAggregate` is MPNN.aggregate (`lamp_mpnn_*` over `Graph.edgeCsr()` and the degree factors the graph caches); the chains of
+IndexSelect / Concatenate and Mult / IndexAdd / Add nodes (`mpnnMessageComposed`, `mpnnAggregateComposed`) are the fallback, `mpnnFused`
+switches between the two.
 """
 from __future__ import annotations
 
@@ -119,9 +124,9 @@ def computeEdgeCsr(edgeI: STen, edgeJ: STen, numNodes: int) -> EdgeCsr:
 
 
 class Graph:
-    """Graph(nodeFeatures, edgeFeatures, edgeI, edgeJ, vertexPoolingIndices) (Graph.scala).  The adjacency of the edge list and its
-    grouping by endpoint are built on first use and shared by every copy(nodeFeatures = ...), so stacked GCN or GraphAttention layers
-    over one graph build them once."""
+    """Graph(nodeFeatures, edgeFeatures, edgeI, edgeJ, vertexPoolingIndices) (Graph.scala).  The adjacency of the edge list, its
+    grouping by endpoint and MPNN's degree factors (keyed by N, type, exponent and side) are built on first use and shared by every
+    copy(nodeFeatures = ...), so stacked GCN, GraphAttention or MPNN layers over one graph build them once."""
 
     def __init__(self, nodeFeatures: Variable, edgeFeatures: Optional[Variable], edgeI: STen, edgeJ: STen, vertexPoolingIndices: Optional[STen] = None,
                  _adjacencies: Optional[dict] = None):
@@ -343,3 +348,158 @@ class GraphAttention:
         assert len(st) == len(tensors), f"state has {len(st)} tensors, got {len(tensors)}"
         for v, t in zip(st, tensors):
             v.value.copyFrom(t)
+
+
+# ---- message passing (MPNN.scala) ----------------------------------------------------------------------------------------------------------------
+_mpnn_fused = True
+
+
+def mpnnFused(on: bool) -> bool:
+    """process-wide: MPNN's message and MPNN.aggregate as one MpnnMessage / MpnnAggregate node each over the edge CSR (True, the default) or
+    as chains of IndexSelect / Concatenate and Mult / IndexAdd / Add nodes; returns the previous setting."""
+    global _mpnn_fused
+    prev, _mpnn_fused = _mpnn_fused, bool(on)
+    return prev
+
+
+def mpnnLongRow() -> int:
+    """nodes of more edges than this are split across the waves of a workgroup (lamp_mpnn_long_row)"""
+    n = C.c_int64(); lib.lamp_mpnn_long_row(C.byref(n)); return n.value
+
+
+def countOccurences(t: STen, elems: int) -> STen:
+    """MPNN.countOccurences (MPNN.scala:75-81): how often each of 0 .. elems - 1 occurs in the long vector t, as a long vector (the
+    reference adds ones into zeros with indexAdd; a bincount gives the same counts)"""
+    return t.bincount(None, int(elems))
+
+
+def mpnnDegreeFactor(rowptr: STen, p: float, dtype) -> STen:
+    """countOccurences(index, N).pow(p).castToType(dtype) from the rowptr of index's grouping: [N], computed in f32 whatever dtype is (the
+    pow of a long tensor is an f32 tensor in the reference) and then cast; a node that does not occur gets inf"""
+    o = C.c_void_p(); lib.lamp_mpnn_degree_factor(C.byref(o), rowptr.h, float(p), int(dtype)); return STen(o)
+
+
+def _mpnn_factors(csr: EdgeCsr, dtype, degreeNormalizeI: bool, degreeNormalizeJ: bool, cache: Optional[dict] = None):
+    """(fI, fJ): the factor vectors of MPNN.aggregate, None where the normalisation is off; kept in `cache` under (N, dtype, p, side)"""
+    p = -0.5 if degreeNormalizeI and degreeNormalizeJ else -1.0
+
+    def build(rowptr):               # the kernel writes f32 / f64; any other type (the composed chain's) is a cast of the f32 vector
+        return mpnnDegreeFactor(rowptr, p, dtype) if dtype in (F32, F64) else mpnnDegreeFactor(rowptr, p, F32).castToType(dtype)
+
+    def factor(side, rowptr):
+        key = ("mpnnFactor", csr.numNodes, dtype, p, side)
+        if cache is None:
+            return build(rowptr)
+        if key not in cache:
+            cache[key] = build(rowptr)
+        return cache[key]
+    return (factor("I", csr.outRowptr) if degreeNormalizeI else None, factor("J", csr.inRowptr) if degreeNormalizeJ else None)
+
+
+def _check_csr(csr: EdgeCsr, edgeI: STen, edgeJ: STen, numNodes: int):
+    """a grouping handed in beside an edge list must be that edge list's: the same node count and edge count (its contents are not
+    compared; the kernels index with edgeI and edgeJ, whose range the grouping's construction checked)"""
+    assert csr.numNodes == int(numNodes), f"the edge CSR belongs to a graph of {csr.numNodes} nodes, not {numNodes}"
+    assert csr.edgeI.numel == edgeI.numel and csr.edgeJ.numel == edgeJ.numel, \
+        f"the edge CSR was built from {csr.edgeI.numel} edges, the edge list has {edgeI.numel} / {edgeJ.numel}"
+
+
+def mpnnMessageComposed(nodeFeatures: Variable, edgeFeatures: Variable, edgeI: STen, edgeJ: STen) -> Variable:
+    """cat(edgeFeatures, nodeFeatures[edgeI], nodeFeatures[edgeJ]) (MPNN.scala:21-25) out of IndexSelect and Concatenate.  Each gather
+    goes through a `view` of nodeFeatures of its own: IndexSelect's backward closure doubles a gradient its input has already received
+    (ops.scala's `out += out.indexAdd(...)`, mirrored in host/ops.cpp), and nodeFeatures has other consumers (the second gather, and in
+    MPNN.forward the vertex transform's input and the residual), so IndexSelect's input must be a node no one else reads; View's closure
+    then adds to nodeFeatures and the chain gives the true gradient."""
+    shape = nodeFeatures.shape
+    vI = nodeFeatures.view(shape).indexSelect(0, const(edgeI))
+    vJ = nodeFeatures.view(shape).indexSelect(0, const(edgeJ))
+    return apply_op("Concatenate", [edgeFeatures, vI, vJ], i=[1])
+
+
+def mpnnMessage(nodeFeatures: Variable, edgeFeatures: Variable, edgeI: STen, edgeJ: STen, csr: Optional[EdgeCsr] = None) -> Variable:
+    """the message of every edge, [E, Fe + 2 D].  f32 / f64 with mpnnFused(True): one MpnnMessage node over `csr` (built here if not
+    given: that is where the endpoints' range is checked); otherwise the composed chain.  Either way nodeFeatures receives the true
+    gradient, not the doubled one of the reference's literal chain."""
+    dt = nodeFeatures.value.dtype
+    if not _mpnn_fused or dt not in (F32, F64):
+        return mpnnMessageComposed(nodeFeatures, edgeFeatures, edgeI, edgeJ)
+    if csr is None:
+        csr = computeEdgeCsr(edgeI, edgeJ, nodeFeatures.shape[0])
+    _check_csr(csr, edgeI, edgeJ, nodeFeatures.shape[0])
+    return apply_op("MpnnMessage", [nodeFeatures, edgeFeatures], tensors=[edgeI, edgeJ] + csr.incoming + csr.outgoing)
+
+
+def mpnnAggregateComposed(numVertices: int, message: Variable, edgeI: STen, edgeJ: STen, degreeNormalizeI: bool, degreeNormalizeJ: bool,
+                          aggregateJ: bool, csr: Optional[EdgeCsr] = None, _cache: Optional[dict] = None) -> Variable:
+    """MPNN.aggregate (MPNN.scala:84-126) as the reference writes it: up to two broadcast Mults, an IndexAdd per direction, an Add.  The
+    factor vectors alone do not come from the chain: the library has no pow of a long tensor, so they are lamp_mpnn_degree_factor's (the
+    same f32 arithmetic) from the groupings' row pointers."""
+    normalized = message
+    if degreeNormalizeI or degreeNormalizeJ:
+        if csr is None:
+            csr = computeEdgeCsr(edgeI, edgeJ, numVertices)
+        fI, fJ = _mpnn_factors(csr, message.value.dtype, degreeNormalizeI, degreeNormalizeJ, _cache)
+        if fI is not None:
+            normalized = normalized * const(fI.indexSelect(0, edgeI).view(-1, 1))
+        if fJ is not None:
+            normalized = normalized * const(fJ.indexSelect(0, edgeJ).view(-1, 1))
+    aggI = normalized.indexAdd(const(edgeJ), 0, numVertices)
+    if aggregateJ:
+        return aggI + normalized.indexAdd(const(edgeI), 0, numVertices)
+    return aggI
+
+
+def mpnnAggregate(numVertices: int, message: Variable, edgeI: STen, edgeJ: STen, degreeNormalizeI: bool, degreeNormalizeJ: bool, aggregateJ: bool,
+                  csr: Optional[EdgeCsr] = None, _cache: Optional[dict] = None) -> Variable:
+    """MPNN.aggregate: message [E, M] -> [numVertices, M], every message scaled by count(edgeI)^p of its source and count(edgeJ)^p of its
+    destination where those normalisations are on (p = -0.5 with both, else -1), summed per destination and, with aggregateJ, per source
+    too.  f32 / f64 with mpnnFused(True): one MpnnAggregate node over `csr` (built here if not given); otherwise the composed chain."""
+    dt = message.value.dtype
+    if not _mpnn_fused or dt not in (F32, F64):
+        return mpnnAggregateComposed(numVertices, message, edgeI, edgeJ, degreeNormalizeI, degreeNormalizeJ, aggregateJ, csr, _cache)
+    if csr is None:
+        csr = computeEdgeCsr(edgeI, edgeJ, numVertices)
+    _check_csr(csr, edgeI, edgeJ, numVertices)
+    fI, fJ = _mpnn_factors(csr, dt, degreeNormalizeI, degreeNormalizeJ, _cache)
+    return apply_op("MpnnAggregate", [message], tensors=[edgeI, edgeJ] + csr.incoming + csr.outgoing + [f for f in (fI, fJ) if f is not None],
+                    i=[int(bool(aggregateJ)), int(fI is not None), int(fJ is not None)])
+
+
+class MPNN:
+    """MPNN(messageTransform, vertexTransform, degreeNormalizeI, degreeNormalizeJ, aggregateJ) (MPNN.scala:8-48): forward(graph) =
+    graph.copy(nodeFeatures = [graph.nodeFeatures +] vertexTransform(cat(graph.nodeFeatures, aggregate(messageTransform(message))))); the
+    residual applies only where the widths agree.  State: the message transform's followed by the vertex transform's."""
+
+    def __init__(self, messageTransform, vertexTransform, degreeNormalizeI: bool = True, degreeNormalizeJ: bool = True, aggregateJ: bool = True):
+        self.messageTransform, self.vertexTransform = messageTransform, vertexTransform
+        self.degreeNormalizeI, self.degreeNormalizeJ, self.aggregateJ = bool(degreeNormalizeI), bool(degreeNormalizeJ), bool(aggregateJ)
+
+    def forward(self, x: Graph) -> Graph:
+        assert x.edgeFeatures is not None, "MPNN needs edge features"
+        n = x.nodeFeatures.shape[0]
+        # built whatever the form and the type, on purpose: its construction is the endpoints' range check, and the degree factors come from
+        # its row pointers in the composed chain too; the cost is two sorts per graph, once (the graph caches it)
+        csr = x.edgeCsr()
+        message = mpnnMessage(x.nodeFeatures, x.edgeFeatures, x.edgeI, x.edgeJ, csr)
+        messageTx = self.messageTransform.forward(message)
+        aggregated = mpnnAggregate(n, messageTx, x.edgeI, x.edgeJ, self.degreeNormalizeI, self.degreeNormalizeJ, self.aggregateJ, csr, x._adjacencies)
+        updated = self.vertexTransform.forward(apply_op("Concatenate", [x.nodeFeatures, aggregated], i=[1]))
+        return x.copy(nodeFeatures=x.nodeFeatures + updated if updated.shape[1] == x.nodeFeatures.shape[1] else updated)
+
+    @property
+    def state(self) -> List[Variable]: return list(self.messageTransform.state) + list(self.vertexTransform.state)
+
+    @property
+    def parameters(self) -> List[Variable]: return [v for v in self.state if v.needsGrad]
+
+    def zeroGrad(self): self.messageTransform.zeroGrad(); self.vertexTransform.zeroGrad()
+    def asEval(self): self.messageTransform.asEval(); self.vertexTransform.asEval(); return self
+    def asTraining(self): self.messageTransform.asTraining(); self.vertexTransform.asTraining(); return self
+
+    def load(self, tensors: Sequence[STen]):
+        """Load.compose: the first len(messageTransform.state) tensors go to the message transform, the rest to the vertex transform"""
+        tensors = list(tensors)
+        k, m = len(self.messageTransform.state), len(self.vertexTransform.state)
+        assert len(tensors) == k + m, f"state has {k + m} tensors, got {len(tensors)}"
+        self.messageTransform.load(tensors[:k])
+        self.vertexTransform.load(tensors[k:])
