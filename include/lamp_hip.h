@@ -575,6 +575,16 @@ int lamp_convolution_chain_pair(lamp_tensor* out3[3], const lamp_tensor* x, cons
                                 const int64_t* dilation_a, const lamp_tensor* w_b, const lamp_tensor* bias_b_or_null,
                                 const int64_t* stride_b, const int64_t* padding_b, const int64_t* dilation_b, int nspatial,
                                 int64_t groups);
+/* out3 = {dx, dw_a, dw_b}: lamp_convolution_backward_input_pair (dx, with the optional addend) and lamp_convolution_backward_weight_pair (dw_a,
+ * dw_b) of the same arguments from one call - the whole backward of the two convolutions a residual block applies to its input.  The paired
+ * input gradient and the weight gradients read the same two output gradients; where a kernel takes all three (bf16, stride-2 3x3 pad 1 + 1x1
+ * pad 0 of narrow layers such as 6 -> 6 on 32x32 or 6 -> 16 on 16x16 maps) they are one launch that reads x and the gradients once; dx is
+ * bitwise the pair call's.  Every other geometry or dtype runs the two calls inside the entry point. */
+int lamp_convolution_backward_pair(lamp_tensor* out3[3], const lamp_tensor* x, const lamp_tensor* grad_out_a, const lamp_tensor* w_a,
+                                   const int64_t* stride_a, const int64_t* padding_a, const int64_t* dilation_a,
+                                   const lamp_tensor* grad_out_b, const lamp_tensor* w_b, const int64_t* stride_b,
+                                   const int64_t* padding_b, const int64_t* dilation_b, int nspatial, int64_t groups,
+                                   const lamp_tensor* addend_or_null);
 int lamp_avg_pool2d(lamp_tensor** out, const lamp_tensor* x, int64_t kernel, int64_t stride, int64_t padding,
                     int ceil_mode, int count_include_pad);
 int lamp_avg_pool2d_backward(lamp_tensor** out, const lamp_tensor* grad_out, const lamp_tensor* x, int64_t kernel,

@@ -28,6 +28,7 @@ constexpr int64_t SW_NO_CLAMP = INT64_MIN;
   X(conv_dgrad_accumulate, "LAMP_CONV_DGRAD_ACCUMULATE", BOOL, 1, 0, "a convolution's input gradient adds into the existing one in its epilogue") \
   X(conv_dgrad_pair, "LAMP_CONV_DGRAD_PAIR", BOOL, 1, 0, "input gradients of a block's 3x3 and sibling 1x1 from one launch")             \
   X(conv_wgrad_pair, "LAMP_CONV_WGRAD_PAIR", BOOL, 1, 0, "weight gradients of a block's 3x3 and sibling 1x1 from one launch")            \
+  X(conv_bwd_pair, "LAMP_CONV_BWD_PAIR", BOOL, 1, 0, "a block's paired input gradient and its two weight gradients from one call (0: the two pair calls)") \
   X(linear_bias_fused, "LAMP_LINEAR_BIAS_FUSED", BOOL, 1, 0, "a linear layer's bias in the GEMM epilogue (0: mm then add)")               \
   X(mult_add_fused, "LAMP_MULT_ADD_FUSED", BOOL, 1, 0, "x * scale + residual in one pass (0: mult then add)")                             \
   X(attention_as_written_for_cuda, "LAMP_ATTENTION_AS_WRITTEN_FOR_CUDA", BOOL, 0, 0, "multi-head attention as the reference's op chain instead of the fused kernels") \

@@ -735,6 +735,10 @@ struct ConvPairGrad {
   int64_t groups = 1;
   int waiting = -1;                            // which side's derivative is held for the input gradient
   int wwaiting = -1;                           // ... and for the weight gradients (pw, wout: the derivative and the parameter it belongs to)
+  // the merged call (lamp_convolution_backward_pair) made by the second input-gradient closure: both weight gradients, for the weight closure
+  // that runs next with the derivative dwp
+  Ten dw[2], dwp;
+  void drop_merged() { dw[0] = Ten(); dw[1] = Ten(); dwp = Ten(); }
 };
 static Var convolution_node(const Var& input, const Var& weight, const Var& bias, const std::vector<int64_t>& stride,
                             const std::vector<int64_t>& padding, const std::vector<int64_t>& dilation, bool transposed,
@@ -745,6 +749,8 @@ static Var convolution_node(const Var& input, const Var& weight, const Var& bias
   Ten iv = input->value, wv = weight->value;
   const bool fuse_accumulate = sw().conv_dgrad_accumulate;
   const bool fuse_pair = sw().conv_dgrad_pair;
+  const bool fuse_bwd_pair = sw().conv_bwd_pair && sw().conv_wgrad_pair;
+  Variable* const wvar = weight.get();
   auto back = [=](int which) {
     // (a plain function object: the pair's deferred form calls it again)
     std::function<void(const Ten&, Variable&)> single;
@@ -781,6 +787,7 @@ static Var convolution_node(const Var& input, const Var& weight, const Var& bias
           inp->pending.push_back([=] {
             ConvPairGrad& s2 = *pair;
             if (s2.wwaiting != pair_side) return;
+            s2.drop_merged();
             const Ten held = s2.side[pair_side].pw;
             Variable* wo = s2.side[pair_side].wout;
             s2.side[pair_side].pw = Ten(); s2.side[pair_side].wout = nullptr; s2.wwaiting = -1;
@@ -793,6 +800,15 @@ static Var convolution_node(const Var& input, const Var& weight, const Var& bias
         const Ten po = st.side[other].pw;
         Variable* wo = st.side[other].wout;
         st.side[other].pw = Ten(); st.side[other].wout = nullptr; st.wwaiting = -1;
+        if (st.dw[0].defined() && st.dwp.defined() && st.dwp.h() == p.h()) {
+          // this node's input-gradient closure has just made the merged call for (p, po): both weight gradients are waiting
+          const Ten da = st.dw[0], db = st.dw[1];
+          st.drop_merged();
+          (pair_side == 0 ? out : *wo).accumulate(da, true);
+          (pair_side == 0 ? *wo : out).accumulate(db, true);
+          return;
+        }
+        st.drop_merged();
         const Ten& pa = pair_side == 0 ? p : po;
         const Ten& pb = pair_side == 0 ? po : p;
         lamp_tensor* o2[2] = {nullptr, nullptr};
@@ -830,6 +846,20 @@ static Var convolution_node(const Var& input, const Var& weight, const Var& bias
       const Ten& pb = pair_side == 0 ? po : p;
       const bool have = out.has_grad() && out.grad.h()->is_device() && out.grad.dtype() == p.dtype();
       if (out.has_grad() && !have) { single(po, out); single(p, out); return; }
+      // The sibling's weight derivative is parked as well, and this node's weight closure runs next with p: the paired input gradient and
+      // both weight gradients read the same two derivatives - one call, which is one launch for the narrow stride-2 blocks.  The weight
+      // gradients wait in the pair for that closure (LAMP_CONV_BWD_PAIR=0, or any other order or condition: the two pair calls as before)
+      if (fuse_bwd_pair && !tls_backprop_hooked && st.wwaiting == other && st.side[other].pw.defined() && st.side[other].pw.h() == po.h() &&
+          st.side[other].wout && !wvar->op && wvar->needsGrad() && wvar->value.h()->is_device()) {
+        lamp_tensor* o3[3] = {nullptr, nullptr, nullptr};
+        HCALL(lamp_convolution_backward_pair(o3, iv.h(), pa.h(), st.side[0].w.h(), st.side[0].stride.data(), st.side[0].padding.data(),
+                                             st.side[0].dilation.data(), pb.h(), st.side[1].w.h(), st.side[1].stride.data(),
+                                             st.side[1].padding.data(), st.side[1].dilation.data(), ns, st.groups, have ? out.grad.h() : nullptr));
+        out.grad = Ten(o3[0]);
+        out.grad_shared = false;
+        st.dw[0] = Ten(o3[1]); st.dw[1] = Ten(o3[2]); st.dwp = p;
+        return;
+      }
       lamp_tensor* r = nullptr;
       HCALL(lamp_convolution_backward_input_pair(&r, iv.h(), pa.h(), st.side[0].w.h(), st.side[0].stride.data(), st.side[0].padding.data(),
                                                  st.side[0].dilation.data(), pb.h(), st.side[1].w.h(), st.side[1].stride.data(),
@@ -844,6 +874,7 @@ static Var convolution_node(const Var& input, const Var& weight, const Var& bias
   if (pair) op->reset = [pair] {
     pair->waiting = pair->wwaiting = -1;
     for (auto& sd : pair->side) { sd.p = Ten(); sd.pw = Ten(); sd.wout = nullptr; }
+    pair->drop_merged();
   };
   if (computed) return make_result(op, *computed);
   lamp_tensor* o = nullptr;

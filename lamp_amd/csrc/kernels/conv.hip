@@ -683,4 +683,44 @@ int lamp_convolution_backward_weight_pair(lamp_tensor* out2[2], const lamp_tenso
   LAMP_API_END
 }
 
+int lamp_convolution_backward_pair(lamp_tensor* out3[3], const lamp_tensor* x, const lamp_tensor* grad_out_a, const lamp_tensor* w_a,
+                                   const int64_t* stride_a, const int64_t* padding_a, const int64_t* dilation_a, const lamp_tensor* grad_out_b,
+                                   const lamp_tensor* w_b, const int64_t* stride_b, const int64_t* padding_b, const int64_t* dilation_b, int nspatial,
+                                   int64_t groups, const lamp_tensor* addend) {
+  LAMP_API_BEGIN
+  out3[0] = out3[1] = out3[2] = nullptr;
+  check_device_tensor(x, "input"); check_device_tensor(w_a, "first weight"); check_device_tensor(grad_out_a, "first grad_out");
+  check_device_tensor(w_b, "second weight"); check_device_tensor(grad_out_b, "second grad_out");
+  if (addend) check_device_tensor(addend, "addend");
+  const bool bf = x->dtype == kBF16 && w_a->dtype == kBF16 && w_b->dtype == kBF16 && grad_out_a->dtype == kBF16 && grad_out_b->dtype == kBF16 &&
+                  (!addend || addend->dtype == kBF16);
+  if (bf && nspatial == 2 && x->ndim == 4 && w_a->ndim == 4 && w_b->ndim == 4 && grad_out_a->ndim == 4 && grad_out_b->ndim == 4 &&
+      (!addend || addend->shape() == x->shape())) {
+    const int64_t zero2[2] = {0, 0};
+    ConvGeom ga = make_geom(x, w_a, stride_a, padding_a, dilation_a, nspatial, 0, zero2, groups);
+    ConvGeom gb = make_geom(x, w_b, stride_b, padding_b, dilation_b, nspatial, 0, zero2, groups);
+    auto grad_ok = [&](const lamp_tensor* gy, const ConvGeom& g) { return gy->sizes[0] == g.N && gy->sizes[1] == g.Cout && gy->sizes[2] == g.Ho && gy->sizes[3] == g.Wo; };
+    if (grad_ok(grad_out_a, ga) && grad_ok(grad_out_b, gb)) {
+      Hold xc(contiguous(x)), wa(contiguous_filter(w_a)), wb(contiguous_filter(w_b)), gya(contiguous(grad_out_a)), gyb(contiguous(grad_out_b));
+      Hold ac(addend ? contiguous(addend) : nullptr);
+      hipStream_t st = current_stream(x->device());
+      Hold dx(new_tensor(std::vector<int64_t>(x->sizes, x->sizes + x->ndim), x->dtype, x->device())), dwa(new_like(wa.get())), dwb(new_like(wb.get()));
+      if (narrow_conv_backward_pair(gya.get(), gyb.get(), xc.get(), wa.get(), wb.get(), ga, gb, dx.get(), dwa.get(), dwb.get(), st, ac.get())) {
+        out3[0] = dx.take(); out3[1] = dwa.take(); out3[2] = dwb.take();
+        return 0;
+      }
+    }
+  }
+  // the two pair calls (each validates its own arguments)
+  lamp_tensor* dxo = nullptr;
+  if (lamp_convolution_backward_input_pair(&dxo, x, grad_out_a, w_a, stride_a, padding_a, dilation_a, grad_out_b, w_b, stride_b, padding_b, dilation_b, nspatial,
+                                           groups, addend) != 0) throw Error(lamp_last_error());
+  Hold hdx(dxo);
+  lamp_tensor* o2[2] = {nullptr, nullptr};
+  if (lamp_convolution_backward_weight_pair(o2, x, grad_out_a, w_a, stride_a, padding_a, dilation_a, grad_out_b, w_b, stride_b, padding_b, dilation_b, nspatial,
+                                            groups) != 0) throw Error(lamp_last_error());
+  out3[0] = hdx.take(); out3[1] = o2[0]; out3[2] = o2[1];
+  LAMP_API_END
+}
+
 }  // extern "C"

@@ -39,6 +39,9 @@ bool narrow_conv_dgrad(const Tensor* dy, const Tensor* w, Tensor* dx, const Conv
 bool narrow_conv_dgrad_pair(const Tensor* dy, const Tensor* w, const ConvGeom& g, const Tensor* dy1, const Tensor* w1, const ConvGeom& g1, Tensor* dx,
                             hipStream_t st, const Tensor* addend, bool* addend_fused);
 bool narrow_conv_wgrad(const Tensor* dy, const Tensor* x, Tensor* dw, const ConvGeom& g, hipStream_t st);
+// dx (+ addend), dw and dw1 of a stride-2 3x3 + 1x1 pair of the same x from one launch (false: nothing launched)
+bool narrow_conv_backward_pair(const Tensor* dy, const Tensor* dy1, const Tensor* x, const Tensor* w, const Tensor* w1, const ConvGeom& g, const ConvGeom& g1,
+                               Tensor* dx, Tensor* dw, Tensor* dw1, hipStream_t st, const Tensor* addend = nullptr);
 bool narrow_conv_wgrad_pair(const Tensor* dy, const Tensor* dy1, const Tensor* x, Tensor* dw, Tensor* dw1, const ConvGeom& g, const ConvGeom& g1, hipStream_t st);
 
 // ---- conv_small.hip: narrow layers, image-per-workgroup LDS kernels (bf16 / f32 / f64)

@@ -90,6 +90,12 @@ __device__ __forceinline__ void ncv_stage_load(NcvPreT<NPF>& r, const NcvPlanT<N
     if (pl.dst[k] >= 0) r.v[k] = *reinterpret_cast<const uint4*>(((pl.src[k] >> 30) ? sp2 : sp) + (pl.src[k] & ((1 << 30) - 1)));
   });
 }
+// the 8 values of a packet, `dil` elements apart (the zero-dilated image of an input gradient)
+__device__ __forceinline__ void ncv_scatter8(unsigned short* d, const uint4& v, int dil) {
+  const unsigned int u[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int j = 0; j < 4; j++) { d[(2 * j) * dil] = (unsigned short)(u[j] & 0xffffu); d[(2 * j + 1) * dil] = (unsigned short)(u[j] >> 16); }
+}
 template <int NPF>
 __device__ __forceinline__ void ncv_stage_store(unsigned short* xs, const NcvPreT<NPF>& r, const NcvPlanT<NPF>& pl, int dil) {
   ncv_static_for<0, NPF>([&](auto kc) {
@@ -97,12 +103,7 @@ __device__ __forceinline__ void ncv_stage_store(unsigned short* xs, const NcvPre
     if (pl.dst[k] < 0) return;
     // (member-wise: a whole-struct copy is a memcpy, and a register array that only memcpys touch - dil a compile-time 1 - stays in scratch memory)
     if (dil == 1) *reinterpret_cast<uint4*>(xs + pl.dst[k]) = make_uint4(r.v[k].x, r.v[k].y, r.v[k].z, r.v[k].w);
-    else {
-      unsigned short* d = xs + pl.dst[k];
-      const unsigned int u[4] = {r.v[k].x, r.v[k].y, r.v[k].z, r.v[k].w};
-#pragma unroll
-      for (int j = 0; j < 4; j++) { d[(2 * j) * dil] = (unsigned short)(u[j] & 0xffffu); d[(2 * j + 1) * dil] = (unsigned short)(u[j] >> 16); }
-    }
+    else ncv_scatter8(xs + pl.dst[k], r.v[k], dil);
   });
 }
 
@@ -251,6 +252,19 @@ __device__ __forceinline__ void ncv_frag_setup(const NcvGeom& q, const nv_bf8* _
     koff[ks] = (c * q.Hs + r) * q.Ws * 2;
   });
 }
+//   ... of ONE parity class of the packed image only (PAR; cls 0: filter rows 0 and 2, k-steps [0, NK / 2); cls 1: the centre row and the
+//   second source, k-steps [NK / 2, NK)): what a wave needs whose super-tiles all start on rows of one parity
+template <int NK>
+__device__ __forceinline__ void ncv_frag_setup_class(const NcvGeom& q, const nv_bf8* __restrict__ wpk, int lane, int cls, nv_bf8 (&wfr)[NK / 2], int (&koff)[NK / 2]) {
+  ncv_static_for<0, NK / 2>([&](auto ksc) {
+    constexpr int i = decltype(ksc)::value;
+    wfr[i] = wpk[((cls ? NK / 2 : 0) + i) * 64 + lane];
+    const int p2 = i * 4 + (lane >> 4);
+    int c = cls ? p2 : p2 >> 1, r = cls ? 1 : 2 * (p2 & 1);
+    if (c >= (cls ? q.C : q.C1)) { c = 0; r = 0; }        // (padded pairs: zero weights, any valid address)
+    koff[i] = (c * q.Hs + r) * q.Ws * 2;
+  });
+}
 //   sum y (every row of st1 alike) and sum y^2 (diagonal of st2: row j of column j = lane & 15 is register j & 3 of lane group j >> 2) of a
 //   wave's `tiles` super-tiles
 struct NcvStatAcc { nv_f4 st1, st2; int tiles; };
@@ -288,13 +302,19 @@ __device__ __forceinline__ void ncv_stats_flush(float (*sst)[16][3], int lane, i
 //   smem: the LDS image; ap (ADD): this lane's plane of the addend; sa (STATS): the wave's running sums.
 //   MIRROR (stride 1, plain tiles): every 16-byte packet stored to yc also goes to row (h, column cg * 8) of the lane's channel plane mc (row
 //   pitch mws elements) of a second LDS image - the staged input of the convolution that reads this output next (ncv_chain_kernel)
-template <int NK, int SW, int PH0, int NS, bool ADD, bool STATS, bool PAR, bool MIRROR>
-__device__ __forceinline__ void ncv_super_tiles(const char* smem, const NcvGeom& q, const nv_bf8 (&wfr)[NK], const int (&koff)[NK], int a_off, float bv, int co,
+//   NW = NK / 2 (PAR, an even number of waves): a wave's super-tiles all have the parity of its index, so wfr / koff hold its class alone
+//   (ncv_frag_setup_class), k-step ks at index ks % NW
+//   KGRP > 0: the scheduler keeps the window reads of at most KGRP k-steps ahead of their MFMAs (a fence behind every KGRP-th k-step).  Left
+//   alone it hoists a whole class's reads - 8 k-steps of 8 to 12 registers with 16 k-steps - which a kernel that holds other state across
+//   the super-tiles (ncv_bwd_pair_kernel: the weight gradient's accumulators and the next round's packets) pays for in scratch memory
+template <int NK, int SW, int PH0, int NS, bool ADD, bool STATS, bool PAR, bool MIRROR, int NW = NK, int KGRP = 0>
+__device__ __forceinline__ void ncv_super_tiles(const char* smem, const NcvGeom& q, const nv_bf8 (&wfr)[NW], const int (&koff)[NW], int a_off, float bv, int co,
                                                 bf16_t* yc, const bf16_t* ap, NcvStatAcc& sa, unsigned short* mc, int mws, int lane, int wid, int nwaves) {
   constexpr int P = 8 / SW;
   constexpr int ND = P / NS;                               // accumulators (MFMAs per k-step) of a super-tile
   constexpr int NSEG = (PH0 + (ND - 1) * NS * SW + 7) < 16 ? 2 : 3;
   static_assert(!MIRROR || (P == 8 && !PAR), "the LDS copy takes whole 16-byte packets of plain tiles");
+  static_assert(NW == NK || (PAR && NW * 2 == NK), "all k-steps, or one parity class of them");
   const int ncg = q.Wo / P, TR = 16 / ncg;
   const int nsuper = q.Ho / TR;
   for (int st = wid; st < nsuper; st += nwaves) {
@@ -315,7 +335,7 @@ __device__ __forceinline__ void ncv_super_tiles(const char* smem, const NcvGeom&
       unsigned int sg[NSEG * 4 + 1];
 #pragma unroll
       for (int e = 0; e < NSEG; e++) {
-        const uint4 v = *reinterpret_cast<const uint4*>(base + koff[ks] + e * 16);
+        const uint4 v = *reinterpret_cast<const uint4*>(base + koff[ks % NW] + e * 16);
         sg[e * 4 + 0] = v.x; sg[e * 4 + 1] = v.y; sg[e * 4 + 2] = v.z; sg[e * 4 + 3] = v.w;
       }
       sg[NSEG * 4] = 0;
@@ -328,8 +348,9 @@ __device__ __forceinline__ void ncv_super_tiles(const char* smem, const NcvGeom&
         for (int j = 0; j < 4; j++) f[j] = (o & 1) ? __builtin_amdgcn_alignbit(sg[dq + j + 1], sg[dq + j], 16) : sg[dq + j];
         typedef unsigned int u4v __attribute__((ext_vector_type(4)));
         const u4v fv = {f[0], f[1], f[2], f[3]};
-        acc[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(nv_bf8, fv), wfr[ks], acc[d], 0, 0, 0);
+        acc[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(nv_bf8, fv), wfr[ks % NW], acc[d], 0, 0, 0);
       }
+      if constexpr (KGRP > 0) { if ((ks % NW) % KGRP == KGRP - 1) __builtin_amdgcn_sched_barrier(0); }
     };
     if constexpr (PAR) {
       // rows h0 + 2 tr of the dilated image hold values iff (row + r - top) is even: the class of k-steps whose r has the parity of (h0 + top)
@@ -687,6 +708,216 @@ __global__ __launch_bounds__(256) void ncv_wgrad_kernel(const bf16_t* __restrict
 // (s - pw) >> 1 in {-1, 0} (KW <= 3).  acc[pair tile][s] holds dW[co][(ci, r)][s].
 constexpr int NCV_OFFA = 8;   // column origin of the staged rows (both strides): 16-byte aligned segments
 constexpr int NCV_WPF = 6;    // 16-byte packets per thread the image-group prefetch holds
+// The pieces of the aligned-read kernel as device functions: ncv_wgrad2_kernel runs them for one weight gradient (or a 3x3's with its sibling
+// 1x1's), ncv_bwd_pair_kernel runs them beside the input gradient's super-tiles over the same staged gradients.
+//   Staging in two halves (as in ncv_fwd2_kernel): the x and dy packets of the NEXT image group are loaded into registers while this group is
+//   multiplied, and written to LDS after the barrier.  A group is [image][x packets | dy packets | second dy packets] of 16 bytes.  A thread
+//   handles the same packets of every group: source offsets (elements, from the group's first image; negative: a dy packet, below -2^30: a
+//   packet of the second gradient tensor) and LDS destinations (elements from xs) are computed once; im = image index within the group, or
+//   -1 (no packet).  The staged gradient image of one input image is [drows][HoWo], the second tensor's rows start at row2.
+//   DIL: dst2 = where the packet's 8 values go in the input gradient's zero-dilated image qd (ncv_stage_plan's placement; the group's first
+//   image only, -1 otherwise)
+template <int WPF> struct NcvWPlan { int src[WPF], dst[WPF], im[WPF], dst2[WPF]; };
+template <int SW, int WPF, bool DIL>
+__device__ __forceinline__ bool ncv_wg_plan(NcvWPlan<WPF>& pl, const NcvWGeom& q, int ximg, int drows, int row2, int tid, int nthreads, const NcvGeom& qd) {
+  const int HoWo = q.Ho * q.Wo;
+  const int xpk = (q.Cin * q.H * q.W) >> 3, dpk = (q.Cout * HoWo) >> 3, dpk2 = (q.Cout2 * HoWo) >> 3, per = xpk + dpk + dpk2;
+  const int rc = q.W >> 3, rcd = q.Wo >> 3;
+  const bool pf = q.IG * per <= WPF * nthreads;
+#pragma unroll
+  for (int k = 0; k < WPF; k++) {
+    const int idx = tid + k * nthreads;
+    const int im = idx / per, j = idx - im * per;
+    pl.im[k] = (pf && im < q.IG) ? im : -1;
+    pl.dst2[k] = -1;
+    if (j < xpk) {
+      const int b = j % rc, a = (j / rc) % q.H, c = j / (rc * q.H);
+      pl.src[k] = im * q.Cin * q.H * q.W + j * 8;
+      pl.dst[k] = im * ximg + (SW == 1 ? (c * q.Hs + q.ph + a) * q.Ws + NCV_OFFA + b * 8 : ((c * q.Hs + q.ph + a) * 2) * q.Ws + NCV_OFFA + b * 4);
+    } else {
+      const bool second = j >= xpk + dpk;
+      const int e = j - xpk - (second ? dpk : 0);
+      if (!second) {
+        pl.src[k] = -(im * q.Cout * HoWo + e * 8) - 1;
+        pl.dst[k] = q.IG * ximg + im * drows * HoWo + e * 8;
+      } else {
+        pl.src[k] = -(im * q.Cout2 * HoWo + e * 8) - 1 - (1 << 30);
+        pl.dst[k] = q.IG * ximg + im * drows * HoWo + row2 * HoWo + e * 8;
+      }
+      if (DIL && im == 0) {
+        const int b = e % rcd, a = (e / rcd) % q.Ho, c = e / (rcd * q.Ho) + (second ? qd.C1 : 0);
+        pl.dst2[k] = (c * qd.Hs + qd.top + a * qd.dil) * qd.Ws + qd.left + b * 8 * qd.dil;
+      }
+    }
+  }
+  return pf;
+}
+template <int WPF>
+__device__ __forceinline__ void ncv_wg_load(uint4 (&pre)[WPF], const NcvWPlan<WPF>& pl, const NcvWGeom& q, const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy,
+                                            const bf16_t* __restrict__ dy2, int64_t nb, int ig) {
+  const int HoWo = q.Ho * q.Wo;
+  const bf16_t* xg = x + nb * q.Cin * q.H * q.W;
+  const bf16_t* dg = dy + nb * q.Cout * HoWo;
+  const bf16_t* dg2 = dy2 + nb * q.Cout2 * HoWo;
+#pragma unroll
+  for (int k = 0; k < WPF; k++)
+    if (pl.im[k] >= 0 && pl.im[k] < ig) {
+      const bf16_t* sp = pl.src[k] >= 0 ? xg + pl.src[k] : pl.src[k] >= -(1 << 30) ? dg + (-pl.src[k] - 1) : dg2 + (-pl.src[k] - 1 - (1 << 30));
+      pre[k] = *reinterpret_cast<const uint4*>(sp);
+    }
+}
+//   one 16-byte packet of an x row; stride 2: de-interleaved into the row's even / odd column planes (Ws apart)
+template <int SW>
+__device__ __forceinline__ void ncv_wg_stage_x(unsigned short* dst, const uint4 v, int Ws) {
+  if (SW == 1) {
+    *reinterpret_cast<uint4*>(dst) = v;
+  } else {
+    uint2 ev, od;
+    ev.x = (v.x & 0xffffu) | (v.y << 16); ev.y = (v.z & 0xffffu) | (v.w << 16);
+    od.x = (v.x >> 16) | (v.y & 0xffff0000u); od.y = (v.z >> 16) | (v.w & 0xffff0000u);
+    *reinterpret_cast<uint2*>(dst) = ev;
+    *reinterpret_cast<uint2*>(dst + Ws) = od;
+  }
+}
+template <int SW, int WPF, bool DIL>
+__device__ __forceinline__ void ncv_wg_store(unsigned short* xs, unsigned short* xd, const uint4 (&pre)[WPF], const NcvWPlan<WPF>& pl, int ig, int Ws, int dil) {
+#pragma unroll
+  for (int k = 0; k < WPF; k++) {
+    if (pl.im[k] < 0 || pl.im[k] >= ig) continue;
+    const uint4 v = pre[k];
+    if (SW == 1 || pl.src[k] < 0) *reinterpret_cast<uint4*>(xs + pl.dst[k]) = v;      // stride 1 rows and dy packets: one 16-byte write
+    else ncv_wg_stage_x<SW>(xs + pl.dst[k], v, Ws);
+    if (DIL && pl.dst2[k] >= 0) ncv_scatter8(xd + pl.dst2[k], v, dil);
+  }
+}
+//   per-lane row offset (bytes) of pair tile pt: pair = pt*16 + (lane & 15) -> (ci, r)
+template <int SW, int NPT>
+__device__ __forceinline__ void ncv_wg_pair_offsets(const NcvWGeom& q, int lane, int (&poff)[NPT]) {
+  const int npairs = q.Cin * q.kh;
+#pragma unroll
+  for (int pt = 0; pt < NPT; pt++) {
+    int pair = pt * 16 + (lane & 15);
+    if (pair >= npairs) pair = 0;                                    // padded columns: computed, never written
+    const int ci = pair / q.kh, r = pair - ci * q.kh;
+    poff[pt] = (SW == 1 ? (ci * q.Hs + r) * q.Ws : (ci * q.Hs + r) * 2 * q.Ws) * 2;
+  }
+}
+//   The k-loop over the `nchunks` 32-pixel chunks of a staged image group, this wave's share (chunk wid, wid + 4, ...: four waves).
+//   W2: a second A fragment, rows [16, 32) of the staged gradient image (a sibling 1x1's output gradient that does not fit beside the
+//   3x3's in the 16 MFMA rows), multiplied with the centre-tap fragment only: acc2[pair tile] holds its dW[co2][(ci, r)] at s = KW / 2
+template <int KW, int PW, int SW, int NPT, bool W2>
+__device__ __forceinline__ void ncv_wg_chunks(const unsigned short* xs, const unsigned short* ds, int drows, const NcvWGeom& q, int ximg, const int (&poff)[NPT],
+                                              nv_f4 (&acc)[NPT][KW], nv_f4 (&acc2)[NPT], int nchunks, int wid, int lane) {
+  const int HoWo = q.Ho * q.Wo;
+  for (int ch = wid; ch < nchunks; ch += 4) {
+    const int pg = ch * 32 + (lane >> 4) * 8;
+    const int im = pg / HoWo, pp = pg - im * HoWo;
+    const int ho = pp / q.Wo, wo0 = pp - ho * q.Wo;
+    const nv_s8 a = *reinterpret_cast<const nv_s8*>(ds + (im * drows + (lane & 15)) * HoWo + pp);
+    const nv_bf8 af = __builtin_bit_cast(nv_bf8, a);
+    nv_bf8 af2 = af;
+    if constexpr (W2) af2 = __builtin_bit_cast(nv_bf8, *reinterpret_cast<const nv_s8*>(ds + (im * drows + 16 + (lane & 15)) * HoWo + pp));
+    // byte address of element column (wo0 + NCV_OFFA - 8) of this lane's group row: segment -1
+    const char* xb = reinterpret_cast<const char*>(xs + im * ximg) +
+                     (SW == 1 ? (ho * q.Ws + wo0 + NCV_OFFA - 8) * 2 : ((ho * 2) * 2 * q.Ws + wo0 + NCV_OFFA - 8) * 2);
+#pragma unroll
+    for (int pt = 0; pt < NPT; pt++) {
+      const char* rowp = xb + poff[pt];
+      if (SW == 1) {
+        // 24 elements around the aligned window: [seg-1 | seg0 | seg+1]
+        constexpr bool need_m = PW > 0, need_p = (KW - 1 - PW) > 0;
+        unsigned int sg[13];
+        const uint4 z = make_uint4(0, 0, 0, 0);
+        const uint4 v0 = need_m ? *reinterpret_cast<const uint4*>(rowp) : z;
+        const uint4 v1 = *reinterpret_cast<const uint4*>(rowp + 16);
+        const uint4 v2 = need_p ? *reinterpret_cast<const uint4*>(rowp + 32) : z;
+        sg[0] = v0.x; sg[1] = v0.y; sg[2] = v0.z; sg[3] = v0.w; sg[4] = v1.x; sg[5] = v1.y; sg[6] = v1.z; sg[7] = v1.w;
+        sg[8] = v2.x; sg[9] = v2.y; sg[10] = v2.z; sg[11] = v2.w; sg[12] = 0;
+#pragma unroll
+        for (int s = 0; s < KW; s++) {
+          const int o = 8 + s - PW;                              // compile-time element offset of the window
+          const int dq = o >> 1;
+          typedef unsigned int u4v __attribute__((ext_vector_type(4)));
+          u4v f;
+#pragma unroll
+          for (int j = 0; j < 4; j++) f[j] = (o & 1) ? __builtin_amdgcn_alignbit(sg[dq + j + 1], sg[dq + j], 16) : sg[dq + j];
+          acc[pt][s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, __builtin_bit_cast(nv_bf8, f), acc[pt][s], 0, 0, 0);
+          if (W2 && s == KW / 2) acc2[pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af2, __builtin_bit_cast(nv_bf8, f), acc2[pt], 0, 0, 0);
+        }
+      } else {
+        // per parity plane: [seg-1 | seg0]; filter column s -> plane (s - PW) & 1, element offset 8 + ((s - PW) >> 1)
+        unsigned int sg[2][9];
+#pragma unroll
+        for (int par = 0; par < 2; par++) {
+          const uint4 v0 = *reinterpret_cast<const uint4*>(rowp + par * q.Ws * 2);
+          const uint4 v1 = *reinterpret_cast<const uint4*>(rowp + par * q.Ws * 2 + 16);
+          sg[par][0] = v0.x; sg[par][1] = v0.y; sg[par][2] = v0.z; sg[par][3] = v0.w;
+          sg[par][4] = v1.x; sg[par][5] = v1.y; sg[par][6] = v1.z; sg[par][7] = v1.w; sg[par][8] = 0;
+        }
+#pragma unroll
+        for (int s = 0; s < KW; s++) {
+          const int t = s - PW, par = t & 1, half = (t - par) >> 1;   // compile time
+          const int o = 8 + half, dq = o >> 1;
+          typedef unsigned int u4v __attribute__((ext_vector_type(4)));
+          u4v f;
+#pragma unroll
+          for (int j = 0; j < 4; j++) f[j] = (o & 1) ? __builtin_amdgcn_alignbit(sg[par][dq + j + 1], sg[par][dq + j], 16) : sg[par][dq + j];
+          acc[pt][s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, __builtin_bit_cast(nv_bf8, f), acc[pt][s], 0, 0, 0);
+          if (W2 && s == KW / 2) acc2[pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af2, __builtin_bit_cast(nv_bf8, f), acc2[pt], 0, 0, 0);
+        }
+      }
+    }
+  }
+}
+//   The end of a workgroup: the four k-loop waves' sums through red ([4 waves][16][NPT * KW * 16]; W2: and red2, [4 waves][16][NPT * 16]),
+//   added in wave order by all `nthreads` threads -> this workgroup's partial sums.  D: column = pair within the tile, rows = 4 output channels.
+template <int KW, int NPT, bool W2>
+__device__ __forceinline__ void ncv_wg_finish(float* red, float* red2, const nv_f4 (&acc)[NPT][KW], const nv_f4 (&acc2)[NPT], const NcvWGeom& q,
+                                              float* __restrict__ partial, float* __restrict__ partial2, int tid, int nthreads, int wid, int lane) {
+  constexpr int NCOLT = NPT * KW * 16;                               // accumulator columns per output channel
+  if (wid < 4) {
+#pragma unroll
+    for (int pt = 0; pt < NPT; pt++)
+#pragma unroll
+      for (int s = 0; s < KW; s++)
+#pragma unroll
+        for (int rr = 0; rr < 4; rr++) red[(wid * 16 + (lane >> 4) * 4 + rr) * NCOLT + (pt * KW + s) * 16 + (lane & 15)] = acc[pt][s][rr];
+    if constexpr (W2) {
+#pragma unroll
+      for (int pt = 0; pt < NPT; pt++)
+#pragma unroll
+        for (int rr = 0; rr < 4; rr++) red2[(wid * 16 + (lane >> 4) * 4 + rr) * (NPT * 16) + pt * 16 + (lane & 15)] = acc2[pt][rr];
+    }
+  }
+  __syncthreads();
+  const int O = q.Cout * q.ncol;
+  for (int i = tid; i < O; i += nthreads) {
+    const int co = i / q.ncol, cidx = i - co * q.ncol;              // cidx = (ci*kh + r)*kw + s
+    const int pair = cidx / KW, s = cidx - pair * KW;
+    const int col = ((pair >> 4) * KW + s) * 16 + (pair & 15);
+    float a = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; w++) a += red[(w * 16 + co) * NCOLT + col];
+    partial[(int64_t)blockIdx.x * O + i] = a;
+  }
+  // the sibling 1x1's weight gradient [Cout2][Cin]: the centre tap of rows Cout ... (W2: of the second fragment's rows)
+  const int O2 = q.Cout2 * q.Cin;
+  for (int i = tid; i < O2; i += nthreads) {
+    const int co2 = i / q.Cin, ci = i - co2 * q.Cin;
+    const int pair = ci * q.kh + (q.kh >> 1), s = KW >> 1;
+    float a = 0.f;
+    if constexpr (W2) {
+      const int col = (pair >> 4) * 16 + (pair & 15);
+#pragma unroll
+      for (int w = 0; w < 4; w++) a += red2[(w * 16 + co2) * (NPT * 16) + col];
+    } else {
+      const int col = ((pair >> 4) * KW + s) * 16 + (pair & 15);
+#pragma unroll
+      for (int w = 0; w < 4; w++) a += red[(w * 16 + q.Cout + co2) * NCOLT + col];
+    }
+    partial2[(int64_t)blockIdx.x * O2 + i] = a;
+  }
+}
 template <int KW, int PW, int SW, int NPT>
 __global__ __launch_bounds__(256) void ncv_wgrad2_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, float* __restrict__ partial, NcvWGeom q,
                                                          int images_per_block, const bf16_t* __restrict__ dy2, float* __restrict__ partial2) {
@@ -696,23 +927,14 @@ __global__ __launch_bounds__(256) void ncv_wgrad2_kernel(const bf16_t* __restric
   const int ximg = q.Cin * q.Hs * q.Ws * (SW == 2 ? 2 : 1);
   unsigned short* xs = reinterpret_cast<unsigned short*>(smem);
   unsigned short* ds = xs + q.IG * ximg;
-  constexpr int NCOLT = NPT * KW * 16;                               // accumulator columns per output channel
-  float* red = reinterpret_cast<float*>(ds + q.IG * 16 * HoWo);      // [4 waves][16][NCOLT]
+  float* red = reinterpret_cast<float*>(ds + q.IG * 16 * HoWo);      // [4 waves][16][NPT * KW * 16]
   {
     const int tot = q.IG * (ximg + 16 * HoWo);
     for (int o = tid * 8; o < tot; o += 256 * 8) *reinterpret_cast<uint4*>(xs + o) = make_uint4(0, 0, 0, 0);
   }
-  // per-lane row offset (bytes) of pair tile pt: pair = pt*16 + (lane & 15) -> (ci, r)
-  const int npairs = q.Cin * q.kh;
   int poff[NPT];
-#pragma unroll
-  for (int pt = 0; pt < NPT; pt++) {
-    int pair = pt * 16 + (lane & 15);
-    if (pair >= npairs) pair = 0;                                    // padded columns: computed, never written
-    const int ci = pair / q.kh, r = pair - ci * q.kh;
-    poff[pt] = (SW == 1 ? (ci * q.Hs + r) * q.Ws : (ci * q.Hs + r) * 2 * q.Ws) * 2;
-  }
-  nv_f4 acc[NPT][KW];
+  ncv_wg_pair_offsets<SW, NPT>(q, lane, poff);
+  nv_f4 acc[NPT][KW], none[NPT];
 #pragma unroll
   for (int pt = 0; pt < NPT; pt++)
 #pragma unroll
@@ -720,80 +942,28 @@ __global__ __launch_bounds__(256) void ncv_wgrad2_kernel(const bf16_t* __restric
 
   const int64_t n0 = (int64_t)blockIdx.x * images_per_block, n1 = min<int64_t>(n0 + images_per_block, q.N);
   const int chunks_per_img = HoWo >> 5;
-  // Staging in two halves (as in ncv_fwd2_kernel): the x and dy packets of the NEXT image group are loaded into registers while this
-  // group is multiplied, and written to LDS after the barrier.  A group is [image][x packets | dy packets] of 16 bytes.
-  const int xpk = (q.Cin * q.H * q.W) >> 3, dpk = (q.Cout * HoWo) >> 3, dpk2 = (q.Cout2 * HoWo) >> 3, per = xpk + dpk + dpk2;
+  const int xpk = (q.Cin * q.H * q.W) >> 3, dpk = (q.Cout * HoWo) >> 3, dpk2 = (q.Cout2 * HoWo) >> 3;
   const int rc = q.W >> 3;
-  // a thread handles the same packets of every group: source offsets (elements, from the group's first image) and LDS destinations
-  // (elements from xs) are computed once; meta = image index within the group, or -1 (no packet)
-  const bool pf = q.IG * per <= NCV_WPF * 256;
   uint4 pre[NCV_WPF];
-  int p_src[NCV_WPF], p_dst[NCV_WPF], p_im[NCV_WPF];
-#pragma unroll
-  for (int k = 0; k < NCV_WPF; k++) {
-    const int idx = tid + k * 256;
-    const int im = idx / per, j = idx - im * per;
-    p_im[k] = (pf && im < q.IG) ? im : -1;
-    if (j < xpk) {
-      const int b = j % rc, a = (j / rc) % q.H, c = j / (rc * q.H);
-      p_src[k] = im * q.Cin * q.H * q.W + j * 8;
-      p_dst[k] = im * ximg + (SW == 1 ? (c * q.Hs + q.ph + a) * q.Ws + NCV_OFFA + b * 8 : ((c * q.Hs + q.ph + a) * 2) * q.Ws + NCV_OFFA + b * 4);
-    } else if (j < xpk + dpk) {
-      p_src[k] = -(im * q.Cout * HoWo + (j - xpk) * 8) - 1;          // negative: a dy packet
-      p_dst[k] = q.IG * ximg + im * 16 * HoWo + (j - xpk) * 8;
-    } else {
-      p_src[k] = -(im * q.Cout2 * HoWo + (j - xpk - dpk) * 8) - 1 - (1 << 30);   // below -2^30: a packet of the second gradient tensor
-      p_dst[k] = q.IG * ximg + im * 16 * HoWo + q.Cout * HoWo + (j - xpk - dpk) * 8;
-    }
-  }
-  auto pre_load = [&](int64_t nb, int ig) {
-    const bf16_t* xg = x + nb * q.Cin * q.H * q.W;
-    const bf16_t* dg = dy + nb * q.Cout * HoWo;
-    const bf16_t* dg2 = dy2 + nb * q.Cout2 * HoWo;
-#pragma unroll
-    for (int k = 0; k < NCV_WPF; k++)
-      if (p_im[k] >= 0 && p_im[k] < ig) {
-        const bf16_t* sp = p_src[k] >= 0 ? xg + p_src[k] : p_src[k] >= -(1 << 30) ? dg + (-p_src[k] - 1) : dg2 + (-p_src[k] - 1 - (1 << 30));
-        pre[k] = *reinterpret_cast<const uint4*>(sp);
-      }
-  };
-  auto stage_x = [&](unsigned short* dst, const uint4 v) {
-    if (SW == 1) {
-      *reinterpret_cast<uint4*>(dst) = v;
-    } else {
-      uint2 ev, od;
-      ev.x = (v.x & 0xffffu) | (v.y << 16); ev.y = (v.z & 0xffffu) | (v.w << 16);
-      od.x = (v.x >> 16) | (v.y & 0xffff0000u); od.y = (v.z >> 16) | (v.w & 0xffff0000u);
-      *reinterpret_cast<uint2*>(dst) = ev;
-      *reinterpret_cast<uint2*>(dst + q.Ws) = od;
-    }
-  };
-  auto pre_store = [&](int ig) {
-#pragma unroll
-    for (int k = 0; k < NCV_WPF; k++) {
-      if (p_im[k] < 0 || p_im[k] >= ig) continue;
-      const uint4 v = pre[k];
-      if (SW == 1 || p_src[k] < 0) *reinterpret_cast<uint4*>(xs + p_dst[k]) = v;      // stride 1 rows and dy packets: one 16-byte write
-      else stage_x(xs + p_dst[k], v);
-    }
-  };
+  NcvWPlan<NCV_WPF> plan;
+  const bool pf = ncv_wg_plan<SW, NCV_WPF, false>(plan, q, ximg, 16, q.Cout, tid, 256, NcvGeom{});
   auto x_dst = [&](unsigned short* xi, int j) {
     const int b = j % rc, a = (j / rc) % q.H, c = j / (rc * q.H);
     return xi + (SW == 1 ? (c * q.Hs + q.ph + a) * q.Ws + NCV_OFFA + b * 8 : ((c * q.Hs + q.ph + a) * 2) * q.Ws + NCV_OFFA + b * 4);
   };
 
-  if (pf && n0 < n1) pre_load(n0, (int)min<int64_t>(q.IG, n1 - n0));
+  if (pf && n0 < n1) ncv_wg_load(pre, plan, q, x, dy, dy2, n0, (int)min<int64_t>(q.IG, n1 - n0));
   for (int64_t nb = n0; nb < n1; nb += q.IG) {
     const int ig = (int)min<int64_t>(q.IG, n1 - nb);
     __syncthreads();
 #if defined(NCV_WSKIP) && (NCV_WSKIP & 4)   // diagnostic builds only: 1 = no k-loop, 4 = no staging (requests and LDS writes)
     if (nb < 0)
 #endif
-    if (pf) pre_store(ig);
+    if (pf) ncv_wg_store<SW, NCV_WPF, false>(xs, nullptr, pre, plan, ig, q.Ws, 1);
     else for (int im = 0; im < ig; im++) {
       const bf16_t* xp = x + (nb + im) * q.Cin * q.H * q.W;
       unsigned short* xi = xs + im * ximg;
-      for (int i = tid; i < xpk; i += 256) stage_x(x_dst(xi, i), *reinterpret_cast<const uint4*>(xp + i * 8));
+      for (int i = tid; i < xpk; i += 256) ncv_wg_stage_x<SW>(x_dst(xi, i), *reinterpret_cast<const uint4*>(xp + i * 8), q.Ws);
       const bf16_t* dp = dy + (nb + im) * q.Cout * HoWo;
       unsigned short* di = ds + im * 16 * HoWo;
       for (int i = tid; i < dpk; i += 256) *reinterpret_cast<uint4*>(di + i * 8) = *reinterpret_cast<const uint4*>(dp + i * 8);
@@ -804,96 +974,101 @@ __global__ __launch_bounds__(256) void ncv_wgrad2_kernel(const bf16_t* __restric
 #if defined(NCV_WSKIP) && (NCV_WSKIP & 4)
     if (nb < 0)
 #endif
-    if (pf && nb + q.IG < n1) pre_load(nb + q.IG, (int)min<int64_t>(q.IG, n1 - nb - q.IG));      // in flight during the MFMAs
-    const int nchunks = ig * chunks_per_img;
+    if (pf && nb + q.IG < n1) ncv_wg_load(pre, plan, q, x, dy, dy2, nb + q.IG, (int)min<int64_t>(q.IG, n1 - nb - q.IG));      // in flight during the MFMAs
 #if defined(NCV_WSKIP) && (NCV_WSKIP & 1)
     if (nb < 0)
 #endif
-    for (int ch = wid; ch < nchunks; ch += 4) {
-      const int pg = ch * 32 + (lane >> 4) * 8;
-      const int im = pg / HoWo, pp = pg - im * HoWo;
-      const int ho = pp / q.Wo, wo0 = pp - ho * q.Wo;
-      const nv_s8 a = *reinterpret_cast<const nv_s8*>(ds + (im * 16 + (lane & 15)) * HoWo + pp);
-      const nv_bf8 af = __builtin_bit_cast(nv_bf8, a);
-      // byte address of element column (wo0 + NCV_OFFA - 8) of this lane's group row: segment -1
-      const char* xb = reinterpret_cast<const char*>(xs + im * ximg) +
-                       (SW == 1 ? (ho * q.Ws + wo0 + NCV_OFFA - 8) * 2 : ((ho * 2) * 2 * q.Ws + wo0 + NCV_OFFA - 8) * 2);
+    ncv_wg_chunks<KW, PW, SW, NPT, false>(xs, ds, 16, q, ximg, poff, acc, none, ig * chunks_per_img, wid, lane);
+  }
+  ncv_wg_finish<KW, NPT, false>(red, nullptr, acc, none, q, partial, partial2, tid, 256, wid, lane);
+}
+
+// A block's whole backward over its entry pair in ONE launch: dx = round(dgrad3x3(dy, w) + dgrad1x1(dy2, w2)) [+ addend], dW of the 3x3 and
+// dW of the 1x1 (stride 2, 3x3 pad 1 + 1x1 pad 0 of the same x; the geometries narrow_conv_dgrad_pair and ncv_wgrad2_kernel<3, 1, 2, .> take).
+// The paired input gradient and the weight gradients read the same two output gradients: per round of IG images a workgroup requests x
+// and both gradients ONCE (the register prefetch of ncv_wgrad2_kernel) and writes the gradients into LDS twice from the same registers -
+// as the plain [drows][Ho*Wo] image the weight gradient's k-loop reads and (the round's first image; the others are copied over from the
+// plain image when their turn comes) as the zero-dilated, padded image the parity super-tiles of ncv_fwd2_kernel<.., PAR> read.  Then
+// ncv_wg_chunks and ncv_super_tiles run as in the kernels they come from: same MFMA chains over the same values, same partition of the
+// images over workgroups as the weight gradient's own launch where two workgroups fit a CU, so dx and (then) dW keep their bits.
+// `red` lies over the dilated image: it is only used after the last round.
+// 256 threads run the k-loop and then the super-tiles of a staged round.  (The form with 512 threads - waves 0-3 in the k-loop while waves 4-7
+// run the super-tiles - needs four waves per SIMD for two workgroups per CU, 128 registers: it spilled 100 - 215 of them in every
+// instantiation, the k-loop's side alone holds 127 and the super-tiles' 153.  Not kept.)
+// A wave's super-tiles all start on rows of one parity (four waves, super-tile st = wid + 4 k), so it keeps the weight fragments of that
+// parity class only: NK / 2 of them.
+//   W2: see ncv_wg_chunks (6 -> 16 + 6 -> 16: the 1x1's 16 rows are a second A fragment).  WPF: packets per thread of the prefetch.
+template <int NK, bool ADD, int NPT, bool W2, int WPF>
+__global__ __launch_bounds__(256, 2) void ncv_bwd_pair_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ dy2, const bf16_t* __restrict__ x,
+                                                               const nv_bf8* __restrict__ wpk, bf16_t* dx, const bf16_t* add, float* __restrict__ partial,
+                                                               float* __restrict__ partial2, NcvWGeom q, NcvGeom qd, int images_per_block) {
+  constexpr int KW = 3, PW = 1, SW = 2, PH0 = 7, NS = 2;
+  constexpr int NCOLT = NPT * KW * 16;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int HoWo = q.Ho * q.Wo;
+  const int ximg = q.Cin * q.Hs * q.Ws * 2;
+  const int drows = W2 ? 32 : 16;
+  unsigned short* xs = reinterpret_cast<unsigned short*>(smem);      // [IG][ximg]
+  unsigned short* ds = xs + q.IG * ximg;                             // [IG][drows][HoWo]
+  unsigned short* xd = ds + q.IG * drows * HoWo;                     // the dilated image of ONE input image [qd.C][qd.Hs][qd.Ws]
+  float* red = reinterpret_cast<float*>(xd);
+  float* red2 = red + 4 * 16 * NCOLT;
+  const int64_t n0 = (int64_t)blockIdx.x * images_per_block, n1 = min<int64_t>(n0 + images_per_block, q.N);
+  uint4 pre[WPF];
+  NcvWPlan<WPF> plan;
+  ncv_wg_plan<SW, WPF, true>(plan, q, ximg, drows, W2 ? 16 : q.Cout, tid, 256, qd);      // (the launcher takes only groups that fit the prefetch)
+  if (n0 < n1) ncv_wg_load(pre, plan, q, x, dy, dy2, n0, (int)min<int64_t>(q.IG, n1 - n0));
+  nv_bf8 wfr[NK / 2];
+  int koff[NK / 2];
+  ncv_frag_setup_class<NK>(qd, wpk, lane, (wid + qd.top) & 1, wfr, koff);
+  {
+    const int tot = q.IG * (ximg + drows * HoWo) + qd.C * qd.Hs * qd.Ws;
+    for (int o = tid * 8; o < tot; o += 256 * 8) *reinterpret_cast<uint4*>(xs + o) = make_uint4(0, 0, 0, 0);
+  }
+  int poff[NPT];
+  ncv_wg_pair_offsets<SW, NPT>(q, lane, poff);
+  nv_f4 acc[NPT][KW], acc2[NPT];
 #pragma unroll
-      for (int pt = 0; pt < NPT; pt++) {
-        const char* rowp = xb + poff[pt];
-        if (SW == 1) {
-          // 24 elements around the aligned window: [seg-1 | seg0 | seg+1]
-          constexpr bool need_m = PW > 0, need_p = (KW - 1 - PW) > 0;
-          unsigned int sg[13];
-          const uint4 z = make_uint4(0, 0, 0, 0);
-          const uint4 v0 = need_m ? *reinterpret_cast<const uint4*>(rowp) : z;
-          const uint4 v1 = *reinterpret_cast<const uint4*>(rowp + 16);
-          const uint4 v2 = need_p ? *reinterpret_cast<const uint4*>(rowp + 32) : z;
-          sg[0] = v0.x; sg[1] = v0.y; sg[2] = v0.z; sg[3] = v0.w; sg[4] = v1.x; sg[5] = v1.y; sg[6] = v1.z; sg[7] = v1.w;
-          sg[8] = v2.x; sg[9] = v2.y; sg[10] = v2.z; sg[11] = v2.w; sg[12] = 0;
+  for (int pt = 0; pt < NPT; pt++) {
+    acc2[pt] = nv_f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-          for (int s = 0; s < KW; s++) {
-            const int o = 8 + s - PW;                              // compile-time element offset of the window
-            const int dq = o >> 1;
-            typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-            u4v f;
-#pragma unroll
-            for (int j = 0; j < 4; j++) f[j] = (o & 1) ? __builtin_amdgcn_alignbit(sg[dq + j + 1], sg[dq + j], 16) : sg[dq + j];
-            acc[pt][s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, __builtin_bit_cast(nv_bf8, f), acc[pt][s], 0, 0, 0);
-          }
-        } else {
-          // per parity plane: [seg-1 | seg0]; filter column s -> plane (s - PW) & 1, element offset 8 + ((s - PW) >> 1)
-          unsigned int sg[2][9];
-#pragma unroll
-          for (int par = 0; par < 2; par++) {
-            const uint4 v0 = *reinterpret_cast<const uint4*>(rowp + par * q.Ws * 2);
-            const uint4 v1 = *reinterpret_cast<const uint4*>(rowp + par * q.Ws * 2 + 16);
-            sg[par][0] = v0.x; sg[par][1] = v0.y; sg[par][2] = v0.z; sg[par][3] = v0.w;
-            sg[par][4] = v1.x; sg[par][5] = v1.y; sg[par][6] = v1.z; sg[par][7] = v1.w; sg[par][8] = 0;
-          }
-#pragma unroll
-          for (int s = 0; s < KW; s++) {
-            const int t = s - PW, par = t & 1, half = (t - par) >> 1;   // compile time
-            const int o = 8 + half, dq = o >> 1;
-            typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-            u4v f;
-#pragma unroll
-            for (int j = 0; j < 4; j++) f[j] = (o & 1) ? __builtin_amdgcn_alignbit(sg[par][dq + j + 1], sg[par][dq + j], 16) : sg[par][dq + j];
-            acc[pt][s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, __builtin_bit_cast(nv_bf8, f), acc[pt][s], 0, 0, 0);
-          }
-        }
+    for (int s = 0; s < KW; s++) acc[pt][s] = nv_f4{0.f, 0.f, 0.f, 0.f};
+  }
+  // the input gradient's lane constants (as ncv_fwd2_kernel, parity tiles)
+  const int co = lane & 7;
+  const int ncg = qd.Wo / 8;
+  const int a_tr = (lane & 15) / ncg, a_cg = (lane & 15) - a_tr * ncg;
+  const int a_off = (2 * a_tr * qd.sh * qd.Ws + a_cg * 8 + (qd.wx - PH0)) * 2;
+  const int HoWo_d = qd.Ho * qd.Wo;
+  NcvStatAcc none{nv_f4{0.f, 0.f, 0.f, 0.f}, nv_f4{0.f, 0.f, 0.f, 0.f}, 0};
+  const int chunks_per_img = HoWo >> 5;
+  for (int64_t nb = n0; nb < n1; nb += q.IG) {
+    const int ig = (int)min<int64_t>(q.IG, n1 - nb);
+    __syncthreads();                                     // zero fill / the previous round's reads are done
+    ncv_wg_store<SW, WPF, true>(xs, xd, pre, plan, ig, q.Ws, qd.dil);
+    __syncthreads();
+    if (nb + q.IG < n1) ncv_wg_load(pre, plan, q, x, dy, dy2, nb + q.IG, (int)min<int64_t>(q.IG, n1 - nb - q.IG));      // in flight during the MFMAs
+    ncv_wg_chunks<KW, PW, SW, NPT, W2>(xs, ds, drows, q, ximg, poff, acc, acc2, ig * chunks_per_img, wid, lane);
+    for (int im = 0; im < ig; im++) {
+      if (im > 0) {
+        // images 1 .. IG-1 of a round reach the dilated image from the plain one: ncv_stage_plan's packets, read from LDS
+        __syncthreads();                                 // the super-tiles of image im - 1 are done
+        const NcvPlanT<2> dplan = ncv_stage_plan<2>(qd, tid, 256);
+        const bf16_t* pa = reinterpret_cast<const bf16_t*>(ds + im * drows * HoWo);
+        NcvPreT<2> t;
+        ncv_stage_load(t, dplan, pa, pa + (W2 ? 16 : q.Cout) * HoWo);
+        ncv_stage_store(xd, t, dplan, qd.dil);
+        __syncthreads();
       }
+      const int64_t n = nb + im;
+      bf16_t* yc = dx + (n * qd.CO + co) * HoWo_d;
+      const bf16_t* ap = ADD ? add + (n * qd.CO + co) * HoWo_d : nullptr;
+      ncv_super_tiles<NK, 1, PH0, NS, ADD, false, true, false, NK / 2, (NK >= 8 ? 2 : 0)>(reinterpret_cast<const char*>(xd), qd, wfr, koff, a_off, 0.f, co, yc, ap, none, nullptr, 0, lane, wid, 4);
     }
   }
-  // D: column = pair within the tile, rows = 4 output channels; combine the 4 waves in a fixed order
-#pragma unroll
-  for (int pt = 0; pt < NPT; pt++)
-#pragma unroll
-    for (int s = 0; s < KW; s++)
-#pragma unroll
-      for (int rr = 0; rr < 4; rr++) red[(wid * 16 + (lane >> 4) * 4 + rr) * NCOLT + (pt * KW + s) * 16 + (lane & 15)] = acc[pt][s][rr];
-  __syncthreads();
-  const int O = q.Cout * q.ncol;
-  for (int i = tid; i < O; i += 256) {
-    const int co = i / q.ncol, cidx = i - co * q.ncol;              // cidx = (ci*kh + r)*kw + s
-    const int pair = cidx / KW, s = cidx - pair * KW;
-    const int col = ((pair >> 4) * KW + s) * 16 + (pair & 15);
-    float a = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; w++) a += red[(w * 16 + co) * NCOLT + col];
-    partial[(int64_t)blockIdx.x * O + i] = a;
-  }
-  // the sibling 1x1's weight gradient [Cout2][Cin]: the centre tap of rows Cout ...
-  const int O2 = q.Cout2 * q.Cin;
-  for (int i = tid; i < O2; i += 256) {
-    const int co2 = i / q.Cin, ci = i - co2 * q.Cin;
-    const int pair = ci * q.kh + (q.kh >> 1), s = KW >> 1;
-    const int col = ((pair >> 4) * KW + s) * 16 + (pair & 15);
-    float a = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; w++) a += red[(w * 16 + q.Cout + co2) * NCOLT + col];
-    partial2[(int64_t)blockIdx.x * O2 + i] = a;
-  }
+  __syncthreads();                                       // the last super-tiles are done: red lies over their image
+  ncv_wg_finish<KW, NPT, W2>(red, red2, acc, acc2, q, partial, partial2, tid, 256, wid, lane);
 }
 
 // (the reduction of the per-block partial sums lives in wgrad_reduce.h: it runs batched with the other layers' reductions)
@@ -1331,6 +1506,43 @@ static void ncv_wg_launch(const bf16_t* dy, const bf16_t* x, float* partial, con
   hipLaunchKernelGGL((ncv_wgrad_kernel<NT, SW>), dim3(blocks), dim3(256), lds, st, dy, x, partial, q, ipb);
 }
 
+// the instantiation of ncv_wgrad2_kernel for (filter width, stride, pair tiles)
+static const void* ncv_wgrad2_fn(int kw, int SW, int npt) {
+  const void* kfn = nullptr;
+#define NCV_WG2(KWv, PWv, SWv, NPTv) kfn = (const void*)ncv_wgrad2_kernel<KWv, PWv, SWv, NPTv>
+#define NCV_WG2_NPT(KWv, PWv, SWv) do { if (npt == 1) NCV_WG2(KWv, PWv, SWv, 1); else if (npt == 2) NCV_WG2(KWv, PWv, SWv, 2); else NCV_WG2(KWv, PWv, SWv, 3); } while (0)
+  if (kw == 5) NCV_WG2_NPT(5, 2, 1);
+  else if (kw == 3 && SW == 1) NCV_WG2_NPT(3, 1, 1);
+  else if (kw == 3) NCV_WG2_NPT(3, 1, 2);
+  else if (SW == 1) NCV_WG2_NPT(1, 0, 1);
+  else NCV_WG2_NPT(1, 0, 2);
+#undef NCV_WG2_NPT
+#undef NCV_WG2
+  return kfn;
+}
+// workgroups per CU of an aligned weight-gradient launch (LDS and registers), and the partition of N images in rounds of IG over the
+// workgroups that are co-resident then: the number of workgroups, ipb = images per workgroup
+static int ncv_wgrad2_per_cu(const void* kfn, int threads, size_t lds) {
+  return std::min((int)std::max<size_t>(1, std::min<size_t>(4, (size_t)(150 * 1024) / lds)), kernel_occupancy(kfn, threads, lds));
+}
+static int ncv_partition(int per_cu, int64_t N, int IG, int& ipb) {
+  const int64_t rounds = (N + IG - 1) / IG;
+  const int nb = (int)std::min<int64_t>(rounds, (int64_t)num_cus() * per_cu);
+  ipb = (int)((rounds + nb - 1) / nb) * IG;
+  return (int)((N + ipb - 1) / ipb);
+}
+static int ncv_wgrad2_partition(const void* kfn, size_t lds, int64_t N, int IG, int& ipb) { return ncv_partition(ncv_wgrad2_per_cu(kfn, 256, lds), N, IG, ipb); }
+// the aligned kernel's staged geometry (x parity planes / rows at column NCV_OFFA); returns the pair tiles
+static int ncv_wgrad2_geom(const ConvGeom& g, int cout2, NcvWGeom& q) {
+  q.N = (int)g.N; q.Cin = (int)g.Cin; q.Cout = (int)g.Cout; q.H = (int)g.H; q.W = (int)g.W; q.Ho = (int)g.Ho; q.Wo = (int)g.Wo;
+  q.kh = g.kh; q.kw = g.kw; q.ph = g.ph; q.pw = g.pw; q.Cout2 = cout2;
+  q.ncol = (int)g.Cin * g.kh * g.kw;
+  q.Hs = std::max((int)g.H + 2 * g.ph, ((int)g.Ho - 1) * g.sh + g.kh);
+  if (g.sh == 1) q.Ws = round_up(NCV_OFFA + std::max((int)g.W, (int)g.Wo + 8) + 8, 8);
+  else q.Ws = round_up(NCV_OFFA + std::max((int)g.W / 2, (int)g.Wo) + 8, 8);
+  q.IG = std::max(1, 256 / (int)(g.Ho * g.Wo));                      // >= 8 chunks of 32 pixels per round
+  return (int)((g.Cin * g.kh + 15) / 16);
+}
 // second (optional): the output gradient of a sibling 1x1 convolution of the same x and ITS weight gradient: both from the one launch of the
 // aligned kernel (false, nothing launched, when that kernel does not take the pair)
 struct NcvSecondWgrad { const Tensor* dy; Tensor* dw; };
@@ -1357,29 +1569,16 @@ static bool ncv_wgrad_run(const Tensor* dy, const Tensor* x, Tensor* dw, const C
   const bool aligned = g.kh == g.kw && npt <= 3 &&
                        ((g.kw == 5 && g.pw == 2 && SW == 1) || (g.kw == 3 && g.pw == 1) || (g.kw == 1 && g.pw == 0));
   if (aligned) {
-    if (SW == 1) q.Ws = round_up(NCV_OFFA + std::max((int)g.W, (int)g.Wo + 8) + 8, 8);
-    else q.Ws = round_up(NCV_OFFA + std::max((int)g.W / 2, (int)g.Wo) + 8, 8);
+    ncv_wgrad2_geom(g, cout2, q);
     const int ximg2 = q.Cin * q.Hs * q.Ws * (SW == 2 ? 2 : 1);
     const int ncolt = npt * g.kw * 16;
     const size_t lds2 = (size_t)q.IG * (ximg2 + 16 * HoWo) * 2 + (size_t)4 * 16 * ncolt * 4;
     if (lds2 <= 150 * 1024) {
       const int O = q.Cout * q.ncol;
-      const void* kfn = nullptr;
-#define NCV_WG2(KWv, PWv, SWv, NPTv) kfn = (const void*)ncv_wgrad2_kernel<KWv, PWv, SWv, NPTv>
-#define NCV_WG2_NPT(KWv, PWv, SWv) do { if (npt == 1) NCV_WG2(KWv, PWv, SWv, 1); else if (npt == 2) NCV_WG2(KWv, PWv, SWv, 2); else NCV_WG2(KWv, PWv, SWv, 3); } while (0)
-      if (g.kw == 5) NCV_WG2_NPT(5, 2, 1);
-      else if (g.kw == 3 && SW == 1) NCV_WG2_NPT(3, 1, 1);
-      else if (g.kw == 3) NCV_WG2_NPT(3, 1, 2);
-      else if (SW == 1) NCV_WG2_NPT(1, 0, 1);
-      else NCV_WG2_NPT(1, 0, 2);
-#undef NCV_WG2_NPT
-#undef NCV_WG2
+      const void* kfn = ncv_wgrad2_fn(g.kw, SW, npt);
       allow_big_lds(kfn);
-      const int per_cu = std::min((int)std::max<size_t>(1, std::min<size_t>(4, (size_t)(150 * 1024) / lds2)), kernel_occupancy(kfn, 256, lds2));
-      const int64_t rounds = (g.N + q.IG - 1) / q.IG;
-      const int nb = (int)std::min<int64_t>(rounds, (int64_t)num_cus() * per_cu);
-      const int ipb = (int)((rounds + nb - 1) / nb) * q.IG;
-      const int nblocks = (int)((g.N + ipb - 1) / ipb);
+      int ipb = 0;
+      const int nblocks = ncv_wgrad2_partition(kfn, lds2, g.N, q.IG, ipb);
       int64_t ps[1] = {(int64_t)nblocks * O};
       Hold partial(new_tensor(ps, 1, kF32, dy->device()));
       const int O2 = cout2 * q.Cin;
@@ -1467,6 +1666,93 @@ bool narrow_conv_wgrad_pair(const Tensor* dy, const Tensor* dy1, const Tensor* x
   if (g.groups != 1 || g1.groups != 1 || g.dh != 1 || g.dw != 1 || g1.dh != 1 || g1.dw != 1) return false;
   const NcvSecondWgrad sw{dy1, dw1};
   return ncv_wgrad_run(dy, x, dw, g, st, &sw);
+}
+
+
+// dx, dw and dw1 of a block's 3x3 pad 1 + 1x1 pad 0 stride-2 pair from ONE launch of ncv_bwd_pair_kernel: the values of narrow_conv_dgrad_pair
+// and of the weight-gradient launches (narrow_conv_wgrad_pair, or two narrow_conv_wgrad where the two gradients do not share the 16 MFMA rows).
+// false = nothing launched: the caller runs those.  Taken when the input gradient is the parity form of the aligned-window kernel (two-shift,
+// window phase 7), the weight gradient the aligned-read form with two pair tiles, a round fits the register prefetch and one workgroup's images
+// fit the LDS.  The workgroups and their images are those of the 3x3 weight gradient's own launch wherever as many workgroups fit a CU.
+bool narrow_conv_backward_pair(const Tensor* dy, const Tensor* dy1, const Tensor* x, const Tensor* w, const Tensor* w1, const ConvGeom& g, const ConvGeom& g1,
+                               Tensor* dx, Tensor* dw, Tensor* dw1, hipStream_t st, const Tensor* addend) {
+  if (!sw().conv_bwd_pair || !sw().conv_dgrad_pair || !sw().conv_wgrad_pair) return false;
+  if (x->dtype != kBF16 || dy->dtype != kBF16 || dy1->dtype != kBF16 || w->dtype != kBF16 || w1->dtype != kBF16) return false;
+  if (g.kh != 3 || g.kw != 3 || g.ph != 1 || g.pw != 1 || g1.kh != 1 || g1.kw != 1 || g1.ph != 0 || g1.pw != 0) return false;
+  if (g.sh != 2 || g.sw != 2 || g1.sh != 2 || g1.sw != 2 || g.Ho != g1.Ho || g.Wo != g1.Wo || g.H != g1.H || g.W != g1.W || g.Cin != g1.Cin || g.N != g1.N) return false;
+  if (g.groups != 1 || g1.groups != 1 || g.dh != 1 || g.dw != 1 || g1.dh != 1 || g1.dw != 1 || g1.Cout > 16) return false;
+  if (g.W % 8 != 0 || g.Wo % 8 != 0 || (g.Ho * g.Wo) % 32 != 0) return false;
+  const int cout2 = (int)g1.Cout;
+  // the input gradient: the plan of narrow_conv_dgrad_pair
+  NcvLaunchPlan lp;
+  if (!ncv_plan(g, x->dtype, true, false, true, cout2, lp)) return false;
+  if (!lp.aligned || lp.nke <= 0 || lp.NS != 2 || lp.ph0 != 7 || lp.q.sw != 1 || lp.q.W % 8 != 0) return false;
+  if (!(lp.NK2 == 6 || lp.NK2 == 8 || lp.NK2 == 16)) return false;
+  NcvGeom qd = lp.q;
+  qd.pf = 1;
+  // the weight gradients: the geometry of ncv_wgrad2_kernel<3, 1, 2, .>
+  const bool w2 = g.Cout + cout2 > 16;
+  NcvWGeom q;
+  if (ncv_wgrad2_geom(g, cout2, q) != 2) return false;
+  const int HoWo = q.Ho * q.Wo, cpi = HoWo >> 5;
+  const int ximg = q.Cin * q.Hs * q.Ws * 2, drows = w2 ? 32 : 16;
+  const int ncolt = 2 * 3 * 16;
+  const size_t red_bytes = (size_t)4 * 16 * ncolt * 4 + (w2 ? (size_t)4 * 16 * 32 * 4 : 0);
+  auto lds_of = [&](int IG) { return (size_t)IG * (ximg + drows * HoWo) * 2 + std::max(lp.lds, red_bytes); };
+  // the reference launch's rounds decide the partition; this kernel's rounds may be shorter (a wave meets the same chunks in the same order
+  // as long as a round is a multiple of four chunks), which is what lets two workgroups share a CU beside the dilated image
+  const int IG_ref = q.IG;
+  while (lds_of(q.IG) * 2 > 150 * 1024 && q.IG % 2 == 0 && ((q.IG / 2) * cpi) % 4 == 0) q.IG /= 2;
+  const size_t lds = lds_of(q.IG);
+  if (lds > 150 * 1024) return false;
+  const int per = (q.Cin * q.H * q.W + (q.Cout + cout2) * HoWo) >> 3;
+  if (q.IG * per > NCV_WPF * 256) return false;                      // (the kernel stages through the register prefetch only)
+  const int threads = 256;
+  if (q.IG > 1 && (int64_t)qd.C * qd.H * qd.W > (int64_t)2 * threads * 8) return false;      // (an image's copy from the plain to the dilated image: two packets per thread)
+  const bool with_add = addend != nullptr;
+  // (the 16-k-step forms hold four packets per thread: with six their registers do not fit two workgroups per CU)
+  const void* kfn = nullptr;
+#define NCV_BP(NKv, W2v, WPFv) kfn = with_add ? (const void*)ncv_bwd_pair_kernel<NKv, true, 2, W2v, WPFv> : (const void*)ncv_bwd_pair_kernel<NKv, false, 2, W2v, WPFv>
+  if (lp.NK2 == 6 && !w2) NCV_BP(6, false, NCV_WPF);
+  else if (lp.NK2 == 8 && !w2) NCV_BP(8, false, NCV_WPF);
+  else if (lp.NK2 == 16 && q.IG * per <= 4 * 256) { if (w2) NCV_BP(16, true, 4); else NCV_BP(16, false, 4); }
+  else return false;
+#undef NCV_BP
+  allow_big_lds(kfn);
+  // the partition of the 3x3 weight gradient's own launch, unless fewer of these workgroups fit a CU
+  const void* kref = ncv_wgrad2_fn(3, 2, 2);
+  const size_t lds_ref = (size_t)IG_ref * (ximg + 16 * HoWo) * 2 + (size_t)4 * 16 * ncolt * 4;
+  const int per_cu = std::min(ncv_wgrad2_per_cu(kref, 256, lds_ref), ncv_wgrad2_per_cu(kfn, threads, lds));
+  int ipb = 0;
+  const int nblocks = ncv_partition(per_cu, g.N, IG_ref, ipb);
+  const NcvW wq = ncv_weights_of(w, g, true, lp, w1, cout2);
+  Hold wpk_h(ncv_packed_weights(w, wq, st, w1));
+  const nv_bf8* wpk = reinterpret_cast<const nv_bf8*>(static_cast<const Tensor*>(wpk_h.get())->ptr<bf16_t>());
+  const int O = q.Cout * q.ncol, O2 = cout2 * q.Cin;
+  int64_t ps[1] = {(int64_t)nblocks * O}, ps2[1] = {(int64_t)nblocks * O2};
+  Hold partial(new_tensor(ps, 1, kF32, dy->device())), partial2(new_tensor(ps2, 1, kF32, dy->device()));
+  {
+    // the three parts' work and traffic, less the second read of the two gradients
+    const double dy_by = (double)g.N * (g.Cout + cout2) * HoWo * 2.0;
+    const double pair_fl = 2.0 * (double)g.N * cout2 * (double)g.Ho * g.Wo * (double)g.Cin;
+    const double pair_by = ((double)g.N * cout2 * g.Ho * g.Wo + (double)cout2 * g.Cin) * 2.0;
+    KernelTimer kt("conv_bwd_narrow", 2.0 * (conv_flops(g) + pair_fl), 2.0 * (conv_bytes(g, 2) + pair_by) - dy_by, st);
+    const bf16_t* dp = dy->ptr<bf16_t>(); const bf16_t* dp2 = dy1->ptr<bf16_t>(); const bf16_t* xp = x->ptr<bf16_t>();
+    bf16_t* dxp = dx->ptr<bf16_t>();
+    const bf16_t* addp = with_add ? addend->ptr<bf16_t>() : (const bf16_t*)nullptr;
+    float* pp = partial->ptr<float>(); float* pp2 = partial2->ptr<float>();
+    int ipb_arg = ipb;
+    void* args[] = {(void*)&dp, (void*)&dp2, (void*)&xp, (void*)&wpk, (void*)&dxp, (void*)&addp, (void*)&pp, (void*)&pp2, (void*)&q, (void*)&qd, (void*)&ipb_arg};
+    HIP_CHECK(hipLaunchKernel(kfn, dim3(nblocks), dim3(threads), args, lds, st));
+    LAMP_LAUNCH_CHECK();
+  }
+  WgradReduceArgs ra{};
+  ra.kind = 1; ra.O = O; ra.nsplit = nblocks; ra.blocks = (int)(((int64_t)O * 64 + 255) / 256);
+  wgrad_reduce_enqueue(ra, partial.get(), dw, st);
+  WgradReduceArgs rb{};
+  rb.kind = 1; rb.O = O2; rb.nsplit = nblocks; rb.blocks = (int)(((int64_t)O2 * 64 + 255) / 256);
+  wgrad_reduce_enqueue(rb, partial2.get(), dw1, st);
+  return true;
 }
 
 }  // namespace lamp
