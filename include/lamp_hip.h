@@ -827,6 +827,16 @@ int lamp_adamw_step_(lamp_tensor* const* params, lamp_tensor* const* grads, lamp
 int lamp_sgdw_step_(lamp_tensor* const* params, lamp_tensor* const* grads, lamp_tensor* const* velocity_or_null,
                     int n, const double* lr, const double* weight_decay, const double* momentum,
                     double schedule_factor);
+/* Rectified Adam (nn/RAdam.scala:67-140) and Yogi (nn/Yogi.scala:73-133): params/grads/m/v are n tensors of one dtype each
+ * (no mixed-precision mode: the reference's moments are zeros_like(param)); every hyperparameter array holds one value per
+ * tensor.  RAdam takes the rectified or the plain-momentum branch per tensor from step_count and that tensor's beta2.
+ * Yogi OVERWRITES grads with g*g*sign(v - g*g), as the reference's in-place pow_ / *= do (its two-step KAT depends on it). */
+int lamp_radam_step_(lamp_tensor* const* params, lamp_tensor* const* grads, lamp_tensor* const* m,
+                     lamp_tensor* const* v, int n, const double* lr, const double* weight_decay, const double* beta1,
+                     const double* beta2, double eps, double schedule_factor, int64_t step_count);
+int lamp_yogi_step_(lamp_tensor* const* params, lamp_tensor* const* grads, lamp_tensor* const* m,
+                    lamp_tensor* const* v, int n, const double* lr, const double* weight_decay, const double* beta1,
+                    const double* beta2, double eps, double schedule_factor, int64_t step_count, int debias);
 /* flat bucket helpers for data parallel training: pack n tensors into one
  * contiguous f32 bucket scaled by `scale`, and unpack with a (device-resident) divisor */
 int lamp_flatten_into_(lamp_tensor* bucket, lamp_tensor* const* ts, int n, double scale);

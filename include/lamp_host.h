@@ -135,6 +135,12 @@ int lamp_optimizer_adamw_tagged(lamp_optimizer** out, lamp_tensor* const* params
                                 const double* beta1, const double* beta2, double eps, double clip, int debias, int mixed_precision);
 int lamp_optimizer_sgdw(lamp_optimizer** out, lamp_tensor* const* params, int n, double learning_rate, double weight_decay,
                         double momentum /* < 0: none */, double clip);
+/* nn/RAdam.scala, nn/Yogi.scala: arrays of n values (OptimizerHyperparameter resolved per parameter); state = [stepCount] ++ mt ++ vt.
+ * Yogi.step overwrites the gradient tensors it is handed (Yogi.scala:95-98). */
+int lamp_optimizer_radam(lamp_optimizer** out, lamp_tensor* const* params, int n, const double* weight_decay, const double* learning_rate,
+                         const double* beta1, const double* beta2, double eps, double clip);
+int lamp_optimizer_yogi(lamp_optimizer** out, lamp_tensor* const* params, int n, const double* weight_decay, const double* learning_rate,
+                        const double* beta1, const double* beta2, double eps, double clip, int debias);
 int lamp_optimizer_step(lamp_optimizer* o, lamp_tensor* const* gradients /* NULL entries = None */, int n, double schedule_factor);
 int lamp_optimizer_num_state(lamp_optimizer* o, int64_t* out);
 int lamp_optimizer_state(lamp_optimizer* o, int64_t index, lamp_tensor** out);

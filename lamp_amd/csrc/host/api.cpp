@@ -375,6 +375,30 @@ int lamp_optimizer_adamw_tagged(lamp_optimizer** out, lamp_tensor* const* params
   *out = o;
   LAMP_API_END
 }
+int lamp_optimizer_radam(lamp_optimizer** out, lamp_tensor* const* params, int n, const double* wd, const double* lr, const double* b1,
+                         const double* b2, double eps, double clip) {
+  LAMP_API_BEGIN
+  LAMP_CHECK(wd && lr && b1 && b2, "lamp_optimizer_radam: one value per parameter for every hyperparameter");
+  std::vector<Ten> ps;
+  for (int i = 0; i < n; i++) ps.push_back(borrow(params[i]));
+  auto* o = new lamp_optimizer();
+  o->o = std::make_shared<RAdam>(ps, wd, lr, b1, b2, eps, clip >= 0, clip);
+  *out = o;
+  LAMP_API_END
+}
+int lamp_optimizer_yogi(lamp_optimizer** out, lamp_tensor* const* params, int n, const double* wd, const double* lr, const double* b1,
+                        const double* b2, double eps, double clip, int debias) {
+  LAMP_API_BEGIN
+  LAMP_CHECK(wd && lr && b1 && b2, "lamp_optimizer_yogi: one value per parameter for every hyperparameter");
+  std::vector<Ten> ps;
+  for (int i = 0; i < n; i++) ps.push_back(borrow(params[i]));
+  auto y = std::make_shared<Yogi>(ps, wd, lr, b1, b2, eps, clip >= 0, clip);
+  y->debias = debias != 0;
+  auto* o = new lamp_optimizer();
+  o->o = y;
+  *out = o;
+  LAMP_API_END
+}
 int lamp_optimizer_sgdw(lamp_optimizer** out, lamp_tensor* const* params, int n, double lr, double wd, double momentum, double clip) {
   LAMP_API_BEGIN
   std::vector<Ten> ps;

@@ -377,6 +377,52 @@ void AdamW::step(const std::vector<Ten>& gradients, double scheduleFactor) {
                          stepCount, debias));
 }
 
+// ---- RAdam, Yogi (nn/RAdam.scala, nn/Yogi.scala) ------------------------------------------------------
+MomentOptimizer::MomentOptimizer(const std::vector<Ten>& params, const double* wd, const double* lr, const double* b1, const double* b2,
+                                 double eps_, bool has_clip_, double clip_)
+    : parameters(params), weightDecay(wd, wd + params.size()), learningRate(lr, lr + params.size()), beta1(b1, b1 + params.size()),
+      beta2(b2, b2 + params.size()), eps(eps_), has_clip(has_clip_), clip(clip_) {
+  for (auto& p : parameters) { mt.push_back(ops::zeros_like(p)); vt.push_back(ops::zeros_like(p)); }
+  stepCountSTen = ops::scalar(0.0, kF64, parameters.empty() ? 0 : parameters[0].device());
+}
+std::vector<Ten> MomentOptimizer::state() {
+  ops::fill_(stepCountSTen, (double)stepCount);
+  std::vector<Ten> s = {stepCountSTen};
+  for (auto& t : mt) s.push_back(t);
+  for (auto& t : vt) s.push_back(t);
+  return s;
+}
+void MomentOptimizer::load(const std::vector<Ten>& tensors) {
+  Optimizer::load(tensors);
+  if (!tensors.empty()) counters_from_state();
+}
+void MomentOptimizer::counters_from_state() {
+  double v = 0;
+  HCALL(lamp_item(stepCountSTen.h(), &v));
+  stepCount = (int64_t)v;
+}
+void MomentOptimizer::step(const std::vector<Ten>& gradients, double scheduleFactor) {
+  LAMP_CHECK(gradients.size() == parameters.size(), "Optimizer.step: got " << gradients.size() << " gradients for " << parameters.size() << " parameters");
+  std::vector<lamp_tensor*> p, g, m, v;
+  std::vector<double> lr, wd, b1, b2;
+  for (size_t i = 0; i < parameters.size(); i++) {
+    if (!gradients[i].defined()) continue;     // skipped: its moments stay as they are
+    p.push_back(parameters[i].h()); g.push_back(gradients[i].h()); m.push_back(mt[i].h()); v.push_back(vt[i].h());
+    lr.push_back(learningRate[i]); wd.push_back(weightDecay[i]); b1.push_back(beta1[i]); b2.push_back(beta2[i]);
+  }
+  if (has_clip && !g.empty()) HCALL(lamp_gradient_clipping_(g.data(), (int)g.size(), clip));
+  stepCount += 1;               // once per step, whatever is defined; stepCountSTen follows when the state is asked for
+  update(p.data(), g.data(), m.data(), v.data(), (int)p.size(), lr.data(), wd.data(), b1.data(), b2.data(), scheduleFactor);
+}
+void RAdam::update(lamp_tensor* const* p, lamp_tensor* const* g, lamp_tensor* const* m, lamp_tensor* const* v, int n, const double* lr,
+                   const double* wd, const double* b1, const double* b2, double scheduleFactor) {
+  HCALL(lamp_radam_step_(p, g, m, v, n, lr, wd, b1, b2, eps, scheduleFactor, stepCount));
+}
+void Yogi::update(lamp_tensor* const* p, lamp_tensor* const* g, lamp_tensor* const* m, lamp_tensor* const* v, int n, const double* lr,
+                  const double* wd, const double* b1, const double* b2, double scheduleFactor) {
+  HCALL(lamp_yogi_step_(p, g, m, v, n, lr, wd, b1, b2, eps, scheduleFactor, stepCount, debias));
+}
+
 SGDW::SGDW(const std::vector<Ten>& params, double lr, double wd, bool has_m, double mom, bool has_clip_, double clip_)
     : parameters(params), learningRate(lr), weightDecay(wd), momentum(mom), has_momentum(has_m), has_clip(has_clip_), clip(clip_) {
   if (has_momentum) for (auto& p : parameters) velocity.push_back(ops::zeros_like(p));

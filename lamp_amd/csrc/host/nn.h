@@ -157,6 +157,35 @@ struct AdamW : Optimizer {      // nn/AdamW.scala:29-177
   void load(const std::vector<Ten>& tensors) override;   // also restores stepCount from state()[0]
   void counters_from_state() override;
 };
+// RAdam and Yogi share everything but the update: moments of the parameter's own dtype (no mixed-precision mode), one hyperparameter
+// value per parameter, state() = [stepCountSTen] ++ mt ++ vt
+struct MomentOptimizer : Optimizer {
+  std::vector<Ten> parameters, mt, vt;
+  std::vector<double> weightDecay, learningRate, beta1, beta2;   // one value per parameter
+  double eps; bool has_clip; double clip;
+  int64_t stepCount = 0;
+  Ten stepCountSTen;            // f64 scalar, state()[0]
+  MomentOptimizer(const std::vector<Ten>& params, const double* wd, const double* lr, const double* b1, const double* b2, double eps,
+                  bool has_clip, double clip);
+  void step(const std::vector<Ten>& gradients, double scheduleFactor) override;
+  std::vector<Ten> state() override;
+  void load(const std::vector<Ten>& tensors) override;   // also restores stepCount from state()[0]
+  void counters_from_state() override;
+  // the fused update over the tensors whose gradient is defined (stepCount is already this step's)
+  virtual void update(lamp_tensor* const* p, lamp_tensor* const* g, lamp_tensor* const* m, lamp_tensor* const* v, int n, const double* lr,
+                      const double* wd, const double* b1, const double* b2, double scheduleFactor) = 0;
+};
+struct RAdam : MomentOptimizer {   // nn/RAdam.scala:32-141; the branch of a step depends on stepCount, so load() must restore it
+  using MomentOptimizer::MomentOptimizer;
+  void update(lamp_tensor* const* p, lamp_tensor* const* g, lamp_tensor* const* m, lamp_tensor* const* v, int n, const double* lr,
+              const double* wd, const double* b1, const double* b2, double scheduleFactor) override;
+};
+struct Yogi : MomentOptimizer {    // nn/Yogi.scala:38-134; step() overwrites the gradients it is handed (Yogi.scala:95-98)
+  bool debias = true;
+  using MomentOptimizer::MomentOptimizer;
+  void update(lamp_tensor* const* p, lamp_tensor* const* g, lamp_tensor* const* m, lamp_tensor* const* v, int n, const double* lr,
+              const double* wd, const double* b1, const double* b2, double scheduleFactor) override;
+};
 struct SGDW : Optimizer {       // nn/SGD.scala:19-99
   std::vector<Ten> parameters, velocity;
   double learningRate, weightDecay, momentum; bool has_momentum, has_clip; double clip;

@@ -1,10 +1,10 @@
-// Fused multi-tensor optimiser kernels: AdamW, SGDW, global-norm gradient clipping and the
+// Fused multi-tensor optimiser kernels: AdamW, SGDW, RAdam, Yogi, global-norm gradient clipping and the
 // flat gradient bucket used by data-parallel training.
 //
 // Replaces the per-tensor ATen call chains of lamp's optimisers with ONE launch over all
 // parameter tensors (reference: lamp-core/src/main/scala/lamp/nn/AdamW.scala:101-176 - mul_,
 // add_out, mul_, addcmul_out, sqrt, add_(eps), add_out(wd), addcdiv_out per tensor;
-// nn/SGD.scala:46-98; nn/package.scala:72-100 gradientClippingInPlace;
+// nn/SGD.scala:46-98; nn/RAdam.scala:86-137; nn/Yogi.scala:93-129; nn/package.scala:72-100 gradientClippingInPlace;
 // lamp-data/.../distributed/package.scala:690-719 averageGradients).
 // The arithmetic and its order follow the reference line by line; the ResNet step has 37
 // parameter tensors, i.e. ~300 tiny launches become one.
@@ -76,6 +76,115 @@ __global__ __launch_bounds__(256) void adamw_kernel(MultiArgs a) {
     p[i] = store_as<T>(pv);
     if (model) model[i] = store_as<G>(load_as<acc_t<G>>(store_as<T>(pv)));
   }
+}
+
+// One chunk of an update over (param, grad, m, v) of ONE dtype: f(p, g, m, v) on acc_t values per element, every stored value rounded
+// once.  These kernels are pure bandwidth (7 or 8 streams per element), so the chunk moves in 16-byte packets where all four bases are
+// on one (a chunk starts a multiple of MT_CHUNK elements into its tensor: aligned iff the tensor is) and element-wise past the last
+// whole packet.  WRITE_G: the gradient is written back (Yogi).
+template <class T, bool WRITE_G, class F>
+__device__ __forceinline__ void mt_update_chunk(const MultiArgs& a, int t, F f) {
+  using A = acc_t<T>;
+  constexpr int W = 16 / sizeof(T);
+  const int64_t begin = (int64_t)(blockIdx.x - a.blk_start[t]) * MT_CHUNK;
+  const int64_t end = min(begin + MT_CHUNK, a.numel[t]);
+  T* p = (T*)a.p[0][t];
+  T* g = (T*)a.p[1][t];
+  T* m = (T*)a.p[2][t];
+  T* v = (T*)a.p[3][t];
+  int64_t i0 = begin;
+  if (((((uintptr_t)(p + begin)) | ((uintptr_t)(g + begin)) | ((uintptr_t)(m + begin)) | ((uintptr_t)(v + begin))) & 15) == 0) {
+    const int nv = (int)((end - begin) / W);
+    Vec<T, W>* pq = reinterpret_cast<Vec<T, W>*>(p + begin);
+    Vec<T, W>* gq = reinterpret_cast<Vec<T, W>*>(g + begin);
+    Vec<T, W>* mq = reinterpret_cast<Vec<T, W>*>(m + begin);
+    Vec<T, W>* vq = reinterpret_cast<Vec<T, W>*>(v + begin);
+    for (int q = threadIdx.x; q < nv; q += blockDim.x) {
+      Vec<T, W> pk = pq[q], gk = gq[q], mk = mq[q], vk = vq[q];
+#pragma unroll
+      for (int k = 0; k < W; k++) {
+        A pv = load_as<A>(pk.v[k]), gr = load_as<A>(gk.v[k]), mt = load_as<A>(mk.v[k]), vt = load_as<A>(vk.v[k]);
+        f(pv, gr, mt, vt);
+        pk.v[k] = store_as<T>(pv); mk.v[k] = store_as<T>(mt); vk.v[k] = store_as<T>(vt);
+        if (WRITE_G) gk.v[k] = store_as<T>(gr);
+      }
+      pq[q] = pk; mq[q] = mk; vq[q] = vk;
+      if (WRITE_G) gq[q] = gk;
+    }
+    i0 = begin + (int64_t)nv * W;
+  }
+  for (int64_t i = i0 + threadIdx.x; i < end; i += blockDim.x) {
+    A pv = load_as<A>(p[i]), gr = load_as<A>(g[i]), mt = load_as<A>(m[i]), vt = load_as<A>(v[i]);
+    f(pv, gr, mt, vt);
+    p[i] = store_as<T>(pv); m[i] = store_as<T>(mt); v[i] = store_as<T>(vt);
+    if (WRITE_G) g[i] = store_as<T>(gr);
+  }
+}
+template <class A> __device__ __forceinline__ A mt_sqrt(A x) { return (A)sqrt((double)x); }
+template <> __device__ __forceinline__ float mt_sqrt<float>(float x) { return sqrtf(x); }
+
+// RAdam.scala:86-137, in adamw_kernel's expression order.  RECT = this step is rectified for every tensor of the launch (rho > 4, a host
+// decision per tensor from stepCount and its beta2: the host groups the tensors of a call by branch).
+// p[0]=param, p[1]=grad, p[2]=m, p[3]=v; h[0]=stepParam, h[1]=stepWd (= sched*wd, NOT times lr), h[2]=beta1, h[3]=beta2, s[0]=eps
+template <class T, bool RECT>
+__global__ __launch_bounds__(256) void radam_kernel(MultiArgs a) {
+  using A = acc_t<T>;
+  const int t = mt_find(a, blockIdx.x);
+  const A stepParam = (A)a.h[0][t], stepWd = (A)a.h[1][t], b1 = (A)a.h[2][t], b2 = (A)a.h[3][t];
+  const A one_m_b1 = (A)(1.0 - a.h[2][t]), one_m_b2 = (A)(1.0 - a.h[3][t]);
+  const A eps = (A)a.s[0];
+  mt_update_chunk<T, false>(a, t, [&](A& pv, A& gr, A& mt, A& vt) {
+    mt = mt * b1;                          // mt *= b1
+    mt = mt + one_m_b1 * gr;               // add_out(mt, mt, g, 1-b1)
+    vt = vt * b2;                          // vt *= b2
+    vt = vt + (one_m_b2 * gr) * gr;        // addcmul_out(vt, vt, g, g, 1-b2)
+    if (stepWd != A(0)) pv = pv + (-stepWd) * pv;      // add_out(param, param, param, -stepWd)
+    if (RECT) {
+      const A denom = mt_sqrt<A>(vt) + eps;
+      pv = pv + ((-stepParam) * mt) / denom;           // addcdiv_out(param, param, mt, denom, -stepParam)
+    } else {
+      pv = pv + (-stepParam) * mt;                     // add_out(param, param, mt, -stepParam)
+    }
+  });
+}
+
+// a product rounded to A that the compiler may not contract into the operation that consumes it
+template <class A> __device__ __forceinline__ A rounded_mul(A x, A y) {
+#pragma clang fp contract(off)
+  A r = x * y;
+  asm volatile("" : "+v"(r));
+  return r;
+}
+
+// Yogi.scala:93-129.  The gradient is OVERWRITTEN with g*g*sign(v - g*g), as the reference's gradients.pow_(2); gradients *= sign do: its
+// KAT steps twice with one gradient tensor, and the second step's values are those of a step on -g^2 (adamw.test.scala:128-155).
+// g*g is a rounded value BEFORE the subtraction: contracted into v - g*g the sign would be that of the exact product, non-zero wherever
+// v == round(g*g), and v would move by 2(1-b2)g^2 there.
+// h[0]=stepParam (= sched*lr / (1-b1^t) or sched*lr), h[1]=stepWd (= sched*wd), h[2]=beta1, h[3]=beta2, s[0]=eps,
+// s[1]=1/sqrt(1-b2^t) (flags & 1: debias; a launch holds tensors of one such factor)
+template <class T>
+__global__ __launch_bounds__(256) void yogi_kernel(MultiArgs a) {
+  using A = acc_t<T>;
+  const int t = mt_find(a, blockIdx.x);
+  const A stepParam = (A)a.h[0][t], stepWd = (A)a.h[1][t], b1 = (A)a.h[2][t];
+  const A one_m_b1 = (A)(1.0 - a.h[2][t]), one_m_b2 = (A)(1.0 - a.h[3][t]);
+  const A eps = (A)a.s[0], debiasDenom = (A)a.s[1];
+  const bool debias = a.flags & 1;
+  mt_update_chunk<T, true>(a, t, [&](A& pv, A& gr, A& mt, A& vt) {
+    mt = mt * b1;                          // mt *= b1
+    mt = mt + one_m_b1 * gr;               // add_out(mt, mt, g, 1-b1)
+    const A g2 = rounded_mul(gr, gr);      // gradients.pow_(2)
+    const A diff = vt - g2;                // sub(vt, gradients)
+    const A sgn = (A)((diff > A(0)) - (diff < A(0)));   // sign_(): -1, 0, +1
+    const A gn = g2 * sgn;                 // gradients *= tmp (exact)
+    vt = vt - one_m_b2 * gn;               // sub_out(vt, vt, gradients, 1-b2)
+    A denom = mt_sqrt<A>(vt);
+    if (debias) denom = denom * debiasDenom;
+    denom = denom + eps;
+    if (stepWd != A(0)) pv = pv + (-stepWd) * pv;      // addOut(param, param, param, -stepWd)
+    pv = pv + ((-stepParam) * mt) / denom;             // addcdiv_out(param, param, mt, denom, -stepParam)
+    gr = gn;
+  });
 }
 
 // SGD.scala:46-98. p[0]=param, p[1]=grad, p[2]=velocity (or null); h[0]=lr*sched, h[1]=wd*sched, h[2]=momentum
@@ -233,6 +342,36 @@ static void check_list(lamp_tensor* const* ts, int n, const char* what, int dtyp
   }
 }
 
+// RAdam / Yogi: parameter, gradient and both moments of a tensor have one dtype (RAdam.scala:44-49: the moments are zeros_like(param)).
+// Everything is checked before the first launch, so a rejected call has written nothing.
+static void check_moment_step(const char* who, lamp_tensor* const* params, lamp_tensor* const* grads, lamp_tensor* const* m,
+                              lamp_tensor* const* v, int n) {
+  check_device_tensor(params[0], "parameter");                 // host parameters: the staging layer runs the step on GPU copies
+  const int dev = params[0]->device();
+  for (int i = 0; i < n; i++) {
+    const struct { lamp_tensor* t; const char* what; } lists[4] = {{params[i], "parameter"}, {grads[i], "gradient"}, {m[i], "first moment"}, {v[i], "second moment"}};
+    for (const auto& l : lists) {
+      check_device_tensor(l.t, l.what);
+      LAMP_CHECK(l.t->device() == dev, who << ": " << l.what << " " << i << " is on another device");
+      LAMP_CHECK(l.t->is_contiguous(), who << ": " << l.what << " " << i << " must be contiguous");
+      LAMP_CHECK(l.t->dtype == params[i]->dtype, who << ": " << l.what << " " << i << " has dtype " << dtype_name(l.t->dtype) << ", the parameter " << dtype_name(params[i]->dtype));
+      LAMP_CHECK(l.t->numel() == params[i]->numel(), who << ": " << l.what << " " << i << " has " << l.t->numel() << " elements, the parameter " << params[i]->numel());
+    }
+    const int dt = params[i]->dtype;
+    LAMP_CHECK(dt == kF32 || dt == kF64 || dt == kBF16 || dt == kF16, who << ": unsupported dtype " << dtype_name(dt));
+  }
+}
+// one homogeneous launch sequence per (dtype, key) class of the tensors: launch(dtype, indices of the class)
+template <class Launch>
+static void for_each_class(lamp_tensor* const* params, const std::vector<int>& key, int nkeys, Launch launch) {
+  for (int dt : {kF32, kF64, kBF16, kF16})
+    for (int k = 0; k < nkeys; k++) {
+      std::vector<int> sel;
+      for (size_t i = 0; i < key.size(); i++) if (params[i]->dtype == dt && key[i] == k) sel.push_back((int)i);
+      if (!sel.empty()) launch(dt, sel);
+    }
+}
+
 }  // namespace lamp
 
 using namespace lamp;
@@ -363,6 +502,88 @@ int lamp_adamw_step_(lamp_tensor* const* params, lamp_tensor* const* grads, lamp
     }
   }
   conv_repack_cached(params, n, st);      // the convolution weights' packed images follow the update (conv.hip)
+  LAMP_API_END
+}
+
+int lamp_radam_step_(lamp_tensor* const* params, lamp_tensor* const* grads, lamp_tensor* const* m, lamp_tensor* const* v, int n,
+                     const double* lr, const double* weight_decay, const double* beta1, const double* beta2, double eps,
+                     double schedule_factor, int64_t step_count) {
+  LAMP_API_BEGIN
+  if (n == 0) return 0;
+  check_moment_step("radam", params, grads, m, v, n);
+  hipStream_t st = current_stream(params[0]->device());
+  // RAdam.scala:98-115,135: the branch and the step size are host scalars per tensor
+  std::vector<int> rect(n);
+  std::vector<double> stepParam(n);
+  for (int i = 0; i < n; i++) {
+    const double b1 = beta1[i], b2 = beta2[i], t = (double)step_count;
+    const double beta2PowT = std::pow(b2, t);
+    const double rhoInf = (2.0 / (1.0 - b2)) - 1;
+    const double rho = rhoInf - (2.0 * t * beta2PowT / (1.0 - beta2PowT));
+    rect[i] = rho > 4;          // rhoInf <= 4 (beta2 <= 0.6) is never rectified: (rhoInf - 4) is evaluated under rho > 4 only
+    stepParam[i] = rect[i] ? schedule_factor * lr[i] * std::sqrt((1 - beta2PowT) * ((rho - 4) / (rhoInf - 4)) * ((rho - 2) / rho) * (rhoInf / (rhoInf - 2))) / (1 - std::pow(b1, t))
+                           : schedule_factor * lr[i] / (1 - std::pow(b1, t));
+  }
+  for_each_class(params, rect, 2, [&](int dt, const std::vector<int>& sel) {
+    std::vector<int64_t> numels(sel.size());
+    for (size_t k = 0; k < sel.size(); k++) numels[k] = params[sel[k]]->numel();
+    auto fill = [&](MultiArgs& a, int t, int gi) {
+      const int i = sel[gi];
+      a.p[0][t] = params[i]->data(); a.p[1][t] = grads[i]->data(); a.p[2][t] = m[i]->data(); a.p[3][t] = v[i]->data();
+      a.h[0][t] = stepParam[i];
+      a.h[1][t] = schedule_factor * weight_decay[i];
+      a.h[2][t] = beta1[i];
+      a.h[3][t] = beta2[i];
+      a.s[0] = eps;
+    };
+    const bool r = rect[sel[0]];
+    LAMP_DISPATCH_FLOAT(dt, T, for_each_group((int)sel.size(), numels.data(), fill, [&](MultiArgs& a, int blk) {
+      if (r) hipLaunchKernelGGL((radam_kernel<T, true>), dim3(blk), dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((radam_kernel<T, false>), dim3(blk), dim3(256), 0, st, a);
+    }));
+    LAMP_LAUNCH_CHECK();
+  });
+  conv_repack_cached(params, n, st);      // the convolution weights' packed images follow the update (conv.hip)
+  LAMP_API_END
+}
+
+int lamp_yogi_step_(lamp_tensor* const* params, lamp_tensor* const* grads, lamp_tensor* const* m, lamp_tensor* const* v, int n,
+                    const double* lr, const double* weight_decay, const double* beta1, const double* beta2, double eps,
+                    double schedule_factor, int64_t step_count, int debias) {
+  LAMP_API_BEGIN
+  if (n == 0) return 0;
+  check_moment_step("yogi", params, grads, m, v, n);
+  hipStream_t st = current_stream(params[0]->device());
+  // Yogi.scala:113-116: denom *= 1/sqrt(1-b2^t), a scalar of the launch - tensors are grouped by its value (one class unless beta2 differs)
+  std::vector<int> cls(n, 0);
+  std::vector<double> denomFactor;
+  for (int i = 0; i < n; i++) {
+    const double f = debias ? 1.0 / std::sqrt(1 - std::pow(beta2[i], (double)step_count)) : 1.0;
+    size_t k = 0;
+    while (k < denomFactor.size() && denomFactor[k] != f) k++;
+    if (k == denomFactor.size()) denomFactor.push_back(f);
+    cls[i] = (int)k;
+  }
+  for_each_class(params, cls, (int)denomFactor.size(), [&](int dt, const std::vector<int>& sel) {
+    std::vector<int64_t> numels(sel.size());
+    for (size_t k = 0; k < sel.size(); k++) numels[k] = params[sel[k]]->numel();
+    auto fill = [&](MultiArgs& a, int t, int gi) {
+      const int i = sel[gi];
+      a.p[0][t] = params[i]->data(); a.p[1][t] = grads[i]->data(); a.p[2][t] = m[i]->data(); a.p[3][t] = v[i]->data();
+      const double debiasTerm = debias ? 1.0 / (1 - std::pow(beta1[i], (double)step_count)) : 1.0;
+      a.h[0][t] = schedule_factor * lr[i] * debiasTerm;
+      a.h[1][t] = schedule_factor * weight_decay[i];
+      a.h[2][t] = beta1[i];
+      a.h[3][t] = beta2[i];
+      a.s[0] = eps;
+      a.s[1] = denomFactor[cls[i]];
+      a.flags = debias ? 1 : 0;
+    };
+    LAMP_DISPATCH_FLOAT(dt, T, for_each_group((int)sel.size(), numels.data(), fill,
+                                              [&](MultiArgs& a, int blk) { hipLaunchKernelGGL((yogi_kernel<T>), dim3(blk), dim3(256), 0, st, a); }));
+    LAMP_LAUNCH_CHECK();
+  });
+  conv_repack_cached(params, n, st);
   LAMP_API_END
 }
 

@@ -1,7 +1,7 @@
 """lamp.nn mirror over the host C ABI: modules, optimisers, SupervisedModel, training steps.
 
 Reference: lamp-core/src/main/scala/lamp/nn/{Module,Linear,Conv2D,BatchNorm,BatchNorm2D,LayerNorm,
-MLP,AdamW,SGD,SupervisedModel,LossFunctions}.scala and example-cifar100/.../cnn.scala.
+MLP,AdamW,SGD,RAdam,Yogi,LearningRateSchedule,SupervisedModel,LossFunctions}.scala and example-cifar100/.../cnn.scala.
 """
 from __future__ import annotations
 
@@ -152,6 +152,120 @@ def SGDW(parameters: Sequence[STen], learningRate, weightDecay, momentum=None, c
     opt = Optimizer(o)
     opt._keep = list(parameters)
     return opt
+
+
+def _per_parameter(n, *values):
+    """OptimizerHyperparameter resolved per parameter: a scalar is repeated, a sequence holds one value per parameter."""
+    from ._capi import f64_array
+    out = []
+    for v in values:
+        xs = [float(x) for x in v] if hasattr(v, "__len__") else [float(v)] * n
+        assert len(xs) == n, f"{len(xs)} hyperparameter values for {n} parameters"
+        out.append(f64_array(xs))
+    return out
+
+
+def RAdam(parameters: Sequence[STen], weightDecay, learningRate=0.001, beta1=0.9, beta2=0.999, eps=1e-8, clip=None) -> Optimizer:
+    """Rectified Adam (RAdam.scala:32-141) as one fused launch per step.  Every hyperparameter is a scalar or one value per parameter."""
+    n = len(parameters)
+    o = C.c_void_p()
+    lib.lamp_optimizer_radam(C.byref(o), handle_array([p.h for p in parameters]), n, *_per_parameter(n, weightDecay, learningRate, beta1, beta2),
+                             float(eps), -1.0 if clip is None else float(clip))
+    opt = Optimizer(o)
+    opt._keep = list(parameters)
+    return opt
+
+
+def RAdam_factory(weightDecay, learningRate=0.001, beta1=0.9, beta2=0.999, eps=1e-8, clip=None):
+    return lambda params: RAdam(params, weightDecay, learningRate, beta1, beta2, eps, clip)
+
+
+def Yogi(parameters: Sequence[STen], weightDecay, learningRate=0.01, beta1=0.9, beta2=0.999, eps=1e-3, clip=None, debias=True) -> Optimizer:
+    """Yogi with decoupled weight decay (Yogi.scala:38-134) as one fused launch per step.  `step` OVERWRITES the gradient tensors it is
+    handed with g*g*sign(v - g*g), as the reference's in-place pow_ / *= do (Yogi.scala:95-98)."""
+    n = len(parameters)
+    o = C.c_void_p()
+    lib.lamp_optimizer_yogi(C.byref(o), handle_array([p.h for p in parameters]), n, *_per_parameter(n, weightDecay, learningRate, beta1, beta2),
+                            float(eps), -1.0 if clip is None else float(clip), int(debias))
+    opt = Optimizer(o)
+    opt._keep = list(parameters)
+    return opt
+
+
+def Yogi_factory(weightDecay, learningRate=0.01, beta1=0.9, beta2=0.999, eps=1e-3, clip=None, debias=True):
+    return lambda params: Yogi(params, weightDecay, learningRate, beta1, beta2, eps, clip, debias)
+
+
+class LearningRateSchedule:
+    """nn/LearningRateSchedule.scala: `init` is the schedule's first state, `learningRateFactor(state, epoch, lastValidationLoss)` returns
+    (next state, factor); the factor is what `loops.oneEpoch` and `Optimizer.step` take as scheduleFactor."""
+
+    def __init__(self, init, fn):
+        self.init = init
+        self._fn = fn
+
+    def learningRateFactor(self, state, epoch: int, lastValidationLoss: Optional[float] = None):
+        return self._fn(state, epoch, lastValidationLoss)
+
+    @staticmethod
+    def fromEpochCount(f) -> "LearningRateSchedule":
+        return LearningRateSchedule(None, lambda state, epoch, loss: (None, float(f(epoch))))
+
+    @staticmethod
+    def interpolate(startY: float, endY: float, endX: float, x: float) -> float:
+        return startY + (endY - startY) * (x / endX)
+
+    @staticmethod
+    def noop() -> "LearningRateSchedule":
+        return LearningRateSchedule.fromEpochCount(lambda _: 1.0)
+
+    @staticmethod
+    def decrement(every: int, decrementFraction: float) -> "LearningRateSchedule":
+        return LearningRateSchedule.fromEpochCount(lambda stepCount: decrementFraction ** float(stepCount // every))
+
+    @staticmethod
+    def linear(start: float, end: float, maxSteps: int) -> "LearningRateSchedule":
+        return LearningRateSchedule.fromEpochCount(
+            lambda stepCount: max(end, LearningRateSchedule.interpolate(start, end, float(maxSteps), float(stepCount))))
+
+    @staticmethod
+    def stepAfter(steps: int, factor: float) -> "LearningRateSchedule":
+        return LearningRateSchedule.fromEpochCount(lambda stepCount: factor if stepCount > steps else 1.0)
+
+    @staticmethod
+    def cyclicSchedule(maxFactor: float, periodLength: int) -> "LearningRateSchedule":
+        def f(stepCount):
+            l = stepCount % periodLength
+            if l > periodLength // 2:      # the falling half, LearningRateSchedule.scala:105-111 as written (integer half period)
+                return maxFactor + LearningRateSchedule.interpolate(maxFactor, 1.0, float(periodLength // 2), float(l))
+            return LearningRateSchedule.interpolate(1.0, maxFactor, periodLength / 2.0, float(l))
+        return LearningRateSchedule.fromEpochCount(f)
+
+    @staticmethod
+    def reduceLROnPlateau(startFactor=1.0, reduceFactor=0.5, patience=10, threshold=1e-4, relativeThresholdMode=True,
+                          stopFactor=1e-4) -> "LearningRateSchedule":
+        """State = (min, minLoc, activeFactor) (ReduceLROnPlateauState)."""
+        import sys
+        big = sys.float_info.max
+
+        def f(state, epoch, loss):
+            assert loss is not None, "reduce lr on plateau needs validation loss"
+            mn, minLoc, active = state
+            if mn == big:
+                decrease = loss < mn
+            elif relativeThresholdMode:
+                decrease = loss < mn * (1.0 - threshold)
+            else:
+                decrease = loss < (mn - threshold)
+            if decrease:
+                return (loss, epoch, active), active
+            if epoch - minLoc >= patience:
+                x = active * reduceFactor
+                if x <= stopFactor:
+                    x = 0.0
+                return (mn, epoch, x), x
+            return state, active
+        return LearningRateSchedule((big, -1, startFactor), f)
 
 
 def gradientClippingInPlace(gradients: Sequence[Optional[STen]], theta: float):
