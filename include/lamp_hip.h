@@ -837,6 +837,23 @@ int lamp_radam_step_(lamp_tensor* const* params, lamp_tensor* const* grads, lamp
 int lamp_yogi_step_(lamp_tensor* const* params, lamp_tensor* const* grads, lamp_tensor* const* m,
                     lamp_tensor* const* v, int n, const double* lr, const double* weight_decay, const double* beta1,
                     const double* beta2, double eps, double schedule_factor, int64_t step_count, int debias);
+/* Batched symmetric eigendecomposition in f64 by one-sided Jacobi (kernels/eig.hip), the decomposition Shampoo's preconditioners need:
+ * matrices are n square f32 / f64 tensors of side <= 512 (both triangles are read), values_out n f64 [side] tensors that receive the
+ * singular values (= the eigenvalues of a positive semi-definite matrix) in descending order, vectors_out_or_null n f64 [side, side]
+ * tensors that receive U with its columns in that order (or NULL).  status_out_or_null: i32 [n], the sweeps each matrix took (a
+ * negative code where the call fails).  Fails - before anything is written - on a NaN or an infinity in any matrix, and when a matrix
+ * does not converge within the sweep cap.  Reads the status words back: one synchronisation of the current stream per call. */
+int lamp_symmetric_eig(lamp_tensor* const* matrices, int n, lamp_tensor* const* values_out, lamp_tensor* const* vectors_out_or_null,
+                       lamp_tensor* status_out_or_null);
+/* Shampoo (nn/Shampoo.scala:86-197, as written - DESIGN.md section 16): per tensor the statistics lt [d1, d1] / rt [d2, d2] (d1 =
+ * shape(0), d2 = the rest; a side > 512 is a vector [d]), their inverse fourth roots ltinv / rtinv of the same shapes and lastGradient,
+ * all of the parameter's dtype (f32 or f64).  With momentum[i] > 0 grads[i] is OVERWRITTEN with the blended gradient, as the reference
+ * does in place.  The roots are recomputed when step_count <= 100 or step_count % update_every == 0: reference mode stores
+ * diag(s^-1/4) with s descending (what the reference's row-scaled product evaluates to), paper_preconditioner != 0 stores
+ * U diag(s^-1/4) U^T. */
+int lamp_shampoo_step_(lamp_tensor* const* params, lamp_tensor* const* grads, lamp_tensor* const* lt, lamp_tensor* const* ltinv,
+                       lamp_tensor* const* rt, lamp_tensor* const* rtinv, lamp_tensor* const* last, int n, const double* lr,
+                       const double* momentum, int64_t step_count, int64_t update_every, int paper_preconditioner);
 /* flat bucket helpers for data parallel training: pack n tensors into one
  * contiguous f32 bucket scaled by `scale`, and unpack with a (device-resident) divisor */
 int lamp_flatten_into_(lamp_tensor* bucket, lamp_tensor* const* ts, int n, double scale);

@@ -141,6 +141,11 @@ int lamp_optimizer_radam(lamp_optimizer** out, lamp_tensor* const* params, int n
                          const double* beta1, const double* beta2, double eps, double clip);
 int lamp_optimizer_yogi(lamp_optimizer** out, lamp_tensor* const* params, int n, const double* weight_decay, const double* learning_rate,
                         const double* beta1, const double* beta2, double eps, double clip, int debias);
+/* nn/Shampoo.scala: learning_rate / momentum hold n values; state = [stepCount] ++ (lt, ltinv)* ++ (rt, rtinv)* ++ lastGradient.
+ * With momentum > 0 step overwrites the gradient tensors it is handed (Shampoo.scala:107-110).  paper_preconditioner is not in the
+ * reference: the stored inverse roots are U diag(s^-1/4) U^T instead of the diagonal matrix the reference computes. */
+int lamp_optimizer_shampoo(lamp_optimizer** out, lamp_tensor* const* params, int n, const double* learning_rate, double clip, double eps,
+                           int64_t update_preconditioner_every_n_iterations, const double* momentum, int paper_preconditioner);
 int lamp_optimizer_step(lamp_optimizer* o, lamp_tensor* const* gradients /* NULL entries = None */, int n, double schedule_factor);
 int lamp_optimizer_num_state(lamp_optimizer* o, int64_t* out);
 int lamp_optimizer_state(lamp_optimizer* o, int64_t index, lamp_tensor** out);

@@ -399,6 +399,17 @@ int lamp_optimizer_yogi(lamp_optimizer** out, lamp_tensor* const* params, int n,
   *out = o;
   LAMP_API_END
 }
+int lamp_optimizer_shampoo(lamp_optimizer** out, lamp_tensor* const* params, int n, const double* lr, double clip, double eps,
+                           int64_t update_every, const double* momentum, int paper_preconditioner) {
+  LAMP_API_BEGIN
+  LAMP_CHECK(lr && momentum, "lamp_optimizer_shampoo: one value per parameter for every hyperparameter");
+  std::vector<Ten> ps;
+  for (int i = 0; i < n; i++) ps.push_back(borrow(params[i]));
+  auto* o = new lamp_optimizer();
+  o->o = std::make_shared<Shampoo>(ps, lr, momentum, eps, clip >= 0, clip, update_every, paper_preconditioner != 0);
+  *out = o;
+  LAMP_API_END
+}
 int lamp_optimizer_sgdw(lamp_optimizer** out, lamp_tensor* const* params, int n, double lr, double wd, double momentum, double clip) {
   LAMP_API_BEGIN
   std::vector<Ten> ps;

@@ -423,6 +423,69 @@ void Yogi::update(lamp_tensor* const* p, lamp_tensor* const* g, lamp_tensor* con
   HCALL(lamp_yogi_step_(p, g, m, v, n, lr, wd, b1, b2, eps, scheduleFactor, stepCount, debias));
 }
 
+// ---- Shampoo (nn/Shampoo.scala) ------------------------------------------------------------------------------
+Shampoo::Shampoo(const std::vector<Ten>& params, const double* lr, const double* mom, double eps_, bool has_clip_, double clip_,
+                 int64_t updateEvery_, bool paper)
+    : parameters(params), learningRate(lr, lr + params.size()), momentum(mom, mom + params.size()), eps(eps_), has_clip(has_clip_), clip(clip_),
+      updateEvery(updateEvery_), paperPreconditioner(paper) {
+  LAMP_CHECK(updateEvery >= 1, "Shampoo: updatePreconditionerEveryNIterations must be positive, got " << updateEvery);
+  for (auto& p : parameters) {
+    LAMP_CHECK(p.dtype() == kF32 || p.dtype() == kF64, "Shampoo: parameters must be f32 or f64, got " << p.h()->describe());
+    LAMP_CHECK(p.ndim() >= 1 && p.numel() > 0, "Shampoo: a 0-d or empty parameter has no shape(0): " << p.h()->describe());
+  }
+  // Shampoo.scala:44-62: eps * I up to side 512, eps * ones beyond; the inverse starts as a clone of the statistics
+  auto side = [&](const Ten& p, int64_t d) {
+    lamp_tensor* o = nullptr;
+    if (d > 512) { const int64_t s[1] = {d}; HCALL(lamp_ones(&o, s, 1, p.dtype(), p.device())); }
+    else HCALL(lamp_eye(&o, d, d, p.dtype(), p.device()));
+    Ten t(o);
+    ops::mul_scalar_(t, eps);
+    return t;
+  };
+  for (auto& p : parameters) {
+    const int64_t d1 = p.size(0), d2 = p.numel() / d1;
+    lt.push_back(side(p, d1)); ltinv.push_back(side(p, d1));
+    rt.push_back(side(p, d2)); rtinv.push_back(side(p, d2));
+    lastGradient.push_back(ops::zeros_like(p));
+  }
+  stepCountSTen = ops::scalar(0.0, kF64, parameters.empty() ? 0 : parameters[0].device());
+}
+std::vector<Ten> Shampoo::state() {
+  ops::fill_(stepCountSTen, (double)stepCount);
+  std::vector<Ten> s = {stepCountSTen};
+  for (size_t i = 0; i < lt.size(); i++) { s.push_back(lt[i]); s.push_back(ltinv[i]); }
+  for (size_t i = 0; i < rt.size(); i++) { s.push_back(rt[i]); s.push_back(rtinv[i]); }
+  for (auto& t : lastGradient) s.push_back(t);
+  return s;
+}
+void Shampoo::load(const std::vector<Ten>& tensors) {
+  Optimizer::load(tensors);
+  if (!tensors.empty()) counters_from_state();
+}
+void Shampoo::counters_from_state() {
+  double v = 0;
+  HCALL(lamp_item(stepCountSTen.h(), &v));
+  stepCount = (int64_t)v;
+}
+void Shampoo::step(const std::vector<Ten>& gradients, double) {
+  LAMP_CHECK(gradients.size() == parameters.size(), "Optimizer.step: got " << gradients.size() << " gradients for " << parameters.size() << " parameters");
+  std::vector<lamp_tensor*> p, g, l, li, r, ri, last;
+  std::vector<double> lr, mom;
+  for (size_t i = 0; i < parameters.size(); i++) {
+    if (!gradients[i].defined()) continue;     // skipped: its statistics stay as they are
+    LAMP_CHECK(gradients[i].shape() == parameters[i].shape(), "Shampoo.step: gradient " << i << " is " << gradients[i].h()->describe() << ", the parameter "
+               << parameters[i].h()->describe());
+    p.push_back(parameters[i].h()); g.push_back(gradients[i].h()); l.push_back(lt[i].h()); li.push_back(ltinv[i].h());
+    r.push_back(rt[i].h()); ri.push_back(rtinv[i].h()); last.push_back(lastGradient[i].h());
+    lr.push_back(learningRate[i]); mom.push_back(momentum[i]);
+  }
+  if (has_clip && !g.empty()) HCALL(lamp_gradient_clipping_(g.data(), (int)g.size(), clip));
+  // stepCount advances once per step, whatever is defined - after the update, so that a rejected step leaves the state as it was
+  HCALL(lamp_shampoo_step_(p.data(), g.data(), l.data(), li.data(), r.data(), ri.data(), last.data(), (int)p.size(), lr.data(), mom.data(),
+                           stepCount + 1, updateEvery, paperPreconditioner ? 1 : 0));
+  stepCount += 1;
+}
+
 SGDW::SGDW(const std::vector<Ten>& params, double lr, double wd, bool has_m, double mom, bool has_clip_, double clip_)
     : parameters(params), learningRate(lr), weightDecay(wd), momentum(mom), has_momentum(has_m), has_clip(has_clip_), clip(clip_) {
   if (has_momentum) for (auto& p : parameters) velocity.push_back(ops::zeros_like(p));

@@ -186,6 +186,24 @@ struct Yogi : MomentOptimizer {    // nn/Yogi.scala:38-134; step() overwrites th
   void update(lamp_tensor* const* p, lamp_tensor* const* g, lamp_tensor* const* m, lamp_tensor* const* v, int n, const double* lr,
               const double* wd, const double* b1, const double* b2, double scheduleFactor) override;
 };
+// nn/Shampoo.scala:32-199 as written.  Not a MomentOptimizer: its state is the statistics of both sides of every
+// parameter, their inverse fourth roots and the last gradient: state() = [stepCountSTen] ++ (lt, ltinv)* ++ (rt, rtinv)* ++ lastGradient.
+// A side is a matrix up to 512 and a vector beyond (Shampoo.scala:47,57; diagonalThreshold is never read).  With momentum > 0 step()
+// overwrites the gradients it is handed (Shampoo.scala:107-110).  The preconditioner schedule depends on stepCount, so load() restores it.
+struct Shampoo : Optimizer {
+  std::vector<Ten> parameters, lt, ltinv, rt, rtinv, lastGradient;
+  std::vector<double> learningRate, momentum;   // one value per parameter
+  double eps; bool has_clip; double clip;
+  int64_t updateEvery; bool paperPreconditioner;
+  int64_t stepCount = 0;
+  Ten stepCountSTen;            // f64 scalar, state()[0]
+  Shampoo(const std::vector<Ten>& params, const double* lr, const double* mom, double eps, bool has_clip, double clip, int64_t updateEvery,
+          bool paperPreconditioner);
+  void step(const std::vector<Ten>& gradients, double scheduleFactor) override;   // scheduleFactor is not read (Shampoo.scala:86-197)
+  std::vector<Ten> state() override;
+  void load(const std::vector<Ten>& tensors) override;
+  void counters_from_state() override;
+};
 struct SGDW : Optimizer {       // nn/SGD.scala:19-99
   std::vector<Ten> parameters, velocity;
   double learningRate, weightDecay, momentum; bool has_momentum, has_clip; double clip;

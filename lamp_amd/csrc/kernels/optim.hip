@@ -315,6 +315,74 @@ __global__ __launch_bounds__(256) void mt_unflatten_kernel(MultiArgs a, const fl
   for (int64_t i = begin + threadIdx.x; i < end; i += blockDim.x) dst[i] = store_as<T>((acc_t<T>)(src[i] / div));
 }
 
+// ---- Shampoo (nn/Shampoo.scala:86-197) -----------------------------------------------------------------------
+// The momentum blend of every tensor with momentum > 0, in place in the GRADIENT as the reference does (Shampoo.scala:107-113):
+// g *= 1-mom; g = g + mom*last; last = g.   p[0]=grad, p[1]=lastGradient; h[0]=momentum
+template <class T>
+__global__ __launch_bounds__(256) void shampoo_blend_kernel(MultiArgs a) {
+  const int t = mt_find(a, blockIdx.x);
+  const int64_t begin = (int64_t)(blockIdx.x - a.blk_start[t]) * MT_CHUNK;
+  const int64_t end = min(begin + MT_CHUNK, a.numel[t]);
+  T* g = (T*)a.p[0][t];
+  T* last = (T*)a.p[1][t];
+  const T mom = (T)a.h[0][t], one_m = (T)(1.0 - a.h[0][t]);
+  for (int64_t i = begin + threadIdx.x; i < end; i += blockDim.x) {
+    T v = rounded_mul(g[i], one_m);        // gradients *= (1 - mom)
+    v = v + mom * last[i];                 // addOut(gradients, gradients, lastGradient, mom)
+    g[i] = v;
+    last[i] = v;                           // lastGradient.copyFrom(gradients)
+  }
+}
+// the statistics of a side kept as a vector: stat[i] += sum_j g[i][j]^2 (one wave per row) and stat[j] += sum_i g[i][j]^2 (one thread per column)
+template <class T>
+__global__ __launch_bounds__(256) void shampoo_row_sumsq_kernel(T* __restrict__ stat, const T* __restrict__ g, int64_t d1, int64_t d2) {
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= d1) return;
+  T s = 0;
+  for (int64_t j = threadIdx.x & 63; j < d2; j += 64) { const T v = g[row * d2 + j]; s += v * v; }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) stat[row] += s;
+}
+template <class T>
+__global__ __launch_bounds__(256) void shampoo_col_sumsq_kernel(T* __restrict__ stat, const T* __restrict__ g, int64_t d1, int64_t d2) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= d2) return;
+  T s = 0;
+  for (int64_t i = 0; i < d1; i++) { const T v = g[i * d2 + j]; s += v * v; }
+  stat[j] += s;
+}
+// out[i][j] = (accumulate ? out[i][j] : 0) + alpha * ((l ? l[i] : 1) * in[i][j]) * (r ? r[j] : 1): a vector side of the update
+template <class T>
+__global__ __launch_bounds__(256) void shampoo_scale_kernel(T* __restrict__ out, const T* __restrict__ in, const T* __restrict__ l,
+                                                            const T* __restrict__ r, int64_t d1, int64_t d2, T alpha, int accumulate) {
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < d1 * d2; e += (int64_t)gridDim.x * 256) {
+    const int64_t i = e / d2, j = e - i * d2;
+    T v = in[e];
+    if (l) v = l[i] * v;
+    if (r) v = v * r[j];
+    out[e] = accumulate ? out[e] + alpha * v : v;
+  }
+}
+// the inverse fourth roots.  Reference mode: diag(s^-1/4) dense, s in descending order (what Shampoo.scala:143-146 evaluates to).
+template <class T>
+__global__ __launch_bounds__(256) void shampoo_diag_root_kernel(T* __restrict__ out, const double* __restrict__ s, int n) {
+  for (int e = blockIdx.x * 256 + threadIdx.x; e < n * n; e += gridDim.x * 256) {
+    const int i = e / n, j = e - i * n;
+    out[e] = i == j ? (T)pow(s[i], -0.25) : T(0);
+  }
+}
+// paper mode: out = U diag(s^-1/4), the left factor of U diag(s^-1/4) U^T
+__global__ __launch_bounds__(256) void shampoo_scale_cols_kernel(double* __restrict__ out, const double* __restrict__ U, const double* __restrict__ s, int n) {
+  for (int e = blockIdx.x * 256 + threadIdx.x; e < n * n; e += gridDim.x * 256) out[e] = U[e] * pow(s[e % n], -0.25);
+}
+template <class T> __device__ __forceinline__ T shampoo_root(T x) { return (T)pow((double)x, -0.25); }
+template <> __device__ __forceinline__ float shampoo_root<float>(float x) { return powf(x, -0.25f); }
+template <class T>
+__global__ __launch_bounds__(256) void shampoo_vec_root_kernel(T* __restrict__ out, const T* __restrict__ stat, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = shampoo_root<T>(stat[i]);
+}
+
 // host: iterate over the tensor lists in groups of MT_MAX
 template <class Fill, class Launch>
 static void for_each_group(int n, const int64_t* numels, Fill fill, Launch launch) {
@@ -584,6 +652,142 @@ int lamp_yogi_step_(lamp_tensor* const* params, lamp_tensor* const* grads, lamp_
     LAMP_LAUNCH_CHECK();
   });
   conv_repack_cached(params, n, st);
+  LAMP_API_END
+}
+
+// One Shampoo step over the tensors whose gradient is defined (Shampoo.scala:96-196, as written).  A side of the
+// statistics is a matrix ([d, d], d <= 512) or a vector ([d]); the shapes of lt / rt say which.  Everything is checked before the first
+// launch, so a rejected call has written nothing.
+int lamp_shampoo_step_(lamp_tensor* const* params, lamp_tensor* const* grads, lamp_tensor* const* lt, lamp_tensor* const* ltinv,
+                       lamp_tensor* const* rt, lamp_tensor* const* rtinv, lamp_tensor* const* last, int n, const double* lr,
+                       const double* momentum, int64_t step_count, int64_t update_every, int paper_preconditioner) {
+  LAMP_API_BEGIN
+  if (n == 0) return 0;
+  LAMP_CHECK(update_every >= 1, "shampoo: updatePreconditionerEveryNIterations must be positive, got " << update_every);
+  check_device_tensor(params[0], "parameter");                 // host parameters: the staging layer runs the step on GPU copies
+  const int dev = params[0]->device();
+  std::vector<int64_t> d1(n), d2(n);
+  for (int i = 0; i < n; i++) {
+    const struct { lamp_tensor* t; const char* what; } lists[7] = {{params[i], "parameter"}, {grads[i], "gradient"}, {lt[i], "lt"}, {ltinv[i], "ltinv"},
+                                                                   {rt[i], "rt"}, {rtinv[i], "rtinv"}, {last[i], "lastGradient"}};
+    for (const auto& l : lists) {
+      check_device_tensor(l.t, l.what);
+      LAMP_CHECK(l.t->device() == dev, "shampoo: " << l.what << " " << i << " is on another device");
+      LAMP_CHECK(l.t->is_contiguous(), "shampoo: " << l.what << " " << i << " must be contiguous");
+      LAMP_CHECK(l.t->dtype == params[i]->dtype, "shampoo: " << l.what << " " << i << " has dtype " << dtype_name(l.t->dtype) << ", the parameter " << dtype_name(params[i]->dtype));
+    }
+    const lamp_tensor* p = params[i];
+    // no half precisions: the reference has no mixed mode, and eps = 1e-4 statistics do not survive bf16 accumulation
+    LAMP_CHECK(p->dtype == kF32 || p->dtype == kF64, "shampoo: parameter " << i << " is " << dtype_name(p->dtype) << ", only f32 and f64 are supported");
+    LAMP_CHECK(p->ndim >= 1 && p->numel() > 0, "shampoo: parameter " << i << " is " << p->describe() << ": a 0-d or empty parameter has no shape(0)");
+    LAMP_CHECK(grads[i]->shape() == p->shape(), "shampoo: gradient " << i << " is " << grads[i]->describe() << ", the parameter " << p->describe());
+    LAMP_CHECK(last[i]->numel() == p->numel(), "shampoo: lastGradient " << i << " is " << last[i]->describe() << ", the parameter " << p->describe());
+    d1[i] = p->sizes[0];
+    d2[i] = p->numel() / d1[i];
+    const struct { const lamp_tensor* t; const lamp_tensor* inv; int64_t d; const char* what; } sides[2] = {{lt[i], ltinv[i], d1[i], "lt"}, {rt[i], rtinv[i], d2[i], "rt"}};
+    for (const auto& sd : sides) {
+      const bool matrix = sd.t->ndim == 2 && sd.t->sizes[0] == sd.d && sd.t->sizes[1] == sd.d && sd.d <= 512;
+      const bool vector = sd.t->ndim == 1 && sd.t->sizes[0] == sd.d;
+      LAMP_CHECK(matrix || vector, "shampoo: " << sd.what << " " << i << " is " << sd.t->describe() << ", expected [" << sd.d << "," << sd.d << "] (side <= 512) or [" << sd.d << "]");
+      LAMP_CHECK(sd.inv->shape() == sd.t->shape(), "shampoo: " << sd.what << "inv " << i << " is " << sd.inv->describe() << ", " << sd.what << " " << sd.t->describe());
+    }
+  }
+  hipStream_t st = current_stream(dev);
+#define SH_CALL(expr) do { if ((expr) != 0) throw Error(lamp_last_error()); } while (0)
+#define SH_DISPATCH(DT, T, ...) do { if ((DT) == kF32) { using T = float; __VA_ARGS__; } else { using T = double; __VA_ARGS__; } } while (0)
+  // 1. momentum, one launch per dtype over the tensors that have one
+  for (int dt : {kF32, kF64}) {
+    std::vector<int> sel;
+    for (int i = 0; i < n; i++) if (params[i]->dtype == dt && momentum[i] > 0) sel.push_back(i);
+    if (sel.empty()) continue;
+    std::vector<int64_t> numels(sel.size());
+    for (size_t k = 0; k < sel.size(); k++) numels[k] = params[sel[k]]->numel();
+    auto fill = [&](MultiArgs& a, int t, int gi) { const int i = sel[gi]; a.p[0][t] = grads[i]->data(); a.p[1][t] = last[i]->data(); a.h[0][t] = momentum[i]; };
+    SH_DISPATCH(dt, T, for_each_group((int)sel.size(), numels.data(), fill,
+                                      [&](MultiArgs& a, int blk) { hipLaunchKernelGGL((shampoo_blend_kernel<T>), dim3(blk), dim3(256), 0, st, a); }));
+    LAMP_LAUNCH_CHECK();
+  }
+  // 2. statistics: lt += G G^T, rt += G^T G through the GEMMs' beta = 1 epilogue; a vector side takes the sums of squares
+  std::vector<Hold> g2(n), p2(n);
+  for (int i = 0; i < n; i++) {
+    const int64_t sz[2] = {d1[i], d2[i]}, sr[2] = {d2[i], 1};
+    g2[i] = Hold(new_view(grads[i], sz, sr, 2, grads[i]->offset));
+    p2[i] = Hold(new_view(params[i], sz, sr, 2, params[i]->offset));
+    if (lt[i]->ndim == 2) SH_CALL(lamp_addmm_out_transposed2(lt[i], lt[i], g2[i].get(), g2[i].get(), 1.0, 1.0));
+    if (rt[i]->ndim == 2) SH_CALL(lamp_addmm_out_transposed1(rt[i], rt[i], g2[i].get(), g2[i].get(), 1.0, 1.0));
+    if (params[i]->dtype == kF32) {
+      if (lt[i]->ndim == 1) hipLaunchKernelGGL((shampoo_row_sumsq_kernel<float>), dim3((unsigned)((d1[i] + 3) / 4)), dim3(256), 0, st, lt[i]->ptr<float>(), grads[i]->ptr<const float>(), d1[i], d2[i]);
+      if (rt[i]->ndim == 1) hipLaunchKernelGGL((shampoo_col_sumsq_kernel<float>), dim3((unsigned)((d2[i] + 255) / 256)), dim3(256), 0, st, rt[i]->ptr<float>(), grads[i]->ptr<const float>(), d1[i], d2[i]);
+    } else {
+      if (lt[i]->ndim == 1) hipLaunchKernelGGL((shampoo_row_sumsq_kernel<double>), dim3((unsigned)((d1[i] + 3) / 4)), dim3(256), 0, st, lt[i]->ptr<double>(), grads[i]->ptr<const double>(), d1[i], d2[i]);
+      if (rt[i]->ndim == 1) hipLaunchKernelGGL((shampoo_col_sumsq_kernel<double>), dim3((unsigned)((d2[i] + 255) / 256)), dim3(256), 0, st, rt[i]->ptr<double>(), grads[i]->ptr<const double>(), d1[i], d2[i]);
+    }
+  }
+  LAMP_LAUNCH_CHECK();
+  // 3. the inverse fourth roots: on every step up to 100, then on every update_every-th (Shampoo.scala:137-139)
+  if (!(step_count > 100 && step_count % update_every != 0)) {
+    std::vector<lamp_tensor*> mats, invs;
+    std::vector<Hold> vals, vecs;
+    for (int i = 0; i < n; i++)
+      for (int side = 0; side < 2; side++) {
+        lamp_tensor* s = side ? rt[i] : lt[i];
+        lamp_tensor* inv = side ? rtinv[i] : ltinv[i];
+        if (s->ndim == 2) {
+          mats.push_back(s); invs.push_back(inv);
+          const int64_t vs[1] = {s->sizes[0]};
+          vals.emplace_back(new_tensor(vs, 1, kF64, dev));
+          if (paper_preconditioner) vecs.emplace_back(new_tensor(s->sizes, 2, kF64, dev));
+        } else {
+          const int64_t len = s->sizes[0];
+          if (s->dtype == kF32) hipLaunchKernelGGL((shampoo_vec_root_kernel<float>), dim3((unsigned)((len + 255) / 256)), dim3(256), 0, st, inv->ptr<float>(), s->ptr<const float>(), len);
+          else hipLaunchKernelGGL((shampoo_vec_root_kernel<double>), dim3((unsigned)((len + 255) / 256)), dim3(256), 0, st, inv->ptr<double>(), s->ptr<const double>(), len);
+        }
+      }
+    LAMP_LAUNCH_CHECK();
+    if (!mats.empty()) {
+      std::vector<lamp_tensor*> vh, uh;
+      for (auto& h : vals) vh.push_back(h.get());
+      for (auto& h : vecs) uh.push_back(h.get());
+      SH_CALL(lamp_symmetric_eig(mats.data(), (int)mats.size(), vh.data(), paper_preconditioner ? uh.data() : nullptr, nullptr));
+      for (size_t k = 0; k < mats.size(); k++) {
+        const int side = (int)mats[k]->sizes[0], blocks = std::min(1024, (side * side + 255) / 256);
+        if (!paper_preconditioner) {
+          if (invs[k]->dtype == kF32) hipLaunchKernelGGL((shampoo_diag_root_kernel<float>), dim3(blocks), dim3(256), 0, st, invs[k]->ptr<float>(), vh[k]->ptr<const double>(), side);
+          else hipLaunchKernelGGL((shampoo_diag_root_kernel<double>), dim3(blocks), dim3(256), 0, st, invs[k]->ptr<double>(), vh[k]->ptr<const double>(), side);
+        } else {
+          Hold us(new_like(uh[k])), root(invs[k]->dtype == kF64 ? retain(invs[k]) : new_like(uh[k]));
+          hipLaunchKernelGGL(shampoo_scale_cols_kernel, dim3(blocks), dim3(256), 0, st, us->ptr<double>(), uh[k]->ptr<const double>(), vh[k]->ptr<const double>(), side);
+          SH_CALL(lamp_addmm_out_transposed2(root.get(), nullptr, us.get(), uh[k], 0.0, 1.0));       // (U diag(s^-1/4)) U^T in f64
+          if (invs[k]->dtype != kF64) copy_into(invs[k], root.get());                               // ... cast to the gradient's dtype
+        }
+      }
+      LAMP_LAUNCH_CHECK();
+    }
+  }
+  // 4. p += -lr * ltinv G rtinv; the second product carries -lr and the accumulation in its epilogue
+  for (int i = 0; i < n; i++) {
+    const bool lm = lt[i]->ndim == 2, rm = rt[i]->ndim == 2;
+    const int blocks = (int)std::min<int64_t>(4096, (d1[i] * d2[i] + 255) / 256);
+    Hold t1;
+    if (lm) { lamp_tensor* o = nullptr; SH_CALL(lamp_mm(&o, ltinv[i], g2[i].get())); t1 = Hold(o); }
+    SH_DISPATCH(params[i]->dtype, T, {
+      {
+        if (!lm && rm) {
+          t1 = Hold(new_like(g2[i].get()));
+          hipLaunchKernelGGL((shampoo_scale_kernel<T>), dim3(blocks), dim3(256), 0, st, t1->ptr<T>(), grads[i]->ptr<const T>(), ltinv[i]->ptr<const T>(), (const T*)nullptr, d1[i], d2[i], T(1), 0);
+        } else if (lm && !rm) {
+          hipLaunchKernelGGL((shampoo_scale_kernel<T>), dim3(blocks), dim3(256), 0, st, params[i]->ptr<T>(), t1->ptr<const T>(), (const T*)nullptr, rtinv[i]->ptr<const T>(), d1[i], d2[i], (T)(-lr[i]), 1);
+        } else if (!lm && !rm) {
+          hipLaunchKernelGGL((shampoo_scale_kernel<T>), dim3(blocks), dim3(256), 0, st, params[i]->ptr<T>(), grads[i]->ptr<const T>(), ltinv[i]->ptr<const T>(), rtinv[i]->ptr<const T>(), d1[i], d2[i], (T)(-lr[i]), 1);
+        }
+      }
+    });
+    if (rm) SH_CALL(lamp_addmm_out(p2[i].get(), p2[i].get(), t1.get(), rtinv[i], 1.0, -lr[i]));
+  }
+  LAMP_LAUNCH_CHECK();
+#undef SH_CALL
+#undef SH_DISPATCH
+  conv_repack_cached(params, n, st);      // the convolution weights' packed images follow the update (conv.hip)
   LAMP_API_END
 }
 

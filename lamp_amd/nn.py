@@ -196,6 +196,30 @@ def Yogi_factory(weightDecay, learningRate=0.01, beta1=0.9, beta2=0.999, eps=1e-
     return lambda params: Yogi(params, weightDecay, learningRate, beta1, beta2, eps, clip, debias)
 
 
+def Shampoo(parameters: Sequence[STen], learningRate=0.001, clip=None, eps=1e-4, diagonalThreshold=256,
+            updatePreconditionerEveryNIterations=100, momentum=0.0, paperPreconditioner=False) -> Optimizer:
+    """Shampoo (Shampoo.scala:32-199) as the reference writes it: the stored inverse fourth roots are diag(s^-1/4) with s the singular
+    values in descending order (its row-scaled product evaluates to that; its own known answer depends on it), a side is a matrix up to
+    512 and a vector beyond, and with momentum > 0 `step` OVERWRITES the gradient tensors it is handed with the blended gradient.
+    `diagonalThreshold` is accepted and IGNORED, as in the reference, which never reads it.  `paperPreconditioner=True` (not in the
+    reference) stores U diag(s^-1/4) U^T instead, the paper's L^-1/4; nothing else differs.  f32 and f64 parameters only.
+    learningRate and momentum are scalars or one value per parameter."""
+    n = len(parameters)
+    o = C.c_void_p()
+    lr, mom = _per_parameter(n, learningRate, momentum)
+    lib.lamp_optimizer_shampoo(C.byref(o), handle_array([p.h for p in parameters]), n, lr, -1.0 if clip is None else float(clip), float(eps),
+                               int(updatePreconditionerEveryNIterations), mom, int(bool(paperPreconditioner)))
+    opt = Optimizer(o)
+    opt._keep = list(parameters)
+    return opt
+
+
+def Shampoo_factory(learningRate=0.001, clip=None, eps=1e-4, diagonalThreshold=256, updatePreconditionerEveryNIterations=100, momentum=0.0,
+                    paperPreconditioner=False):
+    return lambda params: Shampoo(params, learningRate, clip, eps, diagonalThreshold, updatePreconditionerEveryNIterations, momentum,
+                                  paperPreconditioner)
+
+
 class LearningRateSchedule:
     """nn/LearningRateSchedule.scala: `init` is the schedule's first state, `learningRateFactor(state, epoch, lastValidationLoss)` returns
     (next state, factor); the factor is what `loops.oneEpoch` and `Optimizer.step` take as scheduleFactor."""

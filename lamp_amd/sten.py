@@ -434,6 +434,20 @@ def synchronize():
     lib.lamp_device_synchronize()
 
 
+def symmetricEig(tensors: Sequence[STen], vectors: bool = False):
+    """Batched eigendecomposition of symmetric positive semi-definite matrices (square f32 / f64, side <= 512) in f64, every matrix of
+    the call in one launch per kernel form (lamp_symmetric_eig, kernels/eig.hip).  Returns (values, vectors or None, sweeps): per matrix
+    the eigenvalues in descending order as f64 [n], U with its columns in that order as f64 [n, n], and the Jacobi sweeps it took."""
+    n = len(tensors)
+    dev = tensors[0].device if n else 0
+    vals = [STen.zeros([t.shape[0]], F64, dev) for t in tensors]
+    vecs = [STen.zeros([t.shape[0], t.shape[0]], F64, dev) for t in tensors] if vectors else None
+    status = STen.zeros([n], I32, dev)
+    lib.lamp_symmetric_eig(handle_array([t.h for t in tensors]), n, handle_array([v.h for v in vals]),
+                           handle_array([u.h for u in vecs]) if vectors else None, status.h)
+    return vals, vecs, [int(x) for x in status.to_numpy()]
+
+
 def live_tensor_count() -> int:
     n = C.c_int64(); lib.lamp_live_tensor_count(C.byref(n)); return n.value
 
