@@ -799,6 +799,27 @@ int lamp_embedding(lamp_tensor** out, const lamp_tensor* weight, const lamp_tens
 /* ATen embedding_backward(grad, indices, num_weights, padding_idx, false, false): rows equal to padding_idx get no gradient;
  * lamp always passes padding_idx = 0 (ops.scala:2150-2158) */
 int lamp_embedding_backward(lamp_tensor** out, const lamp_tensor* grad, const lamp_tensor* indices, int64_t num_weights, int64_t padding_idx);
+/* BERT's input embedding (nn/bert/bert.scala:395-404): tokenEmbedding(tokens) + segmentEmbedding(segments) + positionalEmbedding[:, :T]
+ * as one launch forward and a grouped, gather-only gradient (kernels/bert.hip); f32 / f64 / bf16, no call synchronises with the host.
+ * tokenWeight [V, D], segmentWeight [Vs, D], positional [1, L, D] or [L, D] of one type, tokens / segments int64 [B, T], T <= L ->
+ *   out[b, t, :] = (tokenWeight[tokens[b, t], :] + segmentWeight[segments[b, t], :]) + positional[t, :]
+ * added in that order: f32 / f64 round after each addition (the bits of the composed chain), bf16 adds in f32 and rounds once.  An index
+ * is treated as lamp_embedding treats it: a negative one wraps once, one that is still outside reads as a row of zeros. */
+int lamp_bert_embedding_forward(lamp_tensor** out, const lamp_tensor* tokenWeight, const lamp_tensor* segmentWeight, const lamp_tensor* positional,
+                                const lamp_tensor* tokens, const lamp_tensor* segments);
+/* the three gradients given dout [B, T, D]; an output that is NULL costs no launch.
+ *   dPositional[0, t, :] = sum over b ascending of dout[b, t, :] for t < T, zero for T <= t < L
+ *   dToken[v, :]         = sum of dout[n, :] over the flat positions n = b T + t with tokens[n] == v, in ascending n
+ *   dSegment[s, :]       = the same over segments
+ * Row paddingIdx and every row whose id does not occur are written as zeros; an id outside [0, V) (no wrap, as lamp_embedding_backward)
+ * contributes nothing.  The positions are grouped by id (an integer histogram, one prefix sum, one stable sort for both tables), then
+ * every row is summed by one wave in acc_t, rounded once.  A row of more than lamp_bert_long_row occurrences is summed in chunks of that
+ * many positions by a launch of its own and the partial sums are added in chunk order: no floating atomics, the result depends on the
+ * input alone. */
+int lamp_bert_embedding_backward(lamp_tensor** dToken_or_null, lamp_tensor** dSegment_or_null, lamp_tensor** dPositional_or_null, const lamp_tensor* dout,
+                                 const lamp_tensor* tokens, const lamp_tensor* segments, int64_t V, int64_t Vs, int64_t L, int64_t paddingIdx);
+/* a table row of more occurrences than this is summed in chunks of this many positions (partial sums added in chunk order) */
+int lamp_bert_long_row(int64_t* out);
 /* RNG: Philox4x32-10 counter streams; bit-compat with libtorch streams is not required by any
  * reference test (SURVEY.md 8b "RNG / globals") */
 int lamp_rand(lamp_tensor** out, const int64_t* sizes, int ndim, int dtype, int device);

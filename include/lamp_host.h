@@ -95,6 +95,34 @@ int lamp_language_model_forward(lamp_module* m, lamp_var* tokens, const lamp_ten
                                 lamp_var** encoded, lamp_var** logits);
 int lamp_sequence_mask(lamp_var** out, const lamp_tensor* max_length, lamp_var* maskable, double fill);   /* MultiheadAttention.sequenceMask :667-749 */
 int lamp_masked_softmax(lamp_var** out, lamp_var* input, const lamp_tensor* max_length);                  /* MultiheadAttention.maskedSoftmax :751-762 */
+/* ---- BERT pretraining (lamp-core nn/bert/bert.scala).  State order = the reference's `state`: token table, segment table, the positional
+ * table (a parameter, [1, max_length, embedding_dim]), the blocks (gptOrder = false, no causal mask), then the masked-language-model
+ * decoder (Linear, LayerNorm without scale / bias, Linear) and the whole-sentence classifier (Linear, Linear).  position_embedding_or_null
+ * [max_length, embedding_dim]: NULL = PositionalEmbedding.vaswani in single precision, cast to dtype.  per_row_positions (not in the
+ * reference): 0 = positions index encoded.view(-1, D) as written (no b * T offset), 1 = every batch row gathers from its own rows. */
+int lamp_module_bert_encoder(lamp_module** out, int64_t max_length, int64_t vocabulary_size, int64_t segment_vocabulary_size, int64_t num_blocks,
+                             int64_t embedding_dim, int64_t attention_hidden_per_head, int64_t attention_num_heads, int64_t mlp_hidden, double dropout,
+                             int dtype, int device, int linearized,
+                             const lamp_tensor* position_embedding_or_null);   /* bert.scala:485-534; vars (tokens, segments), tensors (maxLength?) */
+int lamp_module_masked_language_model(lamp_module** out, int64_t input_dim, int64_t hidden_dim, int64_t vocabulary_size, int dtype, int device,
+                                      int per_row_positions);                   /* :347-359; vars (encoderOutput), tensors (predictionPositions) */
+int lamp_module_bert_pretrain(lamp_module** out, int64_t max_length, int64_t vocabulary_size, int64_t segment_vocabulary_size, int64_t mlm_hidden,
+                              int64_t whole_sentence_hidden, int64_t num_blocks, int64_t embedding_dim, int64_t attention_hidden_per_head,
+                              int64_t attention_num_heads, int64_t encoder_mlp_hidden, double dropout, int dtype, int device, int linearized,
+                              const lamp_tensor* position_embedding_or_null,
+                              int per_row_positions);   /* :244-285; vars (tokens, segments), tensors (positions, maxLength?) -> language model scores */
+int lamp_module_bert_loss(lamp_module** out, int64_t max_length, int64_t vocabulary_size, int64_t segment_vocabulary_size, int64_t mlm_hidden,
+                          int64_t whole_sentence_hidden, int64_t num_blocks, int64_t embedding_dim, int64_t attention_hidden_per_head,
+                          int64_t attention_num_heads, int64_t encoder_mlp_hidden, double dropout, int64_t pad_token, int dtype, int device,
+                          int linearized, const lamp_tensor* position_embedding_or_null,
+                          int per_row_positions);   /* :96-140; vars (tokens, segments), tensors (positions, maxLength?, mlmTarget, wholeSentenceTarget) -> loss */
+/* BertPretrainOutput(encoded, languageModelScores, wholeSentenceBinaryClassifierScore) (bert.scala:216-228) of a BertPretrainModule or
+ * a BertLoss; any output pointer may be NULL */
+int lamp_bert_pretrain_forward(lamp_module* m, lamp_var* tokens, lamp_var* segments, const lamp_tensor* positions, const lamp_tensor* max_length_or_null,
+                               lamp_var** encoded, lamp_var** language_model_scores, lamp_var** whole_sentence_score);
+/* BertEncoder's input embedding as one BertEmbedding node over the kernels of kernels/bert.hip (1) or as the reference's chain of
+ * Embedding, Embedding, Add, Slice and Add (0).  Process-wide; returns the previous value in *previous_or_null. */
+int lamp_bert_fused(int on, int* previous_or_null);
 /* ---- recurrent family (lamp-core nn/RNN.scala, GRU.scala, LSTM.scala, SeqLinear.scala, StatefulSeq.scala).  Inputs [time, batch, in], outputs
  * [time, batch, hidden].  State order = the reference's `state` (LSTM: Xi Xf Xo Hi Hf Ho Xc Hc bI bF bO bC; GRU: Xh Hh Xr Xz Hr Hz bR bZ bH;
  * RNN: Xh Hh bH; SeqLinear: weight, bias).  The plain constructors are the factories (normal(0, sqrt(2 / (fanIn + fanOut))), zero [1, hidden]

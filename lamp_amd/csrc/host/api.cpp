@@ -2,6 +2,7 @@
 #include "nn.h"
 #include "transformer.h"
 #include "recurrent.h"
+#include "bert.h"
 #include "../../../include/lamp_host.h"
 
 #include <cstring>
@@ -117,6 +118,7 @@ int lamp_op_apply(lamp_var** out, const char* name, lamp_var* const* vars, int n
     const bool hasFI = I(1) != 0, hasFJ = I(2) != 0;
     r = F::mpnn_aggregate(V(0), T(0), T(1), T(2), T(3), T(4), T(5), hasFI ? T(6) : Ten(), hasFJ ? T(hasFI ? 7 : 6) : Ten(), I(0) != 0);
   }
+  else if (n == "BertEmbedding") r = F::bert_embedding(V(0), V(1), V(2), V(3), V(4));   // (tokens, segments, tokenWeight, segmentWeight, positional)
   else if (n == "RepeatInterleave") r = F::repeat_interleave(V(0), V(1), I(0));
   else if (n == "ExpandAs") r = F::expand_as(V(0), T(0));
   else if (n == "Expand") r = F::expand(V(0), IV(0, ni));
@@ -261,6 +263,58 @@ int lamp_sequence_mask(lamp_var** out, const lamp_tensor* max_length, lamp_var* 
 }
 int lamp_masked_softmax(lamp_var** out, lamp_var* input, const lamp_tensor* max_length) {
   LAMP_API_BEGIN *out = wrap(MultiheadAttention::maskedSoftmax(input->v, borrow(max_length))); LAMP_API_END
+}
+// ---- BERT pretraining (bert.scala) ---------------------------------------------------------------------------
+int lamp_module_bert_encoder(lamp_module** out, int64_t max_length, int64_t vocabulary_size, int64_t segment_vocabulary_size, int64_t num_blocks,
+                             int64_t embedding_dim, int64_t attention_hidden_per_head, int64_t attention_num_heads, int64_t mlp_hidden, double dropout,
+                             int dtype, int device, int linearized, const lamp_tensor* position_embedding) {
+  LAMP_API_BEGIN
+  *out = wrapm(BertEncoder::make(max_length, vocabulary_size, segment_vocabulary_size, num_blocks, embedding_dim, attention_hidden_per_head,
+                                 attention_num_heads, mlp_hidden, dropout, dtype, device, linearized, position_embedding ? borrow(position_embedding) : Ten()));
+  LAMP_API_END
+}
+int lamp_module_masked_language_model(lamp_module** out, int64_t input_dim, int64_t hidden_dim, int64_t vocabulary_size, int dtype, int device,
+                                      int per_row_positions) {
+  LAMP_API_BEGIN *out = wrapm(MaskedLanguageModelModule::make(input_dim, hidden_dim, vocabulary_size, dtype, device, per_row_positions != 0)); LAMP_API_END
+}
+int lamp_module_bert_pretrain(lamp_module** out, int64_t max_length, int64_t vocabulary_size, int64_t segment_vocabulary_size, int64_t mlm_hidden,
+                              int64_t whole_sentence_hidden, int64_t num_blocks, int64_t embedding_dim, int64_t attention_hidden_per_head,
+                              int64_t attention_num_heads, int64_t encoder_mlp_hidden, double dropout, int dtype, int device, int linearized,
+                              const lamp_tensor* position_embedding, int per_row_positions) {
+  LAMP_API_BEGIN
+  *out = wrapm(BertPretrainModule::make(max_length, vocabulary_size, segment_vocabulary_size, mlm_hidden, whole_sentence_hidden, num_blocks, embedding_dim,
+                                        attention_hidden_per_head, attention_num_heads, encoder_mlp_hidden, dropout, dtype, device, linearized,
+                                        position_embedding ? borrow(position_embedding) : Ten(), per_row_positions != 0));
+  LAMP_API_END
+}
+int lamp_module_bert_loss(lamp_module** out, int64_t max_length, int64_t vocabulary_size, int64_t segment_vocabulary_size, int64_t mlm_hidden,
+                          int64_t whole_sentence_hidden, int64_t num_blocks, int64_t embedding_dim, int64_t attention_hidden_per_head,
+                          int64_t attention_num_heads, int64_t encoder_mlp_hidden, double dropout, int64_t pad_token, int dtype, int device,
+                          int linearized, const lamp_tensor* position_embedding, int per_row_positions) {
+  LAMP_API_BEGIN
+  *out = wrapm(BertLoss::make(max_length, vocabulary_size, segment_vocabulary_size, mlm_hidden, whole_sentence_hidden, num_blocks, embedding_dim,
+                              attention_hidden_per_head, attention_num_heads, encoder_mlp_hidden, dropout, pad_token, dtype, device, linearized,
+                              position_embedding ? borrow(position_embedding) : Ten(), per_row_positions != 0));
+  LAMP_API_END
+}
+int lamp_bert_pretrain_forward(lamp_module* m, lamp_var* tokens, lamp_var* segments, const lamp_tensor* positions, const lamp_tensor* max_length,
+                               lamp_var** encoded, lamp_var** language_model_scores, lamp_var** whole_sentence_score) {
+  LAMP_API_BEGIN
+  auto pm = std::dynamic_pointer_cast<BertPretrainModule>(m->m);
+  if (!pm) if (auto l = std::dynamic_pointer_cast<BertLoss>(m->m)) pm = l->pretrain;
+  LAMP_CHECK(pm, "lamp_bert_pretrain_forward: not a BertPretrainModule / BertLoss");
+  LAMP_CHECK(positions, "lamp_bert_pretrain_forward: NULL positions");
+  auto r = pm->run(tokens->v, segments->v, borrow(positions), max_length ? borrow(max_length) : Ten());
+  if (encoded) *encoded = wrap(r.encoded);
+  if (language_model_scores) *language_model_scores = wrap(r.languageModelScores);
+  if (whole_sentence_score) *whole_sentence_score = wrap(r.wholeSentenceBinaryClassifierScore);
+  LAMP_API_END
+}
+int lamp_bert_fused(int on, int* previous) {
+  LAMP_API_BEGIN
+  const bool prev = F::set_bert_fused(on != 0);
+  if (previous) *previous = prev ? 1 : 0;
+  LAMP_API_END
 }
 // ---- recurrent family (RNN.scala, GRU.scala, LSTM.scala, SeqLinear.scala, StatefulSeq.scala) ------------------------------
 int lamp_module_rnn(lamp_module** out, int64_t in, int64_t hidden, int dtype, int device) {

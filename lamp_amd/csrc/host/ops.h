@@ -132,6 +132,14 @@ Var mpnn_message(const Var& nodeFeatures, const Var& edgeFeatures, const Ten& ed
 // MPNN.aggregate (nn/graph/MPNN.scala:84-126) over the two groupings; fI / fJ undefined: that degree normalisation is off
 Var mpnn_aggregate(const Var& message, const Ten& edgeI, const Ten& edgeJ, const Ten& inRowptr, const Ten& inPerm, const Ten& outRowptr, const Ten& outPerm,
                    const Ten& fI, const Ten& fJ, bool aggregateJ);
+// BertEncoder's input embedding (nn/bert/bert.scala:397-404): tokenWeight[tokens] + segmentWeight[segments] + positional[:, :T] as one node.
+// tokens / segments: long [B, T] constants; tokenWeight [V, D], segmentWeight [Vs, D], positional [1, L, D].  bert_fused(): one
+// lamp_bert_embedding_forward and one lamp_bert_embedding_backward (padding id 0, as Embedding passes it) for the three gradients; otherwise
+// the reference's chain of Embedding, Embedding, Add, Slice and Add.
+Var bert_embedding(const Var& tokens, const Var& segments, const Var& tokenWeight, const Var& segmentWeight, const Var& positional);
+constexpr bool kBertFusedDefault = true;   // BASELINE.md section 15 holds the measurement behind it
+bool bert_fused();
+bool set_bert_fused(bool on);   // returns the previous value
 
 }  // namespace F
 }  // namespace host

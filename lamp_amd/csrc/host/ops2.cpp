@@ -6,6 +6,8 @@
 // outside SURVEY section 8.
 #include "ops.h"
 
+#include <atomic>
+
 namespace lamp {
 namespace host {
 
@@ -303,6 +305,52 @@ Var mpnn_aggregate(const Var& message, const Ten& edgeI, const Ten& edgeJ, const
     HCALL(lamp_mpnn_aggregate_backward(&dm, p.h(), edgeI.h(), edgeJ.h(), h(fI), h(fJ), aggregateJ ? 1 : 0));
     out.accumulate(Ten(dm), true);
   }});
+  return make_result(op, Ten(o));
+}
+
+// BertEmbedding: (tokenWeight[tokens] + segmentWeight[segments]) + positional[:, :T].  Fused: one forward launch; one
+// lamp_bert_embedding_backward gives the gradients of all the parameters that want one, whichever closure runs first makes the call and
+// leaves the others for its siblings (GraphAttentionAggregate's arrangement).  Padding id 0 for both tables, as Embedding's closure passes it.
+namespace {
+std::atomic<int> g_bert_fused{kBertFusedDefault ? 1 : 0};
+}
+bool bert_fused() { return g_bert_fused.load() != 0; }
+bool set_bert_fused(bool on) { return g_bert_fused.exchange(on ? 1 : 0) != 0; }
+
+Var bert_embedding(const Var& tokens, const Var& segments, const Var& tokenWeight, const Var& segmentWeight, const Var& positional) {
+  const Ten tv = tokens->value, sv = segments->value, pv = positional->value;
+  LAMP_CHECK(tv.ndim() == 2, "BertEmbedding: tokens must be [B, T] (long), got a tensor of " << tv.ndim() << " dimensions");
+  LAMP_CHECK(pv.ndim() == 3 && pv.size(0) == 1, "BertEmbedding: positional must be [1, maxLength, D]");
+  if (!bert_fused()) {   // bert.scala:397-404
+    LAMP_CHECK(tv.size(1) <= pv.size(1), "BertEmbedding: " << tv.size(1) << " tokens per sequence, the positional table has " << pv.size(1) << " rows");
+    return add(add(embedding(tokens, tokenWeight), embedding(segments, segmentWeight)), slice(positional, 1, 0, tv.size(1), 1));
+  }
+  auto op = new_op("BertEmbedding");
+  lamp_tensor* o = nullptr;
+  HCALL(lamp_bert_embedding_forward(&o, tokenWeight->value.h(), segmentWeight->value.h(), pv.h(), tv.h(), sv.h()));
+  const int64_t V = tokenWeight->value.size(0), Vs = segmentWeight->value.size(0), L = pv.size(1);
+  struct Cache { Ten g[3]; Ten p; };                       // dToken, dSegment, dPositional of one backward call, and the p they belong to
+  auto cache = std::make_shared<Cache>();
+  const bool want[3] = {tokenWeight->needsGrad(), segmentWeight->needsGrad(), positional->needsGrad()};
+  auto back = [=](int which) {
+    return [=](const Ten& p, Variable& v) {
+      if (!(cache->p.defined() && cache->p.h() == p.h() && cache->g[which].defined())) {
+        lamp_tensor* d[3] = {nullptr, nullptr, nullptr};
+        auto slot = [&](int k) { return (k == which || want[k]) ? &d[k] : nullptr; };
+        HCALL(lamp_bert_embedding_backward(slot(0), slot(1), slot(2), p.h(), tv.h(), sv.h(), V, Vs, L, /*padding_idx, as Embedding passes it*/ 0));
+        for (int k = 0; k < 3; k++) cache->g[k] = Ten(d[k]);
+        cache->p = p;
+      }
+      const Ten g = cache->g[which];
+      cache->g[which] = Ten();
+      if (!cache->g[0].defined() && !cache->g[1].defined() && !cache->g[2].defined()) cache->p = Ten();
+      v.accumulate(g, true);
+    };
+  };
+  op->reset = [cache]() { cache->g[0] = cache->g[1] = cache->g[2] = cache->p = Ten(); };
+  op->params.push_back({tokenWeight, back(0)});
+  op->params.push_back({segmentWeight, back(1)});
+  op->params.push_back({positional, back(2)});
   return make_result(op, Ten(o));
 }
 
