@@ -97,9 +97,7 @@ __global__ __launch_bounds__(256) void bert_group_keys_kernel(BertTables tb, int
     unsigned long long todo = __ballot(key >= 0);
     while (todo) {
       const int first = __ffsll((long long)todo) - 1;
-      const int klo = __builtin_amdgcn_readlane((int)(uint32_t)(uint64_t)key, first);
-      const int khi = __builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)key >> 32), first);
-      const int64_t k = (int64_t)(((uint64_t)(uint32_t)khi << 32) | (uint32_t)klo);
+      const int64_t k = lane_bcast(key, first);
       const unsigned long long same = __ballot(key == k);
       if (lane == first) atomicAdd(&counts[k], (int)__popcll(same));
       todo &= ~same;

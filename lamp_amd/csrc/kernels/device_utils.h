@@ -100,6 +100,22 @@ template <class T, int N> struct alignas(sizeof(T) * N) Vec {
   T v[N];
 };
 template <class T> constexpr int vec_width() { return 16 / sizeof(T); }
+template <class T, int V> __device__ __forceinline__ Vec<T, V> zero_packet() {
+  Vec<T, V> z;
+#pragma unroll
+  for (int j = 0; j < V; j++) z.v[j] = T(0);
+  return z;
+}
+template <class T, int V> __device__ __forceinline__ Vec<T, V> load_packet(const T* p) { return *reinterpret_cast<const Vec<T, V>*>(p); }
+
+// the value lane k holds, in every lane (k wave-uniform)
+__device__ __forceinline__ int64_t lane_bcast(int64_t v, int k) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(uint64_t)v, k);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), k);
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ float lane_bcast(float v, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k)); }
+__device__ __forceinline__ double lane_bcast(double v, int k) { return __longlong_as_double((long long)lane_bcast((int64_t)__double_as_longlong(v), k)); }
 
 // ---- dtype dispatch ---------------------------------------------------------------------------
 #define LAMP_DISPATCH_FLOAT(DT, T, ...)                                                           \

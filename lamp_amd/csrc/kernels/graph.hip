@@ -1,102 +1,173 @@
-// Graph convolution (lamp-core/src/main/scala/lamp/nn/graph/GCN.scala:30-145): D^-1/2 (A + A' + I) D^-1/2 X as one gather-only kernel
-// over a CSR of A + A', f32 and f64.
+// Graph layers, f32 and f64: graph convolution (GCN), graph attention and message passing (MPNN), each below under a heading of its
+// own.  The reference builds sparse tensors or chains of indexSelect / indexAdd; here the edges are grouped per node once per graph
+// (lamp_gcn_adjacency, lamp_graph_edge_csr: a rowptr and the stably sorted edges) and every sum per node is a gather-only kernel of one
+// shape, the row kernel:
 //
-// The reference builds a sparse COO tensor and multiplies it with `mm`; this library has no sparse tensor.  lamp_gcn_adjacency turns
-// the edge list into (rowptr, col, dinv) once per graph, lamp_gcn_aggregate is the product.  The matrix is symmetric, so the gradient
-// with respect to X is the same kernel applied to the incoming gradient.
-//
-// gcn_aggregate_kernel: a workgroup of kGcnWaves waves owns kGcnWaves neighbouring rows, a wave one row; the 64 lanes run across the
-// feature dimension (V columns each, 16-byte packets where D and the row pitches allow it), so every neighbour row is one coalesced
-// read and the output row one coalesced write.  Per 64 neighbours a wave reads col[p] and dinv[col[p]] once (one entry per lane) and
-// hands them round with v_readlane: the row address is wave-uniform.  kGcnUnroll neighbour rows are in flight per wave.  No atomics: a
-// row's sum runs over its neighbours in CSR order, which lamp_gcn_adjacency fixes (stable sort), so the result is a function of the
-// input alone.  A row longer than kGcnLongRow (a hub) would serialise its wave: all waves of the workgroup take a contiguous share of
-// its neighbours, park their partial sums in LDS, and wave 0 adds them in wave order.  D beyond one wave's reach is tiled in grid.y.
+// A workgroup of kWaves waves owns kWaves neighbouring rows (nodes), a wave one row; the 64 lanes run across the columns in packets of V
+// elements (16 bytes where the widths, pitches and addresses allow it), columns beyond one wave's reach are tiled in grid.y: every row
+// read is one coalesced read and the output row one coalesced write.  Per 64 edges a wave reads what it needs of them once, one entry
+// per lane, and hands the entries round with v_readlane, so a row's address is wave-uniform; U rows are in flight per wave
+// (for_each_edge).  No atomics: a row's sum runs over its edges in the grouping's order, which the stable sort fixes, so a result is a
+// function of the input alone.  A row of more than kLongRow edges (a hub) would serialise its wave: all waves of the workgroup take a
+// contiguous share of its edges (wave_share) and wave 0 adds their partial sums through LDS in wave order (merge_shares).  GCN takes
+// its long rows one after the other inside the workgroup; the other kernels give them a grid slice each (row_turn).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <string>
+#include <type_traits>
 #include "device_utils.h"
 
 namespace lamp {
 namespace {
 
-constexpr int kGcnWaves = 16;       // waves (= rows) per workgroup
-constexpr int kGcnLongRow = 256;    // a row with more neighbours is split across the workgroup's waves
+constexpr int kWaves = 16;          // waves (= rows) per workgroup of a row kernel
+constexpr int kLongRow = 256;       // a row with more edges is split across the workgroup's waves
 constexpr int kGcnUnroll = 8;       // neighbour rows in flight per wave
+constexpr int kMpnnUnroll = 4;      // edge rows in flight per wave
+constexpr int kMpnnEdgeBlock = 256; // threads per workgroup of the per-edge kernels
 
-// the value lane k holds, in every lane (k wave-uniform)
-__device__ __forceinline__ int64_t lane_bcast(int64_t v, int k) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(uint64_t)v, k);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), k);
-  return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ float lane_bcast(float v, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k)); }
-__device__ __forceinline__ double lane_bcast(double v, int k) { return __longlong_as_double((long long)lane_bcast((int64_t)__double_as_longlong(v), k)); }
-
-template <class T, int V> __device__ __forceinline__ Vec<T, V> gcn_zero() {
-  Vec<T, V> z;
+// what a lane reads of one edge before any row is read: NI indices and NF factors
+template <class T, int NI, int NF> struct EdgeEntry {
+  int64_t i[NI] = {};
+  T f[NF ? NF : 1] = {};
+  // lane k's entry, in every lane (k wave-uniform)
+  __device__ __forceinline__ EdgeEntry bcast(int k) const {
+    EdgeEntry r;
 #pragma unroll
-  for (int j = 0; j < V; j++) z.v[j] = T(0);
-  return z;
-}
-template <class T, int V> __device__ __forceinline__ Vec<T, V> gcn_load(const T* p) { return *reinterpret_cast<const Vec<T, V>*>(p); }
+    for (int j = 0; j < NI; j++) r.i[j] = lane_bcast(i[j], k);
+#pragma unroll
+    for (int j = 0; j < NF; j++) r.f[j] = lane_bcast(f[j], k);
+    return r;
+  }
+};
+// what a lane has fetched for one edge: NS scalars and its packet of the edge's row
+template <class T, int V, int NS> struct EdgeItem {
+  T s[NS ? NS : 1];
+  Vec<T, V> v;
+};
 
-// acc += sum over p in [b, e), in that order, of dinv[col[p]] * x[col[p], c0 .. c0 + V).  xc = x + c0; lanes with `active` false hold
-// no column (c0 >= D): they take part in the index reads and load no row.  b and e are wave-uniform.
-template <class T, int V>
-__device__ __forceinline__ void gcn_gather(Vec<T, V>& acc, const T* __restrict__ xc, int64_t ldx, const int64_t* __restrict__ col,
-                                           const T* __restrict__ dinv, int64_t b, int64_t e, int lane, bool active) {
+// use(fetch(entry of edge p)) for p in [b, e), in that order (b and e wave-uniform): lane l reads load(p + l) for 64 edges at a time, the
+// entries go round by bcast, U fetches are in flight before the first is used.  Every lane takes part in the index reads, also one that
+// holds no column and fetches nothing.
+template <int U, class Load, class Fetch, class Use>
+__device__ __forceinline__ void for_each_edge(int64_t b, int64_t e, int lane, Load load, Fetch fetch, Use use) {
   for (int64_t p = b; p < e; p += 64) {
     const int n = (int)(e - p < 64 ? e - p : 64);
-    int64_t c = 0;
-    T dv = T(0);
-    if (lane < n) { c = col[p + lane]; dv = dinv[c]; }
+    decltype(load(p)) mine;
+    if (lane < n) mine = load(p + lane);
     int k = 0;
-    for (; k + kGcnUnroll <= n; k += kGcnUnroll) {
-      Vec<T, V> v[kGcnUnroll];
-      T d[kGcnUnroll];
+    for (; k + U <= n; k += U) {
+      decltype(fetch(mine)) item[U];
 #pragma unroll
-      for (int u = 0; u < kGcnUnroll; u++) {
-        const int64_t cu = lane_bcast(c, k + u);
-        d[u] = lane_bcast(dv, k + u);
-        v[u] = active ? gcn_load<T, V>(xc + cu * ldx) : gcn_zero<T, V>();
-      }
+      for (int u = 0; u < U; u++) item[u] = fetch(mine.bcast(k + u));
 #pragma unroll
-      for (int u = 0; u < kGcnUnroll; u++)
-#pragma unroll
-        for (int j = 0; j < V; j++) acc.v[j] += d[u] * v[u].v[j];
+      for (int u = 0; u < U; u++) use(item[u]);
     }
-    for (; k < n; k++) {
-      const int64_t cu = lane_bcast(c, k);
-      const T d = lane_bcast(dv, k);
-      const Vec<T, V> v = active ? gcn_load<T, V>(xc + cu * ldx) : gcn_zero<T, V>();
-#pragma unroll
-      for (int j = 0; j < V; j++) acc.v[j] += d * v.v[j];
-    }
+    for (; k < n; k++) use(fetch(mine.bcast(k)));
   }
 }
 
-// out[r, :] = dinv[r] * (dinv[r] * x[r, :] + sum over the row's neighbours c, in CSR order, of dinv[c] * x[c, :]).  D % V == 0.
-// grid: (ceil(N / kGcnWaves), ceil(D / (64 * V))), block: kGcnWaves * 64.
+// wave's share [lo, hi) of n items split over the workgroup's waves: contiguous, in wave order
+struct Share { int64_t lo, hi; };
+__device__ __forceinline__ Share wave_share(int64_t n, int wave) {
+  const int64_t chunk = (n + kWaves - 1) / kWaves;
+  const int64_t lo = wave * chunk < n ? wave * chunk : n;
+  return {lo, lo + chunk < n ? lo + chunk : n};
+}
+
+// The row schedule of a grid of (ceil(N / kWaves), tiles, kWaves + 1) workgroups.  Slice z = 0 is the own turn: every wave its own row,
+// unless it is a long one.  Slice z = k + 1 is the turn of the workgroup's k-th row if it is long, by all waves of the workgroup: `own`,
+// r and takes() are then the same in every thread of the workgroup, so the barriers of that turn are.  A grid slice per k, so that long
+// rows that are neighbours (hubs numbered 0, 1, 2, ...) run side by side and not one after the other in their workgroup; the workgroups
+// of the slices k >= 0 whose row is short, nearly all of them, read two row pointers and leave.
+// A kernel writes `for (int k = first_turn(); is_turn(k); k++) { const RowTurn t = row_turn(k, N, wave); ... }`: a loop of one turn, left
+// with `continue`.  It stays a loop because the compiler's choice of which products of GatAcc::merge it contracts into an fma differs
+// between the loop and the straight line, and the results of these kernels are held bitwise from release to release.
+struct RowTurn {
+  bool own;
+  int64_t r;      // -1: no row
+  // whether a row of n edges is this turn's business; and the wave's share of its edges
+  __device__ __forceinline__ bool takes(int64_t n) const { return own != (n > kLongRow); }
+  __device__ __forceinline__ Share share(int64_t n, int wave) const { return own ? Share{0, n} : wave_share(n, wave); }
+};
+__device__ __forceinline__ int first_turn() { return (int)blockIdx.z - 1; }
+__device__ __forceinline__ bool is_turn(int k) { return k < (int)blockIdx.z && k < kWaves; }
+__device__ __forceinline__ RowTurn row_turn(int k, int64_t N, int wave) {
+  const int64_t row0 = (int64_t)blockIdx.x * kWaves;
+  const int nrows = (int)(N - row0 < kWaves ? N - row0 : kWaves), i = k < 0 ? wave : k;
+  return {k < 0, i < nrows ? row0 + i : -1};
+}
+
+// acc[a] of wave 0 += acc[a] of the waves 1, 2, ... in that order.  Every thread of the workgroup calls it.
+template <class T, int V, int NA>
+__device__ __forceinline__ void merge_shares(Vec<T, V> (&acc)[NA], Vec<T, V> (&part)[NA][kWaves][64], int wave, int lane, bool active) {
+#pragma unroll
+  for (int a = 0; a < NA; a++) part[a][wave][lane] = acc[a];
+  __syncthreads();
+  if (wave == 0 && active) {
+#pragma unroll 1
+    for (int w = 1; w < kWaves; w++) {
+#pragma unroll
+      for (int a = 0; a < NA; a++) {
+        const Vec<T, V> q = part[a][w][lane];
+#pragma unroll
+        for (int j = 0; j < V; j++) acc[a].v[j] += q.v[j];
+      }
+    }
+  }
+  __syncthreads();
+}
+
+// ---- graph convolution (lamp-core/src/main/scala/lamp/nn/graph/GCN.scala:30-145) ------------------------------------------------------------
+// D^-1/2 (A + A' + I) D^-1/2 X over a CSR of A + A'.  The reference builds a sparse COO tensor and multiplies it with `mm`; this library
+// has no sparse tensor.  lamp_gcn_adjacency turns the edge list into (rowptr, col, dinv) once per graph, lamp_gcn_aggregate is the
+// product, a row kernel (see the head of the file) whose entry per neighbour is col[p] and dinv[col[p]].  The matrix is symmetric, so
+// the gradient with respect to X is the same kernel applied to the incoming gradient.
+
+// acc += sum over p in [b, e), in that order, of dinv[col[p]] * x[col[p], c0 .. c0 + V).  xc = x + c0; lanes with `active` false hold
+// no column (c0 >= D) and load no row.
 template <class T, int V>
-__global__ __launch_bounds__(kGcnWaves * 64) void gcn_aggregate_kernel(T* __restrict__ out, int64_t ldo, const T* __restrict__ x, int64_t ldx,
+__device__ __forceinline__ void gcn_gather(Vec<T, V>& acc, const T* __restrict__ xc, int64_t ldx, const int64_t* __restrict__ col,
+                                           const T* __restrict__ dinv, int64_t b, int64_t e, int lane, bool active) {
+  using Entry = EdgeEntry<T, 1, 1>;
+  using Item = EdgeItem<T, V, 1>;
+  for_each_edge<kGcnUnroll>(
+      b, e, lane,
+      [&](int64_t p) {
+        Entry en;
+        en.i[0] = col[p];
+        en.f[0] = dinv[en.i[0]];
+        return en;
+      },
+      [&](const Entry& en) { return Item{{en.f[0]}, active ? load_packet<T, V>(xc + en.i[0] * ldx) : zero_packet<T, V>()}; },
+      [&](const Item& it) {
+#pragma unroll
+        for (int j = 0; j < V; j++) acc.v[j] += it.s[0] * it.v.v[j];
+      });
+}
+
+// out[r, :] = dinv[r] * (dinv[r] * x[r, :] + sum over the row's neighbours c, in CSR order, of dinv[c] * x[c, :]).  D % V == 0.
+// grid: (ceil(N / kWaves), ceil(D / (64 * V))), block: kWaves * 64.
+template <class T, int V>
+__global__ __launch_bounds__(kWaves * 64) void gcn_aggregate_kernel(T* __restrict__ out, int64_t ldo, const T* __restrict__ x, int64_t ldx,
                                                                         const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,
                                                                         const T* __restrict__ dinv, int64_t N, int64_t D) {
-  __shared__ Vec<T, V> part[kGcnWaves][64];
+  __shared__ Vec<T, V> part[kWaves][64];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int64_t c0 = ((int64_t)blockIdx.y * 64 + lane) * V;
   const bool active = c0 < D;
-  const int64_t row0 = (int64_t)blockIdx.x * kGcnWaves;
+  const int64_t row0 = (int64_t)blockIdx.x * kWaves;
   const T* xc = x + c0;
 
   // every wave its own row, unless it is a long one
   const int64_t r = row0 + wave;
   if (r < N) {
     const int64_t b = rowptr[r], e = rowptr[r + 1];
-    if (e - b <= kGcnLongRow) {
+    if (e - b <= kLongRow) {
       const T dr = dinv[r];
-      Vec<T, V> acc = active ? gcn_load<T, V>(xc + r * ldx) : gcn_zero<T, V>();
+      Vec<T, V> acc = active ? load_packet<T, V>(xc + r * ldx) : zero_packet<T, V>();
 #pragma unroll
       for (int j = 0; j < V; j++) acc.v[j] *= dr;
       gcn_gather<T, V>(acc, xc, ldx, col, dinv, b, e, lane, active);
@@ -108,25 +179,24 @@ __global__ __launch_bounds__(kGcnWaves * 64) void gcn_aggregate_kernel(T* __rest
     }
   }
 
-  // the long rows of this workgroup, one after the other, by all its waves (the conditions are the same in every thread of the workgroup)
-  const int nrows = (int)(N - row0 < kGcnWaves ? N - row0 : kGcnWaves);
+  // the long rows of this workgroup, one after the other, by all its waves (the conditions are the same in every thread of the workgroup).
+  // Not merge_shares: this sum starts from the row's own term and adds the shares 0 to kWaves - 1 to it.
+  const int nrows = (int)(N - row0 < kWaves ? N - row0 : kWaves);
   for (int k = 0; k < nrows; k++) {
     const int64_t lr = row0 + k;
     const int64_t b = rowptr[lr], e = rowptr[lr + 1];
-    if (e - b <= kGcnLongRow) continue;
-    const int64_t chunk = (e - b + kGcnWaves - 1) / kGcnWaves;
-    const int64_t pb = b + wave * chunk < e ? b + wave * chunk : e;
-    const int64_t pe = pb + chunk < e ? pb + chunk : e;
-    Vec<T, V> acc = gcn_zero<T, V>();
-    gcn_gather<T, V>(acc, xc, ldx, col, dinv, pb, pe, lane, active);
+    if (e - b <= kLongRow) continue;
+    const Share sh = wave_share(e - b, wave);
+    Vec<T, V> acc = zero_packet<T, V>();
+    gcn_gather<T, V>(acc, xc, ldx, col, dinv, b + sh.lo, b + sh.hi, lane, active);
     part[wave][lane] = acc;
     __syncthreads();
     if (wave == 0 && active) {
       const T dr = dinv[lr];
-      Vec<T, V> s = gcn_load<T, V>(xc + lr * ldx);
+      Vec<T, V> s = load_packet<T, V>(xc + lr * ldx);
 #pragma unroll
       for (int j = 0; j < V; j++) s.v[j] *= dr;
-      for (int w = 0; w < kGcnWaves; w++) {
+      for (int w = 0; w < kWaves; w++) {
         const Vec<T, V> q = part[w][lane];
 #pragma unroll
         for (int j = 0; j < V; j++) s.v[j] += q.v[j];
@@ -195,17 +265,13 @@ __global__ __launch_bounds__(1024) void gcn_rowptr_dinv_kernel(const int64_t* __
 // Everything from `activations` to `h`: a softmax of score [E, H] over the edges that share a destination, and the sum of the source
 // nodes' value rows [N, H, V] under those weights.  The reference writes it as exp / indexAdd / log / indexSelect / exp / indexSelect /
 // Mult / indexAdd against one global maximum; here the edges are grouped by destination once per graph (lamp_graph_edge_csr: rowptr
-// [N + 1] and the edge ids stably sorted by endpoint) and every kernel is gather-only, without atomics, with a fixed order.
+// [N + 1] and the edge ids stably sorted by endpoint).
 //
-// gat_forward_kernel and gat_backward_value_kernel have gcn_aggregate_kernel's shape: a wave per row, lanes across the C = H * V columns
-// in packets of VW elements, C tiled in grid.y, edge id and source row read once per 64 edges (one per lane) and passed round with
-// v_readlane, kGatUnroll edges in flight, a row of more than kGatLongRow edges split over the workgroup's waves and merged through LDS
-// by wave 0 in wave order.  A packet of two may straddle a head boundary (V odd): ONE = false keeps a softmax state per element then,
-// ONE = true one per lane; packets of four are used only where V % 4 == 0.  The softmax is the online form with one exp per edge and
-// head: against the row's running maximum m, either the new score is larger (the sums so far are scaled by exp(m - x)) or it is not (it
-// enters as exp(x - m)).
-constexpr int kGatWaves = 16;       // waves (= rows) per workgroup
-constexpr int kGatLongRow = 256;    // a row with more edges is split across the workgroup's waves
+// gat_forward_kernel and gat_backward_value_kernel are row kernels (see the head of the file) over the C = H * V columns in packets of VW
+// elements; an edge's entry is its id and its source row.  A packet of two may straddle a head boundary (V odd): ONE = false keeps a
+// softmax state per element then, ONE = true one per lane; packets of four are used only where V % 4 == 0.  The softmax is the online
+// form with one exp per edge and head: against the row's running maximum m, either the new score is larger (the sums so far are scaled
+// by exp(m - x)) or it is not (it enters as exp(x - m)).
 // edges in flight per wave (f64's exp leaves room for fewer)
 template <class T> constexpr int gat_unroll() { return sizeof(T) == 8 ? 2 : 4; }
 
@@ -223,7 +289,7 @@ template <class T, int VW, bool ONE> struct GatAcc {
   __device__ __forceinline__ void init() {
 #pragma unroll
     for (int h = 0; h < NH; h++) { m[h] = gat_neg_inf<T>(); s[h] = T(0); }
-    a = gcn_zero<T, VW>();
+    a = zero_packet<T, VW>();
   }
   // one edge: its scores x (finite) for the packet's heads and its value packet v
   __device__ __forceinline__ void step(const T (&x)[NH], const Vec<T, VW>& v) {
@@ -259,39 +325,31 @@ template <class T, int VW, bool ONE> struct GatAcc {
   }
 };
 
-// st takes in the edges perm[b .. e) in that order: score[edge, hh[.]] and value row src[edge], columns c0 .. c0 + VW (vc = value + c0).
-// Lanes with `active` false hold no column: they take part in the index reads and load nothing else.  b and e are wave-uniform.
-template <class T, int VW, bool ONE>
-__device__ __forceinline__ void gat_gather(GatAcc<T, VW, ONE>& st, const T* __restrict__ score, int64_t H, const int (&hh)[ONE ? 1 : VW],
-                                           const T* __restrict__ vc, int64_t ldv, const int64_t* __restrict__ perm, const int64_t* __restrict__ src,
-                                           int64_t b, int64_t e, int lane, bool active) {
-  constexpr int NH = ONE ? 1 : VW, kGatUnroll = gat_unroll<T>();
-  for (int64_t p = b; p < e; p += 64) {
-    const int n = (int)(e - p < 64 ? e - p : 64);
-    int64_t ed = 0, sr = 0;
-    if (lane < n) { ed = perm[p + lane]; sr = src[ed]; }
-    int k = 0;
-    for (; k + kGatUnroll <= n; k += kGatUnroll) {
-      Vec<T, VW> v[kGatUnroll];
-      T x[kGatUnroll][NH];
+// use(item) for the edges perm[b .. e) in that order: item.s[.] = tab[edge, hh[.]] (tab [E, H]: the scores or the weights) and item.v =
+// row src[edge], columns c0 .. c0 + VW (rc = rows + c0, pitch ld).  Lanes with `active` false hold no column: they get zeros.
+template <class T, int VW, bool ONE, class Use>
+__device__ __forceinline__ void gat_for_each_edge(const T* __restrict__ tab, int64_t H, const int (&hh)[ONE ? 1 : VW], const T* __restrict__ rc, int64_t ld,
+                                                  const int64_t* __restrict__ perm, const int64_t* __restrict__ src, int64_t b, int64_t e, int lane,
+                                                  bool active, Use use) {
+  constexpr int NH = ONE ? 1 : VW;
+  using Entry = EdgeEntry<T, 2, 0>;
+  using Item = EdgeItem<T, VW, NH>;
+  for_each_edge<gat_unroll<T>()>(
+      b, e, lane,
+      [&](int64_t p) {
+        Entry en;
+        en.i[0] = perm[p];
+        en.i[1] = src[en.i[0]];
+        return en;
+      },
+      [&](const Entry& en) {
+        Item it;
 #pragma unroll
-      for (int u = 0; u < kGatUnroll; u++) {
-        const int64_t eu = lane_bcast(ed, k + u), su = lane_bcast(sr, k + u);
-#pragma unroll
-        for (int h = 0; h < NH; h++) x[u][h] = active ? score[eu * H + hh[h]] : T(0);
-        v[u] = active ? gcn_load<T, VW>(vc + su * ldv) : gcn_zero<T, VW>();
-      }
-#pragma unroll
-      for (int u = 0; u < kGatUnroll; u++) st.step(x[u], v[u]);
-    }
-    for (; k < n; k++) {
-      const int64_t eu = lane_bcast(ed, k), su = lane_bcast(sr, k);
-      T x[NH];
-#pragma unroll
-      for (int h = 0; h < NH; h++) x[h] = active ? score[eu * H + hh[h]] : T(0);
-      st.step(x, active ? gcn_load<T, VW>(vc + su * ldv) : gcn_zero<T, VW>());
-    }
-  }
+        for (int h = 0; h < NH; h++) it.s[h] = active ? tab[en.i[0] * H + hh[h]] : T(0);
+        it.v = active ? load_packet<T, VW>(rc + en.i[1] * ld) : zero_packet<T, VW>();
+        return it;
+      },
+      use);
 }
 
 // out[r, c0 ..] = a / s, and lse[r, h] = m + log s from the lane that holds head h's first column; a row without an edge: zeros and -inf
@@ -309,15 +367,15 @@ __device__ __forceinline__ void gat_finish(const GatAcc<T, VW, ONE>& st, T* __re
 }
 
 // out [N, C], lse [N, H] from score [E, H], value [N, H, V] (C = H * V, C % VW == 0; ONE: V % VW == 0) over the incoming grouping
-// (rowptr, perm).  grid: (ceil(N / kGatWaves), ceil(C / (64 * VW))), block: kGatWaves * 64.
+// (rowptr, perm).  grid: (ceil(N / kWaves), ceil(C / (64 * VW)), kWaves + 1), block: kWaves * 64.
 template <class T, int VW, bool ONE>
-__global__ __launch_bounds__(kGatWaves * 64) void gat_forward_kernel(T* __restrict__ out, T* __restrict__ lse, const T* __restrict__ score,
+__global__ __launch_bounds__(kWaves * 64) void gat_forward_kernel(T* __restrict__ out, T* __restrict__ lse, const T* __restrict__ score,
                                                                       const T* __restrict__ value, const int64_t* __restrict__ edgeI,
                                                                       const int64_t* __restrict__ rowptr, const int64_t* __restrict__ perm, int64_t N,
                                                                       int64_t H, int V) {
   constexpr int NH = ONE ? 1 : VW;
-  __shared__ Vec<T, VW> part[kGatWaves][64];
-  __shared__ T pm[kGatWaves][NH][64], ps[kGatWaves][NH][64];
+  __shared__ Vec<T, VW> part[kWaves][64];
+  __shared__ T pm[kWaves][NH][64], ps[kWaves][NH][64];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int64_t C = H * V;
@@ -326,97 +384,48 @@ __global__ __launch_bounds__(kGatWaves * 64) void gat_forward_kernel(T* __restri
   int hh[NH];
 #pragma unroll
   for (int h = 0; h < NH; h++) hh[h] = active ? (c0 + h) / V : 0;
-  const int64_t row0 = (int64_t)blockIdx.x * kGatWaves;
-  const T* vc = value + c0;
-  const int nrows = (int)(N - row0 < kGatWaves ? N - row0 : kGatWaves);
 
-  // k = blockIdx.z - 1.  k = -1: every wave its own row, unless it is a long one; k >= 0: row row0 + k if it is long, by all waves of the
-  // workgroup (that condition is the same in every thread of the workgroup, so the barriers are).  A grid slice per k, so that long rows
-  // that are neighbours (hubs numbered 0, 1, 2, ...) run side by side and not one after the other in their workgroup; the workgroups of the
-  // slices k >= 0 whose row is short, nearly all of them, read two row pointers and leave.
-  for (int k = (int)blockIdx.z - 1; k < (int)blockIdx.z && k < nrows; k++) {   // one turn: a grid slice per k
-    const bool own = k < 0;
-    const int64_t r = own ? (wave < nrows ? row0 + wave : -1) : row0 + k;
-    int64_t b = 0, e = 0;
-    if (r >= 0) { b = rowptr[r]; e = rowptr[r + 1]; }
-    const bool longRow = e - b > kGatLongRow;
-    if (own == longRow) continue;
-    if (!own) {
-      const int64_t chunk = (e - b + kGatWaves - 1) / kGatWaves;
-      b = b + wave * chunk < e ? b + wave * chunk : e;
-      e = b + chunk < e ? b + chunk : e;
-    }
+  for (int k = first_turn(); is_turn(k); k++) {
+    const RowTurn t = row_turn(k, N, wave);
+    int64_t b = 0, n = 0;
+    if (t.r >= 0) { b = rowptr[t.r]; n = rowptr[t.r + 1] - b; }
+    if (!t.takes(n)) continue;
+    const Share sh = t.share(n, wave);
     GatAcc<T, VW, ONE> st;
     st.init();
-    gat_gather<T, VW, ONE>(st, score, H, hh, vc, C, perm, edgeI, b, e, lane, active);
-    if (own) {
-      if (active && r >= 0) gat_finish<T, VW, ONE>(st, out, lse, r, C, H, V, c0, hh);
+    gat_for_each_edge<T, VW, ONE>(score, H, hh, value + c0, C, perm, edgeI, b + sh.lo, b + sh.hi, lane, active,
+                                  [&](const EdgeItem<T, VW, NH>& it) { st.step(it.s, it.v); });
+    if (t.own) {
+      if (active && t.r >= 0) gat_finish<T, VW, ONE>(st, out, lse, t.r, C, H, V, c0, hh);
       continue;
     }
+    // not merge_shares: a share's state is rescaled to the common maximum as it is added (GatAcc::merge)
     part[wave][lane] = st.a;
 #pragma unroll
     for (int h = 0; h < NH; h++) { pm[wave][h][lane] = st.m[h]; ps[wave][h][lane] = st.s[h]; }
     __syncthreads();
     if (wave == 0 && active) {
 #pragma unroll 1
-      for (int w = 1; w < kGatWaves; w++) {
+      for (int w = 1; w < kWaves; w++) {
         T mw[NH], sw[NH];
 #pragma unroll
         for (int h = 0; h < NH; h++) { mw[h] = pm[w][h][lane]; sw[h] = ps[w][h][lane]; }
         st.merge(mw, sw, part[w][lane]);
       }
-      gat_finish<T, VW, ONE>(st, out, lse, r, C, H, V, c0, hh);
+      gat_finish<T, VW, ONE>(st, out, lse, t.r, C, H, V, c0, hh);
     }
     __syncthreads();
-  }
-}
-
-// acc += sum over the edges perm[b .. e), in that order, of a[edge, hh[.]] * x[src[edge], c0 .. c0 + VW) (xc = x + c0)
-template <class T, int VW, bool ONE>
-__device__ __forceinline__ void gat_weighted_gather(Vec<T, VW>& acc, const T* __restrict__ a, int64_t H, const int (&hh)[ONE ? 1 : VW],
-                                                    const T* __restrict__ xc, int64_t ldx, const int64_t* __restrict__ perm,
-                                                    const int64_t* __restrict__ src, int64_t b, int64_t e, int lane, bool active) {
-  constexpr int NH = ONE ? 1 : VW, kGatUnroll = gat_unroll<T>();
-  for (int64_t p = b; p < e; p += 64) {
-    const int n = (int)(e - p < 64 ? e - p : 64);
-    int64_t ed = 0, sr = 0;
-    if (lane < n) { ed = perm[p + lane]; sr = src[ed]; }
-    int k = 0;
-    for (; k + kGatUnroll <= n; k += kGatUnroll) {
-      Vec<T, VW> v[kGatUnroll];
-      T w[kGatUnroll][NH];
-#pragma unroll
-      for (int u = 0; u < kGatUnroll; u++) {
-        const int64_t eu = lane_bcast(ed, k + u), su = lane_bcast(sr, k + u);
-#pragma unroll
-        for (int h = 0; h < NH; h++) w[u][h] = active ? a[eu * H + hh[h]] : T(0);
-        v[u] = active ? gcn_load<T, VW>(xc + su * ldx) : gcn_zero<T, VW>();
-      }
-#pragma unroll
-      for (int u = 0; u < kGatUnroll; u++)
-#pragma unroll
-        for (int j = 0; j < VW; j++) acc.v[j] += w[u][ONE ? 0 : j] * v[u].v[j];
-    }
-    for (; k < n; k++) {
-      const int64_t eu = lane_bcast(ed, k), su = lane_bcast(sr, k);
-      T w[NH];
-#pragma unroll
-      for (int h = 0; h < NH; h++) w[h] = active ? a[eu * H + hh[h]] : T(0);
-      const Vec<T, VW> v = active ? gcn_load<T, VW>(xc + su * ldx) : gcn_zero<T, VW>();
-#pragma unroll
-      for (int j = 0; j < VW; j++) acc.v[j] += w[ONE ? 0 : j] * v.v[j];
-    }
   }
 }
 
 // dvalue[i, h, :] = sum over the edges e leaving i (the outgoing grouping, in its order) of a[e, h] * dout[edgeJ[e], h, :].  Same grid,
 // same split of a long row; the partial sums are added in wave order.
 template <class T, int VW, bool ONE>
-__global__ __launch_bounds__(kGatWaves * 64) void gat_backward_value_kernel(T* __restrict__ dvalue, const T* __restrict__ a, const T* __restrict__ dout,
+__global__ __launch_bounds__(kWaves * 64) void gat_backward_value_kernel(T* __restrict__ dvalue, const T* __restrict__ a, const T* __restrict__ dout,
                                                                              const int64_t* __restrict__ edgeJ, const int64_t* __restrict__ rowptr,
                                                                              const int64_t* __restrict__ perm, int64_t N, int64_t H, int V) {
   constexpr int NH = ONE ? 1 : VW;
-  __shared__ Vec<T, VW> part[kGatWaves][64];
+  __shared__ Vec<T, VW> part[1][kWaves][64];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int64_t C = H * V;
@@ -425,40 +434,20 @@ __global__ __launch_bounds__(kGatWaves * 64) void gat_backward_value_kernel(T* _
   int hh[NH];
 #pragma unroll
   for (int h = 0; h < NH; h++) hh[h] = active ? (c0 + h) / V : 0;
-  const int64_t row0 = (int64_t)blockIdx.x * kGatWaves;
-  const T* xc = dout + c0;
-  const int nrows = (int)(N - row0 < kGatWaves ? N - row0 : kGatWaves);
 
-  for (int k = (int)blockIdx.z - 1; k < (int)blockIdx.z && k < nrows; k++) {   // one turn: a grid slice per k          // as in gat_forward_kernel
-    const bool own = k < 0;
-    const int64_t r = own ? (wave < nrows ? row0 + wave : -1) : row0 + k;
-    int64_t b = 0, e = 0;
-    if (r >= 0) { b = rowptr[r]; e = rowptr[r + 1]; }
-    const bool longRow = e - b > kGatLongRow;
-    if (own == longRow) continue;
-    if (!own) {
-      const int64_t chunk = (e - b + kGatWaves - 1) / kGatWaves;
-      b = b + wave * chunk < e ? b + wave * chunk : e;
-      e = b + chunk < e ? b + chunk : e;
-    }
-    Vec<T, VW> acc = gcn_zero<T, VW>();
-    gat_weighted_gather<T, VW, ONE>(acc, a, H, hh, xc, C, perm, edgeJ, b, e, lane, active);
-    if (own) {
-      if (active && r >= 0) *reinterpret_cast<Vec<T, VW>*>(dvalue + r * C + c0) = acc;
-      continue;
-    }
-    part[wave][lane] = acc;
-    __syncthreads();
-    if (wave == 0 && active) {
-#pragma unroll 1
-      for (int w = 1; w < kGatWaves; w++) {
-        const Vec<T, VW> q = part[w][lane];
+  for (int k = first_turn(); is_turn(k); k++) {
+    const RowTurn t = row_turn(k, N, wave);
+    int64_t b = 0, n = 0;
+    if (t.r >= 0) { b = rowptr[t.r]; n = rowptr[t.r + 1] - b; }
+    if (!t.takes(n)) continue;
+    const Share sh = t.share(n, wave);
+    Vec<T, VW> acc[1] = {zero_packet<T, VW>()};
+    gat_for_each_edge<T, VW, ONE>(a, H, hh, dout + c0, C, perm, edgeJ, b + sh.lo, b + sh.hi, lane, active, [&](const EdgeItem<T, VW, NH>& it) {
 #pragma unroll
-        for (int j = 0; j < VW; j++) acc.v[j] += q.v[j];
-      }
-      *reinterpret_cast<Vec<T, VW>*>(dvalue + r * C + c0) = acc;
-    }
-    __syncthreads();
+      for (int j = 0; j < VW; j++) acc[0].v[j] += it.s[ONE ? 0 : j] * it.v.v[j];
+    });
+    if (!t.own) merge_shares(acc, part, wave, lane, active);
+    if (active && t.r >= 0 && (t.own || wave == 0)) *reinterpret_cast<Vec<T, VW>*>(dvalue + t.r * C + c0) = acc[0];
   }
 }
 
@@ -500,8 +489,8 @@ __device__ __forceinline__ void gat_score_edges(T* __restrict__ dscore, T* __res
       const bool active = c0 < C;
       const int h = active ? c0 / V : 0;
       const bool writer = active && (lane & (lph - 1)) == 0;
-      const Vec<T, VW> g = active ? gcn_load<T, VW>(dout + j * C + c0) : gcn_zero<T, VW>();
-      const Vec<T, VW> o = active ? gcn_load<T, VW>(out + j * C + c0) : gcn_zero<T, VW>();
+      const Vec<T, VW> g = active ? load_packet<T, VW>(dout + j * C + c0) : zero_packet<T, VW>();
+      const Vec<T, VW> o = active ? load_packet<T, VW>(out + j * C + c0) : zero_packet<T, VW>();
       T delta = T(0);
 #pragma unroll
       for (int q = 0; q < VW; q++) delta += g.v[q] * o.v[q];
@@ -525,7 +514,7 @@ __device__ __forceinline__ void gat_score_edges(T* __restrict__ dscore, T* __res
           for (int u = 0; u < kGatUnroll; u++) {
             const int ku = k + u < n ? k + u : n - 1;            // past the end: the last edge again, not written
             const int64_t eu = lane_bcast(ed, ku), su = lane_bcast(sr, ku);
-            v[u] = active ? gcn_load<T, VW>(vc + su * C) : gcn_zero<T, VW>();
+            v[u] = active ? load_packet<T, VW>(vc + su * C) : zero_packet<T, VW>();
             x[u] = writer ? score[eu * H + h] : T(0);
           }
 #pragma unroll
@@ -576,46 +565,31 @@ __device__ __forceinline__ void gat_score_edges(T* __restrict__ dscore, T* __res
   }
 }
 
-// grid: (ceil(N / kGatWaves), 1, kGatWaves + 1), block: kGatWaves * 64.  A wave per destination; the edges of a long row are shared out among the workgroup's
-// waves (nothing is summed across edges, so nothing is merged).
+// grid: (ceil(N / kWaves), 1, kWaves + 1), block: kWaves * 64.  A wave per destination; the edges of a long row are shared out among the
+// workgroup's waves (nothing is summed across edges, so nothing is merged).
 template <class T, int VW>
-__global__ __launch_bounds__(kGatWaves * 64) __attribute__((amdgpu_num_sgpr(96))) void gat_backward_score_kernel(T* __restrict__ dscore, T* __restrict__ aout, const T* __restrict__ dout,
-                                                                             const T* __restrict__ out, const T* __restrict__ score,
-                                                                             const T* __restrict__ value,
-                                                                             const int64_t* __restrict__ edgeI, const int64_t* __restrict__ rowptr,
-                                                                             const int64_t* __restrict__ perm, int64_t N, int64_t H, int V, int lph) {
+__global__ __launch_bounds__(kWaves * 64) __attribute__((amdgpu_num_sgpr(96))) void gat_backward_score_kernel(
+    T* __restrict__ dscore, T* __restrict__ aout, const T* __restrict__ dout, const T* __restrict__ out, const T* __restrict__ score,
+    const T* __restrict__ value, const int64_t* __restrict__ edgeI, const int64_t* __restrict__ rowptr, const int64_t* __restrict__ perm, int64_t N,
+    int64_t H, int V, int lph) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int64_t row0 = (int64_t)blockIdx.x * kGatWaves;
-  const int nrows = (int)(N - row0 < kGatWaves ? N - row0 : kGatWaves);
-  for (int k = (int)blockIdx.z - 1; k < (int)blockIdx.z && k < nrows; k++) {   // one turn: a grid slice per k          // k = -1: every wave its own short row; k >= 0: row row0 + k if it is long, by all waves
-    const bool own = k < 0;
-    const int64_t r = own ? (wave < nrows ? row0 + wave : -1) : row0 + k;
-    if (r < 0) continue;
-    const int64_t rb = rowptr[r], re = rowptr[r + 1];
-    if (own == (re - rb > kGatLongRow)) continue;
-    int64_t b = rb, e = re;
-    if (!own) {
-      const int64_t chunk = (re - rb + kGatWaves - 1) / kGatWaves;
-      b = rb + wave * chunk < re ? rb + wave * chunk : re;
-      e = b + chunk < re ? b + chunk : re;
-    }
-    gat_score_edges<T, VW>(dscore, aout, dout, out, score, value, edgeI, perm, r, rb, re, b, e, H, V, lph, lane);
+  for (int k = first_turn(); is_turn(k); k++) {
+    const RowTurn t = row_turn(k, N, wave);
+    if (t.r < 0) continue;
+    const int64_t rb = rowptr[t.r], re = rowptr[t.r + 1];
+    if (!t.takes(re - rb)) continue;
+    const Share sh = t.share(re - rb, wave);
+    gat_score_edges<T, VW>(dscore, aout, dout, out, score, value, edgeI, perm, t.r, rb, re, rb + sh.lo, rb + sh.hi, H, V, lph, lane);
   }
 }
 
 // ---- message passing (lamp-core/src/main/scala/lamp/nn/graph/MPNN.scala) ---------------------------------------------------------------------
 // The two data movements of an MPNN layer.  The message cat(edgeFeatures, x[edgeI], x[edgeJ]) and MPNN.aggregate's backward are per
 // edge: a row has no sum, so these kernels run a thread per packet over a flat index of rows x packets (no idle lane at any width,
-// neighbouring lanes on neighbouring packets).  The message's gradient with respect to x and MPNN.aggregate are
-// sums per node over the groupings of lamp_graph_edge_csr: gat_backward_value_kernel's shape (a wave per node, lanes across the columns
-// in packets, columns tiled in grid.y, edge ids read once per 64 edges and passed round with v_readlane, kMpnnUnroll rows in flight, a
-// node of more than kMpnnLongRow edges split over the workgroup's waves in a grid slice of its own and merged through LDS by wave 0 in
-// wave order).  No atomics, every element written once, nothing synchronises with the host.
-constexpr int kMpnnWaves = 16;      // waves (= nodes) per workgroup of the summing kernels
-constexpr int kMpnnLongRow = 256;   // a node with more edges (both groupings together) is split across the workgroup's waves
-constexpr int kMpnnUnroll = 4;      // edge rows in flight per wave
-constexpr int kMpnnEdgeBlock = 256; // threads per workgroup of the per-edge kernels
+// neighbouring lanes on neighbouring packets).  The message's gradient with respect to x and MPNN.aggregate are sums per node over the
+// groupings of lamp_graph_edge_csr: mpnn_node_sum_kernel, a row kernel (see the head of the file) whose entry per edge is the edge id
+// and the factors of its end points.  No atomics, every element written once, nothing synchronises with the host.
 
 // out[n] = (T) f32(count^p), count = rowptr[n + 1] - rowptr[n]: the reference's pow of a long tensor is an f32 tensor, cast afterwards.
 // p = -0.5 (HALF) is 1 / sqrt(count) in two f32 roundings, as ATen's pow computes it; p = -1 is 1 / count.  count = 0 gives +inf.
@@ -652,12 +626,12 @@ __global__ __launch_bounds__(kMpnnEdgeBlock) void mpnn_message_kernel(T* __restr
   T* o = msg + t.row * ((int64_t)Fe + 2 * (int64_t)D);
   if (t.slot < se) {
     const int c = t.slot * VE;
-    *reinterpret_cast<Vec<T, VE>*>(o + c) = gcn_load<T, VE>(edge + t.row * lde + c);
+    *reinterpret_cast<Vec<T, VE>*>(o + c) = load_packet<T, VE>(edge + t.row * lde + c);
   } else {
     const bool second = t.slot - se >= sx;
     const int c = (t.slot - se - (second ? sx : 0)) * VX;
     const int64_t node = second ? edgeJ[t.row] : edgeI[t.row];
-    *reinterpret_cast<Vec<T, VX>*>(o + Fe + (second ? D : 0) + c) = gcn_load<T, VX>(x + node * ldx + c);
+    *reinterpret_cast<Vec<T, VX>*>(o + Fe + (second ? D : 0) + c) = load_packet<T, VX>(x + node * ldx + c);
   }
 }
 
@@ -668,7 +642,7 @@ __global__ __launch_bounds__(kMpnnEdgeBlock) void mpnn_columns_kernel(T* __restr
   const MpnnSlot t = mpnn_slot(slots);
   const int c = t.slot * V;
   if (t.row >= E || c >= C) return;
-  *reinterpret_cast<Vec<T, V>*>(dst + t.row * ldd + c) = gcn_load<T, V>(src + t.row * lds + c);
+  *reinterpret_cast<Vec<T, V>*>(dst + t.row * ldd + c) = load_packet<T, V>(src + t.row * lds + c);
 }
 
 // dmsg[e, :] = ((dout[edgeJ[e], :] [+ dout[edgeI[e], :] if aggregateJ]) [* fJ[edgeJ[e]]]) [* fI[edgeI[e]]]; a null factor is absent
@@ -680,9 +654,9 @@ __global__ __launch_bounds__(kMpnnEdgeBlock) void mpnn_aggregate_backward_kernel
   const int c = t.slot * V;
   if (t.row >= E || c >= M) return;
   const int64_t i = edgeI[t.row], j = edgeJ[t.row];
-  Vec<T, V> g = gcn_load<T, V>(dout + j * M + c);
+  Vec<T, V> g = load_packet<T, V>(dout + j * M + c);
   if (aggregateJ) {
-    const Vec<T, V> h = gcn_load<T, V>(dout + i * M + c);
+    const Vec<T, V> h = load_packet<T, V>(dout + i * M + c);
 #pragma unroll
     for (int q = 0; q < V; q++) g.v[q] += h.v[q];
   }
@@ -701,143 +675,113 @@ __global__ __launch_bounds__(kMpnnEdgeBlock) void mpnn_aggregate_backward_kernel
 
 // acc += sum over the edges ed = perm[b .. e), in that order, of t(ed) = (row[ed * ld + c0 ..] [* fI[edgeI[ed]]]) [* fJ[edgeJ[ed]]] (rc = row
 // + c0).  The products are rounded before they are added (no contraction into an fma): a term has the bits the chain of Mult nodes gives
-// it.  Lanes with `active` false hold no column: they take part in the index reads and load no row.  b and e are wave-uniform.
+// it.  Lanes with `active` false hold no column and load no row.
 template <class T, int V, bool FI, bool FJ>
 __device__ __forceinline__ void mpnn_gather(Vec<T, V>& acc, const T* __restrict__ rc, int64_t ld, const int64_t* __restrict__ perm,
                                             const int64_t* __restrict__ edgeI, const int64_t* __restrict__ edgeJ, const T* __restrict__ fI,
                                             const T* __restrict__ fJ, int64_t b, int64_t e, int lane, bool active) {
+  constexpr int NF = (FI ? 1 : 0) + (FJ ? 1 : 0), J = FI ? 1 : 0;      // fI's factor first, then fJ's
+  using Entry = EdgeEntry<T, 1, NF>;
+  using Item = EdgeItem<T, V, NF>;
+  for_each_edge<kMpnnUnroll>(
+      b, e, lane,
+      [&](int64_t p) {
+        Entry en;
+        en.i[0] = perm[p];
+        if constexpr (FI) en.f[0] = fI[edgeI[en.i[0]]];
+        if constexpr (FJ) en.f[J] = fJ[edgeJ[en.i[0]]];
+        return en;
+      },
+      [&](const Entry& en) {
+        Item it;
+#pragma unroll
+        for (int q = 0; q < NF; q++) it.s[q] = en.f[q];
+        it.v = active ? load_packet<T, V>(rc + en.i[0] * ld) : zero_packet<T, V>();
+        return it;
+      },
+      [&](const Item& it) {
 #pragma clang fp contract(off)
-  for (int64_t p = b; p < e; p += 64) {
-    const int n = (int)(e - p < 64 ? e - p : 64);
-    int64_t ed = 0;
-    T fi = T(0), fj = T(0);
-    if (lane < n) {
-      ed = perm[p + lane];
-      if (FI) fi = fI[edgeI[ed]];
-      if (FJ) fj = fJ[edgeJ[ed]];
-    }
-    int k = 0;
-    for (; k + kMpnnUnroll <= n; k += kMpnnUnroll) {
-      Vec<T, V> v[kMpnnUnroll];
-      T a[kMpnnUnroll], c[kMpnnUnroll];
-#pragma unroll
-      for (int u = 0; u < kMpnnUnroll; u++) {
-        const int64_t eu = lane_bcast(ed, k + u);
-        if (FI) a[u] = lane_bcast(fi, k + u);
-        if (FJ) c[u] = lane_bcast(fj, k + u);
-        v[u] = active ? gcn_load<T, V>(rc + eu * ld) : gcn_zero<T, V>();
-      }
-#pragma unroll
-      for (int u = 0; u < kMpnnUnroll; u++)
 #pragma unroll
         for (int j = 0; j < V; j++) {
-          T t = v[u].v[j];
-          if (FI) t = t * a[u];
-          if (FJ) t = t * c[u];
+          T t = it.v.v[j];
+          if constexpr (FI) t = t * it.s[0];
+          if constexpr (FJ) t = t * it.s[J];
           acc.v[j] = acc.v[j] + t;
         }
-    }
-    for (; k < n; k++) {
-      const int64_t eu = lane_bcast(ed, k);
-      const T a = FI ? lane_bcast(fi, k) : T(0), c = FJ ? lane_bcast(fj, k) : T(0);
-      const Vec<T, V> v = active ? gcn_load<T, V>(rc + eu * ld) : gcn_zero<T, V>();
-#pragma unroll
-      for (int j = 0; j < V; j++) {
-        T t = v.v[j];
-        if (FI) t = t * a;
-        if (FJ) t = t * c;
-        acc.v[j] = acc.v[j] + t;
-      }
-    }
-  }
+      });
 }
 
 // out[r, 0:C] from the rows src[ed, off .. off + C) of the edges of node r: the sum over those of grouping 1 (columns off1) and, where
 // rowptr2 is not null, the sum over those of grouping 2 (columns off2), each in its grouping's order, the two added last - as the chains
 // add them (MPNN.aggregate: aggregateI + aggregateJ over incoming and outgoing; the message's gradient with respect to x: the two
-// gathers' gradients, outgoing at Fe and incoming at Fe + D).  A node whose two groups together hold more than kMpnnLongRow edges is
+// gathers' gradients, outgoing at Fe and incoming at Fe + D).  A node whose two groups together hold more than kLongRow edges is
 // split: the waves take contiguous shares of the concatenated sequence, and either sum's partial sums are added in wave order.
-// grid: (ceil(N / kMpnnWaves), ceil(C / (64 * V)), kMpnnWaves + 1), block: kMpnnWaves * 64.
+// grid: (ceil(N / kWaves), ceil(C / (64 * V)), kWaves + 1), block: kWaves * 64.
 template <class T, int V, bool FI, bool FJ>
-__global__ __launch_bounds__(kMpnnWaves * 64) void mpnn_node_sum_kernel(T* __restrict__ out, const T* __restrict__ src, int64_t ld, int64_t off1, int64_t off2,
+__global__ __launch_bounds__(kWaves * 64) void mpnn_node_sum_kernel(T* __restrict__ out, const T* __restrict__ src, int64_t ld, int64_t off1, int64_t off2,
                                                                         const int64_t* __restrict__ rowptr1, const int64_t* __restrict__ perm1,
                                                                         const int64_t* __restrict__ rowptr2, const int64_t* __restrict__ perm2,
                                                                         const int64_t* __restrict__ edgeI, const int64_t* __restrict__ edgeJ,
                                                                         const T* __restrict__ fI, const T* __restrict__ fJ, int64_t N, int64_t C) {
-  __shared__ Vec<T, V> part[2][kMpnnWaves][64];
+  __shared__ Vec<T, V> part[2][kWaves][64];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int64_t c0 = ((int64_t)blockIdx.y * 64 + lane) * V;
   const bool active = c0 < C;
-  const int64_t row0 = (int64_t)blockIdx.x * kMpnnWaves;
-  const int nrows = (int)(N - row0 < kMpnnWaves ? N - row0 : kMpnnWaves);
 
-  for (int k = (int)blockIdx.z - 1; k < (int)blockIdx.z && k < nrows; k++) {   // one turn: a grid slice per k, as in gat_forward_kernel
-    const bool own = k < 0;
-    const int64_t r = own ? (wave < nrows ? row0 + wave : -1) : row0 + k;
+  for (int k = first_turn(); is_turn(k); k++) {
+    const RowTurn t = row_turn(k, N, wave);
     int64_t b1 = 0, n1 = 0, b2 = 0, n2 = 0;
-    if (r >= 0) {
-      b1 = rowptr1[r]; n1 = rowptr1[r + 1] - b1;
-      if (rowptr2) { b2 = rowptr2[r]; n2 = rowptr2[r + 1] - b2; }
+    if (t.r >= 0) {
+      b1 = rowptr1[t.r]; n1 = rowptr1[t.r + 1] - b1;
+      if (rowptr2) { b2 = rowptr2[t.r]; n2 = rowptr2[t.r + 1] - b2; }
     }
-    const int64_t total = n1 + n2;
-    if (own == (total > kMpnnLongRow)) continue;
-    int64_t lo = 0, hi = total;                 // this wave's share of the n1 + n2 edges
-    if (!own) {
-      const int64_t chunk = (total + kMpnnWaves - 1) / kMpnnWaves;
-      lo = wave * chunk < total ? wave * chunk : total;
-      hi = lo + chunk < total ? lo + chunk : total;
-    }
-    Vec<T, V> acc = gcn_zero<T, V>(), acc2 = gcn_zero<T, V>();
-    if (lo < n1) mpnn_gather<T, V, FI, FJ>(acc, src + off1 + c0, ld, perm1, edgeI, edgeJ, fI, fJ, b1 + lo, b1 + (hi < n1 ? hi : n1), lane, active);
-    if (hi > n1) mpnn_gather<T, V, FI, FJ>(acc2, src + off2 + c0, ld, perm2, edgeI, edgeJ, fI, fJ, b2 + (lo > n1 ? lo - n1 : 0), b2 + hi - n1, lane, active);
-    if (own) {
-      if (active && r >= 0) {
-        if (rowptr2) {
-#pragma unroll
-          for (int j = 0; j < V; j++) acc.v[j] += acc2.v[j];
-        }
-        *reinterpret_cast<Vec<T, V>*>(out + r * C + c0) = acc;
-      }
-      continue;
-    }
-    part[0][wave][lane] = acc;
-    part[1][wave][lane] = acc2;
-    __syncthreads();
-    if (wave == 0 && active) {
-#pragma unroll 1
-      for (int w = 1; w < kMpnnWaves; w++) {
-        const Vec<T, V> q = part[0][w][lane];
-#pragma unroll
-        for (int j = 0; j < V; j++) acc.v[j] += q.v[j];
-        const Vec<T, V> q2 = part[1][w][lane];
-#pragma unroll
-        for (int j = 0; j < V; j++) acc2.v[j] += q2.v[j];
-      }
+    if (!t.takes(n1 + n2)) continue;
+    const Share sh = t.share(n1 + n2, wave);       // of the n1 + n2 edges
+    Vec<T, V> acc[2] = {zero_packet<T, V>(), zero_packet<T, V>()};
+    if (sh.lo < n1) mpnn_gather<T, V, FI, FJ>(acc[0], src + off1 + c0, ld, perm1, edgeI, edgeJ, fI, fJ, b1 + sh.lo, b1 + (sh.hi < n1 ? sh.hi : n1), lane, active);
+    if (sh.hi > n1) mpnn_gather<T, V, FI, FJ>(acc[1], src + off2 + c0, ld, perm2, edgeI, edgeJ, fI, fJ, b2 + (sh.lo > n1 ? sh.lo - n1 : 0), b2 + sh.hi - n1, lane, active);
+    if (!t.own) merge_shares(acc, part, wave, lane, active);
+    if (active && t.r >= 0 && (t.own || wave == 0)) {
       if (rowptr2) {
 #pragma unroll
-        for (int j = 0; j < V; j++) acc.v[j] += acc2.v[j];
+        for (int j = 0; j < V; j++) acc[0].v[j] += acc[1].v[j];
       }
-      *reinterpret_cast<Vec<T, V>*>(out + r * C + c0) = acc;
+      *reinterpret_cast<Vec<T, V>*>(out + t.r * C + c0) = acc[0];
     }
-    __syncthreads();
   }
 }
 
-template <class T, int V>
-void gcn_launch(Tensor* out, const Tensor* x, int64_t ldx, const Tensor* rowptr, const Tensor* col, const Tensor* dinv, int64_t N, int64_t D,
-                hipStream_t st) {
-  const int64_t tiles = (D + 64 * V - 1) / (64 * V), groups = (N + kGcnWaves - 1) / kGcnWaves;
-  LAMP_CHECK(tiles <= 65535 && groups <= INT32_MAX, "x " << x->describe() << " is too large");
-  hipLaunchKernelGGL((gcn_aggregate_kernel<T, V>), dim3((unsigned)groups, (unsigned)tiles), dim3(kGcnWaves * 64), 0, st, out->ptr<T>(), D, x->ptr<T>(), ldx,
-                     rowptr->ptr<int64_t>(), col->ptr<int64_t>(), dinv->ptr<T>(), N, D);
-  LAMP_LAUNCH_CHECK();
-}
-// the widest packet (in elements, at most 16 bytes) that D, x's row pitch and both base addresses allow
-template <class T> int gcn_packet(const Tensor* out, const Tensor* x, int64_t ldx, int64_t D) {
-  for (int v = 16 / (int)sizeof(T); v > 1; v >>= 1)
-    if (D % v == 0 && ldx % v == 0 && ((uintptr_t)x->raw() % (v * sizeof(T))) == 0 && ((uintptr_t)out->raw() % (v * sizeof(T))) == 0) return v;
+// the widest packet (in elements, at most 16 bytes) that divides every length (widths, column offsets, row pitches) and at which every
+// address is aligned
+template <class T> int packet_width(std::initializer_list<int64_t> lengths, std::initializer_list<const Tensor*> ts) {
+  for (int v = 16 / (int)sizeof(T); v > 1; v >>= 1) {
+    bool ok = true;
+    for (int64_t l : lengths) ok = ok && l % v == 0;
+    for (const Tensor* t : ts) ok = ok && ((uintptr_t)t->raw() % (v * sizeof(T))) == 0;
+    if (ok) return v;
+  }
   return 1;
+}
+// f(std::integral_constant<int, v>()) for a packet width of T: four (four-byte types only), two or one
+template <class T, class F> void with_packet(int v, F f) {
+  if constexpr (sizeof(T) == 4) {
+    if (v == 4) { f(std::integral_constant<int, 4>()); return; }
+  }
+  if (v == 2) f(std::integral_constant<int, 2>());
+  else f(std::integral_constant<int, 1>());
+}
+// f(T()) for the floating type T of dtype, which is kF32 or kF64
+template <class F> void with_float(int dtype, F f) {
+  if (dtype == kF32) f(float());
+  else f(double());
+}
+// the grid of a row kernel: a workgroup per kWaves rows, the C columns in packets of v tiled in y (C = v = 1: a kernel that does not
+// tile its columns), `slices` in z
+dim3 row_grid(int64_t N, int64_t C, int v, int slices) {
+  const int64_t tiles = (C + 64 * v - 1) / (64 * v), groups = (N + kWaves - 1) / kWaves;
+  LAMP_CHECK(tiles <= 65535 && groups <= INT32_MAX, "a graph of " << N << " nodes in " << tiles << " column tiles is too large");
+  return dim3((unsigned)groups, (unsigned)tiles, (unsigned)slices);
 }
 
 void check_i64_vector(const Tensor* t, const Tensor* first, const char* what) {
@@ -866,57 +810,21 @@ void check_index_range(const char* tag, const Tensor* a, const Tensor* b, int64_
   LAMP_CHECK(mn >= 0 && mx < N, "edge endpoints must lie in [0, " << N << "), got " << mn << " .. " << mx);
 }
 
-// the widest packet (in elements, at most 16 bytes) that C and the base addresses of contiguous [., C] tensors allow
-template <class T> int gat_packet(int64_t C, std::initializer_list<const Tensor*> ts) {
-  for (int v = 16 / (int)sizeof(T); v > 1; v >>= 1) {
-    bool ok = C % v == 0;
-    for (const Tensor* t : ts) ok = ok && ((uintptr_t)t->raw() % (v * sizeof(T))) == 0;
-    if (ok) return v;
-  }
-  return 1;
-}
-struct GatGrid { dim3 grid, block; };
-GatGrid gat_grid(int64_t N, int64_t C, int vw) {
-  const int64_t tiles = (C + 64 * vw - 1) / (64 * vw), groups = (N + kGatWaves - 1) / kGatWaves;
-  LAMP_CHECK(tiles <= 65535 && groups <= INT32_MAX, "a graph of " << N << " nodes with " << C << " columns is too large");
-  return {dim3((unsigned)groups, (unsigned)tiles, kGatWaves + 1), dim3(kGatWaves * 64)};
-}
 // the packet width of gat_forward_kernel / gat_backward_value_kernel: the widest that C and the addresses allow, but four only where it
 // stays inside a head (a softmax state per element costs an exp each)
 template <class T> int gat_gather_packet(int64_t C, int V, std::initializer_list<const Tensor*> ts) {
-  int vw = gat_packet<T>(C, ts);
+  int vw = packet_width<T>({C}, ts);
   while (vw > 2 && V % vw) vw >>= 1;
   return vw;
 }
-// F<T, VW, ONE>::launch(args...) for that width: ONE where no packet straddles a head boundary
-template <template <class, int, bool> class F, class T, class... A> void gat_dispatch(int vw, int V, A... a) {
-  if constexpr (sizeof(T) == 4) {
-    if (vw == 4) { F<T, 4, true>::launch(a...); return; }
-  }
-  if (vw == 2) { if (V % 2 == 0) F<T, 2, true>::launch(a...); else F<T, 2, false>::launch(a...); return; }
-  F<T, 1, true>::launch(a...);
-}
-template <class T, int VW, bool ONE> struct GatForward {
-  static void launch(GatGrid g, hipStream_t st, Tensor* out, Tensor* lse, const Tensor* score, const Tensor* value, const Tensor* edgeI, const Tensor* rowptr,
-                     const Tensor* perm, int64_t N, int64_t H, int V) {
-    hipLaunchKernelGGL((gat_forward_kernel<T, VW, ONE>), g.grid, g.block, 0, st, out->ptr<T>(), lse->ptr<T>(), score->ptr<T>(), value->ptr<T>(),
-                       edgeI->ptr<int64_t>(), rowptr->ptr<int64_t>(), perm->ptr<int64_t>(), N, H, V);
-  }
-};
-template <class T, int VW, bool ONE> struct GatBackwardValue {
-  static void launch(GatGrid g, hipStream_t st, Tensor* dvalue, const Tensor* a, const Tensor* dout, const Tensor* edgeJ, const Tensor* rowptr, const Tensor* perm,
-                     int64_t N, int64_t H, int V) {
-    hipLaunchKernelGGL((gat_backward_value_kernel<T, VW, ONE>), g.grid, g.block, 0, st, dvalue->ptr<T>(), a->ptr<T>(), dout->ptr<T>(), edgeJ->ptr<int64_t>(),
-                       rowptr->ptr<int64_t>(), perm->ptr<int64_t>(), N, H, V);
-  }
-};
-template <class T, int VW>
-void gat_backward_score_launch(hipStream_t st, Tensor* dscore, Tensor* a, const Tensor* dout, const Tensor* out, const Tensor* score, const Tensor* value,
-                               const Tensor* edgeI, const Tensor* rowptr, const Tensor* perm, int64_t N, int64_t H, int V, int lph) {
-  const int64_t groups = (N + kGatWaves - 1) / kGatWaves;
-  LAMP_CHECK(groups <= INT32_MAX, "a graph of " << N << " nodes is too large");
-  hipLaunchKernelGGL((gat_backward_score_kernel<T, VW>), dim3((unsigned)groups, 1, kGatWaves + 1), dim3(kGatWaves * 64), 0, st, dscore->ptr<T>(), a->ptr<T>(), dout->ptr<T>(),
-                     out->ptr<T>(), score->ptr<T>(), value->ptr<T>(), edgeI->ptr<int64_t>(), rowptr->ptr<int64_t>(), perm->ptr<int64_t>(), N, H, V, lph);
+// f(width, ONE) for those two kernels: ONE where no packet straddles a head boundary
+template <class T, class F> void gat_with_packet(int vw, int V, F f) {
+  with_packet<T>(vw, [&](auto W) {
+    if constexpr (decltype(W)::value == 2) {
+      if (V % 2) { f(W, std::false_type()); return; }
+    }
+    f(W, std::true_type());
+  });
 }
 // the packet form of gat_backward_score_kernel: V = lph * vw with lph a power of two up to 64; 0 where V has no such split
 int gat_lanes_per_head(int V, int vw) {
@@ -925,10 +833,21 @@ int gat_lanes_per_head(int V, int vw) {
   return lph <= 64 && (lph & (lph - 1)) == 0 ? lph : 0;
 }
 
+// every tensor of vs is an int64 vector of n entries on first's device, or the error "<its name> <the tensor> <why>"
+using NamedTensors = std::initializer_list<std::pair<const Tensor*, const char*>>;
+void check_i64_vectors(NamedTensors vs, const Tensor* first, int64_t n, const std::string& why) {
+  for (auto& v : vs) {
+    check_i64_vector(v.first, first, v.second);
+    LAMP_CHECK(v.first->numel() == n, v.second << " " << v.first->describe() << " " << why);
+  }
+}
+void check_rowptrs(NamedTensors vs, const Tensor* first, int64_t N) {
+  check_i64_vectors(vs, first, N + 1, "does not belong to a graph of " + std::to_string(N) + " nodes");
+}
+
 // score [E, H], value [N, H, V] of one floating type, the index vectors int64 [E], the grouping's rowptr [N + 1]
 struct GatShape { int64_t E, H, N, V; };
-GatShape gat_check(const Tensor* score, const Tensor* value, std::initializer_list<std::pair<const Tensor*, const char*>> edgeVectors,
-                   std::initializer_list<std::pair<const Tensor*, const char*>> rowptrs) {
+GatShape gat_check(const Tensor* score, const Tensor* value, NamedTensors edgeVectors, NamedTensors rowptrs) {
   check_device_tensor(score, "score");
   check_device_tensor(value, "value");
   check_same_device(value, score);
@@ -939,41 +858,51 @@ GatShape gat_check(const Tensor* score, const Tensor* value, std::initializer_li
              "value " << value->describe() << " must be [N, H, V] with the H = " << score->sizes[1] << " heads of score " << score->describe());
   const GatShape g{score->sizes[0], score->sizes[1], value->sizes[0], value->sizes[2]};
   LAMP_CHECK(g.H * g.V <= INT32_MAX / 2, "value " << value->describe() << " has too many columns");
-  for (auto& v : edgeVectors) {
-    check_i64_vector(v.first, score, v.second);
-    LAMP_CHECK(v.first->numel() == g.E, v.second << " " << v.first->describe() << " does not have score's " << g.E << " edges: edgeI and edgeJ differ in length?");
-  }
-  for (auto& v : rowptrs) {
-    check_i64_vector(v.first, score, v.second);
-    LAMP_CHECK(v.first->numel() == g.N + 1, v.second << " " << v.first->describe() << " does not belong to a graph of " << g.N << " nodes");
-  }
+  check_i64_vectors(edgeVectors, score, g.E, "does not have score's " + std::to_string(g.E) + " edges: edgeI and edgeJ differ in length?");
+  check_rowptrs(rowptrs, score, g.N);
   return g;
 }
 
-// the widest packet (in elements, at most 16 bytes) that divides every length (widths, column offsets, row pitches) and at which every
-// address is aligned
-template <class T> int mpnn_packet(std::initializer_list<int64_t> lengths, std::initializer_list<const Tensor*> ts) {
-  for (int v = 16 / (int)sizeof(T); v > 1; v >>= 1) {
-    bool ok = true;
-    for (int64_t l : lengths) ok = ok && l % v == 0;
-    for (const Tensor* t : ts) ok = ok && ((uintptr_t)t->raw() % (v * sizeof(T))) == 0;
-    if (ok) return v;
-  }
-  return 1;
-}
 // the grid of a per-edge kernel: rows of `slots` packets (slots >= 1), a thread per packet; see mpnn_slot
 struct MpnnEdgeGrid { dim3 grid; uint32_t slots; };
 MpnnEdgeGrid mpnn_edge_grid(int64_t rows, int64_t slots) {
   LAMP_CHECK(slots >= 1 && rows * slots <= ((int64_t)1 << 31), rows << " rows of " << slots << " packets are too many");
   return {dim3((unsigned)((rows * slots + kMpnnEdgeBlock - 1) / kMpnnEdgeBlock)), (uint32_t)slots};
 }
-// a [rows, cols] tensor whose rows are read in place (unit column stride, rows that do not overlap) or a dense copy; -> its row pitch
-Tensor* mpnn_rows(const Tensor* t, int64_t* ld) {
+// a [rows, cols] tensor whose rows are read in place (unit column stride and rows that do not overlap, whatever the row pitch) or a
+// dense copy (of a broadcast gradient, say); -> its row pitch
+Tensor* rows_in_place(const Tensor* t, int64_t* ld) {
   const int64_t rows = t->sizes[0], cols = t->sizes[1];
   const bool in_place = (cols == 1 || t->strides[1] == 1) && (rows == 1 || t->strides[0] >= cols);
   Tensor* r = in_place ? retain(t) : contiguous(t);
   *ld = rows == 1 ? cols : r->strides[0];
   return r;
+}
+// The groups 0 .. N - 1 of keys (int64 [n], contiguous, every entry in [0, N): check_index_range comes first).  -> rowptr [N + 1];
+// *perm = the stable permutation that sorts the keys ([n]); dinv, where given ([N], f32 or f64) = (group size + 1)^-1/2.
+Tensor* group_keys(const Tensor* keys, int64_t N, Hold* perm, Tensor* dinv, const char* tag, hipStream_t st) {
+  const int dev = keys->device();
+  const int64_t n = keys->numel();
+  int64_t n1[1] = {N + 1}, ns[1] = {n};
+  Hold rp(new_tensor(n1, 1, kI64, dev)), counts;
+  if (n) {
+    lamp_tensor* t = nullptr;
+    LAMP_CHECK(lamp_argsort(&t, keys, 1, 0, 0) == 0, lamp_last_error());
+    *perm = Hold(t);
+    LAMP_CHECK(lamp_bincount(&t, keys, nullptr, N) == 0, lamp_last_error());
+    counts = Hold(t);
+    LAMP_CHECK(counts->numel() == N && (*perm)->numel() == n && (*perm)->dtype == kI64, "internal: counts " << counts->describe() << ", perm " << (*perm)->describe());
+  } else {
+    *perm = Hold(new_tensor(ns, 1, kI64, dev));
+  }
+  KernelTimer kt(tag, 0, (double)N * (16 + (dinv ? dtype_size(dinv->dtype) : 0)), st);
+  with_float(dinv ? dinv->dtype : kF32, [&](auto z) {
+    using T = decltype(z);
+    hipLaunchKernelGGL((gcn_rowptr_dinv_kernel<T>), dim3(1), dim3(1024), 0, st, counts.get() ? counts->ptr<int64_t>() : nullptr, rp->ptr<int64_t>(),
+                       dinv ? dinv->ptr<T>() : nullptr, N);
+  });
+  LAMP_LAUNCH_CHECK();
+  return rp.take();
 }
 void mpnn_check_float(const Tensor* t, const char* what, const Tensor* first) {
   check_device_tensor(t, what);
@@ -988,83 +917,27 @@ void mpnn_check_factor(const Tensor* f, const char* what, const Tensor* first, i
   LAMP_CHECK(f->ndim == 1 && f->numel() == N, what << " " << f->describe() << " must be [" << N << "]");
 }
 
-template <class T, int VE, int VX>
-void mpnn_message_launch(MpnnEdgeGrid g, hipStream_t st, Tensor* msg, const Tensor* edge, int64_t lde, const Tensor* x, int64_t ldx, const Tensor* edgeI,
-                         const Tensor* edgeJ, int64_t E, int Fe, int D) {
-  hipLaunchKernelGGL((mpnn_message_kernel<T, VE, VX>), g.grid, dim3(kMpnnEdgeBlock), 0, st, msg->ptr<T>(), edge->ptr<T>(), lde, x->ptr<T>(), ldx,
-                     edgeI->ptr<int64_t>(), edgeJ->ptr<int64_t>(), E, Fe, D, g.slots);
-}
-template <class T, int VE>
-void mpnn_message_launch_x(int vx, MpnnEdgeGrid g, hipStream_t st, Tensor* msg, const Tensor* edge, int64_t lde, const Tensor* x, int64_t ldx,
-                           const Tensor* edgeI, const Tensor* edgeJ, int64_t E, int Fe, int D) {
-  if constexpr (sizeof(T) == 4) {
-    if (vx == 4) { mpnn_message_launch<T, VE, 4>(g, st, msg, edge, lde, x, ldx, edgeI, edgeJ, E, Fe, D); return; }
-  }
-  if (vx == 2) mpnn_message_launch<T, VE, 2>(g, st, msg, edge, lde, x, ldx, edgeI, edgeJ, E, Fe, D);
-  else mpnn_message_launch<T, VE, 1>(g, st, msg, edge, lde, x, ldx, edgeI, edgeJ, E, Fe, D);
-}
-template <class T>
-void mpnn_message_dispatch(hipStream_t st, Tensor* msg, const Tensor* edge, int64_t lde, const Tensor* x, int64_t ldx, const Tensor* edgeI, const Tensor* edgeJ,
-                           int64_t E, int Fe, int D) {
-  // per segment: the edge segment starts every row (pitch Fe + 2 D), the node segments start at Fe and Fe + D
-  const int64_t W = (int64_t)Fe + 2 * (int64_t)D;
-  const int ve = mpnn_packet<T>({Fe, W, lde}, {msg, edge}), vx = mpnn_packet<T>({D, Fe, W, ldx}, {msg, x});
-  const MpnnEdgeGrid g = mpnn_edge_grid(E, Fe / ve + 2 * (int64_t)(D / vx));
-  if constexpr (sizeof(T) == 4) {
-    if (ve == 4) { mpnn_message_launch_x<T, 4>(vx, g, st, msg, edge, lde, x, ldx, edgeI, edgeJ, E, Fe, D); return; }
-  }
-  if (ve == 2) mpnn_message_launch_x<T, 2>(vx, g, st, msg, edge, lde, x, ldx, edgeI, edgeJ, E, Fe, D);
-  else mpnn_message_launch_x<T, 1>(vx, g, st, msg, edge, lde, x, ldx, edgeI, edgeJ, E, Fe, D);
-}
-
 struct MpnnSum {
   Tensor* out; const Tensor* src; int64_t ld, off1, off2;
   const Tensor *rowptr1, *perm1, *rowptr2, *perm2, *edgeI, *edgeJ, *fI, *fJ;
   int64_t N, C;
 };
-template <class T, int V, bool FI, bool FJ> void mpnn_sum_launch(const MpnnSum& a, hipStream_t st) {
-  const int64_t tiles = (a.C + 64 * V - 1) / (64 * V), groups = (a.N + kMpnnWaves - 1) / kMpnnWaves;
-  LAMP_CHECK(tiles <= 65535 && groups <= INT32_MAX, "a graph of " << a.N << " nodes with " << a.C << " columns is too large");
+// v: the packet width, as packet_width gives it for the widths, offsets and tensors of a
+template <class T, bool FI, bool FJ> void mpnn_sum_launch(int v, const MpnnSum& a, hipStream_t st) {
   auto ip = [](const Tensor* t) { return t ? t->ptr<int64_t>() : nullptr; };
-  hipLaunchKernelGGL((mpnn_node_sum_kernel<T, V, FI, FJ>), dim3((unsigned)groups, (unsigned)tiles, kMpnnWaves + 1), dim3(kMpnnWaves * 64), 0, st,
-                     a.out->ptr<T>(), a.src->ptr<T>(), a.ld, a.off1, a.off2, ip(a.rowptr1), ip(a.perm1), ip(a.rowptr2), ip(a.perm2), ip(a.edgeI), ip(a.edgeJ),
-                     a.fI ? a.fI->ptr<T>() : nullptr, a.fJ ? a.fJ->ptr<T>() : nullptr, a.N, a.C);
-}
-template <class T, bool FI, bool FJ> void mpnn_sum_packet(int v, const MpnnSum& a, hipStream_t st) {
-  if constexpr (sizeof(T) == 4) {
-    if (v == 4) { mpnn_sum_launch<T, 4, FI, FJ>(a, st); return; }
-  }
-  if (v == 2) mpnn_sum_launch<T, 2, FI, FJ>(a, st);
-  else mpnn_sum_launch<T, 1, FI, FJ>(a, st);
+  with_packet<T>(v, [&](auto W) {
+    constexpr int V = decltype(W)::value;
+    hipLaunchKernelGGL((mpnn_node_sum_kernel<T, V, FI, FJ>), row_grid(a.N, a.C, V, kWaves + 1), dim3(kWaves * 64), 0, st, a.out->ptr<T>(), a.src->ptr<T>(), a.ld,
+                       a.off1, a.off2, ip(a.rowptr1), ip(a.perm1), ip(a.rowptr2), ip(a.perm2), ip(a.edgeI), ip(a.edgeJ), a.fI ? a.fI->ptr<T>() : nullptr,
+                       a.fJ ? a.fJ->ptr<T>() : nullptr, a.N, a.C);
+  });
 }
 // MPNN.aggregate: a factor that is null is a kernel without that multiplication
-template <class T> void mpnn_aggregate_dispatch(int v, const MpnnSum& a, hipStream_t st) {
-  if (a.fI && a.fJ) mpnn_sum_packet<T, true, true>(v, a, st);
-  else if (a.fI) mpnn_sum_packet<T, true, false>(v, a, st);
-  else if (a.fJ) mpnn_sum_packet<T, false, true>(v, a, st);
-  else mpnn_sum_packet<T, false, false>(v, a, st);
-}
-template <class T>
-void mpnn_columns_dispatch(hipStream_t st, Tensor* dst, int64_t ldd, const Tensor* src, int64_t lds, int64_t E, int C) {
-  const int v = mpnn_packet<T>({C, ldd, lds}, {dst, src});
-  const MpnnEdgeGrid g = mpnn_edge_grid(E, C / v);
-  if constexpr (sizeof(T) == 4) {
-    if (v == 4) { hipLaunchKernelGGL((mpnn_columns_kernel<T, 4>), g.grid, dim3(kMpnnEdgeBlock), 0, st, dst->ptr<T>(), ldd, src->ptr<T>(), lds, E, C, g.slots); return; }
-  }
-  if (v == 2) hipLaunchKernelGGL((mpnn_columns_kernel<T, 2>), g.grid, dim3(kMpnnEdgeBlock), 0, st, dst->ptr<T>(), ldd, src->ptr<T>(), lds, E, C, g.slots);
-  else hipLaunchKernelGGL((mpnn_columns_kernel<T, 1>), g.grid, dim3(kMpnnEdgeBlock), 0, st, dst->ptr<T>(), ldd, src->ptr<T>(), lds, E, C, g.slots);
-}
-template <class T>
-void mpnn_aggregate_backward_dispatch(hipStream_t st, Tensor* dmsg, const Tensor* dout, const Tensor* edgeI, const Tensor* edgeJ, const Tensor* fI, const Tensor* fJ,
-                                      int aggregateJ, int64_t E, int M) {
-  const int v = mpnn_packet<T>({M}, {dmsg, dout});
-  const MpnnEdgeGrid g = mpnn_edge_grid(E, M / v);
-  const T *pi = fI ? fI->ptr<T>() : nullptr, *pj = fJ ? fJ->ptr<T>() : nullptr;
-  if constexpr (sizeof(T) == 4) {
-    if (v == 4) { hipLaunchKernelGGL((mpnn_aggregate_backward_kernel<T, 4>), g.grid, dim3(kMpnnEdgeBlock), 0, st, dmsg->ptr<T>(), dout->ptr<T>(), edgeI->ptr<int64_t>(), edgeJ->ptr<int64_t>(), pi, pj, aggregateJ, E, M, g.slots); return; }
-  }
-  if (v == 2) hipLaunchKernelGGL((mpnn_aggregate_backward_kernel<T, 2>), g.grid, dim3(kMpnnEdgeBlock), 0, st, dmsg->ptr<T>(), dout->ptr<T>(), edgeI->ptr<int64_t>(), edgeJ->ptr<int64_t>(), pi, pj, aggregateJ, E, M, g.slots);
-  else hipLaunchKernelGGL((mpnn_aggregate_backward_kernel<T, 1>), g.grid, dim3(kMpnnEdgeBlock), 0, st, dmsg->ptr<T>(), dout->ptr<T>(), edgeI->ptr<int64_t>(), edgeJ->ptr<int64_t>(), pi, pj, aggregateJ, E, M, g.slots);
+template <class T> void mpnn_aggregate_launch(int v, const MpnnSum& a, hipStream_t st) {
+  if (a.fI && a.fJ) mpnn_sum_launch<T, true, true>(v, a, st);
+  else if (a.fI) mpnn_sum_launch<T, true, false>(v, a, st);
+  else if (a.fJ) mpnn_sum_launch<T, false, true>(v, a, st);
+  else mpnn_sum_launch<T, false, false>(v, a, st);
 }
 
 }  // namespace
@@ -1076,7 +949,7 @@ extern "C" {
 
 int lamp_gcn_long_row(int64_t* out) {
   LAMP_API_BEGIN
-  *out = kGcnLongRow;
+  *out = kLongRow;
   LAMP_API_END
 }
 
@@ -1094,33 +967,24 @@ int lamp_gcn_adjacency(lamp_tensor** rowptr, lamp_tensor** col, lamp_tensor** di
   LAMP_CHECK(2 * E < ((int64_t)1 << 31), "too many edges: " << E);
   hipStream_t st = current_stream(dev);
   Hold ei(contiguous(edgeI)), ej(contiguous(edgeJ));
-  int64_t ns[1] = {N}, n1[1] = {N + 1}, e2[1] = {2 * E};
-  Hold rp(new_tensor(n1, 1, kI64, dev)), dv(new_tensor(ns, 1, dtype, dev)), cl, counts;
+  int64_t ns[1] = {N};
+  Hold dv(new_tensor(ns, 1, dtype, dev)), keys(retain(ei.get())), vals, cl;
   if (E) {
     // the range of both index vectors, before anything uses one of them as an index
     check_index_range("gcn_index_range", ei.get(), ej.get(), N, st);
-    // the 2E directed entries (row, col) = (i, j) then (j, i), stably sorted by row
+    // the 2E directed entries (row, col) = (i, j) then (j, i), to be stably sorted by row
     lamp_tensor *ks[2] = {ei.get(), ej.get()}, *vs[2] = {ej.get(), ei.get()}, *t = nullptr;
     LAMP_CHECK(lamp_cat(&t, ks, 2, 0) == 0, lamp_last_error());
-    Hold keys(t);
+    keys = Hold(t);
     LAMP_CHECK(lamp_cat(&t, vs, 2, 0) == 0, lamp_last_error());
-    Hold vals(t);
-    LAMP_CHECK(lamp_argsort(&t, keys.get(), 1, 0, 0) == 0, lamp_last_error());
-    Hold perm(t);
-    LAMP_CHECK(lamp_index_select(&t, vals.get(), 0, perm.get()) == 0, lamp_last_error());
-    cl = Hold(t);
-    LAMP_CHECK(lamp_bincount(&t, keys.get(), nullptr, N) == 0, lamp_last_error());
-    counts = Hold(t);
-    LAMP_CHECK(counts->numel() == N && cl->numel() == 2 * E, "internal: counts " << counts->describe() << ", col " << cl->describe());
-  } else {
-    cl = Hold(new_tensor(e2, 1, kI64, dev));
+    vals = Hold(t);
   }
-  {
-    KernelTimer kt("gcn_rowptr_dinv", 0, (double)N * (16 + dtype_size(dtype)), st);
-    const int64_t* cp = counts.get() ? counts->ptr<int64_t>() : nullptr;
-    if (dtype == kF32) hipLaunchKernelGGL((gcn_rowptr_dinv_kernel<float>), dim3(1), dim3(1024), 0, st, cp, rp->ptr<int64_t>(), dv->ptr<float>(), N);
-    else hipLaunchKernelGGL((gcn_rowptr_dinv_kernel<double>), dim3(1), dim3(1024), 0, st, cp, rp->ptr<int64_t>(), dv->ptr<double>(), N);
-    LAMP_LAUNCH_CHECK();
+  Hold rp(group_keys(keys.get(), N, &cl, dv.get(), "gcn_rowptr_dinv", st));
+  if (E) {
+    lamp_tensor* t = nullptr;
+    LAMP_CHECK(lamp_index_select(&t, vals.get(), 0, cl.get()) == 0, lamp_last_error());
+    cl = Hold(t);
+    LAMP_CHECK(cl->numel() == 2 * E, "internal: col " << cl->describe());
   }
   *rowptr = rp.take(); *col = cl.take(); *dinv = dv.take();
   LAMP_API_END
@@ -1132,32 +996,28 @@ int lamp_gcn_aggregate(lamp_tensor** out, const lamp_tensor* x, const lamp_tenso
   LAMP_CHECK(x->dtype == kF32 || x->dtype == kF64, "f32 and f64 only, got " << x->describe());
   LAMP_CHECK(x->ndim == 2, "x " << x->describe() << " must be [N, D]");
   const int64_t N = x->sizes[0], D = x->sizes[1];
-  check_i64_vector(rowptr, x, "rowptr");
+  check_rowptrs({{rowptr, "rowptr"}}, x, N);
   check_i64_vector(col, x, "col");
   check_device_tensor(dinv, "dinv");
   check_same_device(dinv, x);
-  LAMP_CHECK(rowptr->numel() == N + 1, "rowptr " << rowptr->describe() << " does not belong to a graph of " << N << " nodes");
   LAMP_CHECK(dinv->ndim == 1 && dinv->numel() == N && dinv->dtype == x->dtype, "dinv " << dinv->describe() << " must be [" << N << "] of x's type " << x->describe());
-  // unit column stride and rows that do not overlap are read in place, whatever the row pitch; anything else (a broadcast gradient) is copied
-  const bool in_place = (D == 1 || x->strides[1] == 1) && (N == 1 || x->strides[0] >= D);
-  Hold xc(in_place ? retain(x) : contiguous(x)), rc(contiguous(rowptr)), cc(contiguous(col)), dc(contiguous(dinv));
-  const int64_t ldx = N == 1 ? D : xc->strides[0];
+  int64_t ldx = 0;
+  Hold xc(rows_in_place(x, &ldx)), rc(contiguous(rowptr)), cc(contiguous(col)), dc(contiguous(dinv));
   int64_t os[2] = {N, D};
   Hold o(new_tensor(os, 2, x->dtype, x->device()));
   if (N * D) {
     hipStream_t st = current_stream(x->device());
     const double nnz = (double)cc->numel();
     KernelTimer kt("gcn_aggregate", 2.0 * (nnz + 2.0 * N) * D, ((nnz + N) * D + (double)N * D) * dtype_size(x->dtype) + nnz * (8 + dtype_size(x->dtype)) + N * 8.0, st);
-    if (x->dtype == kF32) {
-      switch (gcn_packet<float>(o.get(), xc.get(), ldx, D)) {
-        case 4: gcn_launch<float, 4>(o.get(), xc.get(), ldx, rc.get(), cc.get(), dc.get(), N, D, st); break;
-        case 2: gcn_launch<float, 2>(o.get(), xc.get(), ldx, rc.get(), cc.get(), dc.get(), N, D, st); break;
-        default: gcn_launch<float, 1>(o.get(), xc.get(), ldx, rc.get(), cc.get(), dc.get(), N, D, st);
-      }
-    } else {
-      if (gcn_packet<double>(o.get(), xc.get(), ldx, D) == 2) gcn_launch<double, 2>(o.get(), xc.get(), ldx, rc.get(), cc.get(), dc.get(), N, D, st);
-      else gcn_launch<double, 1>(o.get(), xc.get(), ldx, rc.get(), cc.get(), dc.get(), N, D, st);
-    }
+    with_float(x->dtype, [&](auto z) {
+      using T = decltype(z);
+      with_packet<T>(packet_width<T>({D, ldx}, {o.get(), xc.get()}), [&](auto W) {
+        constexpr int V = decltype(W)::value;
+        hipLaunchKernelGGL((gcn_aggregate_kernel<T, V>), row_grid(N, D, V, 1), dim3(kWaves * 64), 0, st, o->ptr<T>(), D, xc->ptr<T>(), ldx, rc->ptr<int64_t>(),
+                           cc->ptr<int64_t>(), dc->ptr<T>(), N, D);
+      });
+    });
+    LAMP_LAUNCH_CHECK();
   }
   *out = o.take();
   LAMP_API_END
@@ -1165,7 +1025,7 @@ int lamp_gcn_aggregate(lamp_tensor** out, const lamp_tensor* x, const lamp_tenso
 
 int lamp_gat_long_row(int64_t* out) {
   LAMP_API_BEGIN
-  *out = kGatLongRow;
+  *out = kLongRow;
   LAMP_API_END
 }
 
@@ -1174,30 +1034,12 @@ int lamp_graph_edge_csr(lamp_tensor** rowptr, lamp_tensor** perm, const lamp_ten
   check_device_tensor(index, "index");
   check_i64_vector(index, index, "index");
   LAMP_CHECK(numNodes >= 0, "numNodes = " << numNodes);
-  const int dev = index->device();
   const int64_t N = numNodes, E = index->numel();
   LAMP_CHECK(E < ((int64_t)1 << 31), "too many edges: " << E);
-  hipStream_t st = current_stream(dev);
-  Hold ix(contiguous(index));
-  int64_t n1[1] = {N + 1}, es[1] = {E};
-  Hold rp(new_tensor(n1, 1, kI64, dev)), pm, counts;
-  if (E) {
-    check_index_range("graph_index_range", ix.get(), nullptr, N, st);
-    lamp_tensor* t = nullptr;
-    LAMP_CHECK(lamp_argsort(&t, ix.get(), 1, 0, 0) == 0, lamp_last_error());
-    pm = Hold(t);
-    LAMP_CHECK(lamp_bincount(&t, ix.get(), nullptr, N) == 0, lamp_last_error());
-    counts = Hold(t);
-    LAMP_CHECK(counts->numel() == N && pm->numel() == E && pm->dtype == kI64, "internal: counts " << counts->describe() << ", perm " << pm->describe());
-  } else {
-    pm = Hold(new_tensor(es, 1, kI64, dev));
-  }
-  {
-    KernelTimer kt("graph_edge_rowptr", 0, (double)N * 16, st);
-    hipLaunchKernelGGL((gcn_rowptr_dinv_kernel<float>), dim3(1), dim3(1024), 0, st, counts.get() ? counts->ptr<int64_t>() : nullptr, rp->ptr<int64_t>(),
-                       (float*)nullptr, N);
-    LAMP_LAUNCH_CHECK();
-  }
+  hipStream_t st = current_stream(index->device());
+  Hold ix(contiguous(index)), pm;
+  if (E) check_index_range("graph_index_range", ix.get(), nullptr, N, st);
+  Hold rp(group_keys(ix.get(), N, &pm, nullptr, "graph_edge_rowptr", st));
   *rowptr = rp.take(); *perm = pm.take();
   LAMP_API_END
 }
@@ -1214,14 +1056,16 @@ int lamp_gat_forward(lamp_tensor** out, lamp_tensor** lse, const lamp_tensor* sc
     LAMP_CHECK(g.V > 0, "value " << value->describe() << " has no columns");
     hipStream_t st = current_stream(score->device());
     const double sz = (double)dtype_size(score->dtype), E = (double)g.E, N = (double)g.N;
+    const int V = (int)g.V;
     KernelTimer kt("gat_forward", 2.0 * E * C + 4.0 * E * g.H + N * C, (E * C + N * C + E * g.H + N * g.H) * sz + E * 16 + N * 8, st);
-    if (score->dtype == kF32) {
-      const int vw = gat_gather_packet<float>(C, (int)g.V, {o.get(), vc.get()});
-      gat_dispatch<GatForward, float>(vw, (int)g.V, gat_grid(g.N, C, vw), st, o.get(), l.get(), sc.get(), vc.get(), ei.get(), rp.get(), pm.get(), g.N, g.H, (int)g.V);
-    } else {
-      const int vw = gat_gather_packet<double>(C, (int)g.V, {o.get(), vc.get()});
-      gat_dispatch<GatForward, double>(vw, (int)g.V, gat_grid(g.N, C, vw), st, o.get(), l.get(), sc.get(), vc.get(), ei.get(), rp.get(), pm.get(), g.N, g.H, (int)g.V);
-    }
+    with_float(score->dtype, [&](auto z) {
+      using T = decltype(z);
+      gat_with_packet<T>(gat_gather_packet<T>(C, V, {o.get(), vc.get()}), V, [&](auto W, auto one) {
+        constexpr int VW = decltype(W)::value;
+        hipLaunchKernelGGL((gat_forward_kernel<T, VW, decltype(one)::value>), row_grid(g.N, C, VW, kWaves + 1), dim3(kWaves * 64), 0, st, o->ptr<T>(), l->ptr<T>(),
+                           sc->ptr<T>(), vc->ptr<T>(), ei->ptr<int64_t>(), rp->ptr<int64_t>(), pm->ptr<int64_t>(), g.N, g.H, V);
+      });
+    });
     LAMP_LAUNCH_CHECK();
   }
   *out = o.take(); *lse = l.take();
@@ -1254,31 +1098,30 @@ int lamp_gat_backward(lamp_tensor** dscore, lamp_tensor** dvalue, const lamp_ten
     const int V = (int)g.V;
     if (g.E) {
       KernelTimer kt("gat_backward_score", 2.0 * E * C + 2.0 * N * C + 4.0 * E * g.H, (E * C + 2.0 * N * C + 3.0 * E * g.H + N * g.H) * sz + E * 16 + N * 8, st);
-      if (dt == kF32) {
-        int vw = gat_packet<float>(C, {go.get(), oc.get(), vc.get()});
+      with_float(dt, [&](auto z) {
+        using T = decltype(z);
+        // the packet form at the widest packet that has one (vw > 1 leaves the loop only with lph > 0); at vw = 1, lph = 0 where V is no
+        // power of two up to 64: the form with lanes across a head
+        int vw = packet_width<T>({C}, {go.get(), oc.get(), vc.get()});
         while (vw > 1 && !gat_lanes_per_head(V, vw)) vw >>= 1;
         const int lph = gat_lanes_per_head(V, vw);
-        if (lph && vw == 4) gat_backward_score_launch<float, 4>(st, ds.get(), a.get(), go.get(), oc.get(), sc.get(), vc.get(), ei.get(), irp.get(), ipm.get(), g.N, g.H, V, lph);
-        else if (lph && vw == 2) gat_backward_score_launch<float, 2>(st, ds.get(), a.get(), go.get(), oc.get(), sc.get(), vc.get(), ei.get(), irp.get(), ipm.get(), g.N, g.H, V, lph);
-        else gat_backward_score_launch<float, 1>(st, ds.get(), a.get(), go.get(), oc.get(), sc.get(), vc.get(), ei.get(), irp.get(), ipm.get(), g.N, g.H, V, lph);
-      } else {
-        int vw = gat_packet<double>(C, {go.get(), oc.get(), vc.get()});
-        while (vw > 1 && !gat_lanes_per_head(V, vw)) vw >>= 1;
-        const int lph = gat_lanes_per_head(V, vw);
-        if (lph && vw == 2) gat_backward_score_launch<double, 2>(st, ds.get(), a.get(), go.get(), oc.get(), sc.get(), vc.get(), ei.get(), irp.get(), ipm.get(), g.N, g.H, V, lph);
-        else gat_backward_score_launch<double, 1>(st, ds.get(), a.get(), go.get(), oc.get(), sc.get(), vc.get(), ei.get(), irp.get(), ipm.get(), g.N, g.H, V, lph);
-      }
+        with_packet<T>(vw, [&](auto W) {
+          hipLaunchKernelGGL((gat_backward_score_kernel<T, decltype(W)::value>), row_grid(g.N, 1, 1, kWaves + 1), dim3(kWaves * 64), 0, st, ds->ptr<T>(), a->ptr<T>(),
+                             go->ptr<T>(), oc->ptr<T>(), sc->ptr<T>(), vc->ptr<T>(), ei->ptr<int64_t>(), irp->ptr<int64_t>(), ipm->ptr<int64_t>(), g.N, g.H, V, lph);
+        });
+      });
       LAMP_LAUNCH_CHECK();
     }
     {
       KernelTimer kt("gat_backward_value", 2.0 * E * C, (E * C + N * C + E * g.H) * sz + E * 16 + N * 8, st);
-      if (dt == kF32) {
-        const int vw = gat_gather_packet<float>(C, V, {dv.get(), go.get()});
-        gat_dispatch<GatBackwardValue, float>(vw, V, gat_grid(g.N, C, vw), st, dv.get(), a.get(), go.get(), ej.get(), orp.get(), opm.get(), g.N, g.H, V);
-      } else {
-        const int vw = gat_gather_packet<double>(C, V, {dv.get(), go.get()});
-        gat_dispatch<GatBackwardValue, double>(vw, V, gat_grid(g.N, C, vw), st, dv.get(), a.get(), go.get(), ej.get(), orp.get(), opm.get(), g.N, g.H, V);
-      }
+      with_float(dt, [&](auto z) {
+        using T = decltype(z);
+        gat_with_packet<T>(gat_gather_packet<T>(C, V, {dv.get(), go.get()}), V, [&](auto W, auto one) {
+          constexpr int VW = decltype(W)::value;
+          hipLaunchKernelGGL((gat_backward_value_kernel<T, VW, decltype(one)::value>), row_grid(g.N, C, VW, kWaves + 1), dim3(kWaves * 64), 0, st, dv->ptr<T>(),
+                             a->ptr<T>(), go->ptr<T>(), ej->ptr<int64_t>(), orp->ptr<int64_t>(), opm->ptr<int64_t>(), g.N, g.H, V);
+        });
+      });
       LAMP_LAUNCH_CHECK();
     }
   }
@@ -1288,7 +1131,7 @@ int lamp_gat_backward(lamp_tensor** dscore, lamp_tensor** dvalue, const lamp_ten
 
 int lamp_mpnn_long_row(int64_t* out) {
   LAMP_API_BEGIN
-  *out = kMpnnLongRow;
+  *out = kLongRow;
   LAMP_API_END
 }
 
@@ -1325,20 +1168,30 @@ int lamp_mpnn_message_forward(lamp_tensor** out, const lamp_tensor* x, const lam
   LAMP_CHECK(edgeFeatures->ndim == 2, "edgeFeatures " << edgeFeatures->describe() << " must be [E, Fe]");
   check_i64_vector(edgeI, x, "edgeI");
   check_i64_vector(edgeJ, x, "edgeJ");
-  const int64_t E = edgeI->numel(), Fe = edgeFeatures->sizes[1], D = x->sizes[1];
+  const int64_t E = edgeI->numel(), Fe = edgeFeatures->sizes[1], D = x->sizes[1], W = Fe + 2 * D;
   LAMP_CHECK(edgeJ->numel() == E, "edgeI " << edgeI->describe() << " and edgeJ " << edgeJ->describe() << " differ in length");
   LAMP_CHECK(edgeFeatures->sizes[0] == E, "edgeFeatures " << edgeFeatures->describe() << " does not have one row per edge (" << E << " edges)");
   LAMP_CHECK(E == 0 || x->sizes[0] > 0, "x " << x->describe() << " has no rows");
-  LAMP_CHECK(Fe + 2 * D <= INT32_MAX / 2, "a message of " << Fe + 2 * D << " columns is too wide");
+  LAMP_CHECK(W <= INT32_MAX / 2, "a message of " << W << " columns is too wide");
   int64_t lde = 0, ldx = 0;
-  Hold ec(mpnn_rows(edgeFeatures, &lde)), xc(mpnn_rows(x, &ldx)), ei(contiguous(edgeI)), ej(contiguous(edgeJ));
-  int64_t os[2] = {E, Fe + 2 * D};
+  Hold ec(rows_in_place(edgeFeatures, &lde)), xc(rows_in_place(x, &ldx)), ei(contiguous(edgeI)), ej(contiguous(edgeJ));
+  int64_t os[2] = {E, W};
   Hold o(new_tensor(os, 2, x->dtype, x->device()));
-  if (E * (Fe + 2 * D)) {
+  if (E * W) {
     hipStream_t st = current_stream(x->device());
-    KernelTimer kt("mpnn_message", 0, 2.0 * E * (Fe + 2 * D) * dtype_size(x->dtype) + E * 16.0, st);
-    if (x->dtype == kF32) mpnn_message_dispatch<float>(st, o.get(), ec.get(), lde, xc.get(), ldx, ei.get(), ej.get(), E, (int)Fe, (int)D);
-    else mpnn_message_dispatch<double>(st, o.get(), ec.get(), lde, xc.get(), ldx, ei.get(), ej.get(), E, (int)Fe, (int)D);
+    KernelTimer kt("mpnn_message", 0, 2.0 * E * W * dtype_size(x->dtype) + E * 16.0, st);
+    with_float(x->dtype, [&](auto z) {
+      using T = decltype(z);
+      // per segment: the edge segment starts every row (pitch W), the node segments start at Fe and Fe + D
+      const int ve = packet_width<T>({Fe, W, lde}, {o.get(), ec.get()}), vx = packet_width<T>({D, Fe, W, ldx}, {o.get(), xc.get()});
+      const MpnnEdgeGrid g = mpnn_edge_grid(E, Fe / ve + 2 * (D / vx));
+      with_packet<T>(ve, [&](auto VE) {
+        with_packet<T>(vx, [&](auto VX) {
+          hipLaunchKernelGGL((mpnn_message_kernel<T, decltype(VE)::value, decltype(VX)::value>), g.grid, dim3(kMpnnEdgeBlock), 0, st, o->ptr<T>(), ec->ptr<T>(), lde,
+                             xc->ptr<T>(), ldx, ei->ptr<int64_t>(), ej->ptr<int64_t>(), E, (int)Fe, (int)D, g.slots);
+        });
+      });
+    });
     LAMP_LAUNCH_CHECK();
   }
   *out = o.take();
@@ -1360,22 +1213,18 @@ int lamp_mpnn_message_backward(lamp_tensor** dx_or_null, lamp_tensor** dedge_or_
   const double sz = (double)dtype_size(dt);
   Hold g(contiguous(dmsg)), dx, de;
   if (dx_or_null) {
-    for (auto& v : {std::make_pair(inRowptr, "inRowptr"), std::make_pair(outRowptr, "outRowptr")}) {
-      check_i64_vector(v.first, dmsg, v.second);
-      LAMP_CHECK(v.first->numel() == N + 1, v.second << " " << v.first->describe() << " does not belong to a graph of " << N << " nodes");
-    }
-    for (auto& v : {std::make_pair(inPerm, "inPerm"), std::make_pair(outPerm, "outPerm")}) {
-      check_i64_vector(v.first, dmsg, v.second);
-      LAMP_CHECK(v.first->numel() == E, v.second << " " << v.first->describe() << " does not have dmsg's " << E << " edges");
-    }
+    check_rowptrs({{inRowptr, "inRowptr"}, {outRowptr, "outRowptr"}}, dmsg, N);
+    check_i64_vectors({{inPerm, "inPerm"}, {outPerm, "outPerm"}}, dmsg, E, "does not have dmsg's " + std::to_string(E) + " edges");
     Hold irp(contiguous(inRowptr)), ipm(contiguous(inPerm)), orp(contiguous(outRowptr)), opm(contiguous(outPerm));
     int64_t xs[2] = {N, D};
     dx = Hold(new_tensor(xs, 2, dt, dev));
     if (N * D) {
       KernelTimer kt("mpnn_message_backward_x", 2.0 * E * D, (2.0 * E * D + (double)N * D) * sz + E * 16.0 + N * 16.0, st);
       const MpnnSum a{dx.get(), g.get(), W, Fe, Fe + D, orp.get(), opm.get(), irp.get(), ipm.get(), nullptr, nullptr, nullptr, nullptr, N, D};
-      if (dt == kF32) mpnn_sum_packet<float, false, false>(mpnn_packet<float>({D, Fe, W}, {dx.get(), g.get()}), a, st);
-      else mpnn_sum_packet<double, false, false>(mpnn_packet<double>({D, Fe, W}, {dx.get(), g.get()}), a, st);
+      with_float(dt, [&](auto z) {
+        using T = decltype(z);
+        mpnn_sum_launch<T, false, false>(packet_width<T>({D, Fe, W}, {dx.get(), g.get()}), a, st);
+      });
       LAMP_LAUNCH_CHECK();
     }
   }
@@ -1383,9 +1232,16 @@ int lamp_mpnn_message_backward(lamp_tensor** dx_or_null, lamp_tensor** dedge_or_
     int64_t es[2] = {E, Fe};
     de = Hold(new_tensor(es, 2, dt, dev));
     if (E * Fe) {
+      // dedge = dmsg[:, 0:Fe]
       KernelTimer kt("mpnn_message_backward_edge", 0, 2.0 * E * Fe * sz, st);
-      if (dt == kF32) mpnn_columns_dispatch<float>(st, de.get(), Fe, g.get(), W, E, (int)Fe);
-      else mpnn_columns_dispatch<double>(st, de.get(), Fe, g.get(), W, E, (int)Fe);
+      with_float(dt, [&](auto z) {
+        using T = decltype(z);
+        const int v = packet_width<T>({Fe, W}, {de.get(), g.get()});
+        const MpnnEdgeGrid eg = mpnn_edge_grid(E, Fe / v);
+        with_packet<T>(v, [&](auto V) {
+          hipLaunchKernelGGL((mpnn_columns_kernel<T, decltype(V)::value>), eg.grid, dim3(kMpnnEdgeBlock), 0, st, de->ptr<T>(), Fe, g->ptr<T>(), W, E, (int)Fe, eg.slots);
+        });
+      });
       LAMP_LAUNCH_CHECK();
     }
   }
@@ -1408,14 +1264,9 @@ int lamp_mpnn_aggregate_forward(lamp_tensor** out, const lamp_tensor* message, c
   const int64_t N = inRowptr->numel() - 1;
   LAMP_CHECK(!aggregateJ || (outRowptr_or_null && outPerm_or_null), "aggregateJ needs the outgoing grouping");
   const Tensor *orp0 = aggregateJ ? outRowptr_or_null : nullptr, *opm0 = aggregateJ ? outPerm_or_null : nullptr;
-  for (auto& v : {std::make_pair(edgeI, "edgeI"), std::make_pair(edgeJ, "edgeJ"), std::make_pair(inPerm, "inPerm"), std::make_pair(opm0 ? opm0 : inPerm, "outPerm")}) {
-    check_i64_vector(v.first, message, v.second);
-    LAMP_CHECK(v.first->numel() == E, v.second << " " << v.first->describe() << " does not have one entry per row of message " << message->describe());
-  }
-  if (orp0) {
-    check_i64_vector(orp0, message, "outRowptr");
-    LAMP_CHECK(orp0->numel() == N + 1, "outRowptr " << orp0->describe() << " does not belong to a graph of " << N << " nodes");
-  }
+  check_i64_vectors({{edgeI, "edgeI"}, {edgeJ, "edgeJ"}, {inPerm, "inPerm"}, {opm0 ? opm0 : inPerm, "outPerm"}}, message, E,
+                    "does not have one entry per row of message " + message->describe());
+  if (orp0) check_rowptrs({{orp0, "outRowptr"}}, message, N);
   mpnn_check_factor(fI_or_null, "fI", message, N);
   mpnn_check_factor(fJ_or_null, "fJ", message, N);
   Hold mc(contiguous(message)), ei(contiguous(edgeI)), ej(contiguous(edgeJ)), irp(contiguous(inRowptr)), ipm(contiguous(inPerm)), orp(orp0 ? contiguous(orp0) : nullptr),
@@ -1427,8 +1278,10 @@ int lamp_mpnn_aggregate_forward(lamp_tensor** out, const lamp_tensor* message, c
     const double sz = (double)dtype_size(message->dtype), terms = (aggregateJ ? 2.0 : 1.0) * E;
     KernelTimer kt("mpnn_aggregate", 3.0 * terms * M, (terms * M + (double)N * M) * sz + terms * (24 + 2 * sz) + N * 16.0, st);
     const MpnnSum a{o.get(), mc.get(), M, 0, 0, irp.get(), ipm.get(), orp.get(), opm.get(), ei.get(), ej.get(), fi.get(), fj.get(), N, M};
-    if (message->dtype == kF32) mpnn_aggregate_dispatch<float>(mpnn_packet<float>({M}, {o.get(), mc.get()}), a, st);
-    else mpnn_aggregate_dispatch<double>(mpnn_packet<double>({M}, {o.get(), mc.get()}), a, st);
+    with_float(message->dtype, [&](auto z) {
+      using T = decltype(z);
+      mpnn_aggregate_launch<T>(packet_width<T>({M}, {o.get(), mc.get()}), a, st);
+    });
     LAMP_LAUNCH_CHECK();
   }
   *out = o.take();
@@ -1457,8 +1310,15 @@ int lamp_mpnn_aggregate_backward(lamp_tensor** dmsg, const lamp_tensor* dout, co
     hipStream_t st = current_stream(dout->device());
     const double sz = (double)dtype_size(dout->dtype);
     KernelTimer kt("mpnn_aggregate_backward", 3.0 * E * M, ((aggregateJ ? 3.0 : 2.0) * E * M + 2.0 * E) * sz + E * 16.0, st);
-    if (dout->dtype == kF32) mpnn_aggregate_backward_dispatch<float>(st, o.get(), gc.get(), ei.get(), ej.get(), fi.get(), fj.get(), aggregateJ, E, (int)M);
-    else mpnn_aggregate_backward_dispatch<double>(st, o.get(), gc.get(), ei.get(), ej.get(), fi.get(), fj.get(), aggregateJ, E, (int)M);
+    with_float(dout->dtype, [&](auto z) {
+      using T = decltype(z);
+      const int v = packet_width<T>({M}, {o.get(), gc.get()});
+      const MpnnEdgeGrid g = mpnn_edge_grid(E, M / v);
+      with_packet<T>(v, [&](auto V) {
+        hipLaunchKernelGGL((mpnn_aggregate_backward_kernel<T, decltype(V)::value>), g.grid, dim3(kMpnnEdgeBlock), 0, st, o->ptr<T>(), gc->ptr<T>(), ei->ptr<int64_t>(),
+                           ej->ptr<int64_t>(), fi.get() ? fi->ptr<T>() : nullptr, fj.get() ? fj->ptr<T>() : nullptr, aggregateJ, E, (int)M, g.slots);
+      });
+    });
     LAMP_LAUNCH_CHECK();
   }
   *dmsg = o.take();
