@@ -833,6 +833,48 @@ int lamp_multinomial(lamp_tensor** out, const lamp_tensor* probs, int64_t num_sa
 int lamp_dropout_(lamp_tensor* self, double p, int training);
 
 /* ------------------------------------------------------------------------------------------
+ * language-model decode   (lamp-data/src/main/scala/lamp/data/languagemodel/package.scala:35-114 generates a token by running the
+ * whole model over the whole prefix; with cached keys and values a new token needs one row per block).  kernels/decode.hip: f32, f64
+ * and bf16 (bf16 accumulates in f32, f64 in f64), GPU tensors.  No call synchronises with the host, there is no floating-point
+ * atomic, and every sum is taken in a fixed order: a result depends on its inputs alone and is bit-identical from run to run.
+ * ------------------------------------------------------------------------------------------ */
+#define LAMP_DECODE_MAX_ROWS 16
+#define LAMP_DECODE_ACT_NONE 0
+#define LAMP_DECODE_ACT_GELU 1
+/* out[R, N] = residual + scale (.) act( LN(x)[R, K] . W + bias ) for R <= LAMP_DECODE_MAX_ROWS rows (more is an error), every
+ * decoration optional:
+ *   layer_norm != 0: x is normalised over K first (biased variance, ln_eps, then * ln_scale [K] + ln_bias [K] where given), as
+ *                    lamp_layer_norm does;
+ *   bias [1, N] or [N]; act: LAMP_DECODE_ACT_NONE or _GELU (the exact erf form of lamp_gelu);
+ *   scale [N] and residual [R, N] come together: lamp_mul_add(y, scale, residual).
+ * Everything from the normalised row to the residual is computed in the accumulation type on the sum itself and rounded to the tensor
+ * type once, at the store: inside one launch no activation is stored.  W is [K, N] row-major as lamp_mm takes it; transposed != 0: W is
+ * [N, K] (the logits product against an embedding table, no materialised transpose).  K and N need not be multiples of the packet
+ * width (16-byte packets where the sizes and addresses allow them, elements otherwise).
+ * [K, N]: a workgroup owns a tile of columns and a slice of K, its waves split the slice; the waves' sums are added in wave order, the
+ * slices' sums in slice order by the workgroup that finishes last (an integer ticket, no floating atomic).  [N, K]: a wave per column,
+ * the lanes split K. */
+int lamp_decode_linear(lamp_tensor** out, const lamp_tensor* x, const lamp_tensor* w, int transposed, int layer_norm, double ln_eps,
+                       const lamp_tensor* ln_scale_or_null, const lamp_tensor* ln_bias_or_null, const lamp_tensor* bias_or_null, int act,
+                       const lamp_tensor* scale_or_null, const lamp_tensor* residual_or_null);
+/* Single-query attention over a key / value cache.  qkv [R, 3 H d]: the packed projection [q | k | v] of the new token of every
+ * row; kcache, vcache [R, H, Tmax, d] contiguous; 0 <= t < Tmax.  Writes the new key and value rows into position t of the caches
+ * (their bits), then out[R, H d] = softmax(q . K^T / sqrt(d)) . V over the positions 0 .. t with the arithmetic of
+ * MultiheadAttention.maskedSoftmax (Transformer.scala:751-762): exp of the log-softmax of the scaled scores, in the accumulation type,
+ * the output rounded once.  Cache rows beyond t are never read.  d <= 256. */
+int lamp_decode_attention(lamp_tensor** out, const lamp_tensor* qkv, lamp_tensor* kcache, lamp_tensor* vcache, int64_t t, int64_t num_heads);
+/* One launch from logits [R, V] to a token per row (int64 [R]): p = exp((logits - max) / temperature) in f64, the running sum of p in
+ * f64 as lamp_multinomial forms it, and the first index whose running sum exceeds u * total, at most V - 1.  uniforms: f64 [R] in
+ * [0, 1), or NULL: u comes from the library's Philox stream (lamp_manual_seed).  temperature > 0.  A row that holds a NaN or an
+ * infinite logit raises at the host's next wait (the device-side assertion word).  Any R, a workgroup per row.
+ * The _out form writes into an int64 tensor of R elements of any stride (a column of the generated sequence). */
+int lamp_sample_logits(lamp_tensor** out, const lamp_tensor* logits, double temperature, const lamp_tensor* uniforms_or_null);
+int lamp_sample_logits_out(lamp_tensor* out, const lamp_tensor* logits, double temperature, const lamp_tensor* uniforms_or_null);
+/* out[r, :] = tokenWeight[tokens[r], :] + positionWeight[t, :] (one rounding, as Embedding + Embedding): the input row of the token at
+ * position t.  tokens: int64, R elements of any stride; a token outside the table raises as an index out of range and reads as zeros. */
+int lamp_decode_embedding(lamp_tensor** out, const lamp_tensor* tokenWeight, const lamp_tensor* positionWeight, const lamp_tensor* tokens, int64_t t);
+
+/* ------------------------------------------------------------------------------------------
  * fused multi-tensor optimiser steps   (lamp-core/src/main/scala/lamp/nn/AdamW.scala:101-176,
  * SGD.scala:46-98, nn/package.scala:72-100).  One launch for all parameter tensors instead
  * of ~8 ATen calls per tensor; arithmetic order follows the reference line by line.

@@ -93,6 +93,25 @@ int lamp_module_language_model_loss(lamp_module** out, int64_t max_length, int64
 /* LanguageModelOutput(encoded, languageModelLogits) (lm.scala:146-188); either output pointer may be NULL */
 int lamp_language_model_forward(lamp_module* m, lamp_var* tokens, const lamp_tensor* max_length_or_null, const lamp_tensor* positions_or_null,
                                 lamp_var** encoded, lamp_var** logits);
+/* lamp.data.languagemodel.autoregressiveInference (lamp-data languagemodel/package.scala:35-114) for B equal-length prefixes at once.
+ * module: a LanguageModelModule or a LanguageModelLoss.  prefix: int64 [B, P], P >= 1, on the model's device or the host.  *tokens:
+ * int64 [B, P + length] on the model's device, the prefix followed by what was sampled.  *logits_or_null: the untempered logits of
+ * every step, [B, length, V] in the model's type.  Every step sees takeRight(model_block_size) of the sequence at positions
+ * 0 .. len - 1; dropout is off during the call and the module's training flags are as before afterwards.  An empty prefix,
+ * temperature <= 0 and a model_block_size above the position table are errors.  No step synchronises with the host: the sampled token
+ * stays on the device and feeds the next step.
+ * With lamp_language_model_decode_fused on (the default), B <= LAMP_DECODE_MAX_ROWS, a model that is not linearized, f32 / f64 / bf16
+ * and lamp_attention_fused_call_as_written off: the first window min(P, model_block_size) runs once through the operators of the
+ * training forward and fills a key / value cache per block; while the sequence fits model_block_size every further token is one row
+ * through the kernels of kernels/decode.hip (5 launches per block + 4); once the window slides every cached position's embedding has
+ * moved, so each token is one full forward of the window and lamp_sample_logits.  Otherwise every step is the reference's chain: the
+ * full forward, / temperature, logSoftMax, exp, lamp_multinomial. */
+int lamp_language_model_generate(lamp_module* module, const lamp_tensor* prefix, int64_t length, double temperature, int64_t model_block_size,
+                                 lamp_tensor** tokens, lamp_tensor** logits_or_null);
+/* Process-wide; returns the previous value in *previous_or_null. */
+int lamp_language_model_decode_fused(int on, int* previous_or_null);
+/* which path the calling process's last lamp_language_model_generate took: 1 the decode kernels, 0 the chain, -1 none yet */
+int lamp_language_model_generate_path(int* out);
 int lamp_sequence_mask(lamp_var** out, const lamp_tensor* max_length, lamp_var* maskable, double fill);   /* MultiheadAttention.sequenceMask :667-749 */
 int lamp_masked_softmax(lamp_var** out, lamp_var* input, const lamp_tensor* max_length);                  /* MultiheadAttention.maskedSoftmax :751-762 */
 /* ---- BERT pretraining (lamp-core nn/bert/bert.scala).  State order = the reference's `state`: token table, segment table, the positional

@@ -146,6 +146,7 @@ const char* assert_text(int code) {
     case kAssertNllTarget: return "nll_loss: a target class index is outside [0, numClasses) and is not ignore_index";
     case kAssertIndexRange: return "index out of range";
     case kAssertMultinomial: return "multinomial: invalid distribution (a weight is negative, infinite or NaN, or a row sums to zero)";
+    case kAssertSampleLogits: return "sample_logits: a row of logits holds a NaN or an infinite value";
     case kAssertBnExchangeTimeout: return "batch-norm backward (one pass): a workgroup waited two minutes for the partial sums of its channel - "
                                           "another kernel is holding the compute units; the gradients of that launch are invalid (LAMP_BN_FUSED_BWD=0 selects the two-kernel form)";
   }

@@ -215,7 +215,7 @@ void conv_stats_publish(const lamp_tensor* y, lamp_tensor* partial, int P, uint6
 bool conv_stats_wanted(uint64_t producer);   // false: this producer's last statistics were never taken (it probes again every 64th call)
 lamp_tensor* conv_stats_lookup(const lamp_tensor* x, int64_t C, int* P);   // +1 handle or nullptr
 // device-side assertions (runtime.cpp): a kernel stores a code into *device_assert_word(dev); the next host wait raises
-enum DeviceAssert : int { kAssertNllTarget = 1, kAssertIndexRange = 2, kAssertBnExchangeTimeout = 3, kAssertMultinomial = 4 };
+enum DeviceAssert : int { kAssertNllTarget = 1, kAssertIndexRange = 2, kAssertBnExchangeTimeout = 3, kAssertMultinomial = 4, kAssertSampleLogits = 5 };
 // "this device is also running kernels the library does not schedule" (an RCCL collective on the exchange stream while backward
 // continues, a caller's own side-stream work): kernels whose workgroups wait for each other take their non-waiting form meanwhile.
 void device_shared_add(int device, int delta);

@@ -3,6 +3,7 @@
 #include "transformer.h"
 #include "recurrent.h"
 #include "bert.h"
+#include "generate.h"
 #include "../../../include/lamp_host.h"
 
 #include <cstring>
@@ -256,6 +257,29 @@ int lamp_language_model_forward(lamp_module* m, lamp_var* tokens, const lamp_ten
   auto r = lm->run(tokens->v, max_length ? borrow(max_length) : Ten(), positions ? borrow(positions) : Ten());
   if (encoded) *encoded = wrap(r.first);
   if (logits) *logits = wrap(r.second);
+  LAMP_API_END
+}
+int lamp_language_model_generate(lamp_module* m, const lamp_tensor* prefix, int64_t length, double temperature, int64_t model_block_size,
+                                 lamp_tensor** tokens, lamp_tensor** logits) {
+  LAMP_API_BEGIN
+  auto lm = std::dynamic_pointer_cast<LanguageModelModule>(m->m);
+  if (!lm) if (auto l = std::dynamic_pointer_cast<LanguageModelLoss>(m->m)) lm = l->languageModel;
+  LAMP_CHECK(lm, "lamp_language_model_generate: not a LanguageModelModule / LanguageModelLoss");
+  LAMP_CHECK(prefix && tokens, "lamp_language_model_generate: prefix and tokens are required");
+  Generated g = language_model_generate(*lm, borrow(prefix), length, temperature, model_block_size, logits != nullptr);
+  HCALL(lamp_tensor_retain(g.tokens.h(), tokens));
+  if (logits) HCALL(lamp_tensor_retain(g.logits.h(), logits));
+  LAMP_API_END
+}
+int lamp_language_model_decode_fused(int on, int* previous) {
+  LAMP_API_BEGIN
+  const bool prev = set_decode_fused(on != 0);
+  if (previous) *previous = prev ? 1 : 0;
+  LAMP_API_END
+}
+int lamp_language_model_generate_path(int* out) {
+  LAMP_API_BEGIN
+  *out = last_generate_path();
   LAMP_API_END
 }
 int lamp_sequence_mask(lamp_var** out, const lamp_tensor* max_length, lamp_var* maskable, double fill) {

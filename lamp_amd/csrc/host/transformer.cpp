@@ -215,9 +215,10 @@ void TransformerEncoderBlock::collect_state(std::vector<Var>& o) {   // :227-235
   attention->collect_state(o); layerNorm1->collect_state(o); layerNorm2->collect_state(o);
   o.push_back(w1); o.push_back(w2); o.push_back(b1); o.push_back(b2); o.push_back(scale1); o.push_back(scale2);
 }
-Var TransformerEncoderBlock::block(const Var& input, const Ten& maxLength) {   // :237-258
+Var TransformerEncoderBlock::block(const Var& input, const Ten& maxLength, Var* normed1) {   // :237-258
   if (gptOrder) {
     Var a1 = layerNorm1->forward(F::dropout(input, dropout, train));
+    if (normed1) *normed1 = a1;
     Var a2 = mult_add(attention->attend(a1, a1, a1, maxLength), scale1, input);
     Var a3 = layerNorm2->forward(F::dropout(a2, dropout, train));
     Var a4 = mult_add(mm1_bias(F::gelu(mm1_bias(a3, w1, b1)), w2, b2), scale2, a2);

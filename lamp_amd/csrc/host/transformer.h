@@ -57,7 +57,8 @@ struct TransformerEncoderBlock : Module {   // Transformer.scala:212-260; state:
                                                        int64_t mlpHiddenDim, int64_t out, double dropout, int dtype, int device,
                                                        bool linearized, bool gptOrder, bool causalMask);
   void collect_state(std::vector<Var>& o) override;
-  Var block(const Var& input, const Ten& maxLength);
+  // normed1 (gptOrder only): receives layerNorm1's output, the input of the attention projections (the key / value cache of host/generate.cpp)
+  Var block(const Var& input, const Ten& maxLength, Var* normed1 = nullptr);
   Var forward(const Var& x) override { return block(x, Ten()); }
   Var forward_multi(const std::vector<Var>& xs, const std::vector<Ten>& aux) override { return block(xs.at(0), aux.empty() ? Ten() : aux[0]); }
   void set_training(bool t) override { train = t; }
