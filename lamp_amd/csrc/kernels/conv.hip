@@ -705,7 +705,8 @@ int lamp_convolution_backward_pair(lamp_tensor* out3[3], const lamp_tensor* x, c
       Hold ac(addend ? contiguous(addend) : nullptr);
       hipStream_t st = current_stream(x->device());
       Hold dx(new_tensor(std::vector<int64_t>(x->sizes, x->sizes + x->ndim), x->dtype, x->device())), dwa(new_like(wa.get())), dwb(new_like(wb.get()));
-      if (narrow_conv_backward_pair(gya.get(), gyb.get(), xc.get(), wa.get(), wb.get(), ga, gb, dx.get(), dwa.get(), dwb.get(), st, ac.get())) {
+      if (narrow_conv_backward_pair(gya.get(), gyb.get(), xc.get(), wa.get(), wb.get(), ga, gb, dx.get(), dwa.get(), dwb.get(), st, ac.get()) ||
+          igemm_conv_backward_pair(gya.get(), gyb.get(), xc.get(), wa.get(), wb.get(), ga, gb, dx.get(), dwa.get(), dwb.get(), st, ac.get())) {
         out3[0] = dx.take(); out3[1] = dwa.take(); out3[2] = dwb.take();
         return 0;
       }

@@ -18,6 +18,9 @@ bool igemm_conv_dgrad_pair(const Tensor* dy, const Tensor* w, const ConvGeom& g,
                            hipStream_t st, const Tensor* addend, bool* addend_fused);
 bool igemm_conv_wgrad(const Tensor* dy, const Tensor* x, Tensor* dw, const ConvGeom& g, hipStream_t st, const Tensor* affine = nullptr);
 bool igemm_conv_wgrad_pair(const Tensor* dy, const Tensor* dy1, const Tensor* x, Tensor* dw, Tensor* dw1, const ConvGeom& g, const ConvGeom& g1, hipStream_t st);
+// dx (+ addend), dw and dw1 of a stride-1 3x3 + 1x1 pair with at most 16 input channels on 8x8 maps from one launch (false: nothing launched)
+bool igemm_conv_backward_pair(const Tensor* dy, const Tensor* dy1, const Tensor* x, const Tensor* w, const Tensor* w1, const ConvGeom& g, const ConvGeom& g1,
+                              Tensor* dx, Tensor* dw, Tensor* dw1, hipStream_t st, const Tensor* addend = nullptr);
 bool igemm_conv_folds_affine(const ConvGeom& g, int dtype);
 bool igemm_conv_fwd_affine(const Tensor* x, const Tensor* affine, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, hipStream_t st);
 

@@ -32,6 +32,8 @@
 //   * ig_wgrad8v2_kernel: four waves, workgroup = (32-channel slice of Cin, image range), all taps in registers - narrow layers and 1x1s;
 //   * ig_wgrad8h_kernel: eight waves, two per SIMD, the same decomposition - 3x3 layers with more than 32 input and 64 output
 //     channels; takes a sibling 1x1's weight gradient or a second layer into the same launch.
+//   * ig_bwd_pair_kernel: the eight-image form's paired input gradient with both weight gradients of its 3x3 + 1x1 pair accumulated
+//     from the images it holds in LDS - at most 16 input channels (res3's entry pair): one read of the output gradients for all three results.
 #include "device_utils.h"
 #include "conv_geom.h"
 #include "conv_backends.h"
@@ -724,12 +726,94 @@ __device__ __forceinline__ void ig8d_tile_stats(const uint2 (&pk)[4], float& mea
   }
 }
 
-template <int KS, int NCT, int SIBM>
-__global__ __launch_bounds__(512) void ig_conv8d_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp, const bf16_t* __restrict__ bias,
-                                                        bf16_t* y, int N, int CI, int KP, int CO, float* __restrict__ stats, int stats_per_wg,
-                                                        const bf16_t* addend, const float4* __restrict__ affine, const IgSibling sib) {
+// ---- the weight gradients of a short-K entry pair inside the paired input gradient's launch (ig_bwd_pair_kernel) ----
+// The paired input gradient of res3's entry (3x3 16 -> 128 and its sibling 1x1, ig_conv8d_kernel<3, 1, 2>) holds eight images of each output
+// gradient in LDS, one source after the other; the four-wave weight-gradient kernel read the same 67 MB a second time.  Here the weight
+// gradients of a workgroup's eight images are accumulated while each source is resident:
+//   dW[rs][co][ci] += sum_p dY[co][p] * Xshift_rs[ci][p]     wave w = output-channel tile w (16 co), M = co, N = ci (16), K = pixels
+// The gradient images are channel-last ([chunk][image][pixel][32 channels], 64-byte pixel rows, ig8d_swz), the contraction runs over pixels:
+// the A fragment comes from the transposing read.  Lane 4 q + p of 16-lane group g supplies pixel (4 ks + g, q) resp. (4 ks + g, q + 4),
+// channels 4 p .. 4 p + 3 of the wave's tile: 16-byte chunk c = 2 (w & 1) + (p >> 1) of chunk w >> 1, at c ^ swizzle(pixel).  A 32-lane half
+// (g = 0, 1: rows of both parities, ig8d_swz bit 1) touches q x 64 bytes + 16 (c ^ swz) + 8 (p & 1): 32 different 8-byte slots of one bank row.
+// x (pixel-contiguous in memory, 2 KiB per image at 16 channels) is staged once: images 0 - 3 in the 8 KiB behind the gradient images, images
+// 4 - 7 in the halves of ring slots 0 and 1 that the whole-tap stages leave unused; 16-byte row h of channel c at slot h ^ (c & 7).  The B
+// fragment of tap (r, s) is row 4 ks + g + r - 1 of channel lane & 15, shifted by s - 1 elements in registers (as ig_wgrad8v2_kernel), zero
+// where the row leaves the image.  Same images per partial sum and the same order of images and k-steps as the four-wave launch.
+struct IgBwdPair { const bf16_t* x; float* partial; float* partial2; };
+constexpr int IG8D_RING = 3 * 128 * 32 * 2, IG8D_XBUF = 8 * 64 * 64;
+constexpr int IG_BWP_LDS = IG8D_RING + 4 * IG8D_XBUF + 8192;   // 160 KiB
+__device__ __forceinline__ int ig_bwp_x_off(int img) {
+  return img < 4 ? IG8D_RING + 4 * IG8D_XBUF + img * 2048 : ((img - 4) >> 1) * 8192 + 4096 + ((img - 4) & 1) * 2048;
+}
+// CX = channels of x (at most 16); images beyond N and channels beyond CX are zeros
+__device__ __forceinline__ void ig_bwp_stage_x(char* smem, const bf16_t* __restrict__ x, int n0, int N, int CX, int tid) {
+  for (int e = tid; e < 8 * 16 * 8; e += 512) {
+    const int row = e & 7, ci = (e >> 3) & 15, img = e >> 7;
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (ci < CX && n0 + img < N) v = *reinterpret_cast<const uint4*>(x + ((int64_t)(n0 + img) * CX + ci) * 64 + row * 8);
+    *reinterpret_cast<uint4*>(smem + ig_bwp_x_off(img) + ci * 128 + ((row ^ (ci & 7)) << 4)) = v;
+  }
+}
+// the resident source's weight gradient over the eight images: acc[r * KS + s] += dY tile of wave wid x tap-shifted x (KS = 1: the 1x1's)
+template <int KS>
+__device__ __forceinline__ void ig_bwp_accumulate(const char* smem, int wid, int lane, f4v (&acc)[KS * KS]) {
+  typedef short s4v __attribute__((ext_vector_type(4)));
+  typedef __attribute__((address_space(3))) s4v* lds_s4_t;
+  typedef unsigned int u4v_ __attribute__((ext_vector_type(4)));
+  constexpr int PAD = (KS - 1) / 2;
+  const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3, ci = lane & 15;
+  const int c0 = ((2 * (wid & 1) + (p >> 1)) ^ ((g & 1) << 1)) << 4;          // pixel columns 0 - 3; columns 4 - 7: chunk ^ 1
+  const char* dyb = smem + IG8D_RING + (wid >> 1) * IG8D_XBUF + (g * 8 + q) * 64 + ((p & 1) << 3);
+  const char* xb = smem + ci * 128;
+#pragma unroll 2
+  for (int img = 0; img < 8; img++) {
+    const char* xi = xb + ig_bwp_x_off(img);
+#pragma unroll
+    for (int ks = 0; ks < 2; ks++) {
+      const char* b = dyb + img * 4096 + ks * 2048;
+      const s4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t)(b + c0));
+      const s4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t)(b + 256 + (c0 ^ 16)));
+      const bf8v fa = __builtin_bit_cast(bf8v, s8v{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
+#pragma unroll
+      for (int r = 0; r < KS; r++) {
+        const int row = 4 * ks + g + r - PAD;
+        const bool out = row < 0 || row > 7;                                  // (possible only at ks = 0, r = 0 and ks = 1, r = 2)
+        const int rowc = out ? 0 : row;
+        u4v_ xc = *reinterpret_cast<const u4v_*>(xi + ((rowc ^ (ci & 7)) << 4));
+        if (KS == 3 && ((ks == 0 && r == 0) || (ks == 1 && r == 2))) xc = out ? u4v_{0u, 0u, 0u, 0u} : xc;
+#pragma unroll
+        for (int s_ = 0; s_ < KS; s_++) {
+          const u4v_ sh = (KS == 1 || s_ == 1) ? xc
+                        : s_ == 0 ? u4v_{xc[0] << 16, (xc[1] << 16) | (xc[0] >> 16), (xc[2] << 16) | (xc[1] >> 16), (xc[3] << 16) | (xc[2] >> 16)}
+                                  : u4v_{(xc[0] >> 16) | (xc[1] << 16), (xc[1] >> 16) | (xc[2] << 16), (xc[2] >> 16) | (xc[3] << 16), xc[3] >> 16};
+          acc[r * KS + s_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, __builtin_bit_cast(bf8v, sh), acc[r * KS + s_], 0, 0, 0);
+        }
+      }
+    }
+  }
+}
+// partial[(split * RS + t)][COP][16] of wave wid's tile (a lane holds channel ci = lane & 15 of rows 4 (lane >> 4) + rr), as ig_wgrad8v2_kernel
+template <int RS>
+__device__ __forceinline__ void ig_bwp_store(float* __restrict__ partial, const f4v (&acc)[RS], int split, int COP, int CX, int wid, int lane) {
+#pragma unroll
+  for (int t = 0; t < RS; t++) {
+    float* out = partial + (int64_t)(split * RS + t) * COP * 16;
+#pragma unroll
+    for (int rr = 0; rr < 4; rr++) {
+      const int co = wid * 16 + (lane >> 4) * 4 + rr, ci = lane & 15;
+      if (ci < CX) out[co * 16 + ci] = acc[t][rr];
+    }
+  }
+}
+
+// the eight-image form's body: ig_conv8d_kernel (WG = false) and ig_bwd_pair_kernel (WG = true: <3, 1, 2> with the weight gradients above)
+template <int KS, int NCT, int SIBM, bool WG>
+__device__ __forceinline__ void ig_conv8d_body(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp, const bf16_t* __restrict__ bias,
+                                               bf16_t* y, int N, int CI, int KP, int CO, float* __restrict__ stats, int stats_per_wg,
+                                               const bf16_t* addend, const float4* __restrict__ affine, const IgSibling sib, const IgBwdPair bw) {
   constexpr bool SIB = SIBM == 1, DG2 = SIBM == 2;
   static_assert(SIBM == 0 || KS == 3, "the sibling product is the centre tap of a 3x3 staging");
+  static_assert(!WG || (DG2 && NCT == 1), "the weight gradients ride on the paired input gradient's whole-tap form");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int RS = KS * KS;
   constexpr int PAD = (KS - 1) / 2;
@@ -869,6 +953,15 @@ __global__ __launch_bounds__(512) void ig_conv8d_kernel(const bf16_t* __restrict
     }
   };
   load_images(DG2 ? sib.x2 : x);
+  // WG: this wave's tile of the two weight gradients (CO = the channels of the convolutions' input, CI = those of the output gradients)
+  [[maybe_unused]] f4v wacc[WG ? RS : 1], wacc1[1];
+  [[maybe_unused]] const bool wg_wave = WG && wid * 16 < CI;
+  if constexpr (WG) {
+    ig_bwp_stage_x(smem, bw.x, n0, N, CO, tid);
+#pragma unroll
+    for (int t = 0; t < RS; t++) wacc[t] = f4v{0.f, 0.f, 0.f, 0.f};
+    wacc1[0] = f4v{0.f, 0.f, 0.f, 0.f};
+  }
   f4v acc[NCT][4];
 #pragma unroll
   for (int i = 0; i < NCT; i++)
@@ -900,6 +993,11 @@ __global__ __launch_bounds__(512) void ig_conv8d_kernel(const bf16_t* __restrict
     for (int k = 0; k < (NCT + 1) / 2; k++) asm volatile("" : "+v"(bpair[k]));
   }
   IG_STAMP(2);
+  if constexpr (WG) {
+    // the second source (the 1x1's output gradient) and x are resident, nothing is in flight: its weight gradient, LDS reads and MFMAs only
+    // (no wait between waves; the images are overwritten behind the barriers that close the centre-tap stage)
+    if (wg_wave) ig_bwp_accumulate<1>(smem, wid, lane, wacc1);
+  }
 
   // Two-phase ping-pong.  A stage is a READ phase (the fragments' ds_reads, plus the DMA of stage t+2) and an MFMA phase, each closed by a raw
   // s_barrier; the second wave of every SIMD runs one phase behind the first, so while one feeds the matrix core the other reads LDS.
@@ -1010,6 +1108,10 @@ __global__ __launch_bounds__(512) void ig_conv8d_kernel(const bf16_t* __restrict
       load_images(x);
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
+      if constexpr (WG) {
+        // the first source is resident until the epilogue, the ring's requests have landed: the 3x3's weight gradient
+        if (wg_wave) ig_bwp_accumulate<KS>(smem, wid, lane, wacc);
+      }
       slot = 1;
     }
     if (grp == 1) __builtin_amdgcn_s_barrier();
@@ -1354,11 +1456,30 @@ __global__ __launch_bounds__(512) void ig_conv8d_kernel(const bf16_t* __restrict
       }
     }
   }
+  if constexpr (WG) {
+    // one f32 partial filter per workgroup (= image range of eight), behind the input gradient's stores
+    if (wg_wave) {
+      ig_bwp_store<RS>(bw.partial, wacc, (int)blockIdx.x, CI, CO, wid, lane);
+      ig_bwp_store<1>(bw.partial2, wacc1, (int)blockIdx.x, CI, CO, wid, lane);
+    }
+  }
   IG_STAMP(5);
 #ifdef IG8D_STAMP
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   IG_STAMP(6);
 #endif
+}
+template <int KS, int NCT, int SIBM>
+__global__ __launch_bounds__(512) void ig_conv8d_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp, const bf16_t* __restrict__ bias,
+                                                        bf16_t* y, int N, int CI, int KP, int CO, float* __restrict__ stats, int stats_per_wg,
+                                                        const bf16_t* addend, const float4* __restrict__ affine, const IgSibling sib) {
+  ig_conv8d_body<KS, NCT, SIBM, false>(x, wp, bias, y, N, CI, KP, CO, stats, stats_per_wg, addend, affine, sib, IgBwdPair{nullptr, nullptr, nullptr});
+}
+// dx = dgrad3x3(dy, w) + dgrad1x1(dy1, w1) [+ addend] as ig_conv8d_kernel<3, 1, 2> computes it, and the partial sums of both weight gradients over
+// the workgroup's eight images (16 input channels at most, the two Cout equal: igemm_conv_backward_pair)
+__global__ __launch_bounds__(512) void ig_bwd_pair_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ wp, bf16_t* dx, int N, int CI, int KP,
+                                                          int CO, const bf16_t* addend, const IgSibling sib, const IgBwdPair bw) {
+  ig_conv8d_body<3, 1, 2, true>(dy, wp, nullptr, dx, N, CI, KP, CO, nullptr, 0, addend, nullptr, sib, bw);
 }
 #ifdef IG8D_STAMP
 extern "C" int lamp_debug_ig8d_stamps(unsigned long long* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(ig8d_stamps), sizeof(ig8d_stamps)) == hipSuccess ? 0 : 1; }
@@ -2047,8 +2168,11 @@ static IgSibling ig_second_product(const IgRequest& rq, const IgPlan& pl, int64_
 }
 
 // launches pl = ig_plan(g, dgrad, rq): extras of the request that the plan does not fold are NOT computed (the caller has read the plan)
+// bwp (optional, igemm_conv_backward_pair: the eight-image form of a paired input gradient with one channel tile): the launch is
+// ig_bwd_pair_kernel, which also leaves the partial sums of both weight gradients; a timer class of its own with that work added
+struct IgBwdPairLaunch { IgBwdPair k; double flops, bytes; };
 static void run_conv8(const Tensor* in, const Tensor* w, const Tensor* bias, Tensor* out, const ConvGeom& g, bool dgrad, hipStream_t st,
-                      const IgRequest& rq, const IgPlan& pl) {
+                      const IgRequest& rq, const IgPlan& pl, const IgBwdPairLaunch* bwp = nullptr) {
   const int KS = g.kh;
   const int CI = (int)(dgrad ? g.Cout : g.Cin), CO = (int)(dgrad ? g.Cin : g.Cout);
   const int KP = pad_k(CI);
@@ -2073,7 +2197,8 @@ static void run_conv8(const Tensor* in, const Tensor* w, const Tensor* bias, Ten
   const ConvGeom* g2 = pl.sibling ? rq.sibling->g : pl.second ? rq.second->g : nullptr;
   const double fl2 = g2 ? conv_flops(*g2) : 0.0, by2 = g2 ? conv_bytes(*g2, 2) - (double)g.N * g.Cin * 64 * 2 : 0.0;
   // fprop and dgrad are the same kernels, so they share one timer class
-  KernelTimer kt("conv_igemm_fprop_dgrad", conv_flops(g) + fl2, conv_bytes(g, 2) + by2, st);
+  KernelTimer kt(bwp ? "conv_bwd_igemm" : "conv_igemm_fprop_dgrad", conv_flops(g) + fl2 + (bwp ? bwp->flops : 0.0),
+                 conv_bytes(g, 2) + by2 + (bwp ? bwp->bytes : 0.0), st);
   const bf16_t* bp = bias ? bias->ptr<bf16_t>() : (const bf16_t*)nullptr;
   const bf16_t* addp = (rq.addend && pl.folds_addend) ? rq.addend->ptr<bf16_t>() : (const bf16_t*)nullptr;
   const float4* affp = (rq.affine && pl.folds_affine) ? reinterpret_cast<const float4*>(rq.affine->ptr<float>()) : (const float4*)nullptr;
@@ -2099,7 +2224,13 @@ static void run_conv8(const Tensor* in, const Tensor* w, const Tensor* bias, Ten
 #define IG_LAUNCH_D_CO(KS_, SIBM_)                                                                                                             \
   do { if (CO <= 16) IG_LAUNCH_D(KS_, 1, SIBM_); else if (CO <= 64) IG_LAUNCH_D(KS_, 4, SIBM_); else if (CO <= 112) IG_LAUNCH_D(KS_, 7, SIBM_); \
        else IG_LAUNCH_D(KS_, 8, SIBM_); } while (0)
-    IG_FOR_KS_SIBM(IG_LAUNCH_D_CO);
+    if (bwp) {
+      LAMP_CHECK(KS == 3 && sibm == 2 && CO <= 16 && dgrad, "internal: the backward pair rides on the paired input gradient's one-tile form");
+      allow_big_lds((const void*)ig_bwd_pair_kernel);
+      hipLaunchKernelGGL(ig_bwd_pair_kernel, dim3(pl.blocks), dim3(512), (size_t)IG_BWP_LDS, st, inp, wpp, outp, N, CI, KP, CO, addp, sib, bwp->k);
+    } else {
+      IG_FOR_KS_SIBM(IG_LAUNCH_D_CO);
+    }
 #undef IG_LAUNCH_D_CO
 #undef IG_LAUNCH_D
   } else {
@@ -2368,6 +2499,40 @@ bool igemm_conv_wgrad_pair(const Tensor* dy, const Tensor* dy1, const Tensor* x,
   // (more than 32 input and 64 output channels: the eight-wave kernel; else the four-wave kernel, one Cin slice per workgroup)
   const SecondWgradConv sw{dy1, dw1, &g1};
   return igemm_conv_wgrad_impl(dy, x, dw, g, st, nullptr, &sw);
+}
+// dx (+ addend), dw and dw1 of a 3x3 + 1x1 pair of the same x from ONE launch of the eight-image form (ig_bwd_pair_kernel): the short-K entry
+// pair of a wide block (res3: 16 -> 128 + 128 on 8x8 maps), whose paired input gradient (igemm_conv_dgrad_pair) and paired weight gradient
+// (igemm_conv_wgrad_pair, the four-wave kernel) are both bound by reading the same two output gradients.  dx is the input-gradient launch's
+// bit for bit; the partial sums cover the image ranges of the four-wave launch (eight images each) and go through the same deferred, batched
+// reduction.  false = nothing launched: the caller runs the two pair calls.  (Cout = 100: the K-tail geometry stays there - no multiple of 32.)
+bool igemm_conv_backward_pair(const Tensor* dy, const Tensor* dy1, const Tensor* x, const Tensor* w, const Tensor* w1, const ConvGeom& g, const ConvGeom& g1,
+                              Tensor* dx, Tensor* dw, Tensor* dw1, hipStream_t st, const Tensor* addend) {
+  if (!sw().ig_bwd_pair || !sw().conv_bwd_pair || !sw().conv_dgrad_pair || !sw().conv_wgrad_pair) return false;
+  if (x->dtype != kBF16 || dy->dtype != kBF16 || dy1->dtype != kBF16 || w->dtype != kBF16 || w1->dtype != kBF16) return false;
+  if (addend && addend->dtype != kBF16) return false;
+  if (!ig_qualifies(g, kBF16) || !ig_qualifies(g1, kBF16) || g.kh != 3 || g1.kh != 1) return false;   // 8x8 maps, stride / dilation / groups 1
+  if (g.Cin != g1.Cin || g.N != g1.N || g.Cin > 16) return false;
+  if (g.Cout != g1.Cout || g.Cout % 32 != 0 || g.Cout > 128) return false;
+  const SecondGradConv sg{dy1, w1, &g1};
+  IgRequest rq;
+  rq.addend = addend;
+  rq.second = &sg;
+  const IgPlan pl = ig_plan(g, true, rq);
+  if (pl.form != IgForm::Eight || !pl.second) return false;
+  // the four-wave launch's partition: eight images per workgroup (not at batches beyond 8 x CUs, nor under another LAMP_WGRAD_MIN_IPS)
+  const WgradSplit split = wgrad_split(g.N, num_cus(), 1);
+  if (split.ips != 8 || split.nsplit != pl.blocks) return false;
+  const int CO = (int)g.Cout, CIP = 16;
+  int64_t ps[1] = {(int64_t)split.nsplit * 9 * CO * CIP}, ps1[1] = {(int64_t)split.nsplit * CO * CIP};
+  Hold partial(new_tensor(ps, 1, kF32, x->device())), partial1(new_tensor(ps1, 1, kF32, x->device()));
+  // the declared work: the two launches' less the second read of the output gradients (x is counted once, as in the weight-gradient pair)
+  const double dy_by = (double)g.N * (g.Cout + g1.Cout) * 64 * 2;
+  const IgBwdPairLaunch bwp{IgBwdPair{x->ptr<bf16_t>(), partial->ptr<float>(), partial1->ptr<float>()}, conv_flops(g) + conv_flops(g1),
+                            conv_bytes(g, 2) + conv_bytes(g1, 2) - (double)g.N * g.Cin * 64 * 2 - dy_by};
+  run_conv8(dy, w, nullptr, dx, g, true, st, rq, pl, &bwp);
+  wgrad_reduce_enqueue(wgrad_reduce_args(CO, (int)g.Cin, CIP, CO, 9, split.nsplit), partial.get(), dw, st);
+  wgrad_reduce_enqueue(wgrad_reduce_args(CO, (int)g.Cin, CIP, CO, 1, split.nsplit), partial1.get(), dw1, st);
+  return true;
 }
 
 }  // namespace lamp
