@@ -74,6 +74,7 @@ constexpr int64_t SW_NO_CLAMP = INT64_MIN;
   X(ig_w8, "LAMP_IG_W8", BOOL, 1, 0, "two-image 128-row kernel: eight waves per image pair at one workgroup per CU or fewer (0: four)")  \
   X(ig_one_image, "LAMP_IG_ONE_IMAGE", BOOL, 1, 0, "... one image per workgroup at one image per CU or fewer (0: pairs)")                 \
   X(ig_bwd_pair, "LAMP_IG_BWD_PAIR", BOOL, 1, 0, "a wide block's short-K entry pair: input gradient and both weight gradients from one eight-image launch (0: the two pair calls)") \
+  X(ig_fwd_pair, "LAMP_IG_FWD_PAIR", BOOL, 1, 0, "a wide block's short-K entry pair, forward: the barrier-free eight-image kernel with both filters resident in LDS (0: the eight-image kernel's sibling form)") \
   /* bf16 implicit GEMM, weight gradient */                                                                                               \
   X(wgrad_group, "LAMP_WGRAD_GROUP", BOOL, 1, 0, "two layers' eight-wave weight gradients parked and launched as one (0: every layer at once)") \
   X(wgrad_min_ips, "LAMP_WGRAD_MIN_IPS", INT, 0, 2, "fewest images per weight-gradient workgroup; unset (0): 2 up to 512 images, 8 above") \

@@ -32,6 +32,9 @@
 //   * ig_wgrad8v2_kernel: four waves, workgroup = (32-channel slice of Cin, image range), all taps in registers - narrow layers and 1x1s;
 //   * ig_wgrad8h_kernel: eight waves, two per SIMD, the same decomposition - 3x3 layers with more than 32 input and 64 output
 //     channels; takes a sibling 1x1's weight gradient or a second layer into the same launch.
+//   * ig_fwd_pair_k16_kernel: the eight-image form's 3x3 + sibling 1x1 with at most 16 input channels (res3's entry pair, forward): the same
+//     decomposition and MFMAs on a barrier-free schedule - both filters resident in LDS, every wave over its own channel tiles, the output
+//     streamed tile by tile under the other waves' matrix work.
 //   * ig_bwd_pair_kernel: the eight-image form's paired input gradient with both weight gradients of its 3x3 + 1x1 pair accumulated
 //     from the images it holds in LDS - at most 16 input channels (res3's entry pair): one read of the output gradients for all three results.
 #include "device_utils.h"
@@ -845,8 +848,10 @@ __device__ __forceinline__ void ig_conv8d_body(const bf16_t* __restrict__ x, con
   const unsigned d_src = (unsigned)(d_row * KP + (((lane & 3) ^ ((4 - ((d_row >> 2) & 3)) & 3)) << 3)) * 2u;
   // SIB: waves 0 - 3 request BOTH 1 KiB pieces (wid, wid + 4) of every stage and waves 4 - 7 none - the sibling's output is stored by waves
   // 4 - 7 only, whose vmcnt then never gates a weight stage, so the sibling's stores may drain under the 3x3 main loop.  Measured: no faster
-  // than every wave storing its own image behind a vmcnt(0) (1.0903 vs 1.0913 ms per step, EXPERIMENTS (21)) - the pair is bound by the bytes
-  // it writes, wherever the wait stands; kept because it is the form that was tested
+  // than every wave storing its own image behind a vmcnt(0) (1.0903 vs 1.0913 ms per step, EXPERIMENTS (21)); kept because it is the form
+  // that was tested.  That comparison moved ONE wait inside the same chain of barriers and says nothing about the chain: with K = 9 x 128
+  // the epilogues hide behind 36 stages, with one short k-step (res3's entry, 16 input channels) the launch was a prologue and two
+  // epilogues in series at 2.1 TB/s of stores (stamps: EXPERIMENTS (82)) - that geometry runs in ig_fwd_pair_k16_kernel below
   const unsigned d_src4 = d_src + 64u * (unsigned)KP * 2u;      // the same lane of piece wid + 4: 64 rows further
   constexpr int NPIECE = SIB ? 2 : 1;                           // this wave's pieces per stage (when it requests any)
   const bool dma_wave = SIB ? wid < 4 : wid < NCT;
@@ -1480,6 +1485,200 @@ __global__ __launch_bounds__(512) void ig_conv8d_kernel(const bf16_t* __restrict
 __global__ __launch_bounds__(512) void ig_bwd_pair_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ wp, bf16_t* dx, int N, int CI, int KP,
                                                           int CO, const bf16_t* addend, const IgSibling sib, const IgBwdPair bw) {
   ig_conv8d_body<3, 1, 2, true>(dy, wp, nullptr, dx, N, CI, KP, CO, nullptr, 0, addend, nullptr, sib, bw);
+}
+
+// ---- the forward entry pair of a wide block with a short K, without barriers (ig_fwd_pair_k16_kernel) ----
+// res3's entry: a 3x3 and its sibling 1x1, at most 16 input channels -> 64 or 128 output channels each.  K is nine + one stages of one 32-deep
+// k-step, so ig_conv8d_kernel<3, NCT, 1> is a prologue and two epilogues in series behind 2 x 8 + 2 x 9 workgroup barriers: 4 MB read, 67 MB
+// written, and nothing overlaps the stores.  Here the SAME decomposition (workgroup = eight images, wave = image, px_of_col) and the same MFMAs
+// per accumulator (pixels x weights, channels 16 - 31 zero, taps in order 0 .. 8, the 1x1 its centre tap alone) run on another schedule:
+//  * prologue: both packed filters become resident - ten tap images [128 rows][32 k] in the ring's layout (slot 0: the sibling's, 1 .. 9: the
+//    3x3's taps), 80 KiB - beside the eight staged images (32 KiB); one wait, one barrier, and no vector-memory LOAD after it: the waves'
+//    vmcnt queues hold stores only and nobody waits for them;
+//  * every wave keeps the 36 pixel fragments of its image in registers (the 1x1 multiplies tap 4's) and runs over 2 NCT units of its own -
+//    the 1x1's channel tiles, then the 3x3's: 4 or 36 MFMAs into 16 accumulator registers, + bias, v_cvt_pk_bf16_f32, ig8d_tile_stats, the
+//    tile's [16 channels][64 pixels] through one of two wave-private 2 KiB LDS buffers, two 16-byte stores per lane (2 KiB of NCHW);
+//  * no s_barrier until the statistics merge at the end: the two waves of a SIMD drift apart and one's MFMAs run under the other's
+//    conversion, LDS traffic and stores.
+// The per-image (mean, M2) of every channel wait in LDS ([convolution][wave][128 channels]: lane group 0's bits, as ig_conv8d_body publishes)
+// for the eight-image merge - shift = mean_0, w = 0 .. 7 - into one 512-count triple per workgroup.  Host: N % 8 == 0, per-workgroup statistics.
+constexpr int IG_FPK_W = 10 * 128 * 32 * 2;                    // ten tap images
+constexpr int IG_FPK_OUT = IG_FPK_W + IG8D_XBUF;               // behind the images: 8 waves x 2 output tiles of 2 KiB
+constexpr int IG_FPK_STAT = IG_FPK_OUT + 8 * 2 * 2048;         // float2 [2 convolutions][8 waves][128 channels]
+constexpr int IG_FPK_LDS = IG_FPK_STAT + 2 * 8 * 128 * 8;      // 160 KiB
+template <int NCT>
+__global__ __launch_bounds__(512) void ig_fwd_pair_k16_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp, const bf16_t* __restrict__ bias,
+                                                              bf16_t* y, int CI, int KP, float* __restrict__ stats, const IgSibling sib) {
+  static_assert(NCT == 4 || NCT == 8, "64 or 128 output channels");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int CO = NCT * 16;
+  constexpr int WT = 128 * 32 * 2, RB = 64, XIMG = 64 * RB;
+  char* Wl = smem;
+  char* Xl = smem + IG_FPK_W;                 // [8 images][64 pixels][32 channels]; taps outside an image read up to 9 pixels before / after it
+                                              // (the last tap image, the neighbour image, the output tiles) and are zeroed in registers
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);   // = image of this wave
+  const int n0 = blockIdx.x * 8;
+  typedef __attribute__((address_space(3))) char lds_char_t;
+  typedef const __attribute__((address_space(1))) char glb_char_t;
+  IG_STAMP(0);
+  // NCHW -> [pixel][32 channels] as ig_conv8d_body stages one chunk: 8 channels x one image row per thread (waves 0 - 3), an 8x8 transposition in
+  // registers.  The images' requests go out first (HBM), the filters' and the bias behind them (L2): one round trip for the whole prologue
+  const bool stager = tid < 256;
+  const int cg = tid & 3, h = (tid >> 2) & 7, img = (tid >> 5) & 7;
+  uint4 rw[8];
+  if (stager) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const int c = cg * 8 + k;
+      // read once: streamed.  Channels beyond CI re-read channel 0 and become zeros below: eight loads back to back, no branch between them
+      rw[k] = nt_load16(reinterpret_cast<const uint4*>(x + ((int64_t)(n0 + img) * CI + (c < CI ? c : 0)) * 64 + h * 8));
+    }
+  }
+  // the filters: wave w requests its 1 KiB piece (rows 16 w .. 16 w + 15) of every tap image, source-side swizzle as ig_conv8d_body's stages
+  if (wid < NCT) {
+    const int d_row = wid * 16 + (lane >> 2);
+    const unsigned d_src = (unsigned)(d_row * KP + (((lane & 3) ^ ((4 - ((d_row >> 2) & 3)) & 3)) << 3)) * 2u;
+    __builtin_amdgcn_global_load_lds((glb_char_t*)(reinterpret_cast<const char*>(sib.wp) + d_src), (lds_char_t*)(Wl + wid * 1024), 16, 0, 0);
+#pragma unroll
+    for (int rs = 0; rs < 9; rs++)
+      __builtin_amdgcn_global_load_lds((glb_char_t*)(reinterpret_cast<const char*>(wp + (int64_t)rs * IG_M * KP) + d_src),
+                                       (lds_char_t*)(Wl + (1 + rs) * WT + wid * 1024), 16, 0, 0);
+  }
+  // the bias of channels lane (low half) and 64 + lane (high half) of either convolution; a unit fetches its tile's value with a ds_bpermute
+  // (requested here, packed behind the prologue's wait: no wait of the compiler's between the requests)
+  unsigned short braw[4] = {0, 0, 0, 0};
+  if (bias) { braw[0] = bias[lane].bits; if (NCT > 4) braw[1] = bias[64 + lane].bits; }
+  if (sib.bias) { braw[2] = sib.bias[lane].bits; if (NCT > 4) braw[3] = sib.bias[64 + lane].bits; }
+  if (stager) {
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+      if (cg * 8 + k >= CI) rw[k] = make_uint4(0, 0, 0, 0);
+    char* xi = Xl + img * XIMG;
+#pragma unroll
+    for (int p = 0; p < 8; p++) {
+      unsigned int d[4];
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const unsigned int lo = (&rw[2 * j].x)[p >> 1], hi = (&rw[2 * j + 1].x)[p >> 1];
+        d[j] = (p & 1) ? ((lo >> 16) | (hi & 0xffff0000u)) : ((lo & 0xffffu) | (hi << 16));
+      }
+      *reinterpret_cast<uint4*>(xi + (h * 8 + p) * RB + ((cg ^ ig8d_swz(h, p)) << 4)) = make_uint4(d[0], d[1], d[2], d[3]);
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  // the same wait as an instruction the compiler counts: with the filters' LDS-DMA or the bias still pending in ITS bookkeeping it writes a
+  // vmcnt(0) of its own in front of the first LDS store inside the unit loop, where it waits for the previous unit's global stores
+  __builtin_amdgcn_s_waitcnt(0);
+  __builtin_amdgcn_s_barrier();                      // images and filters are in LDS: the last wait for a load in this kernel
+  const unsigned bpk3 = (unsigned)braw[0] | ((unsigned)braw[1] << 16), bpk1 = (unsigned)braw[2] | ((unsigned)braw[3] << 16);
+  IG_STAMP(2);
+
+  // the image's 36 pixel fragments: tap (r, s), pixel tile j = pixel (2 j + rowsel + r - 1, wpix + s - 1), addresses as ig_conv8d_body's
+  int rowsel, wpix;
+  px_of_col(lane & 15, rowsel, wpix);
+  const bool col_lo = wpix == 0, col_hi = wpix == 7, row_lo = rowsel == 0, row_hi = rowsel == 1;
+  const bf8v zero8 = __builtin_bit_cast(bf8v, s8v{0, 0, 0, 0, 0, 0, 0, 0});
+  bf8v fx[9][4];
+  {
+    const char* xw = Xl + wid * XIMG + ((rowsel - 1) * 8 + (wpix - 1)) * RB;
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int s = 0; s < 3; s++) {
+        const char* xb = xw + (((lane >> 4) ^ ig8d_swz(rowsel + (r & 1) - 1, wpix + s - 1)) << 4);
+        const bool colout = (s == 0 && col_lo) || (s == 2 && col_hi);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          const bf8v v = __builtin_bit_cast(bf8v, *reinterpret_cast<const s8v*>(xb + ((r * 8 + s) + 16 * j) * RB));
+          const bool out = colout || (r == 0 && j == 0 && row_lo) || (r == 2 && j == 3 && row_hi);
+          fx[r * 3 + s][j] = out ? zero8 : v;
+        }
+      }
+  }
+  // weight fragment of channel tile i of tap image t: row 16 i + (lane & 15), chunk (lane >> 4) ^ swizzle(row)
+  const char* wa = Wl + (lane & 15) * 64 + ((((lane >> 4) ^ ((4 - ((lane >> 2) & 3)) & 3)) & 3) << 4);
+  const int q = lane >> 4, cl = lane & 15;
+  const int qrow = (q == 1 || q == 2) ? 1 : 0, qw = (q >= 2) ? 4 : 0;
+  char* Sw = smem + IG_FPK_OUT + wid * 4096;
+  float2* stat3 = reinterpret_cast<float2*>(smem + IG_FPK_STAT) + wid * 128;
+  float2* stat1 = stat3 + 8 * 128;
+  // one unit's way out: + bias, two values per v_cvt_pk_bf16_f32, the statistics of the packed values, [16 channels][64 pixels] rows in the
+  // wave's buffer i & 1 (8-byte slot s of row c at s ^ ((c & 7) << 1)), 128-byte rows out as 16-byte stores - ig_conv8d_body's epilogue, one tile
+  auto emit = [&](const f4v (&acc)[4], int i, unsigned bpk, bf16_t* yimg, float2* st) {
+    typedef float f2v __attribute__((ext_vector_type(2)));
+    typedef __bf16 bf2v __attribute__((ext_vector_type(2)));
+    const unsigned bv = (unsigned)__builtin_amdgcn_ds_bpermute((((i & 3) << 4) | cl) << 2, (int)bpk);
+    const float b = __uint_as_float(i >= 4 ? (bv & 0xffff0000u) : (bv << 16));
+    char* S = Sw + (i & 1) * 2048;
+    uint2 pk[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const f2v lo = {acc[j][0] + b, acc[j][1] + b}, hi = {acc[j][2] + b, acc[j][3] + b};
+      pk[j].x = __builtin_bit_cast(unsigned, __builtin_convertvector(lo, bf2v));
+      pk[j].y = __builtin_bit_cast(unsigned, __builtin_convertvector(hi, bf2v));
+      const int sl = (2 * j + qrow) * 2 + (qw >> 2);
+      *reinterpret_cast<uint2*>(S + cl * 128 + ((sl ^ ((cl & 7) << 1)) << 3)) = pk[j];
+    }
+    float mean, m2;
+    ig8d_tile_stats(pk, mean, m2);
+    if (q == 0) st[i * 16 + cl] = make_float2(mean, m2);
+#pragma unroll
+    for (int it = 0; it < 2; it++) {
+      const int idx = it * 64 + lane;
+      const int cr = idx >> 3, c = idx & 7;
+      const uint4 v = *reinterpret_cast<const uint4*>(S + cr * 128 + ((c ^ (cr & 7)) << 4));
+      *reinterpret_cast<uint4*>(yimg + (i * 16 + cr) * 64 + c * 8) = v;        // plain: the batch norm reads it next
+    }
+  };
+  const int64_t img_off = (int64_t)(n0 + wid) * CO * 64;
+#pragma unroll 1
+  for (int i = 0; i < NCT; i++) {                    // the sibling 1x1: the centre tap
+    const bf8v fa = __builtin_bit_cast(bf8v, *reinterpret_cast<const s8v*>(wa + i * 1024));
+    f4v acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fx[4][j], fa, f4v{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+    emit(acc, i, bpk1, sib.y + img_off, stat1);
+  }
+  IG_STAMP(3);
+#pragma unroll 1
+  for (int i = 0; i < NCT; i++) {                    // the 3x3: one MFMA per tap, taps 0 .. 8
+    bf8v fa[9];
+#pragma unroll
+    for (int t = 0; t < 9; t++) fa[t] = __builtin_bit_cast(bf8v, *reinterpret_cast<const s8v*>(wa + (1 + t) * WT + i * 1024));
+    f4v acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) acc[j] = f4v{0.f, 0.f, 0.f, 0.f};
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int t = 0; t < 9; t++)
+#pragma unroll
+      for (int j = 0; j < 4; j++) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fx[t][j], fa[t], acc[j], 0, 0, 0);
+    __builtin_amdgcn_s_setprio(0);
+    emit(acc, i, bpk3, y + img_off, stat3);
+  }
+  IG_STAMP(4);
+  // eight equal-count triples -> one of count 512 per channel and convolution, as ig_conv8d_body merges them: threads 0 .. CO - 1 the 3x3's,
+  // 256 .. 256 + CO - 1 the sibling's
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  {
+    const int conv = tid >> 8, ch = tid & 255;
+    if (ch < CO) {
+      const float2* sl = reinterpret_cast<const float2*>(smem + IG_FPK_STAT) + conv * (8 * 128) + ch;
+      const float shift = sl[0].x;
+      float s1 = 0.f, s2 = 0.f, sm = 0.f;
+#pragma unroll
+      for (int w = 0; w < 8; w++) { const float2 v = sl[w * 128]; const float d = v.x - shift; s1 += d; s2 += d * d; sm += v.y; }
+      float* sp = (conv ? sib.stats : stats) + ((int64_t)ch * gridDim.x + blockIdx.x) * 3;
+      sp[0] = 512.f; sp[1] = shift + s1 * 0.125f; sp[2] = sm + 64.f * (s2 - s1 * s1 * 0.125f);
+    }
+  }
+  IG_STAMP(5);
+#ifdef IG8D_STAMP
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  IG_STAMP(6);
+#endif
 }
 #ifdef IG8D_STAMP
 extern "C" int lamp_debug_ig8d_stamps(unsigned long long* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(ig8d_stamps), sizeof(ig8d_stamps)) == hipSuccess ? 0 : 1; }
@@ -2228,6 +2427,16 @@ static void run_conv8(const Tensor* in, const Tensor* w, const Tensor* bias, Ten
       LAMP_CHECK(KS == 3 && sibm == 2 && CO <= 16 && dgrad, "internal: the backward pair rides on the paired input gradient's one-tile form");
       allow_big_lds((const void*)ig_bwd_pair_kernel);
       hipLaunchKernelGGL(ig_bwd_pair_kernel, dim3(pl.blocks), dim3(512), (size_t)IG_BWP_LDS, st, inp, wpp, outp, N, CI, KP, CO, addp, sib, bwp->k);
+    } else if (sw().ig_fwd_pair && !dgrad && KS == 3 && pl.sibling && CI <= 16 && (CO == 64 || CO == 128) && pl.per_wg && !addp && !affp) {
+      // a forward 3x3 + sibling 1x1 with one short k-step (res3's entry, 16 -> 128): the barrier-free schedule of the same arithmetic
+      // (LAMP_IG_FWD_PAIR=0: ig_conv8d_kernel<3, NCT, 1>).  Whole workgroups of eight images and the per-workgroup statistics only.
+      if (CO == 128) {
+        allow_big_lds((const void*)ig_fwd_pair_k16_kernel<8>);
+        hipLaunchKernelGGL(ig_fwd_pair_k16_kernel<8>, dim3(pl.blocks), dim3(512), (size_t)IG_FPK_LDS, st, inp, wpp, bp, outp, CI, KP, statp, sib);
+      } else {
+        allow_big_lds((const void*)ig_fwd_pair_k16_kernel<4>);
+        hipLaunchKernelGGL(ig_fwd_pair_k16_kernel<4>, dim3(pl.blocks), dim3(512), (size_t)IG_FPK_LDS, st, inp, wpp, bp, outp, CI, KP, statp, sib);
+      }
     } else {
       IG_FOR_KS_SIBM(IG_LAUNCH_D_CO);
     }
