@@ -64,9 +64,6 @@ constexpr int64_t SW_NO_CLAMP = INT64_MIN;
   X(conv_bn_stats, "LAMP_CONV_BN_STATS", BOOL, 1, 0, "forward convolutions hand per-image batch-norm statistics of their output on")     \
   X(ncv_bn_stats, "LAMP_NCV_BN_STATS", BOOL, 1, 0, "... the narrow kernels' alone (needs LAMP_CONV_BN_STATS on as well)")                 \
   X(ncv_dgrad_parity, "LAMP_NCV_DGRAD_PARITY", BOOL, 1, 0, "narrow stride-2 pair input gradient: super-tiles by row parity (0: the plain form)") \
-  X(ncv_pitch, "LAMP_NCV_PITCH", BOOL, 1, 0, "narrow kernels widen the LDS row pitch to a bank-conflict-free one")                        \
-  X(ncv_two_shift, "LAMP_NCV_TWO_SHIFT", BOOL, 1, 0, "narrow kernels: two output phases per MFMA where the columns allow it")             \
-  X(ncv_per_cu, "LAMP_NCV_PER_CU", INT, 4, 1, "narrow kernels: most workgroups per CU")                                                   \
   X(pack_cache, "LAMP_PACK_CACHE", BOOL, 1, 0, "packed filter images are cached per parameter and storage version (all four packing backends: core/pack_cache.h)") \
   X(pack_after_step, "LAMP_PACK_AFTER_STEP", BOOL, 1, 0, "the optimiser repacks every cached filter image of all four backends in place (0: lazily at first use)") \
   /* bf16 implicit GEMM, forward and input gradient (kernels/conv_igemm.hip: ig_form) */                                                  \

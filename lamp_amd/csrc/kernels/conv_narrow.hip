@@ -145,12 +145,10 @@ __global__ __launch_bounds__(256) void ncv_fwd_kernel(const bf16_t* __restrict__
   const int HoWo = q.Ho * q.Wo, ntiles = (HoWo + 15) >> 4;
   const int img_elems = q.C * q.Hs * q.Ws;
   for (int o = tid * 8; o < img_elems; o += 256 * 8) *reinterpret_cast<uint4*>(xs + o) = make_uint4(0, 0, 0, 0);   // img_elems % 8 == 0
-  bool first = true;
   for (int n = blockIdx.x; n < q.N; n += gridDim.x) {
     __syncthreads();                                     // zero fill / previous image's reads are done
     ncv_stage(xs, src + (int64_t)n * q.C * q.H * q.W, q, tid, 256);
     __syncthreads();
-    first = false;
     bf16_t* yp = dst + (int64_t)n * q.CO * HoWo;
     for (int tile = wid; tile < ntiles; tile += 4) {
       const int p = min(tile * 16 + (lane & 15), HoWo - 1);
@@ -173,7 +171,6 @@ __global__ __launch_bounds__(256) void ncv_fwd_kernel(const bf16_t* __restrict__
       }
     }
   }
-  (void)first;
 }
 
 // Aligned-window variant.  An unaligned ds_read_b128 runs at ~1/11 of the aligned rate on gfx950
@@ -1085,10 +1082,46 @@ static bool ncv_common(const ConvGeom& g, int dtype) {
   return true;
 }
 
-template <int NK>
-static void ncv_launch(const bf16_t* src, const nv_bf8* wpk, const bf16_t* bias, bf16_t* dst, const NcvGeom& q, int blocks, size_t lds, hipStream_t st) {
-  hipLaunchKernelGGL((ncv_fwd_kernel<NK>), dim3(blocks), dim3(256), lds, st, src, wpk, bias, dst, q);
+// g a 3x3 pad 1 and g1 a 1x1 pad 0 convolution of one input: same stride, input map, output map, channels in and batch (the two branches of
+// lamp's residual block on its input, cnn.scala:16-20).  Every pair launch below starts here and adds only what is its own.
+static bool ncv_pair_shapes(const ConvGeom& g, const ConvGeom& g1) {
+  if (g.kh != 3 || g.kw != 3 || g.ph != 1 || g.pw != 1 || g1.kh != 1 || g1.kw != 1 || g1.ph != 0 || g1.pw != 0) return false;
+  if (g.sh != g1.sh || g.sw != g1.sw || g.Ho != g1.Ho || g.Wo != g1.Wo || g.H != g1.H || g.W != g1.W || g.Cin != g1.Cin || g.N != g1.N) return false;
+  return g.groups == 1 && g1.groups == 1 && g.dh == 1 && g.dw == 1 && g1.dh == 1 && g1.dw == 1;
 }
+// the work and traffic a sibling 1x1 of cout2 output channels adds to g's launch (its input is the one already counted)
+static double ncv_sibling_flops(const ConvGeom& g, int cout2) { return 2.0 * (double)g.N * cout2 * (double)g.Ho * g.Wo * (double)g.Cin; }
+static double ncv_sibling_bytes(const ConvGeom& g, int cout2) { return ((double)g.N * cout2 * g.Ho * g.Wo + (double)cout2 * g.Cin) * 2.0; }
+
+constexpr size_t NCV_LDS_BUDGET = 150 * 1024;      // LDS the workgroups of a CU share (of its 160 KiB)
+constexpr size_t NCV_LDS_DEFAULT = 64 * 1024;      // dynamic LDS a kernel may ask for without allow_big_lds
+constexpr int NCV_PER_CU_MAX = 4;                  // most workgroups per CU (A/B on one device: 4 beats 8 and 2)
+// workgroups per CU the LDS image allows, and of those the ones that are really co-resident (registers)
+static int ncv_lds_per_cu(size_t lds) { return (int)std::max<size_t>(1, std::min<size_t>(NCV_PER_CU_MAX, NCV_LDS_BUDGET / std::max<size_t>(lds, 1))); }
+static int ncv_per_cu(const void* kfn, int threads, size_t lds) { return std::min(ncv_lds_per_cu(lds), kernel_occupancy(kfn, threads, lds)); }
+// every convolution launch of this file: more than the default LDS has to be asked for (once per kernel and device)
+static void ncv_launch(const void* kfn, int blocks, int threads, size_t lds, void** args, hipStream_t st) {
+  if (lds > NCV_LDS_DEFAULT) allow_big_lds(kfn);
+  HIP_CHECK(hipLaunchKernel(kfn, dim3(blocks), dim3(threads), args, lds, st));
+  LAMP_LAUNCH_CHECK();
+}
+// Per-slice batch-norm statistics of a launch's one or two outputs ([parts][C][3] f32, written by the kernel's epilogue): allocated where
+// the launch takes them, handed to the consuming batch norm behind it.
+struct NcvStats {
+  Hold t, t2;
+  int parts;
+  NcvStats(bool on, int parts_, int64_t C, int64_t C2, int device) : parts(parts_) {
+    if (!on) return;
+    t = Hold(new_tensor({parts * C * 3}, kF32, device));
+    if (C2 > 0) t2 = Hold(new_tensor({parts * C2 * 3}, kF32, device));
+  }
+  float* ptr() { return t.get() ? t->ptr<float>() : nullptr; }
+  float* ptr2() { return t2.get() ? t2->ptr<float>() : nullptr; }
+  void publish(const Tensor* y, uint64_t producer, const Tensor* y2) {
+    if (t.get()) conv_stats_publish(y, t.get(), parts, producer);
+    if (t2.get()) conv_stats_publish(y2, t2.get(), parts);
+  }
+};
 
 // ---- packed weight-fragment images, one per (filter [and sibling], geometry, direction, stream): cached and re-packed in place by the
 // optimiser's hook (core/pack_cache.h).  An entry keeps no data pointers: the hook resolves both filters among the parameters it is handed.
@@ -1175,18 +1208,20 @@ struct NcvSibling { const Tensor* w; const Tensor* bias; Tensor* out; };
 struct NcvSecondGrad { const Tensor* dy; const Tensor* w; };
 // What a narrow forward / input-gradient launch looks like for a geometry: the LDS image, the kernel form and its template arguments.
 // sib / second: a sibling 1x1's cout2 output channels (fprop) or its output gradient as extra image channels (dgrad) take part.
-// false: the narrow kernels do not take it.
+// own_stage: the launch is not ncv_fwd_kernel's / ncv_fwd2_kernel's own but that of a kernel which always stages this image through a register
+// prefetch of its own (ncv_chain_kernel, ncv_bwd_pair_kernel): q.pf is set, and whether the image fits THAT prefetch is the launcher's check.
+// false: the narrow kernels do not take it.  true: the launch is taken, with exactly these parameters.
 struct NcvLaunchPlan {
   NcvGeom q;
   bool aligned;          // the aligned-window kernel (ncv_fwd2_kernel); else ncv_fwd_kernel
   int ncg, ph0;          // aligned: column groups per output row, window phase
-  int NK;                // k-steps of the pairs (an entry of nk_opts); aligned: the kernel's are NK2
+  int NK;                // the kernel's k-steps (its template argument)
   int nke;               // > 0: parity tiles, nke k-steps per class
   int NS;                // output phases per MFMA
   size_t lds;
-  int threads, NK2;      // aligned only
+  int threads;
 };
-static bool ncv_plan(const ConvGeom& g, int dtype, bool dgrad, bool sib, bool second, int cout2, NcvLaunchPlan& lp) {
+static bool ncv_plan(const ConvGeom& g, int dtype, bool dgrad, bool sib, bool second, int cout2, bool own_stage, NcvLaunchPlan& lp) {
   if (!ncv_common(g, dtype)) return false;
   if (sib && (dgrad || g.Cout + cout2 > 16)) return false;
   if (second && (!dgrad || sib || cout2 > 16)) return false;
@@ -1238,38 +1273,56 @@ static bool ncv_plan(const ConvGeom& g, int dtype, bool dgrad, bool sib, bool se
   // DIFFERENT 16-byte bank slots iff (RS * sh * Ws / 8) mod 16 is an odd multiple of ncg.  (Round 6: the res2 pair's image had a 64-byte pitch -
   // rows a_tr and a_tr + 4 on the same banks, and with the parity tiles' two-apart rows a_tr and a_tr + 2: the halved k-loop read twice as slowly
   // and the launch gained nothing.)  The pitch is widened by at most 15 x 16 bytes to the next such value.
-  const bool pitch_on = sw().ncv_pitch;
-  if (pitch_on && aligned) {
+  if (aligned) {
     const int rs = (nke > 0 ? 2 : 1) * q.sh;
     for (int k = 0; k < 16; k++) {
       const int step = (rs * ((q.Ws >> 3) + k)) & 15;
-      if (step % ncg == 0 && ((step / ncg) & 1) == 1 && (size_t)q.C * q.Hs * (q.Ws + 8 * k) * 2 <= 64 * 1024) { q.Ws += 8 * k; break; }
+      if (step % ncg == 0 && ((step / ncg) & 1) == 1 && (size_t)q.C * q.Hs * (q.Ws + 8 * k) * 2 <= NCV_LDS_DEFAULT) { q.Ws += 8 * k; break; }
     }
   }
   const size_t lds = (size_t)q.C * q.Hs * q.Ws * 2;
-  if (lds > 64 * 1024) return false;
-  // two output phases per MFMA where the columns allow it (see NcvW)
-  const bool two_shift_on = sw().ncv_two_shift;
-  const int NS = (two_shift_on && aligned && q.CO <= 8 && g.kw + q.sw <= 8) ? 2 : 1;
-  lp.aligned = aligned; lp.ncg = ncg; lp.ph0 = ph0; lp.NK = NK; lp.nke = nke; lp.NS = NS; lp.lds = lds; lp.threads = 256; lp.NK2 = NK;
-  if (aligned) {
-    const int nsuper = q.Ho / (16 / ncg);
-    lp.threads = 64 * std::min(4, nsuper);
-    q.pf = (q.W % 8 == 0 && (int64_t)q.C * q.H * q.W <= (int64_t)NCV_PF * lp.threads * 8) ? 1 : 0;
-    // (parity tiles: the kernel's k-steps are the packed image's two halves - 2 nke, whatever the plain form would have taken: 12 k-steps of
-    // pairs are 16 there)
-    lp.NK2 = nke > 0 ? 2 * nke : NK <= 2 ? 2 : (NK <= 4 ? 4 : (NK <= 5 ? 5 : (NK <= 6 && second ? 6 : (NK <= 8 && second ? 8 : (NK <= 12 ? 12 : 16)))));
+  if (lds > NCV_LDS_DEFAULT) return false;
+  lp.aligned = aligned; lp.ncg = ncg; lp.ph0 = ph0; lp.nke = nke; lp.lds = lds;
+  if (!aligned) {
+    // ncv_fwd_kernel: one output phase per MFMA, 1, 2, 4, 5, 8 or 12 k-steps
+    if (NK > 12) return false;
+    lp.NK = NK == 6 ? 8 : NK; lp.NS = 1; lp.threads = 256;
+    return true;
   }
+  // two output phases per MFMA where the columns allow it (see NcvW)
+  lp.NS = (q.CO <= 8 && g.kw + q.sw <= 8) ? 2 : 1;
+  const int nsuper = q.Ho / (16 / ncg);
+  lp.threads = 64 * std::min(4, nsuper);
+  q.pf = (own_stage || (q.W % 8 == 0 && (int64_t)q.C * q.H * q.W <= (int64_t)NCV_PF * lp.threads * 8)) ? 1 : 0;
+  if (second && !q.pf) return false;                     // (two sources are staged through the register prefetch only)
+  // ncv_fwd2_kernel: 2, 4, 5 or 12 k-steps; 6, 8 and 16 for the pairs' input gradients only.  (Parity tiles: the kernel's k-steps are the packed
+  // image's two halves - 2 nke, whatever the plain form would have taken: 12 k-steps of pairs are 16 there)
+  if (NK > 12 && !second) return false;
+  lp.NK = nke > 0 ? 2 * nke : NK <= 2 ? 2 : (NK <= 4 ? 4 : (NK <= 5 ? 5 : (NK <= 6 && second ? 6 : (NK <= 8 && second ? 8 : (NK <= 12 ? 12 : 16)))));
   return true;
 }
 // the packed image's description for a planned launch (second: the sibling's / the second gradient's filter)
 static NcvW ncv_weights_of(const Tensor* w, const ConvGeom& g, bool dgrad, const NcvLaunchPlan& lp, const Tensor* wsecond, int cout2) {
   return NcvW{w->ptr<bf16_t>(), (int)g.Cout, (int)g.Cin, g.kh, g.kw, dgrad ? 1 : 0, lp.NS, lp.q.sw, wsecond ? wsecond->ptr<bf16_t>() : (const bf16_t*)nullptr, cout2, lp.nke};
 }
-// workgroups per CU the LDS image allows (LAMP_NCV_PER_CU at most: A/B on one device, 4 beats 8 and 2)
-static int ncv_lds_per_cu(size_t lds) {
-  const int max_per_cu = (int)sw().ncv_per_cu;
-  return (int)std::max<size_t>(1, std::min<size_t>(max_per_cu, (size_t)(150 * 1024) / std::max<size_t>(lds, 1)));
+// the fragment image of a planned launch's filter(s), as the kernels take it (the handle keeps it alive)
+static const nv_bf8* ncv_fragments(const Hold& wpk) { return reinterpret_cast<const nv_bf8*>(static_cast<const Tensor*>(wpk.get())->ptr<bf16_t>()); }
+// Per-image batch-norm statistics of the output(s) from a forward launch's epilogue (LAMP_CONV_BN_STATS=0 turns the hand-off off,
+// LAMP_NCV_BN_STATS=0 the narrow kernels' alone, A/B).  A filter whose output's statistics nobody took last time - the stem of Cnn.resnet feeds
+// res1's convolutions directly - stops paying for them; a pair's are always taken.
+static bool ncv_takes_stats(const NcvGeom& q, bool dgrad, bool addend, bool sib, const Tensor* w) {
+  return sw().conv_bn_stats && sw().ncv_bn_stats && !dgrad && !addend && q.N >= 2 && (int64_t)q.Ho * q.Wo >= 64 && (sib || conv_stats_wanted(w->st->uid));
+}
+// the instantiation of ncv_fwd_kernel for the plan's k-steps
+static const void* ncv_fwd_fn(int NK) {
+  switch (NK) {
+    case 1: return (const void*)ncv_fwd_kernel<1>;
+    case 2: return (const void*)ncv_fwd_kernel<2>;
+    case 4: return (const void*)ncv_fwd_kernel<4>;
+    case 5: return (const void*)ncv_fwd_kernel<5>;
+    case 8: return (const void*)ncv_fwd_kernel<8>;
+    default: return (const void*)ncv_fwd_kernel<12>;
+  }
 }
 // the instantiation of ncv_fwd2_kernel for (k-steps, phases per MFMA, window phase, stride, addend, statistics, parity tiles)
 static const void* ncv_fwd2_fn(int NK2, int NS, int ph0, int sw, bool with_add, bool with_stats, int nke) {
@@ -1301,87 +1354,56 @@ static const void* ncv_fwd2_fn(int NK2, int NS, int ph0, int sw, bool with_add, 
 #undef NCV_F2
   return kfn;
 }
+// persistent grids: at most as many workgroups as are co-resident, each walks a strided range of images
+static int ncv_grid(int64_t N, int per_cu) { return (int)std::min<int64_t>(N, (int64_t)num_cus() * per_cu); }
+// a planned launch of ncv_fwd_kernel
+static void ncv_run_generic(const NcvLaunchPlan& lp, const Tensor* in, const nv_bf8* wpk, const Tensor* bias, Tensor* out, hipStream_t st) {
+  const bf16_t* srcp = in->ptr<bf16_t>();
+  const bf16_t* bp = bias ? bias->ptr<bf16_t>() : (const bf16_t*)nullptr;
+  bf16_t* dstp = out->ptr<bf16_t>();
+  void* args[] = {(void*)&srcp, (void*)&wpk, (void*)&bp, (void*)&dstp, (void*)&lp.q};
+  ncv_launch(ncv_fwd_fn(lp.NK), ncv_grid(lp.q.N, ncv_lds_per_cu(lp.lds)), 256, lp.lds, args, st);
+}
+// a planned launch of ncv_fwd2_kernel
+static void ncv_run_aligned(const NcvLaunchPlan& lp, bool dgrad, const Tensor* in, const Tensor* w, const nv_bf8* wpk, const Tensor* bias, Tensor* out,
+                            hipStream_t st, const Tensor* addend, bool* addend_fused, const NcvSibling* sib, const NcvSecondGrad* second) {
+  const NcvGeom& q = lp.q;
+  const bool with_add = addend != nullptr && q.sw == 1;
+  const bool with_stats = ncv_takes_stats(q, dgrad, addend != nullptr, sib != nullptr, w);
+  const void* kfn = ncv_fwd2_fn(lp.NK, lp.NS, lp.ph0, q.sw, with_add, with_stats, lp.nke);
+  const int blocks = ncv_grid(q.N, ncv_per_cu(kfn, lp.threads, lp.lds));
+  // one triple per workgroup where every workgroup walks the same number of images (equal counts), else one per image
+  int stats_per_wg = q.N % blocks == 0 ? 1 : 0;
+  int co_a = q.CO - (sib ? (int)sib->w->sizes[0] : 0);   // the sibling's output channels are the columns behind w's
+  NcvStats stats(with_stats, stats_per_wg ? blocks : q.N, co_a, q.CO - co_a, in->device());
+  const bf16_t* srcp = in->ptr<bf16_t>();
+  const bf16_t* src2p = second ? second->dy->ptr<bf16_t>() : (const bf16_t*)nullptr;
+  const bf16_t* bp = bias ? bias->ptr<bf16_t>() : (const bf16_t*)nullptr;
+  bf16_t* dstp = out->ptr<bf16_t>();
+  const bf16_t* addp = with_add ? addend->ptr<bf16_t>() : (const bf16_t*)nullptr;
+  if (addend_fused) *addend_fused = with_add;
+  bf16_t* dst2p = sib ? sib->out->ptr<bf16_t>() : (bf16_t*)nullptr;
+  const bf16_t* bias2p = (sib && sib->bias) ? sib->bias->ptr<bf16_t>() : (const bf16_t*)nullptr;
+  float* statp = stats.ptr();
+  float* stat2p = stats.ptr2();
+  void* args[] = {(void*)&srcp, (void*)&wpk, (void*)&bp, (void*)&dstp, (void*)&q, (void*)&addp, (void*)&dst2p, (void*)&bias2p, (void*)&co_a,
+                  (void*)&statp, (void*)&stat2p, (void*)&stats_per_wg, (void*)&src2p};
+  ncv_launch(kfn, blocks, lp.threads, lp.lds, args, st);
+  stats.publish(out, sib ? 0 : w->st->uid, sib ? sib->out : nullptr);
+}
 static bool ncv_run(const Tensor* in, const Tensor* w, const Tensor* bias, Tensor* out, const ConvGeom& g, bool dgrad, hipStream_t st,
                     const Tensor* addend = nullptr, bool* addend_fused = nullptr, const NcvSibling* sib = nullptr,
                     const NcvSecondGrad* second = nullptr) {
   if (addend_fused) *addend_fused = false;
-  const int cout2 = sib ? (int)sib->w->sizes[0] : second ? (int)second->w->sizes[0] : 0;
-  NcvLaunchPlan lp;
-  if (!ncv_plan(g, in->dtype, dgrad, sib != nullptr, second != nullptr, cout2, lp)) return false;
-  const NcvGeom& q = lp.q;
-  const bool aligned = lp.aligned;
-  const int ncg = lp.ncg, ph0 = lp.ph0, NK = lp.NK, nke = lp.nke, NS = lp.NS;
-  const size_t lds = lp.lds;
   const Tensor* wsecond = sib ? sib->w : second ? second->w : nullptr;
-  const NcvW wq = ncv_weights_of(w, g, dgrad, lp, wsecond, cout2);
-  Hold wpk_h(ncv_packed_weights(w, wq, st, wsecond));
-  const nv_bf8* wpk = reinterpret_cast<const nv_bf8*>(static_cast<const Tensor*>(wpk_h.get())->ptr<bf16_t>());
-  const int lds_per_cu = ncv_lds_per_cu(lds);
-  const bf16_t* bp = bias ? bias->ptr<bf16_t>() : (const bf16_t*)nullptr;
-  if (aligned) {
-    const int threads = lp.threads;
-    if (second && !q.pf) return false;                     // (two sources are staged through the register prefetch only)
-    if (NK > 12 && !second) return false;
-    const int NK2 = lp.NK2;
-    const bool with_add = addend != nullptr && q.sw == 1;
-    // fprop: per-image batch-norm statistics of the output(s) from the epilogue (LAMP_CONV_BN_STATS=0 turns the hand-off off)
-    const bool bn_stats = sw().conv_bn_stats && sw().ncv_bn_stats;          // (the second: the narrow kernels' alone, A/B)
-    // (a filter whose output's statistics nobody took last time - the stem of Cnn.resnet feeds res1's convolutions directly - stops paying for them)
-    const bool with_stats = bn_stats && !dgrad && !addend && g.N >= 2 && (int64_t)q.Ho * q.Wo >= 64 && (sib || conv_stats_wanted(w->st->uid));
-    const void* kfn = ncv_fwd2_fn(NK2, NS, ph0, q.sw, with_add, with_stats, nke);
-    // persistent grid: as many workgroups as are really co-resident (registers and LDS), each walks a strided range of images
-    const int per_cu = std::min(lds_per_cu, kernel_occupancy(kfn, threads, lds));
-    const int blocks = (int)std::min<int64_t>(g.N, (int64_t)num_cus() * per_cu);
-    // (the sibling's work is declared with the launch; its input is the one already counted)
-    const double sib_fl = sib ? 2.0 * (double)g.N * cout2 * (double)g.Ho * g.Wo * (double)g.Cin : 0.0;
-    const double sib_by = sib ? ((double)g.N * cout2 * g.Ho * g.Wo + (double)cout2 * g.Cin) * 2.0 : 0.0;
-    const double sec_fl = second ? 2.0 * (double)g.N * cout2 * (double)g.Ho * g.Wo * (double)g.Cin : 0.0;
-    const double sec_by = second ? ((double)g.N * cout2 * g.Ho * g.Wo + (double)cout2 * g.Cin) * 2.0 : 0.0;
-    KernelTimer kt(dgrad ? "conv_dgrad_narrow" : "conv_fwd_narrow", conv_flops(g) + sib_fl + sec_fl, conv_bytes(g, 2) + sib_by + sec_by, st);
-    const bf16_t* srcp = in->ptr<bf16_t>();
-    const bf16_t* src2p = second ? second->dy->ptr<bf16_t>() : (const bf16_t*)nullptr;
-    bf16_t* dstp = out->ptr<bf16_t>();
-    const bf16_t* addp = with_add ? addend->ptr<bf16_t>() : (const bf16_t*)nullptr;
-    if (addend_fused) *addend_fused = with_add;
-    bf16_t* dst2p = sib ? sib->out->ptr<bf16_t>() : (bf16_t*)nullptr;
-    const bf16_t* bias2p = (sib && sib->bias) ? sib->bias->ptr<bf16_t>() : (const bf16_t*)nullptr;
-    int co_a = sib ? (int)g.Cout : q.CO;
-    Hold statt, statt2;
-    float* statp = nullptr;
-    float* stat2p = nullptr;
-    // one triple per workgroup where every workgroup walks the same number of images (equal counts), else one per image
-    int stats_per_wg = g.N % blocks == 0 ? 1 : 0;
-    const int parts = stats_per_wg ? blocks : (int)g.N;
-    if (with_stats) {
-      int64_t ps[1] = {(int64_t)parts * g.Cout * 3};
-      statt = Hold(new_tensor(ps, 1, kF32, in->device()));
-      statp = statt->ptr<float>();
-      if (sib) {
-        int64_t ps2[1] = {(int64_t)parts * cout2 * 3};
-        statt2 = Hold(new_tensor(ps2, 1, kF32, in->device()));
-        stat2p = statt2->ptr<float>();
-      }
-    }
-    void* args[] = {(void*)&srcp, (void*)&wpk, (void*)&bp, (void*)&dstp, (void*)&q, (void*)&addp, (void*)&dst2p, (void*)&bias2p, (void*)&co_a,
-                    (void*)&statp, (void*)&stat2p, (void*)&stats_per_wg, (void*)&src2p};
-    HIP_CHECK(hipLaunchKernel(kfn, dim3(blocks), dim3(threads), args, lds, st));
-    LAMP_LAUNCH_CHECK();
-    if (statt.get()) conv_stats_publish(out, statt.get(), parts, sib ? 0 : w->st->uid);
-    if (statt2.get()) conv_stats_publish(sib->out, statt2.get(), parts);
-    return true;
-  }
-  if (NK > 12) return false;
-  const int blocks = (int)std::min<int64_t>(g.N, (int64_t)num_cus() * lds_per_cu);
-  KernelTimer kt(dgrad ? "conv_dgrad_narrow" : "conv_fwd_narrow", conv_flops(g), conv_bytes(g, 2), st);
-  switch (NK) {
-    case 1: ncv_launch<1>(in->ptr<bf16_t>(), wpk, bp, out->ptr<bf16_t>(), q, blocks, lds, st); break;
-    case 2: ncv_launch<2>(in->ptr<bf16_t>(), wpk, bp, out->ptr<bf16_t>(), q, blocks, lds, st); break;
-    case 4: ncv_launch<4>(in->ptr<bf16_t>(), wpk, bp, out->ptr<bf16_t>(), q, blocks, lds, st); break;
-    case 5: ncv_launch<5>(in->ptr<bf16_t>(), wpk, bp, out->ptr<bf16_t>(), q, blocks, lds, st); break;
-    case 6: case 8: ncv_launch<8>(in->ptr<bf16_t>(), wpk, bp, out->ptr<bf16_t>(), q, blocks, lds, st); break;
-    default: ncv_launch<12>(in->ptr<bf16_t>(), wpk, bp, out->ptr<bf16_t>(), q, blocks, lds, st); break;
-  }
-  LAMP_LAUNCH_CHECK();
+  const int cout2 = wsecond ? (int)wsecond->sizes[0] : 0;
+  NcvLaunchPlan lp;
+  if (!ncv_plan(g, in->dtype, dgrad, sib != nullptr, second != nullptr, cout2, false, lp)) return false;
+  Hold wpk(ncv_packed_weights(w, ncv_weights_of(w, g, dgrad, lp, wsecond, cout2), st, wsecond));
+  // (a sibling's or second gradient's work is declared with the launch)
+  KernelTimer kt(dgrad ? "conv_dgrad_narrow" : "conv_fwd_narrow", conv_flops(g) + ncv_sibling_flops(g, cout2), conv_bytes(g, 2) + ncv_sibling_bytes(g, cout2), st);
+  if (lp.aligned) ncv_run_aligned(lp, dgrad, in, w, ncv_fragments(wpk), bias, out, st, addend, addend_fused, sib, second);
+  else ncv_run_generic(lp, in, ncv_fragments(wpk), bias, out, st);
   return true;
 }
 
@@ -1390,12 +1412,7 @@ bool narrow_conv_fwd(const Tensor* x, const Tensor* w, const Tensor* bias, Tenso
 }
 // the 3x3 pad 1 + 1x1 pad 0 pairs the sibling launch is for (LAMP_CONV_SIBLING=0: none)
 static bool ncv_fwd_pair_shapes(const Tensor* x, const ConvGeom& g, const ConvGeom& g1) {
-  const bool on = sw().conv_sibling;
-  if (!on || x->dtype != kBF16) return false;
-  if (g.kh != 3 || g.kw != 3 || g.ph != 1 || g.pw != 1 || g1.kh != 1 || g1.kw != 1 || g1.ph != 0 || g1.pw != 0) return false;
-  if (g.sh != g1.sh || g.sw != g1.sw || g.Ho != g1.Ho || g.Wo != g1.Wo || g.Cin != g1.Cin || g.N != g1.N || g.groups != 1 || g1.groups != 1) return false;
-  if (g.dh != 1 || g.dw != 1 || g1.dh != 1 || g1.dw != 1) return false;
-  return true;
+  return sw().conv_sibling && x->dtype == kBF16 && ncv_pair_shapes(g, g1);
 }
 // y = conv3x3(x, w) and y1 = conv1x1(x, w1), same stride and output map (the two branches of lamp's residual block on its input,
 // cnn.scala:16-20), Cout + Cout1 <= 16: one launch, the values of the two separate ones (the second filter is the centre tap of extra
@@ -1418,50 +1435,38 @@ bool narrow_conv_chain_pair(const Tensor* x, const Tensor* w0, const Tensor* bia
   if (g0.groups != 1 || g0.sh != 1 || g0.sw != 1 || g0.N != g.N || g0.Cout != g.Cin || g0.Ho != g.H || g0.Wo != g.W) return false;
   const int cout2 = (int)w1->sizes[0];
   NcvLaunchPlan p0, p1;
-  if (!ncv_plan(g0, x->dtype, false, false, false, 0, p0) || !ncv_plan(g, x->dtype, false, true, false, cout2, p1)) return false;
+  // (x reaches the first image through the chain kernel's own register prefetch, the pair's image is written by the first convolution)
+  if (!ncv_plan(g0, x->dtype, false, false, false, 0, true, p0) || !ncv_plan(g, x->dtype, false, true, false, cout2, false, p1)) return false;
   if (!p0.aligned || !p1.aligned || p0.threads != 256 || p1.threads != 256) return false;
   if ((int64_t)p0.q.C * p0.q.H * p0.q.W > (int64_t)NCV_CHAIN_PF * 256 * 8) return false;      // (the chain kernel's register prefetch of x)
-  p0.q.pf = 1;
-  if (p0.NS != 2 || p0.NK2 != 4 || p0.ph0 != 6) return false;
-  if (p1.NS != 1 || p1.q.sw != 2 || p1.ph0 != 7 || !(p1.NK2 == 5 || p1.NK2 == 12)) return false;
+  if (p0.NS != 2 || p0.NK != 4 || p0.ph0 != 6) return false;
+  if (p1.NS != 1 || p1.q.sw != 2 || p1.ph0 != 7 || !(p1.NK == 5 || p1.NK == 12)) return false;
   const size_t lds = p0.lds + p1.lds;
-  if (lds > 150 * 1024) return false;
+  if (lds > NCV_LDS_BUDGET) return false;
   const NcvGeom& q0 = p0.q;
   const NcvGeom& q1 = p1.q;
-  const bool with_stats = sw().conv_bn_stats && sw().ncv_bn_stats && g.N >= 2 && (int64_t)q1.Ho * q1.Wo >= 64;      // as ncv_run decides for a pair
+  const bool with_stats = ncv_takes_stats(q1, false, false, true, w);
   const void* kfn = nullptr;
-  if (p1.NK2 == 5) kfn = with_stats ? (const void*)ncv_chain_kernel<4, 6, 5, 7, true> : (const void*)ncv_chain_kernel<4, 6, 5, 7, false>;
+  if (p1.NK == 5) kfn = with_stats ? (const void*)ncv_chain_kernel<4, 6, 5, 7, true> : (const void*)ncv_chain_kernel<4, 6, 5, 7, false>;
   else kfn = with_stats ? (const void*)ncv_chain_kernel<4, 6, 12, 7, true> : (const void*)ncv_chain_kernel<4, 6, 12, 7, false>;
-  if (lds > 64 * 1024) allow_big_lds(kfn);
   // the grid of the pair's own launch decides how its statistics are partitioned (per workgroup when every workgroup walks the same number
   // of images): this launch takes that grid, or a smaller one where per-image triples are what the pair's launch would have written too
-  const void* kpair = ncv_fwd2_fn(p1.NK2, 1, 7, 2, false, with_stats, 0);
-  const int pair_per_cu = std::min(ncv_lds_per_cu(p1.lds), kernel_occupancy(kpair, 256, p1.lds));
-  const int pair_blocks = (int)std::min<int64_t>(g.N, (int64_t)num_cus() * pair_per_cu);
-  const int per_cu = std::min(pair_per_cu, std::min(ncv_lds_per_cu(lds), kernel_occupancy(kfn, 256, lds)));
-  const int blocks = (int)std::min<int64_t>(g.N, (int64_t)num_cus() * per_cu);
+  const void* kpair = ncv_fwd2_fn(p1.NK, p1.NS, p1.ph0, q1.sw, false, with_stats, p1.nke);
+  const int pair_per_cu = ncv_per_cu(kpair, 256, p1.lds);
+  const int pair_blocks = ncv_grid(g.N, pair_per_cu);
+  const int blocks = ncv_grid(g.N, std::min(pair_per_cu, ncv_per_cu(kfn, 256, lds)));
   const bool pair_per_wg = g.N % pair_blocks == 0;
   if (with_stats && blocks != pair_blocks && pair_per_wg && g.N > pair_blocks) return false;
   int stats_per_wg = (blocks == pair_blocks && pair_per_wg) ? 1 : 0;
-  const int parts = stats_per_wg ? blocks : (int)g.N;
   Hold wpk0_h(ncv_packed_weights(w0, ncv_weights_of(w0, g0, false, p0, nullptr, 0), st));
   Hold wpk1_h(ncv_packed_weights(w, ncv_weights_of(w, g, false, p1, w1, cout2), st, w1));
-  const nv_bf8* wpk0 = reinterpret_cast<const nv_bf8*>(static_cast<const Tensor*>(wpk0_h.get())->ptr<bf16_t>());
-  const nv_bf8* wpk1 = reinterpret_cast<const nv_bf8*>(static_cast<const Tensor*>(wpk1_h.get())->ptr<bf16_t>());
-  Hold statt, statt2;
-  float* statp = nullptr;
-  float* stat2p = nullptr;
-  if (with_stats) {
-    int64_t ps[1] = {(int64_t)parts * g.Cout * 3}, ps2[1] = {(int64_t)parts * cout2 * 3};
-    statt = Hold(new_tensor(ps, 1, kF32, x->device()));
-    statt2 = Hold(new_tensor(ps2, 1, kF32, x->device()));
-    statp = statt->ptr<float>(); stat2p = statt2->ptr<float>();
-  }
+  const nv_bf8* wpk0 = ncv_fragments(wpk0_h);
+  const nv_bf8* wpk1 = ncv_fragments(wpk1_h);
+  NcvStats stats(with_stats, stats_per_wg ? blocks : (int)g.N, g.Cout, cout2, x->device());
   {
     // both convolutions' work and traffic, less the read of s that the LDS image replaces
-    const double fl = conv_flops(g0) + conv_flops(g) + 2.0 * (double)g.N * cout2 * (double)g.Ho * g.Wo * (double)g.Cin;
-    const double by = conv_bytes(g0, 2) + conv_bytes(g, 2) + ((double)g.N * cout2 * g.Ho * g.Wo + (double)cout2 * g.Cin) * 2.0 -
-                      (double)g.N * g.Cin * g.H * g.W * 2.0;
+    const double fl = conv_flops(g0) + conv_flops(g) + ncv_sibling_flops(g, cout2);
+    const double by = conv_bytes(g0, 2) + conv_bytes(g, 2) + ncv_sibling_bytes(g, cout2) - (double)g.N * g.Cin * g.H * g.W * 2.0;
     KernelTimer kt("conv_fwd_narrow", fl, by, st);
     const bf16_t* xp = x->ptr<bf16_t>();
     const bf16_t* b0p = bias0 ? bias0->ptr<bf16_t>() : (const bf16_t*)nullptr;
@@ -1471,13 +1476,13 @@ bool narrow_conv_chain_pair(const Tensor* x, const Tensor* w0, const Tensor* bia
     bf16_t* yp = y->ptr<bf16_t>();
     bf16_t* y1p = y1->ptr<bf16_t>();
     int co_a = (int)g.Cout;
+    float* statp = stats.ptr();
+    float* stat2p = stats.ptr2();
     void* args[] = {(void*)&xp, (void*)&wpk0, (void*)&b0p, (void*)&sp, (void*)&q0, (void*)&wpk1, (void*)&bp, (void*)&b1p, (void*)&yp, (void*)&y1p,
                     (void*)&co_a, (void*)&q1, (void*)&statp, (void*)&stat2p, (void*)&stats_per_wg};
-    HIP_CHECK(hipLaunchKernel(kfn, dim3(blocks), dim3(256), args, lds, st));
-    LAMP_LAUNCH_CHECK();
+    ncv_launch(kfn, blocks, 256, lds, args, st);
   }
-  if (statt.get()) conv_stats_publish(y, statt.get(), parts, 0);
-  if (statt2.get()) conv_stats_publish(y1, statt2.get(), parts);
+  stats.publish(y, 0, y1);
   return true;
 }
 bool narrow_conv_dgrad(const Tensor* dy, const Tensor* w, Tensor* dx, const ConvGeom& g, hipStream_t st, const Tensor* addend, bool* addend_fused) {
@@ -1490,22 +1495,24 @@ bool narrow_conv_dgrad(const Tensor* dy, const Tensor* w, Tensor* dx, const Conv
 bool narrow_conv_dgrad_pair(const Tensor* dy, const Tensor* w, const ConvGeom& g, const Tensor* dy1, const Tensor* w1, const ConvGeom& g1, Tensor* dx,
                             hipStream_t st, const Tensor* addend, bool* addend_fused) {
   if (addend_fused) *addend_fused = false;
-  const bool on = sw().conv_dgrad_pair;
-  if (!on || dy->dtype != kBF16 || dy1->dtype != kBF16) return false;
-  if (g.kh != 3 || g.kw != 3 || g.ph != 1 || g.pw != 1 || g1.kh != 1 || g1.kw != 1 || g1.ph != 0 || g1.pw != 0) return false;
-  if (g.sh != g1.sh || g.sw != g1.sw || g.Ho != g1.Ho || g.Wo != g1.Wo || g.H != g1.H || g.W != g1.W || g.Cin != g1.Cin || g.N != g1.N) return false;
-  if (g.groups != 1 || g1.groups != 1 || g.dh != 1 || g.dw != 1 || g1.dh != 1 || g1.dw != 1 || g1.Cout > 16) return false;
+  if (!sw().conv_dgrad_pair || dy->dtype != kBF16 || dy1->dtype != kBF16) return false;
+  if (!ncv_pair_shapes(g, g1) || g1.Cout > 16) return false;
   const NcvSecondGrad sg{dy1, w1};
   return ncv_run(dy, w, nullptr, dx, g, true, st, addend, addend_fused, nullptr, &sg);
 }
 
-template <int NT, int SW>
-static void ncv_wg_launch(const bf16_t* dy, const bf16_t* x, float* partial, const NcvWGeom& q, int ipb, int blocks, size_t lds, hipStream_t st) {
-  static bool attr = false;
-  allow_big_lds((const void*)ncv_wgrad_kernel<NT, SW>);
-  hipLaunchKernelGGL((ncv_wgrad_kernel<NT, SW>), dim3(blocks), dim3(256), lds, st, dy, x, partial, q, ipb);
+// the instantiation of ncv_wgrad_kernel for (16-column tiles of the Cin x kh x kw filter columns, stride)
+static const void* ncv_wgrad_fn(int NT, int SW) {
+#define NCV_WG(NTv) return SW == 1 ? (const void*)ncv_wgrad_kernel<NTv, 1> : (const void*)ncv_wgrad_kernel<NTv, 2>
+  switch (NT) {
+    case 1: NCV_WG(1);
+    case 2: NCV_WG(2);
+    case 4: NCV_WG(4);
+    case 5: NCV_WG(5);
+    default: NCV_WG(9);
+  }
+#undef NCV_WG
 }
-
 // the instantiation of ncv_wgrad2_kernel for (filter width, stride, pair tiles)
 static const void* ncv_wgrad2_fn(int kw, int SW, int npt) {
   const void* kfn = nullptr;
@@ -1520,154 +1527,110 @@ static const void* ncv_wgrad2_fn(int kw, int SW, int npt) {
 #undef NCV_WG2
   return kfn;
 }
-// workgroups per CU of an aligned weight-gradient launch (LDS and registers), and the partition of N images in rounds of IG over the
-// workgroups that are co-resident then: the number of workgroups, ipb = images per workgroup
-static int ncv_wgrad2_per_cu(const void* kfn, int threads, size_t lds) {
-  return std::min((int)std::max<size_t>(1, std::min<size_t>(4, (size_t)(150 * 1024) / lds)), kernel_occupancy(kfn, threads, lds));
-}
+// the partition of N images in rounds of IG over at most per_cu workgroups per CU: the number of workgroups, ipb = images per workgroup
 static int ncv_partition(int per_cu, int64_t N, int IG, int& ipb) {
   const int64_t rounds = (N + IG - 1) / IG;
   const int nb = (int)std::min<int64_t>(rounds, (int64_t)num_cus() * per_cu);
   ipb = (int)((rounds + nb - 1) / nb) * IG;
   return (int)((N + ipb - 1) / ipb);
 }
-static int ncv_wgrad2_partition(const void* kfn, size_t lds, int64_t N, int IG, int& ipb) { return ncv_partition(ncv_wgrad2_per_cu(kfn, 256, lds), N, IG, ipb); }
-// the aligned kernel's staged geometry (x parity planes / rows at column NCV_OFFA); returns the pair tiles
-static int ncv_wgrad2_geom(const ConvGeom& g, int cout2, NcvWGeom& q) {
+// One weight-gradient launch: the staged geometry, the kernel, its LDS and the partition of the images over the workgroups.
+struct NcvWgradPlan {
+  NcvWGeom q;
+  const void* kfn;
+  int npt;               // aligned-read form: pair tiles
+  size_t lds;
+  int nblocks, ipb;      // workgroups, images per workgroup
+};
+// The form of a geometry's weight-gradient launch, without its partition.  aligned: ncv_wgrad2_kernel, for the filter shapes of the CIFAR ResNet
+// (x parity planes / rows at column NCV_OFFA; it alone takes a sibling's cout2 gradient rows); else ncv_wgrad_kernel.  The two stage x alike but
+// for the row pitch.  false: the geometry has no such form
+static bool ncv_wgrad_form(const ConvGeom& g, int dtype, int cout2, bool aligned, NcvWgradPlan& wp) {
+  if (!ncv_common(g, dtype)) return false;
+  if (g.W % 8 != 0 || g.Wo % 8 != 0 || (g.Ho * g.Wo) % 32 != 0) return false;
+  NcvWGeom& q = wp.q;
   q.N = (int)g.N; q.Cin = (int)g.Cin; q.Cout = (int)g.Cout; q.H = (int)g.H; q.W = (int)g.W; q.Ho = (int)g.Ho; q.Wo = (int)g.Wo;
   q.kh = g.kh; q.kw = g.kw; q.ph = g.ph; q.pw = g.pw; q.Cout2 = cout2;
   q.ncol = (int)g.Cin * g.kh * g.kw;
   q.Hs = std::max((int)g.H + 2 * g.ph, ((int)g.Ho - 1) * g.sh + g.kh);
-  if (g.sh == 1) q.Ws = round_up(NCV_OFFA + std::max((int)g.W, (int)g.Wo + 8) + 8, 8);
-  else q.Ws = round_up(NCV_OFFA + std::max((int)g.W / 2, (int)g.Wo) + 8, 8);
-  q.IG = std::max(1, 256 / (int)(g.Ho * g.Wo));                      // >= 8 chunks of 32 pixels per round
-  return (int)((g.Cin * g.kh + 15) / 16);
+  const int SW = g.sh, HoWo = (int)(g.Ho * g.Wo);
+  q.IG = std::max(1, 256 / HoWo);                                    // >= 8 chunks of 32 pixels per round
+  int red_cols = 0;                                                  // columns of the four waves' 16-row sums
+  if (aligned) {
+    wp.npt = (int)((g.Cin * g.kh + 15) / 16);
+    if (!(g.kh == g.kw && wp.npt <= 3 && ((g.kw == 5 && g.pw == 2 && SW == 1) || (g.kw == 3 && g.pw == 1) || (g.kw == 1 && g.pw == 0)))) return false;
+    q.Ws = SW == 1 ? round_up(NCV_OFFA + std::max((int)g.W, (int)g.Wo + 8) + 8, 8) : round_up(NCV_OFFA + std::max((int)g.W / 2, (int)g.Wo) + 8, 8);
+    wp.kfn = ncv_wgrad2_fn(g.kw, SW, wp.npt);
+    red_cols = wp.npt * g.kw * 16;
+  } else {
+    if (cout2 > 0) return false;
+    const int nt_real = (q.ncol + 15) / 16;
+    static const int nt_opts[] = {1, 2, 4, 5, 9};
+    int NT = 0;
+    for (int o : nt_opts) if (o >= nt_real) { NT = o; break; }
+    if (!NT) return false;
+    const int half_max = (g.kw - 1 - g.pw) >> 1;
+    q.Ws = SW == 1 ? round_up(std::max(NCV_LEFT + (int)g.W, (int)g.Wo - 1 + g.kw - 1 - g.pw + NCV_LEFT + 1), 8)
+                   : round_up(std::max((int)g.W / 2, (int)g.Wo + half_max) + NCV_OFF2 + 1, 8);
+    wp.kfn = ncv_wgrad_fn(NT, SW);
+    red_cols = NT * 16;
+  }
+  const int ximg = q.Cin * q.Hs * q.Ws * (SW == 2 ? 2 : 1);
+  if (!aligned && (q.IG * (ximg + 16 * HoWo)) % 8 != 0) return false;
+  wp.lds = (size_t)q.IG * (ximg + 16 * HoWo) * 2 + (size_t)4 * 16 * red_cols * 4;
+  return true;
+}
+// The planned launch in that form: a workgroup's images fit the LDS, and the N images go in rounds of IG over the workgroups that are
+// co-resident.  The partition fixes the order of the partial sums, and with it the bits of dw: the aligned form counts the workgroups that
+// LDS and registers allow, the generic form those the LDS allows.
+static bool ncv_wgrad_plan(const ConvGeom& g, int dtype, int cout2, bool aligned, NcvWgradPlan& wp) {
+  if (!ncv_wgrad_form(g, dtype, cout2, aligned, wp) || wp.lds > NCV_LDS_BUDGET) return false;
+  const int per_cu = aligned ? ncv_per_cu(wp.kfn, 256, wp.lds) : ncv_lds_per_cu(wp.lds);
+  wp.nblocks = ncv_partition(per_cu, g.N, wp.q.IG, wp.ipb);
+  return true;
 }
 // second (optional): the output gradient of a sibling 1x1 convolution of the same x and ITS weight gradient: both from the one launch of the
 // aligned kernel (false, nothing launched, when that kernel does not take the pair)
 struct NcvSecondWgrad { const Tensor* dy; Tensor* dw; };
+static void ncv_wgrad_launch(const NcvWgradPlan& wp, const ConvGeom& g, const Tensor* dy, const Tensor* x, Tensor* dw, const NcvSecondWgrad* second,
+                             hipStream_t st) {
+  const NcvWGeom& q = wp.q;
+  const int O = q.Cout * q.ncol, O2 = q.Cout2 * q.Cin;
+  Hold partial(new_tensor({(int64_t)wp.nblocks * O}, kF32, dy->device()));
+  Hold partial2(second ? new_tensor({(int64_t)wp.nblocks * O2}, kF32, dy->device()) : nullptr);
+  {
+    // (the sibling's work is declared with the launch; x is the one already counted)
+    KernelTimer kt("conv_wgrad_narrow", conv_flops(g) + ncv_sibling_flops(g, q.Cout2), conv_bytes(g, 2) + ncv_sibling_bytes(g, q.Cout2), st);
+    const bf16_t* dp = dy->ptr<bf16_t>(); const bf16_t* xp = x->ptr<bf16_t>(); float* pp = partial->ptr<float>();
+    const bf16_t* dp2 = second ? second->dy->ptr<bf16_t>() : (const bf16_t*)nullptr;
+    float* pp2 = second ? partial2->ptr<float>() : (float*)nullptr;
+    int ipb = wp.ipb;
+    void* args[] = {(void*)&dp, (void*)&xp, (void*)&pp, (void*)&q, (void*)&ipb, (void*)&dp2, (void*)&pp2};      // (ncv_wgrad_kernel: the first five)
+    ncv_launch(wp.kfn, wp.nblocks, 256, wp.lds, args, st);
+  }
+  wgrad_reduce_flat(O, wp.nblocks, partial.get(), dw, st);
+  if (second) wgrad_reduce_flat(O2, wp.nblocks, partial2.get(), second->dw, st);
+}
 static bool ncv_wgrad_run(const Tensor* dy, const Tensor* x, Tensor* dw, const ConvGeom& g, hipStream_t st, const NcvSecondWgrad* second) {
-  if (!ncv_common(g, x->dtype)) return false;
-  if (g.W % 8 != 0 || g.Wo % 8 != 0 || (g.Ho * g.Wo) % 32 != 0) return false;
   const int cout2 = second ? (int)second->dy->sizes[1] : 0;
   if (second && (g.Cout + cout2 > 16 || g.kh != 3 || g.kw != 3 || g.ph != 1 || g.pw != 1)) return false;
-  NcvWGeom q;
-  q.N = (int)g.N; q.Cin = (int)g.Cin; q.Cout = (int)g.Cout; q.H = (int)g.H; q.W = (int)g.W; q.Ho = (int)g.Ho; q.Wo = (int)g.Wo;
-  q.kh = g.kh; q.kw = g.kw; q.ph = g.ph; q.pw = g.pw; q.Cout2 = cout2;
-  q.ncol = (int)g.Cin * g.kh * g.kw;
-  const int SW = g.sh;
-  q.Hs = std::max((int)g.H + 2 * g.ph, ((int)g.Ho - 1) * g.sh + g.kh);
-  if (SW == 1) q.Ws = round_up(std::max(NCV_LEFT + (int)g.W, (int)g.Wo - 1 + g.kw - 1 - g.pw + NCV_LEFT + 1), 8);
-  else {
-    const int half_max = (g.kw - 1 - g.pw) >> 1;
-    q.Ws = round_up(std::max((int)g.W / 2, (int)g.Wo + half_max) + NCV_OFF2 + 1, 8);
-  }
-  const int HoWo = (int)(g.Ho * g.Wo);
-  q.IG = std::max(1, 256 / HoWo);                                    // >= 8 chunks of 32 pixels per round
-  // aligned-read kernel for the filter shapes of the CIFAR ResNet
-  const int npt = (int)((g.Cin * g.kh + 15) / 16);
-  const bool aligned = g.kh == g.kw && npt <= 3 &&
-                       ((g.kw == 5 && g.pw == 2 && SW == 1) || (g.kw == 3 && g.pw == 1) || (g.kw == 1 && g.pw == 0));
-  if (aligned) {
-    ncv_wgrad2_geom(g, cout2, q);
-    const int ximg2 = q.Cin * q.Hs * q.Ws * (SW == 2 ? 2 : 1);
-    const int ncolt = npt * g.kw * 16;
-    const size_t lds2 = (size_t)q.IG * (ximg2 + 16 * HoWo) * 2 + (size_t)4 * 16 * ncolt * 4;
-    if (lds2 <= 150 * 1024) {
-      const int O = q.Cout * q.ncol;
-      const void* kfn = ncv_wgrad2_fn(g.kw, SW, npt);
-      allow_big_lds(kfn);
-      int ipb = 0;
-      const int nblocks = ncv_wgrad2_partition(kfn, lds2, g.N, q.IG, ipb);
-      int64_t ps[1] = {(int64_t)nblocks * O};
-      Hold partial(new_tensor(ps, 1, kF32, dy->device()));
-      const int O2 = cout2 * q.Cin;
-      Hold partial2;
-      if (second) { int64_t ps2[1] = {(int64_t)nblocks * O2}; partial2 = Hold(new_tensor(ps2, 1, kF32, dy->device())); }
-      {
-        // (the sibling's work is declared with the launch; x is the one already counted)
-        const double sec_fl = second ? 2.0 * (double)g.N * cout2 * (double)g.Ho * g.Wo * (double)g.Cin : 0.0;
-        const double sec_by = second ? ((double)g.N * cout2 * g.Ho * g.Wo + (double)cout2 * g.Cin) * 2.0 : 0.0;
-        KernelTimer kt("conv_wgrad_narrow", conv_flops(g) + sec_fl, conv_bytes(g, 2) + sec_by, st);
-        const bf16_t* dp = dy->ptr<bf16_t>(); const bf16_t* xp = x->ptr<bf16_t>(); float* pp = partial->ptr<float>();
-        const bf16_t* dp2 = second ? second->dy->ptr<bf16_t>() : (const bf16_t*)nullptr;
-        float* pp2 = second ? partial2->ptr<float>() : (float*)nullptr;
-        int ipb_arg = ipb;
-        void* args[] = {(void*)&dp, (void*)&xp, (void*)&pp, (void*)&q, (void*)&ipb_arg, (void*)&dp2, (void*)&pp2};
-        HIP_CHECK(hipLaunchKernel(kfn, dim3(nblocks), dim3(256), args, lds2, st));
-        LAMP_LAUNCH_CHECK();
-      }
-      WgradReduceArgs ra{};
-      ra.kind = 1; ra.O = O; ra.nsplit = nblocks; ra.blocks = (int)(((int64_t)O * 64 + 255) / 256);
-      wgrad_reduce_enqueue(ra, partial.get(), dw, st);
-      if (second) {
-        WgradReduceArgs rb{};
-        rb.kind = 1; rb.O = O2; rb.nsplit = nblocks; rb.blocks = (int)(((int64_t)O2 * 64 + 255) / 256);
-        wgrad_reduce_enqueue(rb, partial2.get(), second->dw, st);
-      }
-      return true;
-    }
-    if (second) return false;
-    // does not fit: restore the geometry of the generic kernel
-    if (SW == 1) q.Ws = round_up(std::max(NCV_LEFT + (int)g.W, (int)g.Wo - 1 + g.kw - 1 - g.pw + NCV_LEFT + 1), 8);
-    else { const int half_max = (g.kw - 1 - g.pw) >> 1; q.Ws = round_up(std::max((int)g.W / 2, (int)g.Wo + half_max) + NCV_OFF2 + 1, 8); }
-  }
-  if (second) return false;
-  const int nt_real = (q.ncol + 15) / 16;
-  static const int nt_opts[] = {1, 2, 4, 5, 9};
-  int NT = 0;
-  for (int o : nt_opts) if (o >= nt_real) { NT = o; break; }
-  if (!NT) return false;
-  const int ximg = q.Cin * q.Hs * q.Ws * (SW == 2 ? 2 : 1);
-  if ((q.IG * (ximg + 16 * HoWo)) % 8 != 0) return false;
-  const size_t lds = (size_t)q.IG * (ximg + 16 * HoWo) * 2 + (size_t)4 * 16 * NT * 16 * 4;
-  if (lds > 150 * 1024) return false;
-  const int O = q.Cout * q.ncol;
-  const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (size_t)(150 * 1024) / lds));
-  const int64_t rounds = (g.N + q.IG - 1) / q.IG;
-  const int nb = (int)std::min<int64_t>(rounds, (int64_t)num_cus() * per_cu);
-  const int ipb = (int)((rounds + nb - 1) / nb) * q.IG;
-  const int nblocks = (int)((g.N + ipb - 1) / ipb);
-  int64_t ps[1] = {(int64_t)nblocks * O};
-  Hold partial(new_tensor(ps, 1, kF32, dy->device()));
-  {
-    KernelTimer kt("conv_wgrad_narrow", conv_flops(g), conv_bytes(g, 2), st);
-    const bf16_t* dp = dy->ptr<bf16_t>(); const bf16_t* xp = x->ptr<bf16_t>(); float* pp = partial->ptr<float>();
-#define NCV_WG(NTv)                                                                                          \
-  do {                                                                                                       \
-    if (SW == 1) ncv_wg_launch<NTv, 1>(dp, xp, pp, q, ipb, nblocks, lds, st);                                \
-    else ncv_wg_launch<NTv, 2>(dp, xp, pp, q, ipb, nblocks, lds, st);                                        \
-  } while (0)
-    switch (NT) {
-      case 1: NCV_WG(1); break;
-      case 2: NCV_WG(2); break;
-      case 4: NCV_WG(4); break;
-      case 5: NCV_WG(5); break;
-      default: NCV_WG(9); break;
-    }
-#undef NCV_WG
-    LAMP_LAUNCH_CHECK();
-  }
-  WgradReduceArgs ra{};
-  ra.kind = 1; ra.O = O; ra.nsplit = nblocks; ra.blocks = (int)(((int64_t)O * 64 + 255) / 256);
-  wgrad_reduce_enqueue(ra, partial.get(), dw, st);
+  NcvWgradPlan wp;
+  if (!ncv_wgrad_plan(g, x->dtype, cout2, true, wp) && !ncv_wgrad_plan(g, x->dtype, cout2, false, wp)) return false;
+  ncv_wgrad_launch(wp, g, dy, x, dw, second, st);
   return true;
 }
+
 
 bool narrow_conv_wgrad(const Tensor* dy, const Tensor* x, Tensor* dw, const ConvGeom& g, hipStream_t st) { return ncv_wgrad_run(dy, x, dw, g, st, nullptr); }
 // dw = wgrad3x3(dy, x) and dw1 = wgrad1x1(dy1, x) - the weight gradients of the two convolutions lamp's residual block applies to its input
 // (cnn.scala:16-20) - from one launch that stages x once: the values of the two separate launches (the second gradient tensor rides in the
 // spare rows of the MFMA tile, its weight gradient is the centre tap of those rows); false = nothing launched
 bool narrow_conv_wgrad_pair(const Tensor* dy, const Tensor* dy1, const Tensor* x, Tensor* dw, Tensor* dw1, const ConvGeom& g, const ConvGeom& g1, hipStream_t st) {
-  const bool on = sw().conv_wgrad_pair;
-  if (!on || x->dtype != kBF16 || dy->dtype != kBF16 || dy1->dtype != kBF16) return false;
-  if (g1.kh != 1 || g1.kw != 1 || g1.ph != 0 || g1.pw != 0) return false;
-  if (g.sh != g1.sh || g.sw != g1.sw || g.Ho != g1.Ho || g.Wo != g1.Wo || g.H != g1.H || g.W != g1.W || g.Cin != g1.Cin || g.N != g1.N) return false;
-  if (g.groups != 1 || g1.groups != 1 || g.dh != 1 || g.dw != 1 || g1.dh != 1 || g1.dw != 1) return false;
-  const NcvSecondWgrad sw{dy1, dw1};
-  return ncv_wgrad_run(dy, x, dw, g, st, &sw);
+  if (!sw().conv_wgrad_pair || x->dtype != kBF16 || dy->dtype != kBF16 || dy1->dtype != kBF16) return false;
+  if (!ncv_pair_shapes(g, g1)) return false;
+  const NcvSecondWgrad sg{dy1, dw1};
+  return ncv_wgrad_run(dy, x, dw, g, st, &sg);
 }
-
 
 // dx, dw and dw1 of a block's 3x3 pad 1 + 1x1 pad 0 stride-2 pair from ONE launch of ncv_bwd_pair_kernel: the values of narrow_conv_dgrad_pair
 // and of the weight-gradient launches (narrow_conv_wgrad_pair, or two narrow_conv_wgrad where the two gradients do not share the 16 MFMA rows).
@@ -1678,22 +1641,19 @@ bool narrow_conv_backward_pair(const Tensor* dy, const Tensor* dy1, const Tensor
                                Tensor* dx, Tensor* dw, Tensor* dw1, hipStream_t st, const Tensor* addend) {
   if (!sw().conv_bwd_pair || !sw().conv_dgrad_pair || !sw().conv_wgrad_pair) return false;
   if (x->dtype != kBF16 || dy->dtype != kBF16 || dy1->dtype != kBF16 || w->dtype != kBF16 || w1->dtype != kBF16) return false;
-  if (g.kh != 3 || g.kw != 3 || g.ph != 1 || g.pw != 1 || g1.kh != 1 || g1.kw != 1 || g1.ph != 0 || g1.pw != 0) return false;
-  if (g.sh != 2 || g.sw != 2 || g1.sh != 2 || g1.sw != 2 || g.Ho != g1.Ho || g.Wo != g1.Wo || g.H != g1.H || g.W != g1.W || g.Cin != g1.Cin || g.N != g1.N) return false;
-  if (g.groups != 1 || g1.groups != 1 || g.dh != 1 || g.dw != 1 || g1.dh != 1 || g1.dw != 1 || g1.Cout > 16) return false;
-  if (g.W % 8 != 0 || g.Wo % 8 != 0 || (g.Ho * g.Wo) % 32 != 0) return false;
+  if (!ncv_pair_shapes(g, g1) || g.sh != 2 || g.sw != 2 || g1.Cout > 16) return false;
   const int cout2 = (int)g1.Cout;
-  // the input gradient: the plan of narrow_conv_dgrad_pair
+  // the input gradient: the plan of narrow_conv_dgrad_pair, staged through this kernel's image-group prefetch (its fit is checked below)
   NcvLaunchPlan lp;
-  if (!ncv_plan(g, x->dtype, true, false, true, cout2, lp)) return false;
+  if (!ncv_plan(g, x->dtype, true, false, true, cout2, true, lp)) return false;
   if (!lp.aligned || lp.nke <= 0 || lp.NS != 2 || lp.ph0 != 7 || lp.q.sw != 1 || lp.q.W % 8 != 0) return false;
-  if (!(lp.NK2 == 6 || lp.NK2 == 8 || lp.NK2 == 16)) return false;
-  NcvGeom qd = lp.q;
-  qd.pf = 1;
-  // the weight gradients: the geometry of ncv_wgrad2_kernel<3, 1, 2, .>
+  if (!(lp.NK == 6 || lp.NK == 8 || lp.NK == 16)) return false;
+  const NcvGeom& qd = lp.q;
+  // the weight gradients: the geometry of ncv_wgrad2_kernel<3, 1, 2, .>, the reference launch whose partition this one takes
   const bool w2 = g.Cout + cout2 > 16;
-  NcvWGeom q;
-  if (ncv_wgrad2_geom(g, cout2, q) != 2) return false;
+  NcvWgradPlan ref;
+  if (!ncv_wgrad_form(g, x->dtype, cout2, true, ref) || ref.npt != 2) return false;
+  NcvWGeom q = ref.q;
   const int HoWo = q.Ho * q.Wo, cpi = HoWo >> 5;
   const int ximg = q.Cin * q.Hs * q.Ws * 2, drows = w2 ? 32 : 16;
   const int ncolt = 2 * 3 * 16;
@@ -1701,10 +1661,9 @@ bool narrow_conv_backward_pair(const Tensor* dy, const Tensor* dy1, const Tensor
   auto lds_of = [&](int IG) { return (size_t)IG * (ximg + drows * HoWo) * 2 + std::max(lp.lds, red_bytes); };
   // the reference launch's rounds decide the partition; this kernel's rounds may be shorter (a wave meets the same chunks in the same order
   // as long as a round is a multiple of four chunks), which is what lets two workgroups share a CU beside the dilated image
-  const int IG_ref = q.IG;
-  while (lds_of(q.IG) * 2 > 150 * 1024 && q.IG % 2 == 0 && ((q.IG / 2) * cpi) % 4 == 0) q.IG /= 2;
+  while (lds_of(q.IG) * 2 > NCV_LDS_BUDGET && q.IG % 2 == 0 && ((q.IG / 2) * cpi) % 4 == 0) q.IG /= 2;
   const size_t lds = lds_of(q.IG);
-  if (lds > 150 * 1024) return false;
+  if (lds > NCV_LDS_BUDGET) return false;
   const int per = (q.Cin * q.H * q.W + (q.Cout + cout2) * HoWo) >> 3;
   if (q.IG * per > NCV_WPF * 256) return false;                      // (the kernel stages through the register prefetch only)
   const int threads = 256;
@@ -1713,45 +1672,32 @@ bool narrow_conv_backward_pair(const Tensor* dy, const Tensor* dy1, const Tensor
   // (the 16-k-step forms hold four packets per thread: with six their registers do not fit two workgroups per CU)
   const void* kfn = nullptr;
 #define NCV_BP(NKv, W2v, WPFv) kfn = with_add ? (const void*)ncv_bwd_pair_kernel<NKv, true, 2, W2v, WPFv> : (const void*)ncv_bwd_pair_kernel<NKv, false, 2, W2v, WPFv>
-  if (lp.NK2 == 6 && !w2) NCV_BP(6, false, NCV_WPF);
-  else if (lp.NK2 == 8 && !w2) NCV_BP(8, false, NCV_WPF);
-  else if (lp.NK2 == 16 && q.IG * per <= 4 * 256) { if (w2) NCV_BP(16, true, 4); else NCV_BP(16, false, 4); }
+  if (lp.NK == 6 && !w2) NCV_BP(6, false, NCV_WPF);
+  else if (lp.NK == 8 && !w2) NCV_BP(8, false, NCV_WPF);
+  else if (lp.NK == 16 && q.IG * per <= 4 * 256) { if (w2) NCV_BP(16, true, 4); else NCV_BP(16, false, 4); }
   else return false;
 #undef NCV_BP
-  allow_big_lds(kfn);
-  // the partition of the 3x3 weight gradient's own launch, unless fewer of these workgroups fit a CU
-  const void* kref = ncv_wgrad2_fn(3, 2, 2);
-  const size_t lds_ref = (size_t)IG_ref * (ximg + 16 * HoWo) * 2 + (size_t)4 * 16 * ncolt * 4;
-  const int per_cu = std::min(ncv_wgrad2_per_cu(kref, 256, lds_ref), ncv_wgrad2_per_cu(kfn, threads, lds));
+  // the partition of the 3x3 weight gradient's own launch (its rounds, its workgroups per CU), unless fewer of these workgroups fit a CU
+  const int per_cu = std::min(ncv_per_cu(ref.kfn, 256, ref.lds), ncv_per_cu(kfn, threads, lds));
   int ipb = 0;
-  const int nblocks = ncv_partition(per_cu, g.N, IG_ref, ipb);
-  const NcvW wq = ncv_weights_of(w, g, true, lp, w1, cout2);
-  Hold wpk_h(ncv_packed_weights(w, wq, st, w1));
-  const nv_bf8* wpk = reinterpret_cast<const nv_bf8*>(static_cast<const Tensor*>(wpk_h.get())->ptr<bf16_t>());
+  const int nblocks = ncv_partition(per_cu, g.N, ref.q.IG, ipb);
+  Hold wpk_h(ncv_packed_weights(w, ncv_weights_of(w, g, true, lp, w1, cout2), st, w1));
+  const nv_bf8* wpk = ncv_fragments(wpk_h);
   const int O = q.Cout * q.ncol, O2 = cout2 * q.Cin;
-  int64_t ps[1] = {(int64_t)nblocks * O}, ps2[1] = {(int64_t)nblocks * O2};
-  Hold partial(new_tensor(ps, 1, kF32, dy->device())), partial2(new_tensor(ps2, 1, kF32, dy->device()));
+  Hold partial(new_tensor({(int64_t)nblocks * O}, kF32, dy->device())), partial2(new_tensor({(int64_t)nblocks * O2}, kF32, dy->device()));
   {
     // the three parts' work and traffic, less the second read of the two gradients
     const double dy_by = (double)g.N * (g.Cout + cout2) * HoWo * 2.0;
-    const double pair_fl = 2.0 * (double)g.N * cout2 * (double)g.Ho * g.Wo * (double)g.Cin;
-    const double pair_by = ((double)g.N * cout2 * g.Ho * g.Wo + (double)cout2 * g.Cin) * 2.0;
-    KernelTimer kt("conv_bwd_narrow", 2.0 * (conv_flops(g) + pair_fl), 2.0 * (conv_bytes(g, 2) + pair_by) - dy_by, st);
+    KernelTimer kt("conv_bwd_narrow", 2.0 * (conv_flops(g) + ncv_sibling_flops(g, cout2)), 2.0 * (conv_bytes(g, 2) + ncv_sibling_bytes(g, cout2)) - dy_by, st);
     const bf16_t* dp = dy->ptr<bf16_t>(); const bf16_t* dp2 = dy1->ptr<bf16_t>(); const bf16_t* xp = x->ptr<bf16_t>();
     bf16_t* dxp = dx->ptr<bf16_t>();
     const bf16_t* addp = with_add ? addend->ptr<bf16_t>() : (const bf16_t*)nullptr;
     float* pp = partial->ptr<float>(); float* pp2 = partial2->ptr<float>();
-    int ipb_arg = ipb;
-    void* args[] = {(void*)&dp, (void*)&dp2, (void*)&xp, (void*)&wpk, (void*)&dxp, (void*)&addp, (void*)&pp, (void*)&pp2, (void*)&q, (void*)&qd, (void*)&ipb_arg};
-    HIP_CHECK(hipLaunchKernel(kfn, dim3(nblocks), dim3(threads), args, lds, st));
-    LAMP_LAUNCH_CHECK();
+    void* args[] = {(void*)&dp, (void*)&dp2, (void*)&xp, (void*)&wpk, (void*)&dxp, (void*)&addp, (void*)&pp, (void*)&pp2, (void*)&q, (void*)&qd, (void*)&ipb};
+    ncv_launch(kfn, nblocks, threads, lds, args, st);
   }
-  WgradReduceArgs ra{};
-  ra.kind = 1; ra.O = O; ra.nsplit = nblocks; ra.blocks = (int)(((int64_t)O * 64 + 255) / 256);
-  wgrad_reduce_enqueue(ra, partial.get(), dw, st);
-  WgradReduceArgs rb{};
-  rb.kind = 1; rb.O = O2; rb.nsplit = nblocks; rb.blocks = (int)(((int64_t)O2 * 64 + 255) / 256);
-  wgrad_reduce_enqueue(rb, partial2.get(), dw1, st);
+  wgrad_reduce_flat(O, nblocks, partial.get(), dw, st);
+  wgrad_reduce_flat(O2, nblocks, partial2.get(), dw1, st);
   return true;
 }
 

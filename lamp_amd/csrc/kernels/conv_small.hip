@@ -540,10 +540,7 @@ template <class T> static bool cs_wgrad_run(const Tensor* dy, const Tensor* x, T
   // the per-block sums join the backward pass's batched reduction (wgrad_reduce.hip: one launch for every layer's partial sums; the same
   // lanes-over-blocks + butterfly order as cs_wgrad_reduce_kernel, so the same bits) - seven ~5 us launches of the f32 ResNet step
   if (std::is_same<T, float>::value || std::is_same<T, bf16_t>::value) {
-    WgradReduceArgs ra{};
-    ra.kind = 1; ra.O = O; ra.nsplit = nblocks; ra.blocks = (int)(((int64_t)O * 64 + 255) / 256);
-    ra.dw_f32 = std::is_same<T, float>::value ? 1 : 0;
-    wgrad_reduce_enqueue(ra, partial.get(), dw, st);
+    wgrad_reduce_flat(O, nblocks, partial.get(), dw, st, std::is_same<T, float>::value);
     return true;
   }
   hipLaunchKernelGGL((cs_wgrad_reduce_kernel<T, A>), dim3((unsigned)(((int64_t)O * 64 + 255) / 256)), dim3(256), 0, st, partial->ptr<A>(), dw->ptr<T>(), O, nblocks);
@@ -680,10 +677,7 @@ template <class T> static bool cs2_wgrad_run(const Tensor* dy, const Tensor* x, 
     LAMP_LAUNCH_CHECK();
   }
   if (std::is_same<T, float>::value) {
-    WgradReduceArgs ra{};
-    ra.kind = 1; ra.O = O; ra.nsplit = nblocks; ra.blocks = (int)(((int64_t)O * 64 + 255) / 256);
-    ra.dw_f32 = 1;
-    wgrad_reduce_enqueue(ra, partial.get(), dw, st);
+    wgrad_reduce_flat(O, nblocks, partial.get(), dw, st, true);
     return true;
   }
   hipLaunchKernelGGL((cs_wgrad_reduce_kernel<T, A>), dim3((unsigned)(((int64_t)O * 64 + 255) / 256)), dim3(256), 0, st, partial->ptr<A>(), dw->ptr<T>(), O, nblocks);

@@ -76,6 +76,8 @@ __device__ __forceinline__ void wgrad_reduce_narrow(const WgradReduceArgs& a, in
 // pending one at the owner's next flush_deferred() - the end of backprop - or the moment anything asks for a pointer into dw's storage
 // (Tensor::raw()), whichever comes first.  LAMP_DEFER_WGRAD_REDUCE=0: launch it now.
 void wgrad_reduce_enqueue(const WgradReduceArgs& a, lamp_tensor* partial, lamp_tensor* dw, hipStream_t st);
+// ... of the narrow layout (kind 1): nsplit blocks' partial sums [block][O] into the O elements of dw
+void wgrad_reduce_flat(int O, int nsplit, lamp_tensor* partial, lamp_tensor* dw, hipStream_t st, bool dw_f32 = false);
 bool wgrad_reduce_deferred();      // false: LAMP_DEFER_WGRAD_REDUCE=0 (the producers then leave their partial sums in the caches)
 // wgrad_park parks one layer of the eight-wave kernel the same way - dw pending, and dy / x / affine marked as read by deferred work, so a write
 // into them (Tensor::data()) launches it first - or, if the caller has one of the same batch parked on st's device, launches the two together

@@ -178,5 +178,11 @@ void wgrad_reduce_enqueue(const WgradReduceArgs& a, lamp_tensor* partial, lamp_t
   g_list.push_back(e);
   dw->st->pending.fetch_add(1, std::memory_order_release);
 }
+void wgrad_reduce_flat(int O, int nsplit, lamp_tensor* partial, lamp_tensor* dw, hipStream_t st, bool dw_f32) {
+  WgradReduceArgs ra{};
+  ra.kind = 1; ra.O = O; ra.nsplit = nsplit; ra.dw_f32 = dw_f32 ? 1 : 0;
+  ra.blocks = (int)(((int64_t)O * 64 + 255) / 256);          // a wave per output
+  wgrad_reduce_enqueue(ra, partial, dw, st);
+}
 
 }  // namespace lamp

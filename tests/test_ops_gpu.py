@@ -636,6 +636,9 @@ CONV_CASES = [
     (131, 34, 8, 8, 66, 3, 1, 1, 1, 1),    # ... two channels in the second slice of Cin, two in the fifth 16-row block of Cout, ragged image ranges
     (3, 4, 9, 7, 6, 3, 2, 1, 2, 2),        # odd sizes, dilation, groups
     (1, 2, 3, 3, 1, 3, 1, 0, 1, 1),        # reference KAT geometry (autograd.test.scala:2043)
+    (2, 6, 24, 24, 6, 3, 1, 1, 1, 1),      # narrow path, three column groups per row: generic forward and input gradient, aligned-read weight gradient
+    (3, 3, 32, 32, 6, 5, 2, 2, 1, 1),      # narrow path, 5x5 at stride 2: generic weight gradient (5 column tiles), aligned forward, 12-k-step input gradient over the dilated image
+    (3, 2, 16, 16, 4, 7, 1, 3, 1, 1),      # narrow path, 7-wide filter: generic forward, input gradient and weight gradient (9 column tiles)
 ]
 
 
