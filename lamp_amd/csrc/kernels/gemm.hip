@@ -17,8 +17,8 @@
 // bf16: v_mfma_f32_16x16x32_bf16, fp32 accumulate, one rounding to bf16 in the epilogue.
 // f32 : v_mfma_f32_16x16x4_f32 - exact f32 FMA chain (no tf32 on gfx950), parity <= 1e-5.
 // f64 : v_mfma_f64_16x16x4_f64 (the reference's own tests run in double).
+#include <cstdio>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -951,11 +951,241 @@ static void prep_operand(Operand& o, const Tensor* t, bool batched) {
     rs = o.t->strides[nd - 2];
     cs = o.t->strides[nd - 1];
   }
-  // normalise degenerate strides so exactly one of them is 1
-  if (cols == 1 && rs == 1 && cs != 1 && rows > 1) { /* column vector stored densely: M-contiguous */ }
   o.rs = rs;
   o.cs = cs;
   o.bs = batched ? o.t->strides[0] : 0;
+}
+
+// beta operand: self broadcast to out's [batch, M, N] through zero strides
+static void broadcast_self(GemmArgs& g, const Tensor* self, const Tensor* out, bool batched) {
+  check_device_tensor(self, "self");
+  LAMP_CHECK(self->dtype == out->dtype, "self dtype mismatch");
+  const int nd = out->ndim, lead = nd - self->ndim;
+  LAMP_CHECK(lead >= 0, "self has too many dims");
+  int64_t st[3] = {0, 0, 0};
+  for (int d = lead; d < nd; d++) {
+    const int64_t sz = self->sizes[d - lead];
+    LAMP_CHECK(sz == out->sizes[d] || sz == 1, "self " << self->describe() << " does not broadcast to " << out->describe());
+    st[d] = (sz == 1 && out->sizes[d] != 1) ? 0 : self->strides[d - lead];
+  }
+  g.S = self->data();
+  g.s_rs = st[nd - 2]; g.s_cs = st[nd - 1]; g.s_bs = batched ? st[0] : 0;
+}
+
+// kernel-timer class of a product: one per dtype, or (LAMP_GEMM_SHAPE_TAGS, a profiling aid) one per shape and layout
+static const char* gemm_timer_tag(const GemmArgs& g, int dt) {
+  const char* tag = dt == kBF16 ? "gemm_bf16" : (dt == kF16 ? "gemm_f16" : (dt == kF32 ? "gemm_f32" : "gemm_f64"));
+  if (!sw().gemm_shape_tags) return tag;
+  static std::mutex mu;
+  static std::map<std::string, std::unique_ptr<std::string>> interned;   // the timer keeps the pointer
+  std::ostringstream os;
+  os << tag << "[" << g.batch << "x" << g.M << "x" << g.N << "x" << g.K << (g.a_cs == 1 ? ",Akc" : ",Amc") << (g.b_rs == 1 ? ",Bkc" : ",Bnc") << "]";
+  std::lock_guard<std::mutex> lock(mu);
+  auto& e = interned[os.str()];
+  if (!e) e.reset(new std::string(os.str()));
+  return e->c_str();
+}
+
+// ------------------------------------------------------------------------------------------------
+// the plan of one product: which kernel form it takes and on what grid.  A value worked out from the arguments, the switches and a CU
+// count alone - gemm_plan touches no device, so lamp_debug_gemm_plan (and tests/test_gemm_plan.py through it) can ask without one
+// ------------------------------------------------------------------------------------------------
+enum class GemmForm { T128, T256x128, T256x256, T256x256SplitK, Fp64, Fp64SplitK, F32T128 };
+
+static const char* gemm_form_name(GemmForm f) {
+  switch (f) {
+    case GemmForm::T128: return "128x128";                      // gemm_bf16_kernel (bf16 / f16)
+    case GemmForm::T256x128: return "256x128";                  // gemm_bf16_pp_kernel
+    case GemmForm::T256x256: return "256x256";                  // gemm_bf16_pp2_kernel
+    case GemmForm::T256x256SplitK: return "256x256-splitk";     // gemm_bf16_pp2_kernel + gemm_splitk_reduce_kernel
+    case GemmForm::Fp64: return "fp64x64";                      // gemm_fp_kernel (f32 / f64)
+    case GemmForm::Fp64SplitK: return "fp64x64-splitk";         // gemm_fp_kernel + gemm_fp_splitk_reduce_kernel
+    case GemmForm::F32T128: return "f32-128x128";               // gemm_f32_big_kernel
+  }
+  return "?";
+}
+
+struct GemmPlan {
+  GemmForm form;
+  int dtype;
+  bool akc, bkc;         // the operand's K index is its contiguous one
+  int a_vec, b_vec;      // GemmArgs::a_vec / b_vec (read by the bf16 / f16 kernels only)
+  int tiles_m, tiles_n;
+  int split;             // split forms: K slices on blockIdx.z; otherwise 1 and blockIdx.z is the batch entry
+  int64_t k_chunk;       // split forms: K of one slice (the last f32 / f64 slice may be shorter); otherwise K
+  dim3 grid, block;
+  size_t lds;            // dynamic LDS
+};
+
+static GemmPlan gemm_plan(const GemmArgs& g, int dt, int64_t cus) {
+  GemmPlan p{};
+  p.dtype = dt;
+  p.akc = (g.a_cs == 1); p.bkc = (g.b_rs == 1);
+  p.split = 1; p.k_chunk = g.K;
+  // every form: one workgroup per tm x tn tile of the output on blockIdx.x
+  auto form = [&](GemmForm f, int tm, int tn, int threads, size_t lds) {
+    p.form = f;
+    p.tiles_m = (int)((g.M + tm - 1) / tm); p.tiles_n = (int)((g.N + tn - 1) / tn);
+    p.grid = dim3(p.tiles_m * p.tiles_n, 1, p.split > 1 ? p.split : g.batch);
+    p.block = dim3(threads); p.lds = lds;
+    return p;
+  };
+  if (dt == kBF16 || dt == kF16) {
+    LAMP_CHECK(p.akc || g.a_rs == 1, "internal: A has no unit stride");
+    LAMP_CHECK(p.bkc || g.b_cs == 1, "internal: B has no unit stride");
+    const int64_t lda = p.akc ? g.a_rs : g.a_cs, ldb = p.bkc ? g.b_cs : g.b_rs;
+    auto al16 = [](const void* ptr) { return ((uintptr_t)ptr & 15) == 0; };
+    p.a_vec = (lda % 8 == 0) && al16(g.A) && (g.a_bs % 8 == 0);
+    p.b_vec = (ldb % 8 == 0) && al16(g.B) && (g.b_bs % 8 == 0);
+    // half precision: the 128 x 128 x 64 register-staged kernel (every shape, bounds checked) on v_mfma_f32_16x16x32_f16
+    if (dt == kF16) return form(GemmForm::T128, BM, BN, 256, 4 * TILE_BYTES);
+    // aligned, large problems: 256 x 128 LDS-DMA / ping-pong kernel
+    const bool big = p.a_vec && p.b_vec && g.M % PM == 0 && g.N % PN == 0 && g.K % PK == 0 && (g.ldc % 4 == 0) &&
+                     (((uintptr_t)g.C & 7) == 0) && (g.c_bs % 4 == 0) && (g.M / PM) * (g.N / PN) * g.batch >= 128;
+    bool big2 = big && g.N % QN == 0 && (g.M / QM) * (g.N / QN) * g.batch >= 200;
+    if (big && !big2 && g.batch == 1 && g.M % QM == 0 && g.N % QN == 0) {
+      // fewer than 200 tiles of 256 x 256: still the better choice when the 256 x 128 kernel would need a second, mostly empty round
+      // (rounds x k-steps x ~1.7 / ~1.2 us per 64-deep k-step; 3072 x 3072 x 768: 288 half tiles = 2 rounds, 144 full tiles = 1: 34 -> 25 us)
+      const int64_t nk = g.K / PK;
+      const double c2 = (double)(((g.M / QM) * (g.N / QN) + cus - 1) / cus) * (double)nk * 1.7;
+      const double c1 = (double)(((g.M / PM) * (g.N / PN) + cus - 1) / cus) * (double)nk * 1.2;
+      if (c2 < c1) big2 = true;
+    }
+    // few output tiles over a long K (the weight gradients x^T . p of a token batch): split K over blockIdx.z
+    if (sw().gemm_splitk && !big2 && g.batch == 1 && p.a_vec && p.b_vec && g.M % QM == 0 && g.N % QN == 0 && g.K % PK == 0 && g.K >= 512) {
+      const int64_t tiles = (g.M / QM) * (g.N / QN), nk_total = g.K / PK;
+      // one workgroup per CU.  Cost of a split d in us: rounds x k-steps per chunk x ~1.7 us (one 256 x 256 x 64 stage at the
+      // kernel's ~4.9 TFLOP/s per CU) + writing and re-reading d f32 slices at ~4 TB/s
+      auto cost = [&](int64_t d) {
+        const int64_t wgs = tiles * d;
+        return (double)((wgs + cus - 1) / cus) * (double)(nk_total / d) * 1.7 + (d > 1 ? (double)d * (double)g.M * (double)g.N * 8.0 / 4.0e6 : 0.0);
+      };
+      int split = 1;
+      double best = cost(1);
+      for (int64_t d = 2; d <= nk_total / 4; d++) {
+        if (nk_total % d) continue;
+        const double c = cost(d);
+        if (c < best * 0.97) { best = c; split = (int)d; }
+      }
+      // ... against the 128 x 128 kernel without a split (two workgroups per CU, ~1.1 us per 64-deep k-step, ~5 us fixed): with a short K
+      // and enough 128 x 128 tiles it beats the split, whose second launch and f32 slices cost ~9 us beyond the model above
+      // (3072 x 768 x 768, the attention projections of a 3072-token batch: 29.6 -> 18.8 us)
+      const int64_t t128 = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
+      const double c128 = (double)((t128 + 2 * cus - 1) / (2 * cus)) * (double)nk_total * 1.1 + 5.0;
+      if (split > 1 && !big && c128 < best + 9.0) split = 1;
+      if (split > 1 && tiles * split >= 64) {
+        p.split = split; p.k_chunk = g.K / split;
+        return form(GemmForm::T256x256SplitK, QM, QN, 512, 2 * Q_SLOT);
+      }
+    }
+    if (big2) return form(GemmForm::T256x256, QM, QN, 512, 2 * Q_SLOT);
+    if (big) return form(GemmForm::T256x128, PM, PN, 512, 3 * P_SLOT);
+    return form(GemmForm::T128, BM, BN, 256, 4 * TILE_BYTES);
+  }
+  LAMP_CHECK(dt == kF32 || dt == kF64, "internal: no GEMM plan for dtype " << dt);
+  // Few output tiles over a long K (config 1's MLP: 1024 x 784 . 784 x 256 is 64 tiles on 256 CUs, each walking 49 k-steps one global
+  // round trip at a time: 35 us for 0.4 GFLOP): K is split over blockIdx.z until every CU has a workgroup (chunks of at least 64), the
+  // f32 / f64 slices are summed in order by a second launch.  LAMP_GEMM_SPLITK=0: off.
+  // What this changes: a row's dot product is no longer ONE fma chain over K but `split` chains added in slice order, and
+  // `split` depends on the tile count, i.e. on M and N - the same input row can give different last bits at another batch size (within
+  // the 1e-5 the f32 path is held to; deterministic for a given shape).  The slices carry no epilogue: only (alpha, beta, S) of GemmArgs
+  // are applied, by the reduction - any other epilogue field keeps the un-split path (the condition below lists them).
+  const int64_t fp_tiles = ((g.M + FM - 1) / FM) * ((g.N + FN - 1) / FN);
+  if (sw().gemm_splitk && g.batch == 1 && !g.knn_q && fp_tiles < 128 && g.K >= 128) {
+    const int64_t fp_split_wgs = sw().gemm_fp_split_wgs;
+    int64_t split = std::min<int64_t>(std::min<int64_t>((fp_split_wgs + fp_tiles - 1) / fp_tiles, g.K / 64), 32);
+    auto chunk = [&]() { return ((g.K + split - 1) / split + FK - 1) / FK * FK; };   // a multiple of the 16-deep k-step
+    if (split > 1) split = (g.K + chunk() - 1) / chunk();
+    if (split > 1) {
+      p.split = (int)split; p.k_chunk = chunk();
+      return form(GemmForm::Fp64SplitK, FM, FN, 256, 0);
+    }
+  }
+  const int64_t lda = p.akc ? g.a_rs : g.a_cs, ldb = p.bkc ? g.b_cs : g.b_rs;
+  const bool big32 = dt == kF32 && (lda % 4 == 0) && (ldb % 4 == 0) && (((uintptr_t)g.A | (uintptr_t)g.B) & 15) == 0 &&
+                     (g.a_bs % 4 == 0) && (g.b_bs % 4 == 0) && ((g.M + GM - 1) / GM) * ((g.N + GN - 1) / GN) * g.batch >= 128;
+  return big32 ? form(GemmForm::F32T128, GM, GN, 256, 0) : form(GemmForm::Fp64, FM, FN, 256, 0);
+}
+
+// The 256 x 256 kernel runs one workgroup per CU, so a tile count just above a multiple of the CU count costs a whole extra round
+// (288 tiles: 155 us, 255 tiles: 101 us at K = 3072).  When the last round would be less than a quarter full, the rows of that
+// remainder become a second product, which the split-K path spreads over the idle CUs.  Returns the rows of that second product, or 0.
+static int64_t gemm_tail_rows(const GemmArgs& g, int dt, int64_t cus) {
+  if (dt != kBF16 || !sw().gemm_tail_split || g.batch != 1 || g.M % QM || g.N % QN || g.K % PK) return 0;
+  if (g.K < 2048) return 0;   // shorter K: the second launch costs more than the round
+  const int64_t tn = g.N / QN, t2 = (g.M / QM) * tn, rem = t2 % cus;
+  if (t2 <= cus || rem == 0 || rem * 4 > cus) return 0;
+  const int64_t M2 = (rem + tn - 1) / tn * QM, M1 = g.M - M2;
+  return (M1 > 0 && (M1 / QM) * tn >= 200) ? M2 : 0;
+}
+
+// rows [row0, row0 + rows) of an unbatched product as a product of its own (the plan re-derives the alignment of the moved pointers)
+static GemmArgs gemm_rows(GemmArgs g, int dt, int64_t row0, int64_t rows) {
+  const int64_t esz = (int64_t)dtype_size(dt);
+  g.M = rows;
+  g.A = (const char*)g.A + row0 * g.a_rs * esz;
+  g.C = (char*)g.C + row0 * g.ldc * esz;
+  if (g.S) g.S = (const char*)g.S + row0 * g.s_rs * esz;
+  return g;
+}
+
+// One table per kernel template, indexed [!akc][bkc].  That is the order of the layout ladder these tables replace, and the order in
+// which the templates are instantiated is the order of the kernels in the code object: it stays what it was.
+typedef void (*GemmKernel)(GemmArgs);
+static const GemmKernel kT256x256[2][2] = {{gemm_bf16_pp2_kernel<true, false>, gemm_bf16_pp2_kernel<true, true>},
+                                           {gemm_bf16_pp2_kernel<false, false>, gemm_bf16_pp2_kernel<false, true>}};
+static const GemmKernel kT256x128[2][2] = {{gemm_bf16_pp_kernel<true, false>, gemm_bf16_pp_kernel<true, true>},
+                                           {gemm_bf16_pp_kernel<false, false>, gemm_bf16_pp_kernel<false, true>}};
+static const GemmKernel kT128[2][2][2] = {   // [f16][!akc][bkc]
+    {{gemm_bf16_kernel<true, false>, gemm_bf16_kernel<true, true>}, {gemm_bf16_kernel<false, false>, gemm_bf16_kernel<false, true>}},
+    {{gemm_bf16_kernel<true, false, f16_t>, gemm_bf16_kernel<true, true, f16_t>},
+     {gemm_bf16_kernel<false, false, f16_t>, gemm_bf16_kernel<false, true, f16_t>}}};
+
+// the f32 / f64 kernel on h (the product, or its K slices) and, for a split, the reduction that finishes g
+template <class T>
+static void gemm_launch_fp(const GemmPlan& p, const GemmArgs& g, const GemmArgs& h, const Tensor* ws, hipStream_t stm) {
+  hipLaunchKernelGGL((gemm_fp_kernel<T>), p.grid, p.block, p.lds, stm, h);
+  LAMP_LAUNCH_CHECK();
+  if (p.split == 1) return;
+  hipLaunchKernelGGL((gemm_fp_splitk_reduce_kernel<T>), dim3(grid_for(g.M * g.N, 256)), dim3(256), 0, stm, (const T*)ws->data(), p.split, g.M, g.N,
+                     (T*)g.C, g.ldc, (const T*)g.S, g.s_rs, g.s_cs, (T)g.alpha, (T)g.beta);
+  LAMP_LAUNCH_CHECK();
+}
+
+static void gemm_launch(const GemmPlan& p, const GemmArgs& g, hipStream_t stm, int device) {
+  GemmArgs h = g;   // what the product kernel gets
+  h.a_vec = p.a_vec; h.b_vec = p.b_vec;
+  h.tiles_m = p.tiles_m; h.tiles_n = p.tiles_n;
+  // split forms: slice z walks its K chunk and writes raw sums to ws[z][M][N]; the reduce kernel adds the slices in order and applies
+  // alpha, beta and S
+  const bool bf16 = p.dtype == kBF16;
+  Hold ws;
+  if (p.split > 1) {
+    ws = Hold(new_tensor({(int64_t)p.split, g.M, g.N}, bf16 ? (int)kF32 : p.dtype, device));
+    h.K = p.k_chunk;
+    h.a_bs = h.K * g.a_cs; h.b_bs = h.K * g.b_rs;
+    h.C = ws->data(); h.ldc = g.N; h.c_bs = g.M * g.N; h.S = nullptr;
+    if (bf16) h.split_f32 = 1;
+    else { h.k_split_total = g.K; h.alpha = 1.0; h.beta = 0.0; }
+  }
+  GemmKernel k = nullptr;
+  switch (p.form) {
+    case GemmForm::T128: k = kT128[p.dtype == kF16][!p.akc][p.bkc]; break;
+    case GemmForm::T256x128: k = kT256x128[!p.akc][p.bkc]; break;
+    case GemmForm::T256x256: case GemmForm::T256x256SplitK: k = kT256x256[!p.akc][p.bkc]; break;
+    case GemmForm::F32T128: k = gemm_f32_big_kernel; break;
+    case GemmForm::Fp64: case GemmForm::Fp64SplitK:
+      if (p.dtype == kF32) gemm_launch_fp<float>(p, g, h, ws.get(), stm);
+      else gemm_launch_fp<double>(p, g, h, ws.get(), stm);
+      return;
+  }
+  if (p.lds > 64 * 1024) allow_big_lds((const void*)k);
+  hipLaunchKernelGGL(k, p.grid, p.block, p.lds, stm, h);
+  LAMP_LAUNCH_CHECK();
+  if (p.split == 1) return;
+  hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(grid_for(g.M * g.N / 4, 256)), dim3(256), 0, stm, (const float*)ws->data(), p.split, g.M, g.N,
+                     (bf16_t*)g.C, g.ldc, (const bf16_t*)g.S, g.s_rs, g.s_cs, (float)g.alpha, (float)g.beta, g.round_first);
+  LAMP_LAUNCH_CHECK();
 }
 
 // transA: use a^T, transB: use b^T.  self may be null (beta ignored) and may alias out.
@@ -996,26 +1226,7 @@ static void gemm_dispatch(Tensor* out, const Tensor* self, const Tensor* a, cons
   g.ldc = out->strides[nd - 2];
   g.c_bs = batched ? out->strides[0] : 0;
   g.alpha = alpha; g.beta = beta;
-  if (self && beta != 0.0) {
-    check_device_tensor(self, "self");
-    LAMP_CHECK(self->dtype == out->dtype, "self dtype mismatch");
-    // broadcast self to [batch, M, N]
-    std::vector<int64_t> oshape = out->shape();
-    const Tensor* ops[2] = {out, self};
-    LAMP_CHECK(self->ndim <= nd, "self has too many dims");
-    int lead = nd - self->ndim;
-    int64_t st[3] = {0, 0, 0};
-    for (int d = 0; d < nd; d++) {
-      if (d < lead) continue;
-      int64_t sz = self->sizes[d - lead];
-      LAMP_CHECK(sz == oshape[d] || sz == 1, "self " << self->describe() << " does not broadcast to " << out->describe());
-      st[d] = (sz == 1 && oshape[d] != 1) ? 0 : self->strides[d - lead];
-    }
-    g.S = self->data();
-    g.s_rs = st[nd - 2]; g.s_cs = st[nd - 1]; g.s_bs = batched ? st[0] : 0;
-  } else {
-    g.S = nullptr;
-  }
+  if (self && beta != 0.0) broadcast_self(g, self, out, batched);
   if (g.M == 0 || g.N == 0 || g.batch == 0) return;
   hipStream_t stm = current_stream(out->device());
   if (g.K == 0) {  // out = beta * self
@@ -1023,240 +1234,16 @@ static void gemm_dispatch(Tensor* out, const Tensor* self, const Tensor* a, cons
     else fill_zero(out);
     return;
   }
+  const int dt = a->dtype;
+  LAMP_CHECK(dt == kBF16 || dt == kF16 || dt == kF32 || dt == kF64, "GEMM supports bf16, f16, f32 and f64, got " << a->describe());
   const double g_flops = 2.0 * (double)g.M * (double)g.N * (double)g.K * g.batch;
-  const double g_bytes = ((double)g.M * g.K + (double)g.K * g.N + (double)g.M * g.N * (g.S ? 2 : 1)) * g.batch * (double)dtype_size(a->dtype);
-  const char* kt_tag = a->dtype == kBF16 ? "gemm_bf16" : (a->dtype == kF16 ? "gemm_f16" : (a->dtype == kF32 ? "gemm_f32" : "gemm_f64"));
-  const bool shape_tags = sw().gemm_shape_tags;   // profiling aid: one timer class per shape and layout
-  if (shape_tags) {
-    static std::mutex mu;
-    static std::map<std::string, std::unique_ptr<std::string>> interned;
-    std::ostringstream os;
-    os << kt_tag << "[" << g.batch << "x" << g.M << "x" << g.N << "x" << g.K << (g.a_cs == 1 ? ",Akc" : ",Amc") << (g.b_rs == 1 ? ",Bkc" : ",Bnc") << "]";
-    std::lock_guard<std::mutex> lock(mu);
-    auto& e = interned[os.str()];
-    if (!e) e.reset(new std::string(os.str()));
-    kt_tag = e->c_str();
-  }
-  KernelTimer kt(kt_tag, g_flops, g_bytes, stm);
-  if (a->dtype == kBF16) {
-    const int out_device = out->device();
-    std::function<void(GemmArgs)> run = [&](GemmArgs g) {
-    const bool akc = (g.a_cs == 1), bkc = (g.b_rs == 1);
-    LAMP_CHECK(akc || g.a_rs == 1, "internal: A has no unit stride");
-    LAMP_CHECK(bkc || g.b_cs == 1, "internal: B has no unit stride");
-    const int64_t lda = akc ? g.a_rs : g.a_cs, ldb = bkc ? g.b_cs : g.b_rs;
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    g.a_vec = (lda % 8 == 0) && al16(g.A) && (g.a_bs % 8 == 0);
-    g.b_vec = (ldb % 8 == 0) && al16(g.B) && (g.b_bs % 8 == 0);
-    // aligned, large problems: 256 x 128 LDS-DMA / ping-pong kernel
-    const bool big = g.a_vec && g.b_vec && g.M % PM == 0 && g.N % PN == 0 && g.K % PK == 0 && (g.ldc % 4 == 0) &&
-                     (((uintptr_t)g.C & 7) == 0) && (g.c_bs % 4 == 0) && (g.M / PM) * (g.N / PN) * g.batch >= 128;
-    bool big2 = big && g.N % QN == 0 && (g.M / QM) * (g.N / QN) * g.batch >= 200;
-    if (big && !big2 && g.batch == 1 && g.M % QM == 0 && g.N % QN == 0) {
-      // fewer than 200 tiles of 256 x 256: still the better choice when the 256 x 128 kernel would need a second, mostly empty round
-      // (rounds x k-steps x ~1.7 / ~1.2 us per 64-deep k-step; 3072 x 3072 x 768: 288 half tiles = 2 rounds, 144 full tiles = 1: 34 -> 25 us)
-      const int64_t cusn = num_cus(), nk = g.K / PK;
-      const double c2 = (double)(((g.M / QM) * (g.N / QN) + cusn - 1) / cusn) * (double)nk * 1.7;
-      const double c1 = (double)(((g.M / PM) * (g.N / PN) + cusn - 1) / cusn) * (double)nk * 1.2;
-      if (c2 < c1) big2 = true;
-    }
-    // few output tiles over a long K (the weight gradients x^T . p of a token batch): split K over blockIdx.z
-    const bool allow_split = sw().gemm_splitk;
-    if (allow_split && !big2 && g.batch == 1 && g.a_vec && g.b_vec && g.M % QM == 0 && g.N % QN == 0 && g.K % PK == 0 && g.K >= 512) {
-      const int64_t tiles = (g.M / QM) * (g.N / QN), nk_total = g.K / PK;
-      // one workgroup per CU.  Cost of a split d in us: rounds x k-steps per chunk x ~1.7 us (one 256 x 256 x 64 stage at the
-      // kernel's ~4.9 TFLOP/s per CU) + writing and re-reading d f32 slices at ~4 TB/s
-      const int64_t cus = num_cus();
-      auto cost = [&](int64_t d) {
-        const int64_t wgs = tiles * d;
-        return (double)((wgs + cus - 1) / cus) * (double)(nk_total / d) * 1.7 + (d > 1 ? (double)d * (double)g.M * (double)g.N * 8.0 / 4.0e6 : 0.0);
-      };
-      int split = 1;
-      double best = cost(1);
-      for (int64_t d = 2; d <= nk_total / 4; d++) {
-        if (nk_total % d) continue;
-        const double c = cost(d);
-        if (c < best * 0.97) { best = c; split = (int)d; }
-      }
-      // ... against the 128 x 128 kernel without a split (two workgroups per CU, ~1.1 us per 64-deep k-step, ~5 us fixed): with a short K
-      // and enough 128 x 128 tiles it beats the split, whose second launch and f32 slices cost ~9 us beyond the model above
-      // (3072 x 768 x 768, the attention projections of a 3072-token batch: 29.6 -> 18.8 us)
-      const int64_t t128 = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
-      const double c128 = (double)((t128 + 2 * cus - 1) / (2 * cus)) * (double)nk_total * 1.1 + 5.0;
-      if (split > 1 && !big && c128 < best + 9.0) split = 1;
-      if (split > 1 && tiles * split >= 64) {
-        Hold ws(new_tensor({(int64_t)split, g.M, g.N}, kF32, out_device));
-        GemmArgs h = g;
-        h.K = g.K / split;
-        h.a_bs = h.K * g.a_cs; h.b_bs = h.K * g.b_rs;
-        h.C = ws->data(); h.ldc = g.N; h.c_bs = g.M * g.N; h.S = nullptr; h.split_f32 = 1;
-        h.tiles_m = (int)(g.M / QM); h.tiles_n = (int)(g.N / QN);
-        dim3 grid(h.tiles_m * h.tiles_n, 1, split);
-        const size_t lds = 2 * Q_SLOT;
-#define PP2S_LAUNCH(A_, B_)                                                                                                     \
-  do {                                                                                                                          \
-    static bool attr = false;                                                                                                   \
-    allow_big_lds((const void*)gemm_bf16_pp2_kernel<A_, B_>); \
-    hipLaunchKernelGGL((gemm_bf16_pp2_kernel<A_, B_>), grid, dim3(512), lds, stm, h);                                           \
-  } while (0)
-        if (akc && !bkc) PP2S_LAUNCH(true, false);
-        else if (akc && bkc) PP2S_LAUNCH(true, true);
-        else if (!akc && !bkc) PP2S_LAUNCH(false, false);
-        else PP2S_LAUNCH(false, true);
-#undef PP2S_LAUNCH
-        LAMP_LAUNCH_CHECK();
-        hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(grid_for(g.M * g.N / 4, 256)), dim3(256), 0, stm, (const float*)ws->data(), split, g.M, g.N,
-                           (bf16_t*)g.C, g.ldc, (const bf16_t*)g.S, g.s_rs, g.s_cs, (float)g.alpha, (float)g.beta, g.round_first);
-        LAMP_LAUNCH_CHECK();
-        return;
-      }
-    }
-    if (big2) {
-      g.tiles_m = (int)(g.M / QM);
-      g.tiles_n = (int)(g.N / QN);
-      dim3 grid(g.tiles_m * g.tiles_n, 1, g.batch);
-      const size_t lds = 2 * Q_SLOT;
-#define PP2_LAUNCH(A_, B_)                                                                                                      \
-  do {                                                                                                                          \
-    static bool attr = false;                                                                                                   \
-    allow_big_lds((const void*)gemm_bf16_pp2_kernel<A_, B_>); \
-    hipLaunchKernelGGL((gemm_bf16_pp2_kernel<A_, B_>), grid, dim3(512), lds, stm, g);                                           \
-  } while (0)
-      if (akc && !bkc) PP2_LAUNCH(true, false);
-      else if (akc && bkc) PP2_LAUNCH(true, true);
-      else if (!akc && !bkc) PP2_LAUNCH(false, false);
-      else PP2_LAUNCH(false, true);
-#undef PP2_LAUNCH
-      LAMP_LAUNCH_CHECK();
-      return;
-    }
-    if (big) {
-      g.tiles_m = (int)(g.M / PM);
-      g.tiles_n = (int)(g.N / PN);
-      dim3 grid(g.tiles_m * g.tiles_n, 1, g.batch);
-      const size_t lds = 3 * P_SLOT;
-#define PP_LAUNCH(A_, B_)                                                                                                       \
-  do {                                                                                                                          \
-    static bool attr = false;                                                                                                   \
-    allow_big_lds((const void*)gemm_bf16_pp_kernel<A_, B_>); \
-    hipLaunchKernelGGL((gemm_bf16_pp_kernel<A_, B_>), grid, dim3(512), lds, stm, g);                                            \
-  } while (0)
-      if (akc && !bkc) PP_LAUNCH(true, false);
-      else if (akc && bkc) PP_LAUNCH(true, true);
-      else if (!akc && !bkc) PP_LAUNCH(false, false);
-      else PP_LAUNCH(false, true);
-#undef PP_LAUNCH
-      LAMP_LAUNCH_CHECK();
-      return;
-    }
-    g.tiles_m = (int)((g.M + BM - 1) / BM);
-    g.tiles_n = (int)((g.N + BN - 1) / BN);
-    dim3 grid(g.tiles_m * g.tiles_n, 1, g.batch);
-    size_t lds = 4 * TILE_BYTES;
-    if (akc && !bkc) hipLaunchKernelGGL((gemm_bf16_kernel<true, false>), grid, dim3(256), lds, stm, g);
-    else if (akc && bkc) hipLaunchKernelGGL((gemm_bf16_kernel<true, true>), grid, dim3(256), lds, stm, g);
-    else if (!akc && !bkc) hipLaunchKernelGGL((gemm_bf16_kernel<false, false>), grid, dim3(256), lds, stm, g);
-    else hipLaunchKernelGGL((gemm_bf16_kernel<false, true>), grid, dim3(256), lds, stm, g);
-    LAMP_LAUNCH_CHECK();
-    };
-    // The 256 x 256 kernel runs one workgroup per CU, so a tile count just above a multiple of the CU count costs a whole extra round
-    // (288 tiles: 155 us, 255 tiles: 101 us at K = 3072).  When the last round would be less than a quarter full, the rows of that
-    // remainder become a second product, which the split-K path spreads over the idle CUs.
-    const bool tail_split = sw().gemm_tail_split;
-    const int64_t cus = num_cus();
-    if (tail_split && g.batch == 1 && !g.knn_q && g.M % QM == 0 && g.N % QN == 0 && g.K % PK == 0 && g.K >= 2048) {   // shorter K: the second launch costs more than the round
-      const int64_t tn = g.N / QN, t2 = (g.M / QM) * tn, rem = t2 % cus;
-      if (t2 > cus && rem > 0 && rem * 4 <= cus) {
-        const int64_t rem_rows = (rem + tn - 1) / tn, M2 = rem_rows * QM, M1 = g.M - M2;
-        if (M1 > 0 && (M1 / QM) * tn >= 200) {
-          GemmArgs g1 = g, g2 = g;
-          g1.M = M1;
-          g2.M = M2;
-          g2.A = (const char*)g.A + M1 * g.a_rs * (int64_t)sizeof(bf16_t);
-          g2.C = (char*)g.C + M1 * g.ldc * (int64_t)sizeof(bf16_t);
-          if (g.S) g2.S = (const char*)g.S + M1 * g.s_rs * (int64_t)sizeof(bf16_t);
-          run(g1);
-          run(g2);
-          return;
-        }
-      }
-    }
-    run(g);
-    return;
-  } else if (a->dtype == kF16) {
-    // half precision: the 128 x 128 x 64 register-staged kernel (every shape, bounds checked) on v_mfma_f32_16x16x32_f16
-    const bool akc = (g.a_cs == 1), bkc = (g.b_rs == 1);
-    LAMP_CHECK(akc || g.a_rs == 1, "internal: A has no unit stride");
-    LAMP_CHECK(bkc || g.b_cs == 1, "internal: B has no unit stride");
-    const int64_t lda = akc ? g.a_rs : g.a_cs, ldb = bkc ? g.b_cs : g.b_rs;
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    g.a_vec = (lda % 8 == 0) && al16(g.A) && (g.a_bs % 8 == 0);
-    g.b_vec = (ldb % 8 == 0) && al16(g.B) && (g.b_bs % 8 == 0);
-    g.tiles_m = (int)((g.M + BM - 1) / BM);
-    g.tiles_n = (int)((g.N + BN - 1) / BN);
-    dim3 grid(g.tiles_m * g.tiles_n, 1, g.batch);
-    const size_t lds = 4 * TILE_BYTES;
-    if (akc && !bkc) hipLaunchKernelGGL((gemm_bf16_kernel<true, false, f16_t>), grid, dim3(256), lds, stm, g);
-    else if (akc && bkc) hipLaunchKernelGGL((gemm_bf16_kernel<true, true, f16_t>), grid, dim3(256), lds, stm, g);
-    else if (!akc && !bkc) hipLaunchKernelGGL((gemm_bf16_kernel<false, false, f16_t>), grid, dim3(256), lds, stm, g);
-    else hipLaunchKernelGGL((gemm_bf16_kernel<false, true, f16_t>), grid, dim3(256), lds, stm, g);
-  } else if (a->dtype == kF32 || a->dtype == kF64) {
-    g.tiles_m = (int)((g.M + FM - 1) / FM);
-    g.tiles_n = (int)((g.N + FN - 1) / FN);
-    dim3 grid(g.tiles_m * g.tiles_n, 1, g.batch);
-    const bool a_kc32 = (g.a_cs == 1), b_kc32 = (g.b_rs == 1);
-    const int64_t lda32 = a_kc32 ? g.a_rs : g.a_cs, ldb32 = b_kc32 ? g.b_cs : g.b_rs;
-    const bool big32 = a->dtype == kF32 && (lda32 % 4 == 0) && (ldb32 % 4 == 0) && (((uintptr_t)g.A | (uintptr_t)g.B) & 15) == 0 &&
-                       (g.a_bs % 4 == 0) && (g.b_bs % 4 == 0) && ((g.M + GM - 1) / GM) * ((g.N + GN - 1) / GN) * g.batch >= 128;
-    // Few output tiles over a long K (config 1's MLP: 1024 x 784 . 784 x 256 is 64 tiles on 256 CUs, each walking 49 k-steps one global
-    // round trip at a time: 35 us for 0.4 GFLOP): K is split over blockIdx.z until every CU has a workgroup (chunks of at least 64), the
-    // f32 / f64 slices are summed in order by a second launch.  LAMP_GEMM_SPLITK=0: off.
-    // What this changes: a row's dot product is no longer ONE fma chain over K but `split` chains added in slice order, and
-    // `split` depends on the tile count, i.e. on M and N - the same input row can give different last bits at another batch size (within
-    // the 1e-5 the f32 path is held to; deterministic for a given shape).  The slices carry no epilogue: only (alpha, beta, S) of GemmArgs
-    // are applied, by the reduction - any other epilogue field keeps the un-split path (the condition below lists them).
-    const bool allow_fp_split = sw().gemm_splitk;
-    const int64_t fp_tiles = (int64_t)g.tiles_m * g.tiles_n;
-    if (allow_fp_split && g.batch == 1 && !g.knn_q && fp_tiles < 128 && g.K >= 128) {
-      const int64_t fp_split_wgs = sw().gemm_fp_split_wgs;
-      int64_t split = std::min<int64_t>(std::min<int64_t>((fp_split_wgs + fp_tiles - 1) / fp_tiles, g.K / 64), 32);
-      if (split > 1) {
-        const int64_t kc = ((g.K + split - 1) / split + FK - 1) / FK * FK;
-        split = (g.K + kc - 1) / kc;
-      }
-      if (split > 1) {
-        const int64_t kc = ((g.K + split - 1) / split + FK - 1) / FK * FK;
-        Hold ws(new_tensor({split, g.M, g.N}, a->dtype, out->device()));
-        GemmArgs h = g;
-        h.k_split_total = g.K; h.K = kc;
-        h.a_bs = kc * g.a_cs; h.b_bs = kc * g.b_rs;
-        h.C = ws->data(); h.ldc = g.N; h.c_bs = g.M * g.N; h.S = nullptr; h.alpha = 1.0; h.beta = 0.0;
-        dim3 sgrid(g.tiles_m * g.tiles_n, 1, (unsigned)split);
-        if (a->dtype == kF32) {
-          hipLaunchKernelGGL((gemm_fp_kernel<float>), sgrid, dim3(256), 0, stm, h);
-          LAMP_LAUNCH_CHECK();
-          hipLaunchKernelGGL((gemm_fp_splitk_reduce_kernel<float>), dim3(grid_for(g.M * g.N, 256)), dim3(256), 0, stm, (const float*)ws->data(), (int)split, g.M, g.N,
-                             (float*)g.C, g.ldc, (const float*)g.S, g.s_rs, g.s_cs, (float)g.alpha, (float)g.beta);
-        } else {
-          hipLaunchKernelGGL((gemm_fp_kernel<double>), sgrid, dim3(256), 0, stm, h);
-          LAMP_LAUNCH_CHECK();
-          hipLaunchKernelGGL((gemm_fp_splitk_reduce_kernel<double>), dim3(grid_for(g.M * g.N, 256)), dim3(256), 0, stm, (const double*)ws->data(), (int)split, g.M,
-                             g.N, (double*)g.C, g.ldc, (const double*)g.S, g.s_rs, g.s_cs, g.alpha, g.beta);
-        }
-        LAMP_LAUNCH_CHECK();
-        return;
-      }
-    }
-    if (big32) {
-      g.tiles_m = (int)((g.M + GM - 1) / GM);
-      g.tiles_n = (int)((g.N + GN - 1) / GN);
-      hipLaunchKernelGGL(gemm_f32_big_kernel, dim3(g.tiles_m * g.tiles_n, 1, g.batch), dim3(256), 0, stm, g);
-    } else if (a->dtype == kF32) hipLaunchKernelGGL((gemm_fp_kernel<float>), grid, dim3(256), 0, stm, g);
-    else hipLaunchKernelGGL((gemm_fp_kernel<double>), grid, dim3(256), 0, stm, g);
-  } else {
-    LAMP_CHECK(false, "GEMM supports bf16, f16, f32 and f64, got " << a->describe());
-  }
-  LAMP_LAUNCH_CHECK();
+  const double g_bytes = ((double)g.M * g.K + (double)g.K * g.N + (double)g.M * g.N * (g.S ? 2 : 1)) * g.batch * (double)dtype_size(dt);
+  KernelTimer kt(gemm_timer_tag(g, dt), g_flops, g_bytes, stm);
+  // one product, or two when the last round of 256 x 256 tiles would be nearly empty: each part is planned on its own
+  const int64_t cus = num_cus(), M2 = gemm_tail_rows(g, dt, cus);
+  auto run = [&](const GemmArgs& part) { gemm_launch(gemm_plan(part, dt, cus), part, stm, out->device()); };
+  if (M2 == 0) run(g);
+  else { run(gemm_rows(g, dt, 0, g.M - M2)); run(gemm_rows(g, dt, g.M - M2, M2)); }
 }
 
 // out[i, j] = max(0, qn[i] + dn[j] - 2 * q[i, :] . x[j, :])  in one kernel (f32 / f64): the kNN distance block
@@ -1405,6 +1392,41 @@ int lamp_matmul(lamp_tensor** out, const lamp_tensor* a, const lamp_tensor* b) {
     return lamp_view(out, r, so, 3);
   }
   LAMP_CHECK(false, "matmul: unsupported operand ranks " << a->ndim << " and " << b->ndim);
+  LAMP_API_END
+}
+
+// Test tool, needs no GPU: the launch parts of a product and the plan of each, through the functions gemm_dispatch uses, on a device of
+// `cus` compute units.  dims = {M, N, K, batch}; a_kc / b_kc: the operand's K index is its contiguous one; ld = {lda, ldb, ldc, a_bs,
+// b_bs, c_bs} in elements; align = bytes of A, B, C (and self) past a 16-byte boundary.  One line per part into buf:
+// "<form> rows=<M of the part> tiles=<m>x<n> batch=<blockIdx.z when not split> split=<K slices> kchunk=<K per slice> block=<threads>
+// lds=<bytes> vec=<a_vec><b_vec>"
+int lamp_debug_gemm_plan(int dtype, const int64_t* dims, int a_kc, int b_kc, const int64_t* ld, const int* align, int has_self, int has_knn,
+                         int cus, char* buf, int buflen) {
+  LAMP_API_BEGIN
+  LAMP_CHECK(dims && ld && align && buf && buflen > 0 && cus > 0, "lamp_debug_gemm_plan: bad arguments");
+  LAMP_CHECK(dtype == kBF16 || dtype == kF16 || dtype == kF32 || dtype == kF64, "lamp_debug_gemm_plan: bf16, f16, f32 or f64");
+  char* const base = (char*)(uintptr_t)(1ull << 40);       // never dereferenced: the plan reads the low bits only
+  GemmArgs g{};
+  g.M = dims[0]; g.N = dims[1]; g.K = dims[2]; g.batch = (int)dims[3];
+  g.a_rs = a_kc ? ld[0] : 1; g.a_cs = a_kc ? 1 : ld[0];
+  g.b_rs = b_kc ? 1 : ld[1]; g.b_cs = b_kc ? ld[1] : 1;
+  g.ldc = ld[2]; g.a_bs = ld[3]; g.b_bs = ld[4]; g.c_bs = ld[5];
+  g.A = base + align[0]; g.B = base + align[1]; g.C = base + align[2];
+  if (has_self) { g.S = base + align[2]; g.s_rs = g.ldc; g.s_cs = 1; g.s_bs = g.c_bs; }
+  if (has_knn) g.knn_q = g.knn_d = base;
+  g.alpha = 1.0; g.beta = has_self ? 1.0 : 0.0;
+  std::string text;
+  const int64_t M2 = gemm_tail_rows(g, dtype, cus);
+  for (const GemmArgs& part : {gemm_rows(g, dtype, 0, g.M - M2), gemm_rows(g, dtype, g.M - M2, M2)}) {
+    if (part.M <= 0) continue;
+    const GemmPlan p = gemm_plan(part, dtype, cus);
+    char line[256];
+    snprintf(line, sizeof(line), "%s rows=%lld tiles=%dx%d batch=%u split=%d kchunk=%lld block=%u lds=%zu vec=%d%d\n", gemm_form_name(p.form),
+             (long long)part.M, p.tiles_m, p.tiles_n, p.split > 1 ? 1u : p.grid.z, p.split, (long long)p.k_chunk, p.block.x, p.lds, p.a_vec, p.b_vec);
+    text += line;
+  }
+  LAMP_CHECK((int)text.size() < buflen, "lamp_debug_gemm_plan: buffer too small");
+  memcpy(buf, text.c_str(), text.size() + 1);
   LAMP_API_END
 }
 

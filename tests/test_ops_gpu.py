@@ -14,7 +14,7 @@ import torch
 
 from lamp_amd import sten as S
 from lamp_amd._capi import lib, i64_array, handle_array
-from tests.util import DTYPES, FWD_TOL, TORCH2LAMP, assert_close, closed_form, to_sten, to_torch
+from tests.util import DTYPES, FWD_TOL, TORCH2LAMP, assert_close, closed_form, gemm_plan, to_sten, to_torch
 
 pytestmark = pytest.mark.gpu
 aten = torch.ops.aten
@@ -166,8 +166,8 @@ def test_views_share_storage_and_strided_copy(gpu):
 
 @pytest.mark.parametrize("dt", DTYPES)
 @pytest.mark.parametrize("shape", [(2, 3, 3), (64, 64, 64), (130, 70, 45), (256, 384, 192), (1024, 256, 784), (1024, 10, 256), (1, 1, 1),
-                                   (2048, 2048, 2048)])   # aligned and large: the 256x128 LDS-DMA kernel, all four operand layouts
-def test_gemm_family(gpu, dt, shape):
+                                   (2048, 2048, 2048)])   # aligned and large: in bf16 the 256x256 split-K form (split 2) in all four of its
+def test_gemm_family(gpu, dt, shape):                     # products, in f32 the 128x128 kernel (tests/test_gemm_plan.py pins both)
     M, N, K = shape
     a, b = closed_form((M, K), 1, 2.0, dt), closed_form((K, N), 77, 2.0, dt)
     A, B = to_sten(a), to_sten(b)
@@ -192,10 +192,19 @@ def test_gemm_family(gpu, dt, shape):
     assert_close(to_torch(S.STen(o)), ref + bias.double(), tol * 2, "linear_bias")
 
 
-@pytest.mark.parametrize("K", [128, 192])
-def test_gemm_256_tile_all_layouts(gpu, K):
-    """the 256 x 256 LDS-DMA kernel (>= 200 tiles): all four operand layouts, even and odd stage counts"""
-    dt, n = torch.bfloat16, 4096
+def _device_cus():
+    n = C.c_int(); lib.lamp_device_num_cus(C.byref(n)); return n.value
+
+
+@pytest.mark.parametrize("n,K,form", [(4096, 128, "256x256"), (4096, 192, "256x256"), (2048, 64, "256x128"), (2048, 192, "256x128"),
+                                      (2048, 256, "256x128")], ids=["128", "192", "2048-64", "2048-192", "2048-256"])
+def test_gemm_256_tile_all_layouts(gpu, n, K, form):
+    """the 256 x 256 LDS-DMA kernel (n = 4096, >= 200 tiles: even and odd stage counts) and the 256 x 128 one (n = 2048, 128 tiles: one,
+    three and four K-steps of its three-slot ring, four being the first reuse of a slot): all four operand layouts.  The plan is asked
+    which form each layout takes on this device, so the claim cannot drift."""
+    dt = torch.bfloat16
+    for a_kc, b_kc, has_self in ((True, False, False), (False, True, False), (False, False, True), (True, True, True), (True, False, True)):
+        assert [p["form"] for p in gemm_plan(dt, n, n, K, 1, a_kc, b_kc, _device_cus(), has_self=has_self)] == [form]
     a, b = closed_form((n, K), 1, 2.0, dt), closed_form((K, n), 77, 2.0, dt)
     A, B = to_sten(a), to_sten(b)
     ref = a.double() @ b.double()
@@ -245,7 +254,8 @@ def test_gemm_4096_cube_is_the_benchmarked_linear(gpu):
 def test_gemm_split_k(gpu, M, N, K):
     """few output tiles over a long K (weight gradients of a token batch): K split over blockIdx.z, f32 slices summed by the reduce
     kernel - all operand layouts, beta operand, and the same answer as the unsplit kernel up to bf16 rounding of one result.  The two
-    tall shapes are 288 / 258 tiles of 256 x 256: the rows of the nearly empty last round run as a second, K-split product."""
+    tall shapes are 288 / 258 tiles of 256 x 256.  (24576, 768, 2048): the rows of the nearly empty last round run as a second,
+    K-split product.  (22016, 768, 768): K < 2048, no tail split - one 256 x 256 launch of 258 tiles (tests/test_gemm_plan.py)."""
     dt = torch.bfloat16
     xt, p = closed_form((K, M), 3, 2.0, dt), closed_form((K, N), 9, 2.0, dt)
     ref = xt.double().t() @ p.double()
@@ -324,6 +334,31 @@ def test_bmm_family(gpu, dt):
     S.STen.baddbmm_out_transposed2(O2, O2, P, B, 1.0, 1.0)
     assert_close(to_torch(O2), o2.double() + p.double() @ b.double().transpose(1, 2), tol * 2, "baddbmm_t2")
     assert_close(to_torch(A.matmul(to_sten(b[0]))), a.double() @ b[0].double(), tol, "matmul 3d x 2d")
+
+
+@pytest.mark.parametrize("B,M,N,form", [(128, 256, 128, "256x128"), (200, 256, 256, "256x256")])
+def test_bmm_lds_dma_kernels_batched(gpu, B, M, N, form):
+    """both LDS-DMA kernels with one tile per batch entry (blockIdx.z = entry: the a_bs / b_bs / c_bs / s_bs paths), bf16 at K = 128:
+    bmm and the two accumulating transposed forms into a [B, M, N] output.  Every entry has inputs of its own seed, so a wrong batch
+    stride cannot pass.  Against f64 at 2^-7, twice that for the forms that add a rounded operand (test_gemm_family's rule)."""
+    dt, K, tol = torch.bfloat16, 128, 2.0 ** -7
+    for a_kc, b_kc, has_self in ((True, False, False), (False, False, True), (True, True, True)):
+        assert [p["form"] for p in gemm_plan(dt, M, N, K, B, a_kc, b_kc, _device_cus(), has_self=has_self)] == [form]
+
+    def batch_of(shape, salt, scale):
+        return torch.stack([closed_form(shape, salt + 17 * e, scale, dt) for e in range(B)])
+
+    a, b = batch_of((M, K), 1, 2.0), batch_of((K, N), 5, 2.0)
+    assert_close(to_torch(to_sten(a).bmm(to_sten(b))), a.double() @ b.double(), tol, "bmm")
+    o0 = batch_of((M, N), 3, 1.0)
+    at, p = batch_of((K, M), 7, 2.0), batch_of((K, N), 8, 1.0)                  # out[e] += at[e]^T . p[e]
+    O1 = to_sten(o0)
+    S.STen.baddbmm_out_transposed1(O1, O1, to_sten(at), to_sten(p), 1.0, 1.0)
+    assert_close(to_torch(O1), o0.double() + at.double().transpose(1, 2) @ p.double(), tol * 2, "baddbmm_t1")
+    p2, b2 = batch_of((M, K), 9, 1.0), batch_of((N, K), 11, 2.0)                # out[e] += p2[e] . b2[e]^T
+    O2 = to_sten(o0)
+    S.STen.baddbmm_out_transposed2(O2, O2, to_sten(p2), to_sten(b2), 1.0, 1.0)
+    assert_close(to_torch(O2), o0.double() + p2.double() @ b2.double().transpose(1, 2), tol * 2, "baddbmm_t2")
 
 
 @pytest.mark.parametrize("dt", DTYPES)

@@ -31,6 +31,29 @@ def closed_form(shape, salt=0, scale=1.0, dtype=torch.float32):
     return v.reshape(shape).to(dtype)
 
 
+def gemm_plan(dt, M, N, K, batch=1, a_kc=True, b_kc=False, cus=256, lda=None, ldb=None, ldc=None, align=(0, 0, 0), has_self=False, knn=False):
+    """The launch parts the library plans for a product on a device of `cus` compute units (lamp_debug_gemm_plan: the functions the
+    real path uses, no GPU needed).  a_kc / b_kc: the operand's K index is its contiguous one (a row-major `a`, a transposed `b`);
+    dense leading dimensions and batch strides unless given; align = bytes of A, B, C past a 16-byte boundary.  One dict per part."""
+    import ctypes as C
+    from lamp_amd._capi import lib, i64_array
+    lda = lda if lda is not None else (K if a_kc else M)
+    ldb = ldb if ldb is not None else (K if b_kc else N)
+    ldc = ldc if ldc is not None else N
+    bs = (M * K, K * N, M * N) if batch > 1 else (0, 0, 0)
+    buf = C.create_string_buffer(1024)
+    lib.lamp_debug_gemm_plan(TORCH2LAMP[dt], i64_array([M, N, K, batch]), int(a_kc), int(b_kc), i64_array([lda, ldb, ldc, *bs]),
+                             (C.c_int * 3)(*align), int(has_self), int(knn), int(cus), buf, len(buf))
+    parts = []
+    for line in buf.value.decode().splitlines():
+        form, *kv = line.split()
+        d = dict(x.split("=") for x in kv)
+        tm, tn = (int(x) for x in d["tiles"].split("x"))
+        parts.append(dict(form=form, rows=int(d["rows"]), tiles=tm * tn, tiles_m=tm, tiles_n=tn, batch=int(d["batch"]), split=int(d["split"]),
+                          kchunk=int(d["kchunk"]), block=int(d["block"]), lds=int(d["lds"]), vec=d["vec"]))
+    return parts
+
+
 def rel_err(got, ref):
     got = got.double() if isinstance(got, torch.Tensor) else torch.as_tensor(got).double()
     ref = ref.double()
