@@ -875,6 +875,40 @@ int lamp_sample_logits_out(lamp_tensor* out, const lamp_tensor* logits, double t
 int lamp_decode_embedding(lamp_tensor** out, const lamp_tensor* tokenWeight, const lamp_tensor* positionWeight, const lamp_tensor* tokens, int64_t t);
 
 /* ------------------------------------------------------------------------------------------
+ * recurrent text generation   (lamp-core nn/FreeRunningRNN.scala and lamp-data Text.scala:18-135 run the module's sequence-shaped
+ * forward at one time step for every token).  kernels/recurrent_decode.hip: f32 and f64, GPU tensors, 1 .. LAMP_DECODE_MAX_ROWS rows.
+ * One step of Embedding -> RNN | GRU | LSTM is one launch (GRU two) built as lamp_decode_linear's [K, N] kernel with the cell of
+ * kernels/recurrent.hip as its epilogue.  No call synchronises with the host, there is no floating-point atomic, and every sum is
+ * taken in a fixed order: a result depends on its inputs alone and is bit-identical from run to run.
+ * ------------------------------------------------------------------------------------------ */
+#define LAMP_RECURRENT_RNN 0
+#define LAMP_RECURRENT_GRU 1
+#define LAMP_RECURRENT_LSTM 2
+/* Once per generation.  tensors: the module's n state tensors in `state` order (RNN 3: Xh Hh bH; GRU 9: Xh Hh Xr Xz Hr Hz bR bZ bH; LSTM
+ * 12: Xi Xf Xo Hi Hf Ho Xc Hc bI bF bO bC; biases [H] or [1, H]).  *w_out: [E + H, nG * H], Wx over Wh, gate-interleaved columns: column
+ * j * nG + g is gate g of hidden unit j in the order LSTM i f o c, GRU r z h^, RNN h.  *bias_out: [nG * H] in the same order.  GRU: the
+ * candidate's columns are zero below row E (its recurrent product needs r * h first) and *wh2_out_or_null receives Whh [H, H] for
+ * lamp_recurrent_decode_step's second launch; other kinds leave it NULL. */
+int lamp_recurrent_decode_pack(lamp_tensor** w_out, lamp_tensor** bias_out, lamp_tensor** wh2_out_or_null, int kind, lamp_tensor* const* tensors, int n);
+/* One time step for R rows.  table [vocabulary, E]; tokens: int64, R elements of any stride; w, bias, wh2 as packed above; h_prev (and
+ * c_prev for LSTM) contiguous [Rp, H].  parent_or_null: int64 [R], row r continues row parent[r] of the previous state (a beam search
+ * gathers its states this way, at no extra launch); NULL: Rp == R and row r continues row r.
+ *   gates[r] = bias + table[tokens[r]] . Wx + h_prev[parent[r]] . Wh, the cell of tests/recurrent_ref.py applied to the sums themselves with
+ * the arithmetic of lamp_lstm_cell_forward / lamp_gru_gates_forward + lamp_gru_output_forward / lamp_rnn_cell_forward.
+ * Writes h_out [R, H], c_out [R, H] (LSTM only) and, where given, relu_out = relu(h_out); the outputs must not be the previous
+ * state's buffers (the rows are read while others are written).  A token outside the table or a parent outside h_prev raises as an
+ * index out of range at the host's next wait and reads as zeros.  More than LAMP_DECODE_MAX_ROWS rows are an error. */
+int lamp_recurrent_decode_step(int kind, const lamp_tensor* table, const lamp_tensor* tokens, const lamp_tensor* parent_or_null, const lamp_tensor* w,
+                               const lamp_tensor* bias, const lamp_tensor* wh2_or_null, const lamp_tensor* h_prev, const lamp_tensor* c_prev_or_null,
+                               lamp_tensor* h_out, lamp_tensor* c_out_or_null, lamp_tensor* relu_out_or_null);
+/* One launch from logits [R, V] to the stored outputs and a token per row, a workgroup per row.  log_softmax != 0: out = logits - max -
+ * log(sum exp(logits - max)) as lamp_log_softmax computes it; 0: out = logits.  out: [R, V] of any row pitch (a time step of a
+ * [steps, B, V] buffer).  tokens_out: int64, R elements of any stride (a row of [steps, B]): the index of the largest STORED value of
+ * the row, lowest index among equals, so it equals lamp_argmax of `out` by construction; a row that holds a NaN gives what
+ * lamp_log_softmax and lamp_argmax give (all NaN and 0 with log_softmax, the first NaN's index without). */
+int lamp_log_softmax_argmax_rows(lamp_tensor* out, lamp_tensor* tokens_out, const lamp_tensor* logits, int log_softmax);
+
+/* ------------------------------------------------------------------------------------------
  * fused multi-tensor optimiser steps   (lamp-core/src/main/scala/lamp/nn/AdamW.scala:101-176,
  * SGD.scala:46-98, nn/package.scala:72-100).  One launch for all parameter tensors instead
  * of ~8 ATen calls per tensor; arithmetic order follows the reference line by line.

@@ -156,7 +156,8 @@ int lamp_module_lstm_from(lamp_module** out, const lamp_tensor* const* tensors, 
 int lamp_module_seq_linear_from(lamp_module** out, const lamp_tensor* const* tensors, int n);
 /* statefulSequence(m1, ..., mn): stateless members (Embedding, Fun, SeqLinear) are lifted; the state is the members' states side by side */
 int lamp_module_stateful_sequence(lamp_module** out, lamp_module* const* mods, int n);
-/* number of Variables in a stateful module's state: LSTM 2 (h, c), GRU / RNN 1, a stateful sequence the sum over its members */
+/* number of Variables in a stateful module's state: LSTM 2 (h, c), GRU / RNN 1, a stateful sequence the sum over its members; FreeRunningRNN
+ * and WithInit their module's, Seq2Seq its encoder's */
 int lamp_module_num_state_slots(lamp_module* m, int* out);
 /* StatefulModule.forward((x, state)): `state` holds nstate Variables (NULL entries, or nstate = 0: the reference's None - zeros); returns the
  * output and the next state (state_out: capacity lamp_module_num_state_slots, +1 handles).  Gradients flow through the returned state. */
@@ -164,6 +165,40 @@ int lamp_module_forward_stateful(lamp_module* m, lamp_var* x, lamp_var* const* s
 /* RNN / GRU / LSTM / SeqLinear as one node per sequence over the fused cell kernels (1, the default unless LAMP_RECURRENT_FUSED=0) or as the
  * reference's fold over the time steps built from the plain operators (0).  Process-wide; returns the previous value in *previous_or_null. */
 int lamp_recurrent_fused(int on, int* previous_or_null);
+/* ---- recurrent text generation (lamp-core nn/FreeRunningRNN.scala, nn/Seq2Seq.scala; lamp-data Text.scala:18-135) ----
+ * FreeRunningRNN(module, time_steps): a stateful module; forward((x [T0, B] int64, state)) = (outputs [time_steps, B, V], lastState): the
+ * first iteration forwards the whole prefix, every further one the detached argmax(2) of the last time step, [1, B].  A composition of the
+ * wrapped module's own nodes, so gradients flow through outputs and state.  state / training mode / slots are the wrapped module's. */
+int lamp_module_free_running_rnn(lamp_module** out, lamp_module* module, int64_t time_steps);
+/* Seq2Seq(encoder, decoder): forward(((source, dest), state0)) = decoder.forward((dest, encoder.forward((source, state0)).state)) through
+ * lamp_module_forward_stateful_pair; state = encoder.state ++ decoder.state; the encoder's state is the decoder's initial state, so both have
+ * the same number of slots. */
+int lamp_module_seq2seq(lamp_module** out, lamp_module* encoder, lamp_module* decoder);
+/* WithInit(module, init): the module with an initial state of its own, n = lamp_module_num_state_slots(module) Variables */
+int lamp_module_with_init(lamp_module** out, lamp_module* module, lamp_var* const* init, int n);
+/* InitState: *n = 0 for the reference's None (RNN, GRU, LSTM, statefulSequence), the carried Variables for WithInit (+1 handles, capacity
+ * lamp_module_num_state_slots); FreeRunningRNN answers with its module's, Seq2Seq with its encoder's */
+int lamp_module_init_state(lamp_module* m, lamp_var** out, int* n);
+/* lamp_module_forward_stateful for a module whose input is a pair of Variables (Seq2Seq: source, dest) */
+int lamp_module_forward_stateful_pair(lamp_module* m, lamp_var* x0, lamp_var* x1, lamp_var* const* state, int nstate, lamp_var** out, lamp_var** state_out);
+/* Text.sequencePrediction: FreeRunningRNN(module, steps).forward((prefix, module.initState)), values only.  prefix: int64 [T0, B] on the
+ * module's device.  *tokens: int64 [steps, B], the argmax(2) of *outputs_or_null [steps, B, V].
+ * With lamp_text_generation_fused on, a module of the shape statefulSequence(Embedding, one of RNN | GRU | LSTM, [Fun relu], SeqLinear,
+ * [Fun logsoftmax over dimension 2]) (possibly inside WithInit), f32 or f64 on a device and B <= LAMP_DECODE_MAX_ROWS: the prefix runs once
+ * through the module's own forward, then every token is lamp_recurrent_decode_step (GRU: two launches), lamp_decode_linear and
+ * lamp_log_softmax_argmax_rows; the token stays on the device.  Anything else runs the chain above. */
+int lamp_text_sequence_prediction(lamp_module* module, const lamp_tensor* prefix, int64_t steps, lamp_tensor** tokens, lamp_tensor** outputs_or_null);
+/* Text.sequencePredictionBeam (Text.scala:38-135) for one prefix [T0, 1]: up to k sequences, best first.  Sequence i is
+ * tokens_out[offsets_out[i] .. offsets_out[i + 1]) (it starts with the prefix's last token and has at most steps + 1 entries; a beam whose
+ * last token is end_of_sequence is carried unchanged) with log-probability log_probs_out[i], summed in double on the host.  Capacities:
+ * tokens_out k * (steps + 1), offsets_out k + 1, log_probs_out k.  Per step the live beams are one batch (fused: their states gathered by
+ * the step kernel's parent argument), a sorted per-row lamp_topk and ONE host read; the fused path needs k <= LAMP_DECODE_MAX_ROWS. */
+int lamp_text_sequence_prediction_beam(lamp_module* module, const lamp_tensor* prefix, int64_t steps, int64_t start_sequence, int64_t end_of_sequence,
+                                       int64_t k, int64_t* tokens_out, int64_t* offsets_out, double* log_probs_out, int* num_sequences);
+/* Process-wide, run-time only; returns the previous value in *previous_or_null. */
+int lamp_text_generation_fused(int on, int* previous_or_null);
+/* which path the calling process's last sequence prediction took: 1 the decode kernels, 0 the chain, -1 none yet */
+int lamp_text_generate_path(int* out);
 /* GenericModule[A, B].forward for a tuple / case-class A: its Variables and its plain tensors in the reference's order; a NULL tensor = None */
 int lamp_module_forward_multi(lamp_module* m, lamp_var* const* vars, int nvars, const lamp_tensor* const* tensors, int ntensors, lamp_var** out);
 int lamp_module_forward(lamp_module* m, lamp_var* x, lamp_var** out);

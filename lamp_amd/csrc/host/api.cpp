@@ -4,6 +4,7 @@
 #include "recurrent.h"
 #include "bert.h"
 #include "generate.h"
+#include "text.h"
 #include "../../../include/lamp_host.h"
 
 #include <cstring>
@@ -405,6 +406,74 @@ int lamp_recurrent_fused(int on, int* previous) {
   LAMP_API_BEGIN
   const bool prev = F::set_recurrent_fused(on != 0);
   if (previous) *previous = prev ? 1 : 0;
+  LAMP_API_END
+}
+// ---- recurrent text generation (FreeRunningRNN.scala, Seq2Seq.scala, Text.scala) ------------------------------------------
+int lamp_module_free_running_rnn(lamp_module** out, lamp_module* module, int64_t time_steps) {
+  LAMP_API_BEGIN *out = wrapm(std::make_shared<FreeRunningRNN>(module->m, time_steps)); LAMP_API_END
+}
+int lamp_module_seq2seq(lamp_module** out, lamp_module* encoder, lamp_module* decoder) {
+  LAMP_API_BEGIN *out = wrapm(std::make_shared<Seq2Seq>(encoder->m, decoder->m)); LAMP_API_END
+}
+int lamp_module_with_init(lamp_module** out, lamp_module* module, lamp_var* const* init, int n) {
+  LAMP_API_BEGIN
+  std::vector<Var> st;
+  for (int i = 0; i < n; i++) { LAMP_CHECK(init && init[i], "WithInit: NULL initial state Variable"); st.push_back(init[i]->v); }
+  *out = wrapm(std::make_shared<WithInit>(module->m, st));
+  LAMP_API_END
+}
+int lamp_module_init_state(lamp_module* m, lamp_var** out, int* n) {
+  LAMP_API_BEGIN
+  auto st = stateful(m->m, "lamp_module_init_state").init_state();
+  *n = (int)st.size();
+  for (size_t i = 0; i < st.size(); i++) out[i] = wrap(st[i]);
+  LAMP_API_END
+}
+int lamp_module_forward_stateful_pair(lamp_module* m, lamp_var* x0, lamp_var* x1, lamp_var* const* state, int nstate, lamp_var** out, lamp_var** state_out) {
+  LAMP_API_BEGIN
+  auto* s = dynamic_cast<Seq2Seq*>(m->m.get());
+  LAMP_CHECK(s, "lamp_module_forward_stateful_pair: not a Seq2Seq");
+  LAMP_CHECK(nstate == 0 || nstate == s->slots(), "lamp_module_forward_stateful_pair: " << nstate << " state Variables, the module has " << s->slots() << " slots");
+  std::vector<Var> st, so;
+  bool none = true;
+  for (int i = 0; i < nstate; i++) { st.push_back(state && state[i] ? state[i]->v : nullptr); if (st.back()) none = false; }
+  if (none) st.clear();
+  *out = wrap(s->forward_pair(x0->v, x1->v, st, so));
+  if (state_out) for (size_t i = 0; i < so.size(); i++) state_out[i] = wrap(so[i]);
+  LAMP_API_END
+}
+int lamp_text_sequence_prediction(lamp_module* module, const lamp_tensor* prefix, int64_t steps, lamp_tensor** tokens, lamp_tensor** outputs) {
+  LAMP_API_BEGIN
+  LAMP_CHECK(prefix && tokens, "lamp_text_sequence_prediction: prefix and tokens are required");
+  Predicted r = sequence_prediction(module->m, borrow(prefix), steps);
+  HCALL(lamp_tensor_retain(r.tokens.h(), tokens));
+  if (outputs) HCALL(lamp_tensor_retain(r.outputs.h(), outputs));
+  LAMP_API_END
+}
+int lamp_text_sequence_prediction_beam(lamp_module* module, const lamp_tensor* prefix, int64_t steps, int64_t start_sequence, int64_t end_of_sequence,
+                                       int64_t k, int64_t* tokens_out, int64_t* offsets_out, double* log_probs_out, int* num_sequences) {
+  LAMP_API_BEGIN
+  LAMP_CHECK(prefix && tokens_out && offsets_out && log_probs_out && num_sequences, "lamp_text_sequence_prediction_beam: NULL argument");
+  auto r = sequence_prediction_beam(module->m, borrow(prefix), steps, start_sequence, end_of_sequence, k);
+  int64_t at = 0;
+  for (size_t i = 0; i < r.size(); i++) {
+    offsets_out[i] = at;
+    for (int64_t t : r[i].tokens) tokens_out[at++] = t;
+    log_probs_out[i] = r[i].logProb;
+  }
+  offsets_out[r.size()] = at;
+  *num_sequences = (int)r.size();
+  LAMP_API_END
+}
+int lamp_text_generation_fused(int on, int* previous) {
+  LAMP_API_BEGIN
+  const bool prev = set_text_fused(on != 0);
+  if (previous) *previous = prev ? 1 : 0;
+  LAMP_API_END
+}
+int lamp_text_generate_path(int* out) {
+  LAMP_API_BEGIN
+  *out = last_text_path();
   LAMP_API_END
 }
 int lamp_module_forward_multi(lamp_module* m, lamp_var* const* vars, int nvars, const lamp_tensor* const* tensors, int ntensors, lamp_var** out) {

@@ -356,5 +356,53 @@ Var StatefulSequence::forward_stateful(const Var& x, const std::vector<Var>& sta
   return v;
 }
 
+// ---- FreeRunningRNN, Seq2Seq, WithInit: compositions of the modules above ------------------------------------------------------
+StatefulModule& stateful(const Mod& m, const char* what) {
+  auto* s = dynamic_cast<StatefulModule*>(m.get());
+  LAMP_CHECK(s, what << ": not a stateful module");
+  return *s;
+}
+FreeRunningRNN::FreeRunningRNN(Mod m, int64_t steps) : module(std::move(m)), timeSteps(steps) {
+  stateful(module, "FreeRunningRNN");
+  LAMP_CHECK(timeSteps >= 1, "FreeRunningRNN: timeSteps must be positive, got " << timeSteps);
+}
+Var FreeRunningRNN::forward_stateful(const Var& x, const std::vector<Var>& state, std::vector<Var>& state_out) {
+  StatefulModule& m = stateful(module, "FreeRunningRNN");
+  LAMP_CHECK(x->value.ndim() == 2, "FreeRunningRNN: input " << x->value.h()->describe() << " must be [time, batch] token ids");
+  const int64_t batch = x->value.size(1);
+  Var lastOutput = x;
+  std::vector<Var> lastState = state, buffer;
+  for (int64_t n = 0; n < timeSteps; n++) {                                  // FreeRunningRNN.scala:26-55
+    std::vector<Var> next;
+    Var output = m.forward_stateful(lastOutput, lastState, next);
+    LAMP_CHECK(output->value.ndim() == 3, "FreeRunningRNN: the module's output " << output->value.h()->describe() << " must be [time, batch, dim]");
+    const int64_t T = output->value.size(0);
+    Var lastChar = T > 1 ? F::view(F::select(output, 0, T - 1), {1, output->value.size(1), output->value.size(2)}) : output;
+    lastOutput = make_const(F::argmax(lastChar, 2, false)->value);           // .detached
+    lastState = next;
+    buffer.push_back(lastChar);
+  }
+  for (auto& v : lastState) state_out.push_back(v);
+  return F::view(F::stack(buffer, 0), {timeSteps, batch, -1});
+}
+Seq2Seq::Seq2Seq(Mod e, Mod d) : encoder(std::move(e)), decoder(std::move(d)) {
+  LAMP_CHECK(stateful(encoder, "Seq2Seq").slots() == stateful(decoder, "Seq2Seq").slots(),
+             "Seq2Seq: the encoder's state (" << stateful(encoder, "Seq2Seq").slots() << " Variables) is the decoder's initial state ("
+                                              << stateful(decoder, "Seq2Seq").slots() << ")");
+}
+Var Seq2Seq::forward_stateful(const Var&, const std::vector<Var>&, std::vector<Var>&) {
+  LAMP_CHECK(false, "Seq2Seq takes (source, dest): call lamp_module_forward_stateful_pair");
+  return nullptr;
+}
+Var Seq2Seq::forward_pair(const Var& source, const Var& dest, const std::vector<Var>& state, std::vector<Var>& state_out) {
+  std::vector<Var> encoderState;
+  stateful(encoder, "Seq2Seq").forward_stateful(source, state, encoderState);
+  return stateful(decoder, "Seq2Seq").forward_stateful(dest, encoderState, state_out);
+}
+WithInit::WithInit(Mod m, std::vector<Var> init_) : module(std::move(m)), init(std::move(init_)) {
+  LAMP_CHECK((int)init.size() == stateful(module, "WithInit").slots(),
+             "WithInit: " << init.size() << " initial state Variables for " << stateful(module, "WithInit").slots() << " slots");
+}
+
 }  // namespace host
 }  // namespace lamp

@@ -1,6 +1,6 @@
-// lamp.nn's recurrent family over the C ABI: RNN, GRU, LSTM, SeqLinear, statefulSequence.
+// lamp.nn's recurrent family over the C ABI: RNN, GRU, LSTM, SeqLinear, statefulSequence, FreeRunningRNN, Seq2Seq, WithInit.
 //
-// Reference: lamp-core/src/main/scala/lamp/nn/{RNN,GRU,LSTM,SeqLinear,StatefulSeq}.scala.  A cell is one autograd node over the
+// Reference: lamp-core/src/main/scala/lamp/nn/{RNN,GRU,LSTM,SeqLinear,StatefulSeq,FreeRunningRNN,Seq2Seq}.scala.  A cell is one autograd node over the
 // whole sequence (F::lstm / F::gru / F::rnn): one GEMM for x.Wx + bias of all time steps, per step one GEMM for h.Wh and a fused cell
 // kernel (kernels/recurrent.hip), backpropagation through time in the node's one shared backward.  With the switch off, for types
 // other than f32 / f64 and for host tensors the same functions build the reference's fold out of the existing operators.
@@ -33,6 +33,8 @@ struct StatefulModule : Module {
   virtual int slots() const = 0;
   virtual Var forward_stateful(const Var& x, const std::vector<Var>& state, std::vector<Var>& state_out) = 0;
   Var forward(const Var& x) override { std::vector<Var> so; return forward_stateful(x, {}, so); }
+  // InitState (Module.scala): empty = the reference's None; WithInit carries one
+  virtual std::vector<Var> init_state() { return {}; }
 };
 struct Recurrent : StatefulModule {   // RNN / GRU / LSTM: the case classes' fields in `state` order
   enum Kind { kRNN = 0, kGRU = 1, kLSTM = 2 } kind;
@@ -58,6 +60,44 @@ struct StatefulSequence : StatefulModule {
   int slots() const override;
   Var forward_stateful(const Var& x, const std::vector<Var>& state, std::vector<Var>& state_out) override;
   void set_training(bool t) override { for (auto& m : mods) m->set_training(t); }
+};
+// the StatefulModule behind a module handle; raises for a stateless one
+StatefulModule& stateful(const Mod& m, const char* what);
+// FreeRunningRNN(module, timeSteps) (FreeRunningRNN.scala): greedy generation as a differentiable composition of the wrapped module's
+// forward, argmax(2) detached, and the stack of the last time steps.  x [T0, B] int64 -> (outputs [timeSteps, B, V], lastState)
+struct FreeRunningRNN : StatefulModule {
+  Mod module;
+  int64_t timeSteps;
+  FreeRunningRNN(Mod m, int64_t steps);
+  void collect_state(std::vector<Var>& o) override { module->collect_state(o); }
+  int slots() const override { return stateful(module, "FreeRunningRNN").slots(); }
+  Var forward_stateful(const Var& x, const std::vector<Var>& state, std::vector<Var>& state_out) override;
+  void set_training(bool t) override { module->set_training(t); }
+  std::vector<Var> init_state() override { return stateful(module, "FreeRunningRNN").init_state(); }
+};
+// Seq2Seq(encoder, decoder) (Seq2Seq.scala:6-28): forward(((source, dest), state0)) = decoder.forward((dest, encoder.forward((source, state0)).state))
+struct Seq2Seq : StatefulModule {
+  Mod encoder, decoder;
+  Seq2Seq(Mod e, Mod d);
+  void collect_state(std::vector<Var>& o) override { encoder->collect_state(o); decoder->collect_state(o); }
+  int slots() const override { return stateful(encoder, "Seq2Seq").slots(); }
+  Var forward_stateful(const Var& x, const std::vector<Var>& state, std::vector<Var>& state_out) override;   // raises: the input is a pair
+  Var forward_pair(const Var& source, const Var& dest, const std::vector<Var>& state, std::vector<Var>& state_out);
+  void set_training(bool t) override { encoder->set_training(t); decoder->set_training(t); }
+  std::vector<Var> init_state() override { return stateful(encoder, "Seq2Seq").init_state(); }
+};
+// WithInit(module, init) (Seq2Seq.scala:75-114): the module with an initial state of its own
+struct WithInit : StatefulModule {
+  Mod module;
+  std::vector<Var> init;
+  WithInit(Mod m, std::vector<Var> init_);
+  void collect_state(std::vector<Var>& o) override { module->collect_state(o); }
+  int slots() const override { return stateful(module, "WithInit").slots(); }
+  Var forward_stateful(const Var& x, const std::vector<Var>& state, std::vector<Var>& state_out) override {
+    return stateful(module, "WithInit").forward_stateful(x, state, state_out);
+  }
+  void set_training(bool t) override { module->set_training(t); }
+  std::vector<Var> init_state() override { return init; }
 };
 
 }  // namespace host

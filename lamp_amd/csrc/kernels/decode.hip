@@ -25,8 +25,7 @@
 // (f64).  No kernel of this file uses scratch memory.
 #include <algorithm>
 #include <cstdint>
-#include <map>
-#include <mutex>
+#include "decode_tickets.h"
 #include "device_utils.h"
 #include "philox.h"
 
@@ -36,7 +35,6 @@ namespace {
 constexpr int kDecMaxRows = LAMP_DECODE_MAX_ROWS;
 constexpr int kDecKcMax = 256;        // the longest slice of K a workgroup takes: the LDS image of x is [kDecKcMax][RT]
 constexpr int kDecUnroll = 8;         // weight packets in flight per lane
-constexpr int kDecMaxTiles = 4096;    // tickets per stream
 constexpr int kDecNkWaves = 4;        // columns per workgroup of the [N, K] kernel
 constexpr int kDecWaves = 4;          // waves of a workgroup of the [K, N] kernel: each takes a quarter of the workgroup's slice of K
 constexpr int kDecMaxSlices = 16;     // slices of K across workgroups (8 beyond four rows), unless the LDS image asks for more
@@ -443,21 +441,6 @@ bool dec_aligned(std::initializer_list<const void*> ptrs) {
   for (const void* q : ptrs) if (q && (uintptr_t)q % 16) return false;
   return true;
 }
-// the tickets of a stream's split-K launches: zeroed once, every launch leaves them zero.  One buffer per (device, stream): launches on one
-// stream are ordered, launches on two streams never share a ticket.
-unsigned* dec_tickets(int device, hipStream_t st) {
-  static std::mutex mu;
-  static std::map<std::pair<int, hipStream_t>, unsigned*> bufs;
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = bufs.find({device, st});
-  if (it != bufs.end()) return it->second;
-  void* q = nullptr;
-  HIP_CHECK(hipMalloc(&q, kDecMaxTiles * sizeof(unsigned)));
-  HIP_CHECK(hipMemsetAsync(q, 0, kDecMaxTiles * sizeof(unsigned), st));
-  bufs[{device, st}] = (unsigned*)q;
-  return (unsigned*)q;
-}
-
 template <class T, int V>
 void dec_launch_kn(const DecLinear<T>& p, dim3 grid, hipStream_t st) {
   if (p.R == 1) hipLaunchKernelGGL((decode_linear_kn_kernel<T, V, 1>), grid, dim3(64 * kDecWaves), 0, st, p);

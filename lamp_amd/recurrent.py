@@ -1,7 +1,7 @@
-"""lamp.nn's recurrent family over the host C ABI: RNN, GRU, LSTM, SeqLinear, statefulSequence, SequenceNLL.
+"""lamp.nn's recurrent family over the host C ABI: RNN, GRU, LSTM, SeqLinear, statefulSequence, SequenceNLL, FreeRunningRNN, Seq2Seq, WithInit.
 
-Reference: lamp-core/src/main/scala/lamp/nn/{RNN,GRU,LSTM,SeqLinear,StatefulSeq}.scala, LossFunctions.scala:76-108.  Inputs are
-[time, batch, in]; a stateful module's forward takes (x, state) and returns (output, nextState), `None` for the reference's None.
+Reference: lamp-core/src/main/scala/lamp/nn/{RNN,GRU,LSTM,SeqLinear,StatefulSeq,FreeRunningRNN,Seq2Seq}.scala, LossFunctions.scala:76-108.
+Inputs are [time, batch, in]; a stateful module's forward takes (x, state) and returns (output, nextState), `None` for the reference's None.
 """
 from __future__ import annotations
 
@@ -25,6 +25,14 @@ def recurrentFused(on: bool) -> bool:
 class StatefulModule(Module):
     def __init__(self, m: Module):
         super().__init__(m.h); m.h = None
+
+    @property
+    def initState(self) -> Optional[Tuple[Variable, ...]]:
+        """InitState: None for the reference's None, the carried state of a WithInit"""
+        cap = max(1, self.stateSlots)
+        out = (C.c_void_p * cap)(); n = C.c_int(0)
+        lib.lamp_module_init_state(self.h, out, C.byref(n))
+        return tuple(Variable(C.c_void_p(out[i])) for i in range(n.value)) if n.value else None
 
     @property
     def stateSlots(self) -> int:
@@ -76,3 +84,38 @@ class statefulSequence(StatefulModule):
     def __init__(self, *mods: Module):
         super().__init__(_mk("lamp_module_stateful_sequence", handle_array([m.h for m in mods]), len(mods)))
         self._mods = mods
+
+
+class FreeRunningRNN(StatefulModule):
+    """FreeRunningRNN(module, timeSteps) (FreeRunningRNN.scala): forward(x [T0, B] int64, state) -> (outputs [timeSteps, B, V], lastState), greedy
+    generation as a differentiable composition of the wrapped module's forward.  state, load and the training mode are the wrapped module's."""
+    def __init__(self, module: StatefulModule, timeSteps: int):
+        super().__init__(_mk("lamp_module_free_running_rnn", module.h, int(timeSteps)))
+        self.module, self.timeSteps = module, int(timeSteps)
+
+
+class Seq2Seq(StatefulModule):
+    """Seq2Seq(encoder, decoder) (Seq2Seq.scala:6-28): forward((source, dest), state0) = decoder.forward(dest, encoder.forward(source, state0).state);
+    state = encoder.state ++ decoder.state."""
+    def __init__(self, encoder: StatefulModule, decoder: StatefulModule):
+        super().__init__(_mk("lamp_module_seq2seq", encoder.h, decoder.h))
+        self.encoder, self.decoder = encoder, decoder
+
+    def forward(self, x: Tuple[Variable, Variable], state: Optional[Sequence[Optional[Variable]]] = None) -> Tuple[Variable, Tuple[Variable, ...]]:
+        source, dest = x
+        n = self.stateSlots
+        st = list(state) if state is not None else []
+        assert len(st) in (0, n), f"{n} state slots, got {len(st)} Variables"
+        arr = (C.c_void_p * max(1, len(st)))(*[(v.h if v is not None else None) for v in st])
+        o = C.c_void_p()
+        so = (C.c_void_p * max(1, n))()
+        lib.lamp_module_forward_stateful_pair(self.h, source.h, dest.h, arr, len(st), C.byref(o), so)
+        return Variable(o), tuple(Variable(C.c_void_p(so[i])) for i in range(n))
+
+
+class WithInit(StatefulModule):
+    """WithInit(module, init) (Seq2Seq.scala:75-114): the module with an initial state of its own (`initState`)"""
+    def __init__(self, module: StatefulModule, init: Sequence[Variable]):
+        init = list(init)
+        super().__init__(_mk("lamp_module_with_init", module.h, handle_array([v.h for v in init]), len(init)))
+        self.module, self._init = module, init

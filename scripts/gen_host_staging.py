@@ -69,7 +69,8 @@ def classify(param):
 # (gradients handed to an optimiser step came back re-written into the caller's host tensors after every call)
 READ_ONLY_ARRAYS = {("lamp_cat", "ts"), ("lamp_cat_out", "ts"), ("lamp_stack", "ts"), ("lamp_adamw_step_", "grads"), ("lamp_sgdw_step_", "grads"),
                     ("lamp_flatten_into_", "ts"), ("lamp_radam_step_", "grads"),     # NOT lamp_yogi_step_'s: Yogi writes its gradients,
-                    ("lamp_symmetric_eig", "matrices")}                              # nor lamp_shampoo_step_'s: momentum blends into them
+                    ("lamp_symmetric_eig", "matrices"),                              # nor lamp_shampoo_step_'s: momentum blends into them
+                    ("lamp_recurrent_decode_pack", "tensors")}
 
 
 def generate():
