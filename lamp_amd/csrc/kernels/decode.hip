@@ -3,13 +3,9 @@
 // accumulates in f32, f64 in f64.  R <= 16 rows make every product a weight-streaming problem: the weights go from memory to registers in
 // 16-byte packets, there is no matrix-pipe tile and no LDS round trip for them.
 //
-//   decode_linear_kn_kernel   out = residual + scale * act(LN(x) . W + bias), W [K, N].  A workgroup of four waves owns 64 packets of columns and
-//                             a slice of K (grid.y slices); every wave covers all of the columns and a quarter of the slice.  The normalised
-//                             slice of x sits in LDS (acc_t) as [k][row] and is read as a broadcast; a lane keeps RT x V sums.  The waves' sums
-//                             are added in wave order through LDS.  With more than one slice every workgroup stores its sums into its slab,
-//                             publishes them (agent-scope release, then an integer ticket per tile), and the workgroup that draws the last
-//                             ticket acquires, adds the slabs in slice order (a wave per row, eight slabs' loads in flight), applies the
-//                             epilogue and puts the ticket back to zero.
+//   decode_linear_kn_kernel   out = residual + scale * act(LN(x) . W + bias), W [K, N]: an operation of the body decode_stream_body.h (which
+//                             holds the stream loop, the wave and slab reductions and the ticket protocol).  The operation works out the
+//                             rows' statistics, gives LN(x) as the image and applies the epilogue to a lane's one packet of columns.
 //   decode_linear_nk_kernel   the same for W [N, K] (logits against the embedding table): a wave per column, the lanes split K in packets, the
 //                             64 sums are added by the fixed butterfly of wave_sum.
 //   decode_attention_kernel   a workgroup per (row, head): copies the new key and value into position t, scores q . K^T over 0 .. t (a group of
@@ -20,33 +16,20 @@
 //   decode_embedding_kernel   tokenWeight[token] + positionWeight[t]
 // No kernel uses a floating atomic and every sum has a fixed order: the results are functions of the inputs, bit for bit.
 //
-// Registers (hipcc -Rpass-analysis=kernel-resource-usage, gfx950), decode_linear_kn_kernel: at one row 80 VGPRs (bf16 x 8 columns), 66 (f32 x 4),
-// 68 (f64 x 2); at 2 .. 4 rows 118 / 74 / 62; at 5 .. 16 rows 242 (bf16: 128 sums and 8 packets in flight, two waves per SIMD), 128 (f32), 124
-// (f64).  No kernel of this file uses scratch memory.
-#include <algorithm>
-#include <cstdint>
-#include "decode_tickets.h"
-#include "device_utils.h"
+// Registers (hipcc -Rpass-analysis=kernel-resource-usage, gfx950), decode_linear_kn_kernel at 1 / 2 .. 4 / 5 .. 16 rows:
+//   packet form (bf16 x 8, f32 x 4, f64 x 2 columns)  bf16 104 / 128 / 242 VGPRs    f32  66 /  76 / 136     f64  68 /  88 / 136
+//   element form                                      bf16  46 /  66 /  76          f32  44 /  66 /  72     f64  60 /  64 /  82
+// (bf16 at 5 .. 16 rows: 128 sums and 8 packets in flight, two waves per SIMD).  No kernel of this file uses scratch memory.
+#include <cstdio>
+#include <cstring>
+#include "decode_stream.h"
 #include "philox.h"
 
 namespace lamp {
 namespace {
 
-constexpr int kDecMaxRows = LAMP_DECODE_MAX_ROWS;
-constexpr int kDecKcMax = 256;        // the longest slice of K a workgroup takes: the LDS image of x is [kDecKcMax][RT]
-constexpr int kDecUnroll = 8;         // weight packets in flight per lane
 constexpr int kDecNkWaves = 4;        // columns per workgroup of the [N, K] kernel
-constexpr int kDecWaves = 4;          // waves of a workgroup of the [K, N] kernel: each takes a quarter of the workgroup's slice of K
-constexpr int kDecMaxSlices = 16;     // slices of K across workgroups (8 beyond four rows), unless the LDS image asks for more
 constexpr int kDecAttUnroll = 4;      // positions per lane group of the attention kernel whose key loads are in flight together
-constexpr int kDecSlabBatch = 8;      // slabs whose loads the reducing workgroup keeps in flight
-
-__device__ __forceinline__ float dec_erf(float v) { return erff(v); }
-__device__ __forceinline__ double dec_erf(double v) { return erf(v); }
-__device__ __forceinline__ float dec_exp(float v) { return expf(v); }
-__device__ __forceinline__ double dec_exp(double v) { return exp(v); }
-__device__ __forceinline__ float dec_log(float v) { return logf(v); }
-__device__ __forceinline__ double dec_log(double v) { return log(v); }
 
 template <class T> struct DecLinear {
   const T* x; const T* w; T* out;
@@ -106,140 +89,35 @@ __device__ __forceinline__ void dec_stats(const T* __restrict__ x, int64_t K, in
 }
 
 // ---- W [K, N] -------------------------------------------------------------------------------------------------------------------------------
-// grid (tiles of 64 * V columns, S slices of K), 64 * kDecWaves threads: every wave covers the tile's columns and a quarter of the slice.
-// V > 1 only when N % V == 0 and W is 16-byte aligned.
+// the operation of decode_stream_body.h: the image is LN(x), a finished sum goes through dec_epilogue.  V > 1 only when N % V == 0 and
+// W is 16-byte aligned.
+template <class T, int V, int RT> struct DecLinearOp {
+  using A = acc_t<T>;
+  const DecLinear<T>& p;
+  A* stat;                            // LDS [2 RT]: mean and 1 / std of the rows
+  __device__ __forceinline__ void prepare(int tid, int lane, int wave) {
+    if (p.ln) {
+      dec_stats<T, RT, kDecWaves>(p.x, p.K, p.R, p.eps, lane, wave, stat);
+      __syncthreads();
+    }
+  }
+  __device__ __forceinline__ A image(int r, int64_t k) const {
+    A v = load_as<A>(p.x[(int64_t)r * p.K + k]);
+    if (p.ln) v = dec_normalise<T>(v, stat[2 * r], stat[2 * r + 1], p.lnScale, p.lnBias, k);
+    return v;
+  }
+  __device__ __forceinline__ void finish(const A (&a)[V], int r, int64_t n0) const {
+#pragma unroll
+    for (int j = 0; j < V; j++) p.out[(int64_t)r * p.N + n0 + j] = dec_epilogue<T>(a[j], r, n0 + j, p);
+  }
+};
 template <class T, int V, int RT>
 __global__ __launch_bounds__(64 * kDecWaves) void decode_linear_kn_kernel(DecLinear<T> p) {
-  using A = acc_t<T>;
-  constexpr int RW = (RT + kDecWaves - 1) / kDecWaves;
-  __shared__ A xs[kDecKcMax * RT];                     // [k - k0][row], normalised, in acc_t
-  __shared__ A red[(kDecWaves - 1) * 64 * V];          // one row's sums of the waves 1 ..
-  __shared__ A stat[2 * RT];
-  __shared__ unsigned lastFlag;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t K = p.K, N = p.N;
-  const int R = p.R;
-  const int64_t n0 = ((int64_t)blockIdx.x * 64 + lane) * V;
-  const int64_t k0 = (int64_t)blockIdx.y * p.Kc;
-  const int kn = (int)(min(k0 + (int64_t)p.Kc, K) - k0);
-  if (p.ln) {
-    dec_stats<T, RT, kDecWaves>(p.x, K, R, p.eps, lane, wave, stat);
-    __syncthreads();
-  }
-  for (int i = tid; i < kn * RT; i += 64 * kDecWaves) {
-    const int kk = i / RT, r = i - kk * RT;
-    A v = A(0);
-    if (r < R) {
-      v = load_as<A>(p.x[(int64_t)r * K + k0 + kk]);
-      if (p.ln) v = dec_normalise<T>(v, stat[2 * r], stat[2 * r + 1], p.lnScale, p.lnBias, k0 + kk);
-    }
-    xs[i] = v;
-  }
-  __syncthreads();
-
-  A acc[RT][V];
-#pragma unroll
-  for (int r = 0; r < RT; r++)
-#pragma unroll
-    for (int j = 0; j < V; j++) acc[r][j] = A(0);
-  const bool mine = n0 < N;            // V > 1: N % V == 0, so the whole packet is inside
-  if (mine) {
-    const int kw = (kn + kDecWaves - 1) / kDecWaves, ke = min(kn, (wave + 1) * kw);
-    const T* wp = p.w + k0 * N + n0;
-    int kk = wave * kw;
-    for (; kk + kDecUnroll <= ke; kk += kDecUnroll) {
-      Vec<T, V> wv[kDecUnroll];
-#pragma unroll
-      for (int u = 0; u < kDecUnroll; u++) wv[u] = load_packet<T, V>(wp + (int64_t)(kk + u) * N);
-#pragma unroll
-      for (int u = 0; u < kDecUnroll; u++)
-#pragma unroll
-        for (int r = 0; r < RT; r++) {
-          const A xv = xs[(kk + u) * RT + r];
-#pragma unroll
-          for (int j = 0; j < V; j++) acc[r][j] += xv * load_as<A>(wv[u].v[j]);
-        }
-    }
-    for (; kk < ke; kk++) {
-      const Vec<T, V> wv = load_packet<T, V>(wp + (int64_t)kk * N);
-#pragma unroll
-      for (int r = 0; r < RT; r++) {
-        const A xv = xs[kk * RT + r];
-#pragma unroll
-        for (int j = 0; j < V; j++) acc[r][j] += xv * load_as<A>(wv.v[j]);
-      }
-    }
-  }
-  // the waves' sums, row by row through LDS, added in wave order into wave 0
-#pragma unroll
-  for (int r = 0; r < RT; r++) {
-    if (r < R) {
-      if (wave > 0)
-#pragma unroll
-        for (int j = 0; j < V; j++) red[((wave - 1) * 64 + lane) * V + j] = acc[r][j];
-      __syncthreads();
-      if (wave == 0)
-        for (int w = 0; w < kDecWaves - 1; w++)
-#pragma unroll
-          for (int j = 0; j < V; j++) acc[r][j] += red[(w * 64 + lane) * V + j];
-      __syncthreads();
-    }
-  }
-  if (p.S == 1) {
-    if (wave == 0 && mine)
-#pragma unroll
-      for (int r = 0; r < RT; r++)
-        if (r < R)
-#pragma unroll
-          for (int j = 0; j < V; j++) p.out[(int64_t)r * N + n0 + j] = dec_epilogue<T>(acc[r][j], r, n0 + j, p);
-    return;
-  }
-  // publish this slice's sums, draw a ticket; the workgroup that draws the last one adds the slabs in slice order
-  if (wave == 0 && mine) {
-#pragma unroll
-    for (int r = 0; r < RT; r++)
-      if (r < R)
-#pragma unroll
-        for (int j = 0; j < V; j++) p.slab[((int64_t)blockIdx.y * R + r) * N + n0 + j] = acc[r][j];
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned old = __hip_atomic_fetch_add(&p.ticket[blockIdx.x], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned last = old == (unsigned)(p.S - 1) ? 1u : 0u;
-    if (last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(&p.ticket[blockIdx.x], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // for the stream's next launch
-    }
-    lastFlag = last;
-  }
-  __syncthreads();
-  if (!lastFlag || !mine) return;
-  // the rows wave, wave + 4, ...: kDecSlabBatch slabs' loads in flight, added in slice order
-#pragma unroll
-  for (int q = 0; q < RW; q++) {
-    const int r = wave + kDecWaves * q;
-    if (r >= R) continue;
-    A t[V];
-#pragma unroll
-    for (int j = 0; j < V; j++) t[j] = A(0);
-    for (int s = 0; s < p.S; s += kDecSlabBatch) {
-      A b[kDecSlabBatch][V];
-#pragma unroll
-      for (int i = 0; i < kDecSlabBatch; i++)
-#pragma unroll
-        for (int j = 0; j < V; j++) b[i][j] = s + i < p.S ? p.slab[((int64_t)(s + i) * R + r) * N + n0 + j] : A(0);
-#pragma unroll
-      for (int i = 0; i < kDecSlabBatch; i++)
-#pragma unroll
-        for (int j = 0; j < V; j++) t[j] += b[i][j];
-    }
-#pragma unroll
-    for (int j = 0; j < V; j++) p.out[(int64_t)r * N + n0 + j] = dec_epilogue<T>(t[j], r, n0 + j, p);
-  }
+  __shared__ acc_t<T> stat[2 * RT];
+  DecLinearOp<T, V, RT> op{p, stat};
+  constexpr int CL = V;
+  const int64_t K = p.K;
+#include "decode_stream_body.h"
 }
 
 // ---- W [N, K] -------------------------------------------------------------------------------------------------------------------------------
@@ -437,57 +315,29 @@ __global__ __launch_bounds__(256) void decode_embedding_kernel(const T* __restri
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------------
 bool dec_dtype(int dt) { return dt == kF32 || dt == kF64 || dt == kBF16; }
-bool dec_aligned(std::initializer_list<const void*> ptrs) {
-  for (const void* q : ptrs) if (q && (uintptr_t)q % 16) return false;
-  return true;
-}
-template <class T, int V>
-void dec_launch_kn(const DecLinear<T>& p, dim3 grid, hipStream_t st) {
-  if (p.R == 1) hipLaunchKernelGGL((decode_linear_kn_kernel<T, V, 1>), grid, dim3(64 * kDecWaves), 0, st, p);
-  else if (p.R <= 4) hipLaunchKernelGGL((decode_linear_kn_kernel<T, V, 4>), grid, dim3(64 * kDecWaves), 0, st, p);
-  else hipLaunchKernelGGL((decode_linear_kn_kernel<T, V, 16>), grid, dim3(64 * kDecWaves), 0, st, p);
-}
-template <class T, int V>
-void dec_launch_nk(const DecLinear<T>& p, dim3 grid, hipStream_t st) {
-  if (p.R == 1) hipLaunchKernelGGL((decode_linear_nk_kernel<T, V, 1>), grid, dim3(64 * kDecNkWaves), 0, st, p);
-  else if (p.R <= 4) hipLaunchKernelGGL((decode_linear_nk_kernel<T, V, 4>), grid, dim3(64 * kDecNkWaves), 0, st, p);
-  else hipLaunchKernelGGL((decode_linear_nk_kernel<T, V, 16>), grid, dim3(64 * kDecNkWaves), 0, st, p);
-}
 // p holds the operands and R, K, N; the tiling is decided here
 template <class T>
 void dec_linear_run(DecLinear<T> p, bool transposed, int dev, hipStream_t st) {
-  using A = acc_t<T>;
   constexpr int VW = 16 / (int)sizeof(T);
-  const int64_t K = p.K, N = p.N, R = p.R;
-  p.S = 1; p.Kc = (int)std::min<int64_t>(K, kDecKcMax);
   if (transposed) {
-    const bool vec = K % VW == 0 && dec_aligned({p.x, p.w, p.lnScale, p.lnBias});
-    const dim3 grid((unsigned)((N + kDecNkWaves - 1) / kDecNkWaves));
-    if (vec) dec_launch_nk<T, VW>(p, grid, st); else dec_launch_nk<T, 1>(p, grid, st);
+    const bool vec = p.K % VW == 0 && dec_aligned({p.x, p.w, p.lnScale, p.lnBias});
+    const dim3 grid((unsigned)((p.N + kDecNkWaves - 1) / kDecNkWaves));
+    dec_rt_ladder(p.R, [&](auto rt) {
+      constexpr int RT = decltype(rt)::value;
+      if (vec) hipLaunchKernelGGL((decode_linear_nk_kernel<T, VW, RT>), grid, dim3(64 * kDecNkWaves), 0, st, p);
+      else hipLaunchKernelGGL((decode_linear_nk_kernel<T, 1, RT>), grid, dim3(64 * kDecNkWaves), 0, st, p);
+    });
     return;
   }
-  const bool vec = N % VW == 0 && dec_aligned({p.w});
-  const int V = vec ? VW : 1;
-  const int64_t tiles = (N + 64 * V - 1) / (64 * V);
-  LAMP_CHECK(tiles <= kDecMaxTiles, N << " columns are more than " << kDecMaxTiles << " tiles");
-  // slices of K: about two waves per compute unit in all, at most kDecMaxSlices slices, none shorter than two unrolled steps per wave or
-  // longer than the LDS image, and no more slab bytes than weight bytes
-  constexpr int64_t step = kDecWaves * kDecUnroll;
-  int64_t want = ((int64_t)num_cus() / 2 + tiles - 1) / tiles;
-  want = std::min<int64_t>(std::min<int64_t>(want, R > 4 ? kDecMaxSlices / 2 : kDecMaxSlices), std::max<int64_t>(1, (int64_t)(K * sizeof(T)) / (int64_t)(R * sizeof(A))));
-  int64_t Kc = (K + want - 1) / want;
-  Kc = std::min<int64_t>(kDecKcMax, (std::max<int64_t>(Kc, 2 * step) + step - 1) / step * step);
-  const int64_t S = (K + Kc - 1) / Kc;
-  p.Kc = (int)Kc; p.S = (int)S;
+  const DecForm f = dec_form(kDecFormLinear, p.N, sizeof(T), dec_aligned({p.w}));
+  const DecPlan pl = dec_plan(p.K, p.N, p.R, f.CL, sizeof(T), sizeof(acc_t<T>), num_cus());
   Hold slab;
-  if (S > 1) {
-    int64_t ss[3] = {S, R, N};
-    slab = Hold(new_tensor(ss, 3, sizeof(A) == 8 ? kF64 : kF32, dev));
-    p.slab = slab->ptr<A>();
-    p.ticket = dec_tickets(dev, st);
-  }
-  const dim3 grid((unsigned)tiles, (unsigned)S);
-  if (vec) dec_launch_kn<T, VW>(p, grid, st); else dec_launch_kn<T, 1>(p, grid, st);
+  dec_plan_apply<acc_t<T>>(p, pl, dev, st, slab);
+  dec_rt_ladder(p.R, [&](auto rt) {
+    constexpr int RT = decltype(rt)::value;
+    if (f.V > 1) hipLaunchKernelGGL((decode_linear_kn_kernel<T, VW, RT>), pl.grid, pl.block, 0, st, p);
+    else hipLaunchKernelGGL((decode_linear_kn_kernel<T, 1, RT>), pl.grid, pl.block, 0, st, p);
+  });
 }
 
 }  // namespace
@@ -607,12 +457,7 @@ int lamp_sample_logits_out(lamp_tensor* out, const lamp_tensor* logits, double t
   LAMP_CHECK(temperature > 0.0, "temperature must be positive, got " << temperature);
   const int64_t R = logits->sizes[0], V = logits->sizes[1];
   LAMP_CHECK(out->dtype == kI64 && out->device() == dev && out->numel() == R, "out must hold " << R << " int64 elements on the logits' device, got " << out->describe());
-  int64_t ostride = 1;
-  {
-    int big = 0;
-    for (int i = 0; i < out->ndim; i++) if (out->sizes[i] != 1) { big++; ostride = out->strides[i]; }
-    LAMP_CHECK(big <= 1, "out must be a vector or one column of a matrix, got " << out->describe());
-  }
+  const int64_t ostride = dec_vector_stride(out, "out must be a vector or one column of a matrix");
   if (uniforms_or_null) {
     check_device_tensor(uniforms_or_null, "uniforms");
     LAMP_CHECK(uniforms_or_null->dtype == kF64 && uniforms_or_null->device() == dev && uniforms_or_null->numel() == R && uniforms_or_null->is_contiguous(),
@@ -658,12 +503,7 @@ int lamp_decode_embedding(lamp_tensor** out, const lamp_tensor* tokenWeight, con
   LAMP_CHECK(t >= 0 && t < positionWeight->sizes[0], "position " << t << " is outside a table of " << positionWeight->sizes[0] << " rows");
   LAMP_CHECK(tokens->dtype == kI64 && tokens->device() == dev, "tokens must be int64 on the tables' device, got " << tokens->describe());
   const int64_t R = tokens->numel(), D = tokenWeight->sizes[1];
-  int64_t tstride = 1;
-  {
-    int big = 0;
-    for (int i = 0; i < tokens->ndim; i++) if (tokens->sizes[i] != 1) { big++; tstride = tokens->strides[i]; }
-    LAMP_CHECK(big <= 1, "tokens must be a vector or one column of a matrix, got " << tokens->describe());
-  }
+  const int64_t tstride = dec_vector_stride(tokens, "tokens must be a vector or one column of a matrix");
   Hold tw(contiguous(tokenWeight)), pw(contiguous(positionWeight));
   int64_t os[2] = {R, D};
   Hold o(new_tensor(os, 2, dt, dev));
@@ -681,6 +521,26 @@ int lamp_decode_embedding(lamp_tensor** out, const lamp_tensor* tokenWeight, con
     LAMP_LAUNCH_CHECK();
   }
   *out = o.take();
+  LAMP_API_END
+}
+
+// Test tool, needs no GPU: the launch of a [R, K] . [K, N] product of these kernels through the functions dec_linear_run and rd_step_run use, on
+// a device of `cus` compute units.  form: kDecFormLinear, or the cell (LAMP_RECURRENT_*, kDecFormGru2) whose packed matrix w is; dims =
+// {K, N}; w_aligned: w sits on a 16-byte boundary.  One line into buf:
+// "tiles=<column tiles> kc=<K per slice> s=<slices> grid=<x>x<y> block=<threads> cl=<columns per lane> v=<packet> rt=<rows built for> unroll=<n>"
+int lamp_debug_decode_plan(int dtype, int form, int64_t R, const int64_t* dims, int w_aligned, int cus, char* buf, int buflen) {
+  LAMP_API_BEGIN
+  LAMP_CHECK(dims && buf && buflen > 0 && cus > 0 && R >= 1 && R <= kDecMaxRows && dims[0] >= 1 && dims[1] >= 1, "lamp_debug_decode_plan: bad arguments");
+  LAMP_CHECK(form >= 0 && form <= kDecFormLinear && (form == kDecFormLinear ? dec_dtype(dtype) : dtype == kF32 || dtype == kF64),
+             "lamp_debug_decode_plan: a linear product in f32, f64 or bf16, or a cell in f32 or f64");
+  const size_t tsize = dtype_size(dtype), asize = dtype == kF64 ? 8 : 4;
+  const DecForm f = dec_form(form, dims[1], tsize, w_aligned != 0);
+  const DecPlan pl = dec_plan(dims[0], dims[1], R, f.CL, tsize, asize, cus);
+  char line[256];
+  const int n = snprintf(line, sizeof(line), "tiles=%lld kc=%d s=%d grid=%ux%u block=%u cl=%d v=%d rt=%d unroll=%d\n", (long long)pl.tiles, pl.Kc, pl.S,
+                         pl.grid.x, pl.grid.y, pl.block.x, f.CL, f.V, dec_rt((int)R), f.unroll);
+  LAMP_CHECK(n < buflen, "lamp_debug_decode_plan: buffer too small");
+  memcpy(buf, line, n + 1);
   LAMP_API_END
 }
 

@@ -6,14 +6,12 @@
 //   recurrent_decode_pack_kernel   once per generation: Wx over Wh as one [E + H, nG * H] matrix whose columns are gate-interleaved (column
 //                                  j * nG + g is gate g of hidden unit j; LSTM i f o c, GRU r z h^, RNN h), the biases in the same order.  GRU:
 //                                  the candidate's rows below E are zero, its Whh goes to a matrix of its own for the second phase.
-//   recurrent_decode_step_kernel   gates[r] = bias + table[tokens[r]] . Wx + state[parent[r]] . Wh, then the cell of kernels/recurrent.hip.  Built
-//                                  as decode_linear_kn_kernel: grid (tiles of 64 * CL columns, S slices of K), four waves that each take a
-//                                  quarter of the slice; the input image (the gathered embedding row, then the state row) sits in LDS as
-//                                  [k][row] and is read as a broadcast; a lane owns CL neighbouring columns = whole hidden units (LSTM 4 = one
-//                                  unit, GRU 3 = one unit, RNN one packet of units) and keeps RT x CL sums.  The waves' sums are added in wave
-//                                  order through LDS; with S > 1 the slices' sums go to slabs and the workgroup that draws the tile's last
-//                                  integer ticket adds them in slice order and applies the cell.  GRU takes two launches: the first produces
-//                                  z, r * h and the candidate's x . Wxh + bh, the second adds (r * h) . Whh and produces h.
+//   recurrent_decode_step_kernel   gates[r] = bias + table[tokens[r]] . Wx + state[parent[r]] . Wh, then the cell of kernels/recurrent.hip: an
+//                                  operation of the body decode_stream_body.h (which holds the stream loop, the wave and slab
+//                                  reductions and the ticket protocol).  The operation checks the rows' tokens and parents, gives the image
+//                                  (the gathered embedding row, then the state row) and applies the cell to a lane's CL neighbouring columns =
+//                                  whole hidden units (LSTM 4 = one unit, GRU 3 = one unit, RNN one packet of units).  GRU takes two launches:
+//                                  the first produces z, r * h and the candidate's x . Wxh + bh, the second adds (r * h) . Whh and produces h.
 //   log_softmax_argmax_rows_kernel a workgroup per row: maximum, sum of exp, logits - max - log(sum) stored (or the logits passed through),
 //                                  then the index of the largest STORED value, lowest index among equals, NaN first as lamp_argmax has it.
 // No kernel uses a floating atomic and every sum has a fixed order: the results are functions of the inputs, bit for bit.
@@ -21,34 +19,13 @@
 // Registers (hipcc -Rpass-analysis=kernel-resource-usage, gfx950), recurrent_decode_step_kernel at 1 / 2 .. 4 / 5 .. 16 rows:
 //   LSTM (a unit = one f32 packet, two f64 packets)   f32  64 /  76 / 132 VGPRs     f64 104 / 128 / 232
 //   GRU, first launch (three columns, element loads)  f32  68 /  74 / 106           f64  86 / 104 / 182
-//   RNN and GRU's second launch, packet form          f32  64 /  76 / 128           f64  67 /  76 / 128
+//   RNN and GRU's second launch, packet form          f32  64 /  76 / 128           f64  67 /  76 / 128 (126 in the second launch)
 //   the same, element form                            f32  44 /  68 /  72           f64  59 /  66 /  80
 // log_softmax_argmax_rows_kernel 22 (f32) and 51 (f64), the pack kernel 21.  No kernel of this file uses scratch memory.
-#include <algorithm>
-#include <cstdint>
-#include "decode_tickets.h"
-#include "device_utils.h"
+#include "decode_stream.h"
 
 namespace lamp {
 namespace {
-
-constexpr int kRdMaxRows = LAMP_DECODE_MAX_ROWS;
-constexpr int kRdKcMax = 256;       // the longest slice of K a workgroup takes: the LDS image is [kRdKcMax][RT]
-constexpr int kRdWaves = 4;         // waves of a workgroup: each takes a quarter of the workgroup's slice of K
-constexpr int kRdMaxSlices = 16;    // slices of K across workgroups (8 beyond four rows)
-constexpr int kRdSlabBatch = 8;     // slabs whose loads the reducing workgroup keeps in flight
-constexpr int kRdGru2 = 3;          // the kernel's fourth cell: GRU's second phase (0 .. 2 are LAMP_RECURRENT_RNN / _GRU / _LSTM)
-
-template <class T> __device__ __forceinline__ T rd_exp(T x);
-template <> __device__ __forceinline__ float rd_exp(float x) { return expf(x); }
-template <> __device__ __forceinline__ double rd_exp(double x) { return exp(x); }
-template <class T> __device__ __forceinline__ T rd_log(T x);
-template <> __device__ __forceinline__ float rd_log(float x) { return logf(x); }
-template <> __device__ __forceinline__ double rd_log(double x) { return log(x); }
-template <class T> __device__ __forceinline__ T rd_tanh(T x);
-template <> __device__ __forceinline__ float rd_tanh(float x) { return tanhf(x); }
-template <> __device__ __forceinline__ double rd_tanh(double x) { return tanh(x); }
-template <class T> __device__ __forceinline__ T rd_sigmoid(T x) { return T(1) / (T(1) + rd_exp<T>(-x)); }   // rc_sigmoid of recurrent.hip
 
 // ---- pack -----------------------------------------------------------------------------------------------------------------------------------
 template <class T> struct RdPack {
@@ -89,17 +66,17 @@ __device__ __forceinline__ void rd_cell(const T (&a)[CL], int r, int pr, int64_t
   const int64_t H = p.H;
   if constexpr (CELL == LAMP_RECURRENT_LSTM) {          // CL == 4: i f o c of unit j (LSTM.scala:67-74, lstm_cell_fwd_kernel)
     const int64_t j = n0 / 4;
-    const T gi = rd_sigmoid<T>(a[0] + p.bias[n0]), gf = rd_sigmoid<T>(a[1] + p.bias[n0 + 1]), go = rd_sigmoid<T>(a[2] + p.bias[n0 + 2]);
-    const T gc = rd_tanh<T>(a[3] + p.bias[n0 + 3]);
+    const T gi = dec_sigmoid(a[0] + p.bias[n0]), gf = dec_sigmoid(a[1] + p.bias[n0 + 1]), go = dec_sigmoid(a[2] + p.bias[n0 + 2]);
+    const T gc = dec_tanh(a[3] + p.bias[n0 + 3]);
     const T cp = pr >= 0 ? p.cprev[(int64_t)pr * H + j] : T(0);
     const T cn = gf * cp + gi * gc;
-    const T hn = go * rd_tanh<T>(cn);
+    const T hn = go * dec_tanh(cn);
     p.c[(int64_t)r * H + j] = cn;
     p.h[(int64_t)r * H + j] = hn;
     if (p.relu) p.relu[(int64_t)r * H + j] = hn > T(0) ? hn : T(0);
   } else if constexpr (CELL == LAMP_RECURRENT_GRU) {    // CL == 3: r z h^ of unit j (GRU.scala:52-54, gru_gates_fwd_kernel)
     const int64_t j = n0 / 3;
-    const T gr = rd_sigmoid<T>(a[0] + p.bias[n0]), gz = rd_sigmoid<T>(a[1] + p.bias[n0 + 1]);
+    const T gr = dec_sigmoid(a[0] + p.bias[n0]), gz = dec_sigmoid(a[1] + p.bias[n0 + 1]);
     const T hp = pr >= 0 ? p.hprev[(int64_t)pr * H + j] : T(0);
     p.zo[(int64_t)r * H + j] = gz;
     p.rho[(int64_t)r * H + j] = gr * hp;
@@ -109,12 +86,12 @@ __device__ __forceinline__ void rd_cell(const T (&a)[CL], int r, int pr, int64_t
     for (int u = 0; u < CL; u++) {
       const int64_t j = n0 + u;
       T hn;
-      if constexpr (CELL == kRdGru2) {                  // GRU.scala:54-56, gru_out_fwd_kernel
-        const T gz = p.z[(int64_t)r * H + j], gh = rd_tanh<T>(p.pre[(int64_t)r * H + j] + a[u]);
+      if constexpr (CELL == kDecFormGru2) {                  // GRU.scala:54-56, gru_out_fwd_kernel
+        const T gz = p.z[(int64_t)r * H + j], gh = dec_tanh(p.pre[(int64_t)r * H + j] + a[u]);
         const T hp = pr >= 0 ? p.hprev[(int64_t)pr * H + j] : T(0);
         hn = gz * hp + (gz * T(-1) + T(1)) * gh;
       } else {                                // RNN.scala:40
-        hn = rd_tanh<T>(a[u] + p.bias[j]);
+        hn = dec_tanh(a[u] + p.bias[j]);
       }
       p.h[(int64_t)r * H + j] = hn;
       if (p.relu) p.relu[(int64_t)r * H + j] = hn > T(0) ? hn : T(0);
@@ -122,161 +99,47 @@ __device__ __forceinline__ void rd_cell(const T (&a)[CL], int r, int pr, int64_t
   }
 }
 
-// grid (tiles of 64 * CL columns, S slices of K = E + H), 64 * kRdWaves threads.  CL columns per lane in CL / V packets; V > 1 only when
-// N % CL == 0 and w is 16-byte aligned.  N % CL == 0 always: a lane's columns are inside or outside together.
-template <class T, int CELL, int CL, int V, int RT>
-__global__ __launch_bounds__(64 * kRdWaves) void recurrent_decode_step_kernel(RdStep<T> p) {
-  constexpr int RW = (RT + kRdWaves - 1) / kRdWaves;
-  constexpr int NP = CL / V;
-  constexpr int UN = CL * sizeof(T) > 16 ? 4 : 8;       // steps of k whose weight loads are in flight per lane
-  __shared__ T xs[kRdKcMax * RT];                       // [k - k0][row]
-  __shared__ T red[(kRdWaves - 1) * 64 * CL];           // one row's sums of the waves 1 ..
-  __shared__ long long tok[RT];                         // the row's token, -1 outside the table
-  __shared__ int irow[RT], prow[RT];                    // the row of src for the image, the row of the previous state for the cell; -1 outside
-  __shared__ unsigned lastFlag;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t E = p.E, H = p.H, N = p.N, K = E + H;
-  const int R = p.R;
-  const int64_t n0 = ((int64_t)blockIdx.x * 64 + lane) * CL;
-  const int64_t k0 = (int64_t)blockIdx.y * p.Kc;
-  const int kn = (int)(min(k0 + (int64_t)p.Kc, K) - k0);
-  if (tid < RT) {
-    long long t = -1;
-    int pr = -1;
-    if (tid < R) {
-      if (E > 0) {
-        t = p.tokens[(int64_t)tid * p.tstride];
-        if (t < 0 || t >= p.Vt) { t = -1; *(volatile int*)p.assert_word = kAssertIndexRange; }   // the bound is tested before an address is formed
-      }
-      const int64_t q = p.parent ? p.parent[tid] : (int64_t)tid;
-      if (q < 0 || q >= p.Rp) *(volatile int*)p.assert_word = kAssertIndexRange;
-      else pr = (int)q;
-    }
-    tok[tid] = t;
-    prow[tid] = pr;
-    irow[tid] = CELL == kRdGru2 ? (tid < R ? tid : -1) : pr;
-  }
-  __syncthreads();
-  for (int i = tid; i < kn * RT; i += 64 * kRdWaves) {
-    const int kk = i / RT, r = i - kk * RT;
-    const int64_t k = k0 + kk;
-    T v = T(0);
-    if (r < R) {
-      if (k < E) { if (tok[r] >= 0) v = p.table[(int64_t)tok[r] * E + k]; }
-      else if (irow[r] >= 0) v = p.src[(int64_t)irow[r] * H + (k - E)];
-    }
-    xs[i] = v;
-  }
-  __syncthreads();
-
-  T acc[RT][CL];
-#pragma unroll
-  for (int r = 0; r < RT; r++)
-#pragma unroll
-    for (int j = 0; j < CL; j++) acc[r][j] = T(0);
-  const bool mine = n0 < N;
-  if (mine) {
-    const int kw = (kn + kRdWaves - 1) / kRdWaves, ke = min(kn, (wave + 1) * kw);
-    const T* wp = p.w + k0 * N + n0;
-    int kk = wave * kw;
-    for (; kk + UN <= ke; kk += UN) {
-      Vec<T, V> wv[UN][NP];
-#pragma unroll
-      for (int u = 0; u < UN; u++)
-#pragma unroll
-        for (int q = 0; q < NP; q++) wv[u][q] = load_packet<T, V>(wp + (int64_t)(kk + u) * N + q * V);
-#pragma unroll
-      for (int u = 0; u < UN; u++)
-#pragma unroll
-        for (int r = 0; r < RT; r++) {
-          const T xv = xs[(kk + u) * RT + r];
-#pragma unroll
-          for (int q = 0; q < NP; q++)
-#pragma unroll
-            for (int j = 0; j < V; j++) acc[r][q * V + j] += xv * wv[u][q].v[j];
+// the operation of decode_stream_body.h: the image is the gathered embedding row over the state row, the finished sums of a lane's
+// CL columns (whole hidden units, N % CL == 0) go through rd_cell.  CL columns in CL / V packets; V > 1 only when N % V == 0 and w is
+// 16-byte aligned.
+template <class T, int CELL, int CL, int RT> struct RdStepOp {
+  const RdStep<T>& p;
+  long long* tok;                     // LDS [RT]: the row's token, -1 outside the table
+  int* irow; int* prow;               // LDS [RT]: the row of src for the image, the row of the previous state for the cell; -1 outside
+  __device__ __forceinline__ void prepare(int tid, int, int) {
+    if (tid < RT) {
+      long long t = -1;
+      int pr = -1;
+      if (tid < p.R) {
+        if (p.E > 0) {
+          t = p.tokens[(int64_t)tid * p.tstride];
+          if (t < 0 || t >= p.Vt) { t = -1; *(volatile int*)p.assert_word = kAssertIndexRange; }   // the bound is tested before an address is formed
         }
-    }
-    for (; kk < ke; kk++) {
-      Vec<T, V> wv[NP];
-#pragma unroll
-      for (int q = 0; q < NP; q++) wv[q] = load_packet<T, V>(wp + (int64_t)kk * N + q * V);
-#pragma unroll
-      for (int r = 0; r < RT; r++) {
-        const T xv = xs[kk * RT + r];
-#pragma unroll
-        for (int q = 0; q < NP; q++)
-#pragma unroll
-          for (int j = 0; j < V; j++) acc[r][q * V + j] += xv * wv[q].v[j];
+        const int64_t q = p.parent ? p.parent[tid] : (int64_t)tid;
+        if (q < 0 || q >= p.Rp) *(volatile int*)p.assert_word = kAssertIndexRange;
+        else pr = (int)q;
       }
+      tok[tid] = t;
+      prow[tid] = pr;
+      irow[tid] = CELL == kDecFormGru2 ? (tid < p.R ? tid : -1) : pr;
     }
+    __syncthreads();
   }
-  // the waves' sums, row by row through LDS, added in wave order into wave 0
-#pragma unroll
-  for (int r = 0; r < RT; r++) {
-    if (r < R) {
-      if (wave > 0)
-#pragma unroll
-        for (int j = 0; j < CL; j++) red[((wave - 1) * 64 + lane) * CL + j] = acc[r][j];
-      __syncthreads();
-      if (wave == 0)
-        for (int w = 0; w < kRdWaves - 1; w++)
-#pragma unroll
-          for (int j = 0; j < CL; j++) acc[r][j] += red[(w * 64 + lane) * CL + j];
-      __syncthreads();
-    }
+  __device__ __forceinline__ T image(int r, int64_t k) const {
+    T v = T(0);
+    if (k < p.E) { if (tok[r] >= 0) v = p.table[(int64_t)tok[r] * p.E + k]; }
+    else if (irow[r] >= 0) v = p.src[(int64_t)irow[r] * p.H + (k - p.E)];
+    return v;
   }
-  if (p.S == 1) {
-    if (wave == 0 && mine)
-#pragma unroll
-      for (int r = 0; r < RT; r++)
-        if (r < R) rd_cell<T, CELL, CL>(acc[r], r, prow[r], n0, p);
-    return;
-  }
-  // publish this slice's sums, draw a ticket; the workgroup that draws the last one adds the slabs in slice order (decode_linear_kn_kernel)
-  if (wave == 0 && mine) {
-#pragma unroll
-    for (int r = 0; r < RT; r++)
-      if (r < R)
-#pragma unroll
-        for (int j = 0; j < CL; j++) p.slab[((int64_t)blockIdx.y * R + r) * N + n0 + j] = acc[r][j];
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned old = __hip_atomic_fetch_add(&p.ticket[blockIdx.x], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned last = old == (unsigned)(p.S - 1) ? 1u : 0u;
-    if (last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(&p.ticket[blockIdx.x], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // for the stream's next launch
-    }
-    lastFlag = last;
-  }
-  __syncthreads();
-  if (!lastFlag || !mine) return;
-  // the rows wave, wave + 4, ...: kRdSlabBatch slabs' loads in flight, added in slice order
-#pragma unroll
-  for (int q = 0; q < RW; q++) {
-    const int r = wave + kRdWaves * q;
-    if (r >= R) continue;
-    T t[CL];
-#pragma unroll
-    for (int j = 0; j < CL; j++) t[j] = T(0);
-    for (int s = 0; s < p.S; s += kRdSlabBatch) {
-      T b[kRdSlabBatch][CL];
-#pragma unroll
-      for (int i = 0; i < kRdSlabBatch; i++)
-#pragma unroll
-        for (int j = 0; j < CL; j++) b[i][j] = s + i < p.S ? p.slab[((int64_t)(s + i) * R + r) * N + n0 + j] : T(0);
-#pragma unroll
-      for (int i = 0; i < kRdSlabBatch; i++)
-#pragma unroll
-        for (int j = 0; j < CL; j++) t[j] += b[i][j];
-    }
-    rd_cell<T, CELL, CL>(t, r, prow[r], n0, p);
-  }
+  __device__ __forceinline__ void finish(const T (&a)[CL], int r, int64_t n0) const { rd_cell<T, CELL, CL>(a, r, prow[r], n0, p); }
+};
+template <class T, int CELL, int CL, int V, int RT>
+__global__ __launch_bounds__(64 * kDecWaves) void recurrent_decode_step_kernel(RdStep<T> p) {
+  __shared__ long long tok[RT];
+  __shared__ int irow[RT], prow[RT];
+  RdStepOp<T, CELL, CL, RT> op{p, tok, irow, prow};
+  const int64_t K = p.E + p.H;
+#include "decode_stream_body.h"
 }
 
 // ---- log-softmax + argmax -------------------------------------------------------------------------------------------------------------------
@@ -299,9 +162,9 @@ __global__ __launch_bounds__(256) void log_softmax_argmax_rows_kernel(const T* _
     for (int64_t i = tid; i < V; i += 256) { const T v = xr[i]; m = v > m ? v : m; }
     m = block_max(m, red);
     T s = T(0);
-    for (int64_t i = tid; i < V; i += 256) s += rd_exp<T>(xr[i] - m);
+    for (int64_t i = tid; i < V; i += 256) s += dec_exp(xr[i] - m);
     s = block_sum(s, red);
-    ls = rd_log<T>(s);
+    ls = dec_log(s);
   }
   // ascending indices per thread, lamp_argmax's rule: a larger value or the first NaN replaces the best
   T best = T(0);
@@ -331,50 +194,32 @@ __global__ __launch_bounds__(256) void log_softmax_argmax_rows_kernel(const T* _
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------------
-bool rd_aligned(const void* q) { return (uintptr_t)q % 16 == 0; }
-
 template <class T, int CELL, int CL, int V>
-void rd_launch(const RdStep<T>& p, dim3 grid, hipStream_t st) {
-  if (p.R == 1) hipLaunchKernelGGL((recurrent_decode_step_kernel<T, CELL, CL, V, 1>), grid, dim3(64 * kRdWaves), 0, st, p);
-  else if (p.R <= 4) hipLaunchKernelGGL((recurrent_decode_step_kernel<T, CELL, CL, V, 4>), grid, dim3(64 * kRdWaves), 0, st, p);
-  else hipLaunchKernelGGL((recurrent_decode_step_kernel<T, CELL, CL, V, 16>), grid, dim3(64 * kRdWaves), 0, st, p);
+void rd_launch(const RdStep<T>& p, const DecForm& f, const DecPlan& pl, hipStream_t st) {
+  LAMP_CHECK(f.CL == CL && f.V == V, "the step kernel <" << CL << ", " << V << "> is not the planned form <" << f.CL << ", " << f.V << ">");
+  dec_rt_ladder(p.R, [&](auto rt) {
+    hipLaunchKernelGGL((recurrent_decode_step_kernel<T, CELL, CL, V, decltype(rt)::value>), pl.grid, pl.block, 0, st, p);
+  });
 }
 
-// p holds the operands, R, E, H and N; the tiling is decided here as dec_linear_run decides it.  `slab` keeps the slabs alive for the caller.
+// p holds the operands, R, E, H and N; the form is dec_form's, the tiling dec_plan's.  `slab` keeps the slabs alive for the caller.
 template <class T>
 void rd_step_run(RdStep<T> p, int cell, int dev, hipStream_t st, Hold& slab) {
   constexpr int VW = 16 / (int)sizeof(T);
-  const int64_t K = p.E + p.H, N = p.N, R = p.R;
-  const bool vec = cell != LAMP_RECURRENT_GRU && N % VW == 0 && rd_aligned(p.w);
-  const int CL = cell == LAMP_RECURRENT_LSTM ? 4 : cell == LAMP_RECURRENT_GRU ? 3 : vec ? VW : 1;
-  const int64_t tiles = (N + 64 * CL - 1) / (64 * CL);
-  LAMP_CHECK(tiles <= kDecMaxTiles, N << " columns are more than " << kDecMaxTiles << " tiles");
-  // slices of K: about two waves per compute unit in all, at most kRdMaxSlices slices, none shorter than two unrolled steps per wave or
-  // longer than the LDS image, and no more slab bytes than weight bytes
-  constexpr int64_t step = kRdWaves * 8;
-  int64_t want = ((int64_t)num_cus() / 2 + tiles - 1) / tiles;
-  want = std::min<int64_t>(std::min<int64_t>(want, R > 4 ? kRdMaxSlices / 2 : kRdMaxSlices), std::max<int64_t>(1, K / R));
-  int64_t Kc = (K + want - 1) / want;
-  Kc = std::min<int64_t>(kRdKcMax, (std::max<int64_t>(Kc, 2 * step) + step - 1) / step * step);
-  const int64_t S = (K + Kc - 1) / Kc;
-  p.Kc = (int)Kc; p.S = (int)S;
-  if (S > 1) {
-    int64_t ss[3] = {S, R, N};
-    slab = Hold(new_tensor(ss, 3, sizeof(T) == 8 ? kF64 : kF32, dev));
-    p.slab = slab->ptr<T>();
-    p.ticket = dec_tickets(dev, st);
-  }
-  const dim3 grid((unsigned)tiles, (unsigned)S);
+  const DecForm f = dec_form(cell, p.N, sizeof(T), dec_aligned({p.w}));
+  const DecPlan pl = dec_plan(p.E + p.H, p.N, p.R, f.CL, sizeof(T), sizeof(acc_t<T>), num_cus());
+  dec_plan_apply<acc_t<T>>(p, pl, dev, st, slab);
+  const bool vec = f.V > 1;
   switch (cell) {
     case LAMP_RECURRENT_LSTM:
-      if (vec) rd_launch<T, LAMP_RECURRENT_LSTM, 4, VW>(p, grid, st); else rd_launch<T, LAMP_RECURRENT_LSTM, 4, 1>(p, grid, st);
+      if (vec) rd_launch<T, LAMP_RECURRENT_LSTM, 4, VW>(p, f, pl, st); else rd_launch<T, LAMP_RECURRENT_LSTM, 4, 1>(p, f, pl, st);
       break;
-    case LAMP_RECURRENT_GRU: rd_launch<T, LAMP_RECURRENT_GRU, 3, 1>(p, grid, st); break;
-    case kRdGru2:
-      if (vec) rd_launch<T, kRdGru2, VW, VW>(p, grid, st); else rd_launch<T, kRdGru2, 1, 1>(p, grid, st);
+    case LAMP_RECURRENT_GRU: rd_launch<T, LAMP_RECURRENT_GRU, 3, 1>(p, f, pl, st); break;
+    case kDecFormGru2:
+      if (vec) rd_launch<T, kDecFormGru2, VW, VW>(p, f, pl, st); else rd_launch<T, kDecFormGru2, 1, 1>(p, f, pl, st);
       break;
     default:
-      if (vec) rd_launch<T, LAMP_RECURRENT_RNN, VW, VW>(p, grid, st); else rd_launch<T, LAMP_RECURRENT_RNN, 1, 1>(p, grid, st);
+      if (vec) rd_launch<T, LAMP_RECURRENT_RNN, VW, VW>(p, f, pl, st); else rd_launch<T, LAMP_RECURRENT_RNN, 1, 1>(p, f, pl, st);
       break;
   }
 }
@@ -383,14 +228,6 @@ int rd_gates(int kind) { return kind == LAMP_RECURRENT_LSTM ? 4 : kind == LAMP_R
 void rd_check_kind(int kind) {
   LAMP_CHECK(kind == LAMP_RECURRENT_RNN || kind == LAMP_RECURRENT_GRU || kind == LAMP_RECURRENT_LSTM,
              "kind must be LAMP_RECURRENT_RNN, _GRU or _LSTM, got " << kind);
-}
-// the one stride of an int64 tensor of n elements that is a vector or one row / column of a matrix
-int64_t rd_vector_stride(const lamp_tensor* v, const char* what) {
-  int64_t stride = 1;
-  int big = 0;
-  for (int i = 0; i < v->ndim; i++) if (v->sizes[i] != 1) { big++; stride = v->strides[i]; }
-  LAMP_CHECK(big <= 1, what << " must be a vector or one row or column of a matrix, got " << v->describe());
-  return stride;
 }
 
 }  // namespace
@@ -467,8 +304,8 @@ int lamp_recurrent_decode_step(int kind, const lamp_tensor* table, const lamp_te
   const int64_t Vt = table->sizes[0], E = table->sizes[1];
   LAMP_CHECK(tokens->dtype == kI64 && tokens->device() == dev, "tokens must be int64 on the table's device, got " << tokens->describe());
   const int64_t R = tokens->numel();
-  LAMP_CHECK(R >= 1 && R <= kRdMaxRows, R << " rows: this is the kernel of 1 .. " << kRdMaxRows << " rows, longer inputs are the module's forward");
-  const int64_t tstride = rd_vector_stride(tokens, "tokens");
+  LAMP_CHECK(R >= 1 && R <= kDecMaxRows, R << " rows: this is the kernel of 1 .. " << kDecMaxRows << " rows, longer inputs are the module's forward");
+  const int64_t tstride = dec_vector_stride(tokens, "tokens must be a vector or one row or column of a matrix");
   LAMP_CHECK(w->ndim == 2 && w->dtype == dt && w->device() == dev && w->is_contiguous() && w->sizes[0] > E && w->sizes[1] % nG == 0 &&
                  w->sizes[1] / nG == w->sizes[0] - E && E >= 1,
              "w must be the packed [E + H, " << nG << " H] of lamp_recurrent_decode_pack for a table " << table->describe() << ", got " << w->describe());
@@ -535,7 +372,7 @@ int lamp_recurrent_decode_step(int kind, const lamp_tensor* table, const lamp_te
       q.table = nullptr; q.tokens = nullptr; q.E = 0; q.N = H; q.src = p.rho; q.w = wh2_or_null->ptr<T>(); q.bias = nullptr;                \
       q.z = p.zo; q.pre = p.preo; q.slab = nullptr; q.ticket = nullptr;                                                                     \
       KernelTimer kt("recurrent_decode_gru_out", 2.0 * R * H * H, ((double)H * H + 5.0 * R * H) * sz, st);                                  \
-      rd_step_run<T>(q, kRdGru2, dev, st, slab2);                                                                                           \
+      rd_step_run<T>(q, kDecFormGru2, dev, st, slab2);                                                                                           \
     }                                                                                                                                       \
   }
   if (dt == kF32) RD_STEP(float) else RD_STEP(double)
@@ -555,7 +392,7 @@ int lamp_log_softmax_argmax_rows(lamp_tensor* out, lamp_tensor* tokens_out, cons
              "out must be [" << R << ", " << V << "] of the logits' type with unit column stride, got " << out->describe());
   LAMP_CHECK(tokens_out->dtype == kI64 && tokens_out->device() == dev && tokens_out->numel() == R,
              "tokens_out must hold " << R << " int64 elements on the logits' device, got " << tokens_out->describe());
-  const int64_t tstride = rd_vector_stride(tokens_out, "tokens_out");
+  const int64_t tstride = dec_vector_stride(tokens_out, "tokens_out must be a vector or one row or column of a matrix");
   if (R == 0) return 0;
   LAMP_CHECK(R <= 65535 * 32768LL, R << " rows are more than a grid holds");
   hipStream_t st = current_stream(dev);

@@ -61,16 +61,24 @@ def _timer_counts(fn):
 
 # ---- lamp_recurrent_decode_step -------------------------------------------------------------------------------------------------------------
 TOKENS = [6, 0, 3, 3, 1, 5, 2, 4, 6, 0, 3, 1, 5, 2, 4, 6]       # a table of 7 rows: 0 and 6 present, repeats across rows
+STEP_SHAPES = [(R, E, H) for R in (1, 3, 16) for E in (3, 8) for H in (5, 64, 320)] + [(1, 8, 640), (3, 8, 640)]      # (R, E, H)
 
 
-def _step_case(kind, dt, R, E, H, bias2d):
-    what = f"{kind} {dt} R={R} E={E} H={H} bias2d={bias2d}"
-    ts = lambda t: to_sten(t.to(dt))
+def _step_inputs(kind, dt, R, E, H, bias2d):
+    """the cell's weights, the embedding table, the tokens and the previous state of a step case, f64 holding values of dt (also the
+    inputs of scripts/decode_digest.py)"""
     w = _cell_weights(kind, E, H, dt, bias2d, salt=R + E)
     table = closed_form((7, E), 5, 2.0, F64).to(dt).to(F64)
     tok = torch.tensor(TOKENS[:R] if R > 1 else [6], dtype=torch.int64)
     nstate = 2 if kind == "lstm" else 1
     state = [closed_form((R, H), 201 + k, 1.0, F64).to(dt).to(F64) for k in range(nstate)]
+    return w, table, tok, state
+
+
+def _step_case(kind, dt, R, E, H, bias2d):
+    what = f"{kind} {dt} R={R} E={E} H={H} bias2d={bias2d}"
+    ts = lambda t: to_sten(t.to(dt))
+    w, table, tok, state = _step_inputs(kind, dt, R, E, H, bias2d)
     x = table[tok].unsqueeze(0)                                                     # Embedding(tokens) at one time step
     ref_out, ref_state = TR.cell_forward(kind, x, w, state)
     # e_c: the module's own forward at T = 1
@@ -111,13 +119,10 @@ def _step_case(kind, dt, R, E, H, bias2d):
 @KINDS
 def test_step_kernel_vs_module_and_restatement(gpu, kind, dt):
     """R in {1, 3, 16} x E in {3, 8} x H in {5 (element form, partial tile), 64, 320 (several column tiles and slices of K: the ticket path)},
-    the two bias shapes alternating.  The figures are printed per tensor (run with -s)."""
-    n = 0
-    for R in (1, 3, 16):
-        for E in (3, 8):
-            for H in (5, 64, 320):
-                _step_case(kind, dt, R, E, H, bias2d=bool(n % 2))
-                n += 1
+    then H = 640 at E = 8 and R in {1, 3}: 11 slices of K (10 in GRU's second phase), the smallest shape whose slab reduction runs a
+    partial second batch of eight.  The two bias shapes alternate.  The figures are printed per tensor (run with -s)."""
+    for n, (R, E, H) in enumerate(STEP_SHAPES):
+        _step_case(kind, dt, R, E, H, bias2d=bool(n % 2))
 
 
 def test_step_kernel_refuses_bad_arguments(gpu):

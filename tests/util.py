@@ -54,6 +54,24 @@ def gemm_plan(dt, M, N, K, batch=1, a_kc=True, b_kc=False, cus=256, lda=None, ld
     return parts
 
 
+DECODE_FORMS = {"rnn": 0, "gru": 1, "lstm": 2, "gru2": 3, "linear": 4}      # LAMP_RECURRENT_*, GRU's second phase, decode_linear's [K, N]
+
+
+def decode_plan(dt, form, R, K=None, N=None, E=None, H=None, aligned=True, cus=256):
+    """The launch the library plans for a split-K weight-streaming decode product on a device of `cus` compute units
+    (lamp_debug_decode_plan: the functions the real path uses, no GPU needed).  form "linear": x [R, K] . w [K, N]; a cell ("rnn", "gru",
+    "lstm"): its packed [E + H, gates * H] matrix; "gru2": GRU's second phase, [H, H].  aligned: w sits on a 16-byte boundary."""
+    import ctypes as C
+    from lamp_amd._capi import lib, i64_array
+    if form != "linear":
+        K, N = (H, H) if form == "gru2" else (E + H, {"rnn": 1, "gru": 3, "lstm": 4}[form] * H)
+    buf = C.create_string_buffer(256)
+    lib.lamp_debug_decode_plan(TORCH2LAMP[dt], DECODE_FORMS[form], C.c_int64(R), i64_array([K, N]), int(aligned), int(cus), buf, len(buf))
+    d = dict(x.split("=") for x in buf.value.decode().split())
+    gx, gy = (int(x) for x in d.pop("grid").split("x"))
+    return dict({k: int(v) for k, v in d.items()}, grid=(gx, gy))
+
+
 def rel_err(got, ref):
     got = got.double() if isinstance(got, torch.Tensor) else torch.as_tensor(got).double()
     ref = ref.double()
