@@ -265,8 +265,7 @@ __global__ __launch_bounds__(256) void mt_clip_scale_kernel(MultiArgs a, const a
   // same rounding points as the reference: norm = sqrt(sum) in the gradient dtype, scalar = theta/norm, min(scalar, 1)
   const A norm = (A)load_as<A>(store_as<T>((A)sqrt((double)total[0])));
   A sc = (A)a.s[0] / norm;
-  sc = sc < A(1) ? sc : A(1);
-  if (sc != sc) sc = A(1) < sc ? A(1) : sc;  // NaN norm: ATen minimum propagates NaN
+  sc = (sc < A(1) || sc != sc) ? sc : A(1);  // NaN norm: ATen minimum propagates NaN (a bare `sc < 1 ? sc : 1` turns it into 1)
   const int nblk = a.blk_start[a.n];
   int t = blockIdx.x * per_wg < nblk ? mt_find(a, blockIdx.x * per_wg) : 0;
   for (int j = 0; j < per_wg; j++) {
