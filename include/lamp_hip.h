@@ -519,6 +519,58 @@ int lamp_mpnn_aggregate_backward(lamp_tensor** dmsg, const lamp_tensor* dout, co
                                  const lamp_tensor* fI_or_null, const lamp_tensor* fJ_or_null, int aggregateJ);
 /* a node of more edges than this is split across the waves of its workgroup (partial sums added in wave order) */
 int lamp_mpnn_long_row(int64_t* out);
+/* the gradient of a gather of rows out[e, :] = x[index[e], :] given dout [E, C] (f32 / f64) and (rowptr, perm) = lamp_graph_edge_csr(index, N):
+ * dx[n, :] = sum over e in perm[rowptr[n] .. rowptr[n + 1]), in that order, of dout[e, :]; dx is [N, C].  The node-sum kernel of the message
+ * gradient over one grouping: no atomics, every element written once, a result is a function of the input alone (IndexAdd's atomic sums
+ * are not).  The grouping must be what lamp_graph_edge_csr returned for the gather's index: its contents are not checked again. */
+int lamp_graph_gather_backward(lamp_tensor** dx, const lamp_tensor* dout, const lamp_tensor* rowptr, const lamp_tensor* perm);
+
+/* Graph minibatches (lamp-data/src/main/scala/lamp/data/GraphBatchStream.scala).  The reference folds the graphs of a batch into one
+ * block-diagonal graph with four element-wise launches per graph and five cats; the batch is then a fresh graph whose groupings every
+ * layer sorts anew.  Here the data set is packed once (rows of all graphs one after the other, endpoints with set-wide ids) and grouped
+ * once; a batch is a handful of ragged copies, because graph g's entries in the set-wide groupings are contiguous and stay in order.
+ * `plan` is an int64 [G, 4] table on the device, one row per graph of an epoch in the order of the epoch:
+ * (srcNodeBase, dstNodeBase, srcEdgeBase, dstEdgeBase), the first row of the graph's nodes / edges in the set and in its batch.  A batch
+ * is the rows [planOffset, planOffset + numGraphs) of it; numNodes and numEdges are the batch's totals, known on the host.  The table's
+ * place and size are checked, its contents are not: it must be what the host plan computed from the set's own pointers.  No call
+ * here reads anything back or synchronises. */
+/* src [R, ...] (any type of 1, 2, 4 or 8 bytes per element; made contiguous) -> out [outRows, ...]: out[dstBase[b] + k, :] =
+ * src[srcBase[b] + k, :] for the rows k of graph b, with (srcBase, dstBase) the node columns of the plan (edgeRows = 0) or the edge
+ * columns (edgeRows != 0).  A thread per packet over a flat index of output rows x packets, 16-byte packets where the row width and the
+ * addresses allow them; a thread finds its graph by a binary search of dstBase.  Every element is written once. */
+int lamp_graph_batch_rows(lamp_tensor** out, const lamp_tensor* src, const lamp_tensor* plan, int64_t planOffset, int64_t numGraphs, int64_t outRows,
+                          int edgeRows);
+/* the node-sized integer arrays of a batch in one launch: pool int64 [numNodes] (b for every node of graph b: vertexPoolingIndices),
+ * graphPtr int64 [numGraphs + 1] (dstNodeBase and the total), and for every set-wide array given its batch counterpart:
+ * adjRowptr (lamp_gcn_adjacency's; entries rebased by 2 * (dstEdgeBase - srcEdgeBase), the last is 2 * numEdges), dinv (copied; f32 /
+ * f64), inRowptr / outRowptr (lamp_graph_edge_csr's; rebased by dstEdgeBase - srcEdgeBase, the last is numEdges).  An output whose
+ * set-wide array is NULL is not written and may be NULL itself.  Every graph must have a node. */
+int lamp_graph_batch_nodes(lamp_tensor** pool, lamp_tensor** graphPtr, lamp_tensor** adjRowptr_or_null, lamp_tensor** dinv_or_null,
+                           lamp_tensor** inRowptr_or_null, lamp_tensor** outRowptr_or_null, const lamp_tensor* plan, int64_t planOffset, int64_t numGraphs,
+                           int64_t numNodes, int64_t numEdges, const lamp_tensor* setAdjRowptr_or_null, const lamp_tensor* setDinv_or_null,
+                           const lamp_tensor* setInRowptr_or_null, const lamp_tensor* setOutRowptr_or_null);
+/* the edge-sized integer arrays of a batch in one launch (none where numEdges = 0): edgeI, edgeJ int64 [numEdges] (the set-wide ids
+ * rebased by dstNodeBase - srcNodeBase), and for every set-wide array given its batch counterpart: col int64 [2 * numEdges]
+ * (lamp_gcn_adjacency's, rebased like the endpoints), inPerm / outPerm int64 [numEdges] (lamp_graph_edge_csr's, rebased by dstEdgeBase -
+ * srcEdgeBase).  The set's endpoints must lie inside their own graph: then every value written lies inside the batch. */
+int lamp_graph_batch_edges(lamp_tensor** edgeI, lamp_tensor** edgeJ, lamp_tensor** col_or_null, lamp_tensor** inPerm_or_null, lamp_tensor** outPerm_or_null,
+                           const lamp_tensor* plan, int64_t planOffset, int64_t numGraphs, int64_t numNodes, int64_t numEdges, const lamp_tensor* setEdgeI,
+                           const lamp_tensor* setEdgeJ, const lamp_tensor* setCol_or_null, const lamp_tensor* setInPerm_or_null,
+                           const lamp_tensor* setOutPerm_or_null);
+/* edgeI, edgeJ int64 [E] with set-wide ids, nodePtr / edgePtr int64 [G + 1] (G >= 1) -> bad int64 [1]: 1 where some edge has an endpoint
+ * outside its own graph's rows [nodePtr[g], nodePtr[g + 1]), 0 otherwise.  One comparison kernel, no atomics; the caller reads the word,
+ * once per data set.  Nothing is dereferenced through an endpoint. */
+int lamp_graph_set_check(lamp_tensor** bad, const lamp_tensor* edgeI, const lamp_tensor* edgeJ, const lamp_tensor* nodePtr, const lamp_tensor* edgePtr);
+
+/* VertexPooling (nn/graph/VertexPooling.scala) over a batch whose pooling index is sorted: x [N, D] (f32 / f64), graphPtr int64 [B + 1]
+ * -> out [B, D], out[b, :] = sum of the rows x[graphPtr[b] .. graphPtr[b + 1]) in row order, divided by their number where mean != 0.
+ * A wave per graph, lanes across the columns in packets, columns tiled in the grid; a graph of more than lamp_gcn_long_row nodes is split
+ * over the waves of its workgroup and the partial sums added in wave order.  No atomics, no index read, no host read: a result is a
+ * function of the input alone.  graphPtr's entries are clamped to [0, N]. */
+int lamp_segment_pool_forward(lamp_tensor** out, const lamp_tensor* x, const lamp_tensor* graphPtr, int mean);
+/* dout [B, D], pool int64 [N] (the graph of every node, clamped to [0, B)) -> dx [N, D]: dx[n, :] = dout[pool[n], :], divided by the
+ * graph's node count where mean != 0.  A thread per packet. */
+int lamp_segment_pool_backward(lamp_tensor** dx, const lamp_tensor* dout, const lamp_tensor* graphPtr, const lamp_tensor* pool, int mean);
 
 /* ------------------------------------------------------------------------------------------
  * convolution / pooling   (ATen.convolution, convolution_backward(output_mask[3]),

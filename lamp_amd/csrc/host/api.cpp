@@ -120,6 +120,8 @@ int lamp_op_apply(lamp_var** out, const char* name, lamp_var* const* vars, int n
     const bool hasFI = I(1) != 0, hasFJ = I(2) != 0;
     r = F::mpnn_aggregate(V(0), T(0), T(1), T(2), T(3), T(4), T(5), hasFI ? T(6) : Ten(), hasFJ ? T(hasFI ? 7 : 6) : Ten(), I(0) != 0);
   }
+  else if (n == "GraphGather") r = F::graph_gather(V(0), T(0), T(1), T(2));                    // (x), tensors = [index, rowptr, perm]
+  else if (n == "SegmentPool") r = F::segment_pool(V(0), T(0), T(1), I(0) != 0);               // (x), tensors = [graphPtr, pool], i = [mean]
   else if (n == "BertEmbedding") r = F::bert_embedding(V(0), V(1), V(2), V(3), V(4));   // (tokens, segments, tokenWeight, segmentWeight, positional)
   else if (n == "RepeatInterleave") r = F::repeat_interleave(V(0), V(1), I(0));
   else if (n == "ExpandAs") r = F::expand_as(V(0), T(0));

@@ -132,6 +132,12 @@ Var mpnn_message(const Var& nodeFeatures, const Var& edgeFeatures, const Ten& ed
 // MPNN.aggregate (nn/graph/MPNN.scala:84-126) over the two groupings; fI / fJ undefined: that degree normalisation is off
 Var mpnn_aggregate(const Var& message, const Ten& edgeI, const Ten& edgeJ, const Ten& inRowptr, const Ten& inPerm, const Ten& outRowptr, const Ten& outPerm,
                    const Ten& fI, const Ten& fJ, bool aggregateJ);
+// x[index] for x [N, C] with the gradient summed over the grouping (rowptr, perm) of index (lamp_graph_edge_csr): IndexSelect without the atomics
+// of its closure's IndexAdd, so the gradient is a function of the input alone
+Var graph_gather(const Var& x, const Ten& index, const Ten& rowptr, const Ten& perm);
+// VertexPooling (nn/graph/VertexPooling.scala) over a collated batch: x [N, D] summed (averaged) per graph over the consecutive rows that
+// graphPtr [B + 1] marks; pool [N] is the graph of every node, read by the closure
+Var segment_pool(const Var& x, const Ten& graphPtr, const Ten& pool, bool mean);
 // BertEncoder's input embedding (nn/bert/bert.scala:397-404): tokenWeight[tokens] + segmentWeight[segments] + positional[:, :T] as one node.
 // tokens / segments: long [B, T] constants; tokenWeight [V, D], segmentWeight [Vs, D], positional [1, L, D].  bert_fused(): one
 // lamp_bert_embedding_forward and one lamp_bert_embedding_backward (padding id 0, as Embedding passes it) for the three gradients; otherwise

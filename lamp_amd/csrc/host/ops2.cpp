@@ -308,6 +308,39 @@ Var mpnn_aggregate(const Var& message, const Ten& edgeI, const Ten& edgeJ, const
   return make_result(op, Ten(o));
 }
 
+// GraphGather: the rows x[index] of x [N, C] (lamp_index_select); the closure sums the incoming rows per node over index's grouping in one
+// lamp_graph_gather_backward, in the grouping's order, where IndexSelect's closure adds them with IndexAdd's atomics in whatever order they land.
+Var graph_gather(const Var& x, const Ten& index, const Ten& rowptr, const Ten& perm) {
+  auto op = new_op("GraphGather");
+  const Ten xv = x->value;
+  LAMP_CHECK(xv.ndim() == 2 && rowptr.numel() == xv.size(0) + 1, "GraphGather: x must be [N, C] with the N = " << rowptr.numel() - 1 << " nodes of the grouping, got a tensor of "
+                                                                     << xv.ndim() << " dimensions" << (xv.ndim() ? " whose first is " + std::to_string(xv.size(0)) : std::string()));
+  LAMP_CHECK(perm.numel() == index.numel(), "GraphGather: the grouping holds " << perm.numel() << " edges, the index " << index.numel());
+  op->params.push_back({x, [=](const Ten& p, Variable& out) {
+    lamp_tensor* dx = nullptr;
+    HCALL(lamp_graph_gather_backward(&dx, p.h(), rowptr.h(), perm.h()));
+    out.accumulate(Ten(dx), true);
+  }});
+  return make_result(op, ops::index_select(xv, 0, index));
+}
+
+// SegmentPool: VertexPooling over a collated batch, whose pooling index is sorted: one lamp_segment_pool_forward over the consecutive rows
+// of every graph, the closure one lamp_segment_pool_backward per packet.  Nothing is recorded but the two index vectors.
+Var segment_pool(const Var& x, const Ten& graphPtr, const Ten& pool, bool mean) {
+  auto op = new_op("SegmentPool");
+  const Ten xv = x->value;
+  LAMP_CHECK(xv.ndim() == 2 && pool.numel() == xv.size(0), "SegmentPool: x must be [" << pool.numel() << ", D] (a row per entry of the pooling index), got a tensor of "
+                                                               << xv.ndim() << " dimensions" << (xv.ndim() ? " whose first is " + std::to_string(xv.size(0)) : std::string()));
+  lamp_tensor* o = nullptr;
+  HCALL(lamp_segment_pool_forward(&o, xv.h(), graphPtr.h(), mean ? 1 : 0));
+  op->params.push_back({x, [=](const Ten& p, Variable& out) {
+    lamp_tensor* dx = nullptr;
+    HCALL(lamp_segment_pool_backward(&dx, p.h(), graphPtr.h(), pool.h(), mean ? 1 : 0));
+    out.accumulate(Ten(dx), true);
+  }});
+  return make_result(op, Ten(o));
+}
+
 // BertEmbedding: (tokenWeight[tokens] + segmentWeight[segments]) + positional[:, :T].  Fused: one forward launch; one
 // lamp_bert_embedding_backward gives the gradients of all the parameters that want one, whichever closure runs first makes the call and
 // leaves the others for its siblings (GraphAttentionAggregate's arrangement).  Padding id 0 for both tables, as Embedding's closure passes it.

@@ -1,5 +1,5 @@
-// Graph layers, f32 and f64: graph convolution (GCN), graph attention and message passing (MPNN), each below under a heading of its
-// own.  The reference builds sparse tensors or chains of indexSelect / indexAdd; here the edges are grouped per node once per graph
+// Graph layers, f32 and f64: graph convolution (GCN), graph attention, message passing (MPNN) and the minibatches of small graphs
+// (the collate kernels and the pooling over a sorted batch), each below under a heading of its own.  The reference builds sparse tensors or chains of indexSelect / indexAdd; here the edges are grouped per node once per graph
 // (lamp_gcn_adjacency, lamp_graph_edge_csr: a rowptr and the stably sorted edges) and every sum per node is a gather-only kernel of one
 // shape, the row kernel:
 //
@@ -940,6 +940,202 @@ template <class T> void mpnn_aggregate_launch(int v, const MpnnSum& a, hipStream
   else mpnn_sum_launch<T, false, false>(v, a, st);
 }
 
+// ---- graph minibatches (lamp-data/src/main/scala/lamp/data/GraphBatchStream.scala) ---------------------------------------------------------
+// A batch of whole graphs is block-diagonal: its node and edge rows are ragged copies out of the packed data set, and its groupings are
+// the data set's own with two offsets added, because graph g's entries sit at [edgePtr[g], edgePtr[g + 1]) of inPerm / outPerm, at twice
+// that of the adjacency's col, and its rows at [nodePtr[g], nodePtr[g + 1]) of every rowptr and of dinv, each in the order a grouping of
+// the batch alone would have (the sorts are stable).  So nothing is sorted, counted or scanned per batch, nothing is read back, and the
+// kernels are copies: a thread per output element (or packet), which finds its graph by a binary search of the batch's slice of the
+// epoch's plan - rows of (srcNodeBase, dstNodeBase, srcEdgeBase, dstEdgeBase) - and writes every element once.
+// VertexPooling over such a batch sums consecutive rows: segment_pool_kernel, a row kernel (see the head of the file) without an index.
+constexpr int kPlanCols = 4;      // columns of a plan row: source and destination base of the nodes, then of the edges
+constexpr int kPoolUnroll = 8;    // node rows in flight per wave of segment_pool_kernel
+
+// the graph b in [0, B) of a batch whose rows of column `c` of the plan are the bases of an output: base[b] <= k < base[b + 1], with
+// base[B] = total > k.  Graphs without a row (equal bases) are passed over.
+__device__ __forceinline__ int plan_find(const int64_t* __restrict__ plan, int c, int B, int64_t k) {
+  int lo = 0, hi = B;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (plan[(int64_t)mid * kPlanCols + c] <= k) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// out[dstBase[b] + k, 0:slots) = src[srcBase[b] + k, 0:slots) in packets P, (srcBase, dstBase) = the plan's columns (c, c + 1); rows of
+// `slots` packets, dense
+template <class P>
+__global__ __launch_bounds__(kMpnnEdgeBlock) void graph_batch_rows_kernel(P* __restrict__ out, const P* __restrict__ src, const int64_t* __restrict__ plan, int c,
+                                                                         int B, int64_t rows, uint32_t slots) {
+  const MpnnSlot t = mpnn_slot(slots);
+  if (t.row >= rows) return;
+  const int64_t* pb = plan + (int64_t)plan_find(plan, c + 1, B, t.row) * kPlanCols;
+  out[t.row * slots + t.slot] = src[(pb[c] + t.row - pb[c + 1]) * slots + t.slot];
+}
+
+struct BatchNodes {
+  int64_t *pool, *graphPtr, *adjRowptr, *inRowptr, *outRowptr;
+  const int64_t *setAdjRowptr, *setInRowptr, *setOutRowptr;
+};
+// thread n of [0, N]: node n's entries of the node-sized arrays (a null output is absent), thread N the totals; threads [0, B] graphPtr
+template <class T>
+__global__ __launch_bounds__(256) void graph_batch_nodes_kernel(BatchNodes a, T* __restrict__ dinv, const T* __restrict__ setDinv, const int64_t* __restrict__ plan,
+                                                                int B, int64_t N, int64_t E) {
+  const int64_t n = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (n > N) return;
+  if (n <= B) a.graphPtr[n] = n < B ? plan[n * kPlanCols + 1] : N;
+  if (n == N) {
+    if (a.adjRowptr) a.adjRowptr[N] = 2 * E;
+    if (a.inRowptr) a.inRowptr[N] = E;
+    if (a.outRowptr) a.outRowptr[N] = E;
+    return;
+  }
+  const int b = plan_find(plan, 1, B, n);
+  const int64_t* pb = plan + (int64_t)b * kPlanCols;
+  const int64_t s = pb[0] + n - pb[1], shift = pb[3] - pb[2];
+  a.pool[n] = b;
+  if (a.adjRowptr) a.adjRowptr[n] = a.setAdjRowptr[s] + 2 * shift;
+  if (a.inRowptr) a.inRowptr[n] = a.setInRowptr[s] + shift;
+  if (a.outRowptr) a.outRowptr[n] = a.setOutRowptr[s] + shift;
+  if (dinv) dinv[n] = setDinv[s];
+}
+
+struct BatchEdges {
+  int64_t *edgeI, *edgeJ, *col, *inPerm, *outPerm;
+  const int64_t *setEdgeI, *setEdgeJ, *setCol, *setInPerm, *setOutPerm;
+};
+// thread k of [0, E): edge k's endpoints and its entries of the two permutations, and the two entries of col at the same place in either
+// half of its graph's 2 * Eg entries (so both halves are read and written coalesced)
+__global__ __launch_bounds__(256) void graph_batch_edges_kernel(BatchEdges a, const int64_t* __restrict__ plan, int B, int64_t E) {
+  const int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (k >= E) return;
+  const int b = plan_find(plan, 3, B, k);
+  const int64_t* pb = plan + (int64_t)b * kPlanCols;
+  const int64_t j = k - pb[3], s = pb[2] + j, nodeShift = pb[1] - pb[0], edgeShift = pb[3] - pb[2];
+  a.edgeI[k] = a.setEdgeI[s] + nodeShift;
+  a.edgeJ[k] = a.setEdgeJ[s] + nodeShift;
+  if (a.inPerm) a.inPerm[k] = a.setInPerm[s] + edgeShift;
+  if (a.outPerm) a.outPerm[k] = a.setOutPerm[s] + edgeShift;
+  if (a.col) {
+    const int64_t eg = (b + 1 < B ? pb[kPlanCols + 3] : E) - pb[3];
+    a.col[2 * pb[3] + j] = a.setCol[2 * pb[2] + j] + nodeShift;
+    a.col[2 * pb[3] + eg + j] = a.setCol[2 * pb[2] + eg + j] + nodeShift;
+  }
+}
+
+// *bad (zero before the launch) = 1 where an edge e of [0, E) has an endpoint outside the rows [nodePtr[g], nodePtr[g + 1]) of its own
+// graph g, the one with edgePtr[g] <= e < edgePtr[g + 1]; every thread that finds one stores the same word
+__global__ __launch_bounds__(256) void graph_set_check_kernel(int64_t* __restrict__ bad, const int64_t* __restrict__ edgeI, const int64_t* __restrict__ edgeJ,
+                                                              const int64_t* __restrict__ nodePtr, const int64_t* __restrict__ edgePtr, int64_t G, int64_t E) {
+  const int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (e >= E) return;
+  int64_t lo = 0, hi = G;
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (edgePtr[mid] <= e) lo = mid; else hi = mid;
+  }
+  const int64_t b = nodePtr[lo], t = nodePtr[lo + 1], i = edgeI[e], j = edgeJ[e];
+  if (i < b || i >= t || j < b || j >= t) *bad = 1;
+}
+
+// acc += x[b, c0 ..] + x[b + 1, c0 ..] + ... + x[e - 1, c0 ..], in that order (xc = x + c0), kPoolUnroll rows in flight
+template <class T, int V>
+__device__ __forceinline__ void pool_rows(Vec<T, V>& acc, const T* __restrict__ xc, int64_t ldx, int64_t b, int64_t e) {
+  int64_t r = b;
+  for (; r + kPoolUnroll <= e; r += kPoolUnroll) {
+    Vec<T, V> row[kPoolUnroll];
+#pragma unroll
+    for (int u = 0; u < kPoolUnroll; u++) row[u] = load_packet<T, V>(xc + (r + u) * ldx);
+#pragma unroll
+    for (int u = 0; u < kPoolUnroll; u++) {
+#pragma unroll
+      for (int j = 0; j < V; j++) acc.v[j] += row[u].v[j];
+    }
+  }
+  for (; r < e; r++) {
+    const Vec<T, V> row = load_packet<T, V>(xc + r * ldx);
+#pragma unroll
+    for (int j = 0; j < V; j++) acc.v[j] += row.v[j];
+  }
+}
+
+// out[g, :] = sum of the rows x[graphPtr[g] .. graphPtr[g + 1]) (entries clamped to [0, N]) in row order, over their number if `mean`.
+// D % V == 0.  grid: (ceil(B / kWaves), ceil(D / (64 * V)), kWaves + 1), block: kWaves * 64.
+template <class T, int V>
+__global__ __launch_bounds__(kWaves * 64) void segment_pool_kernel(T* __restrict__ out, const T* __restrict__ x, int64_t ldx, const int64_t* __restrict__ graphPtr,
+                                                                       int64_t B, int64_t N, int64_t D, int mean) {
+  __shared__ Vec<T, V> part[1][kWaves][64];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t c0 = ((int64_t)blockIdx.y * 64 + lane) * V;
+  const bool active = c0 < D;
+
+  for (int k = first_turn(); is_turn(k); k++) {
+    const RowTurn t = row_turn(k, B, wave);
+    int64_t b = 0, n = 0;
+    if (t.r >= 0) {
+      const int64_t lo = graphPtr[t.r], hi = graphPtr[t.r + 1];
+      b = lo < 0 ? 0 : (lo > N ? N : lo);
+      n = (hi < b ? b : (hi > N ? N : hi)) - b;
+    }
+    if (!t.takes(n)) continue;
+    const Share sh = t.share(n, wave);
+    Vec<T, V> acc[1] = {zero_packet<T, V>()};
+    if (active) pool_rows<T, V>(acc[0], x + c0, ldx, b + sh.lo, b + sh.hi);
+    if (!t.own) merge_shares(acc, part, wave, lane, active);
+    if (active && t.r >= 0 && (t.own || wave == 0)) {
+      if (mean) {
+        const T cnt = (T)n;
+#pragma unroll
+        for (int j = 0; j < V; j++) acc[0].v[j] /= cnt;
+      }
+      *reinterpret_cast<Vec<T, V>*>(out + t.r * D + c0) = acc[0];
+    }
+  }
+}
+
+// dx[n, :] = dout[pool[n], :] (pool[n] clamped to [0, B)), over the node count of that graph if `mean`.  A thread per packet.
+template <class T, int V>
+__global__ __launch_bounds__(kMpnnEdgeBlock) void segment_pool_backward_kernel(T* __restrict__ dx, const T* __restrict__ dout, const int64_t* __restrict__ graphPtr,
+                                                                              const int64_t* __restrict__ pool, int64_t N, int64_t B, int D, int mean,
+                                                                              uint32_t slots) {
+  const MpnnSlot t = mpnn_slot(slots);
+  const int c = t.slot * V;
+  if (t.row >= N || c >= D) return;
+  int64_t g = pool[t.row];
+  g = g < 0 ? 0 : (g >= B ? B - 1 : g);
+  Vec<T, V> v = load_packet<T, V>(dout + g * D + c);
+  if (mean) {
+    const T cnt = (T)(graphPtr[g + 1] - graphPtr[g]);
+#pragma unroll
+    for (int q = 0; q < V; q++) v.v[q] /= cnt;
+  }
+  *reinterpret_cast<Vec<T, V>*>(dx + t.row * D + c) = v;
+}
+
+// a batch's slice [off, off + B) of the plan (int64 [G, 4], contiguous on the device) -> its first row
+const int64_t* plan_slice(const Tensor* plan, int64_t off, int64_t B) {
+  check_device_tensor(plan, "plan");
+  LAMP_CHECK(plan->dtype == kI64 && plan->ndim == 2 && plan->sizes[1] == kPlanCols && plan->is_contiguous(),
+             "plan " << plan->describe() << " must be a contiguous int64 [G, " << kPlanCols << "]");
+  LAMP_CHECK(B >= 1 && B <= INT32_MAX / 2 && off >= 0 && off + B <= plan->sizes[0], "the batch's graphs [" << off << ", " << off + B << ") do not lie in plan " << plan->describe());
+  return plan->ptr<int64_t>() + off * kPlanCols;
+}
+// a set-wide array given beside a batch: null, or an int64 vector on the plan's device of at least `least` entries (a batch may repeat a
+// graph, so its totals say nothing about the set's)
+void check_set_vector(const Tensor* t, const char* what, const Tensor* plan, int64_t least) {
+  if (!t) return;
+  check_i64_vector(t, plan, what);
+  LAMP_CHECK(t->is_contiguous() && t->numel() >= least, what << " " << t->describe() << " must be contiguous and hold at least " << least << " entries");
+}
+// the copy unit of lamp_graph_batch_rows: the widest of 16, 8, 4, 2, 1 bytes that divides a row of `bytes` bytes and at which both
+// addresses are aligned
+int copy_unit(int64_t bytes, const void* a, const void* b) {
+  for (int u = 16; u > 1; u >>= 1)
+    if (bytes % u == 0 && (uintptr_t)a % u == 0 && (uintptr_t)b % u == 0) return u;
+  return 1;
+}
+
 }  // namespace
 }  // namespace lamp
 
@@ -1322,6 +1518,238 @@ int lamp_mpnn_aggregate_backward(lamp_tensor** dmsg, const lamp_tensor* dout, co
     LAMP_LAUNCH_CHECK();
   }
   *dmsg = o.take();
+  LAMP_API_END
+}
+
+int lamp_graph_gather_backward(lamp_tensor** dx, const lamp_tensor* dout, const lamp_tensor* rowptr, const lamp_tensor* perm) {
+  LAMP_API_BEGIN
+  check_device_tensor(dout, "dout");
+  LAMP_CHECK(dout->dtype == kF32 || dout->dtype == kF64, "f32 and f64 only, got " << dout->describe());
+  LAMP_CHECK(dout->ndim == 2, "dout " << dout->describe() << " must be [E, C]");
+  const int64_t E = dout->sizes[0], C = dout->sizes[1];
+  LAMP_CHECK(C <= INT32_MAX / 2, "dout " << dout->describe() << " has too many columns");
+  check_i64_vector(rowptr, dout, "rowptr");
+  LAMP_CHECK(rowptr->numel() >= 1, "rowptr " << rowptr->describe() << " must be [N + 1]");
+  check_i64_vectors({{perm, "perm"}}, dout, E, "does not have dout's " + std::to_string(E) + " rows");
+  const int64_t N = rowptr->numel() - 1;
+  Hold g(contiguous(dout)), rp(contiguous(rowptr)), pm(contiguous(perm));
+  int64_t xs[2] = {N, C};
+  Hold o(new_tensor(xs, 2, dout->dtype, dout->device()));
+  if (N * C) {
+    hipStream_t st = current_stream(dout->device());
+    KernelTimer kt("graph_gather_backward", (double)E * C, ((double)E * C + (double)N * C) * dtype_size(dout->dtype) + E * 8.0 + N * 8.0, st);
+    const MpnnSum a{o.get(), g.get(), C, 0, 0, rp.get(), pm.get(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, N, C};
+    with_float(dout->dtype, [&](auto z) {
+      using T = decltype(z);
+      mpnn_sum_launch<T, false, false>(packet_width<T>({C}, {o.get(), g.get()}), a, st);
+    });
+    LAMP_LAUNCH_CHECK();
+  }
+  *dx = o.take();
+  LAMP_API_END
+}
+
+int lamp_graph_batch_rows(lamp_tensor** out, const lamp_tensor* src, const lamp_tensor* plan, int64_t planOffset, int64_t numGraphs, int64_t outRows,
+                          int edgeRows) {
+  LAMP_API_BEGIN
+  check_device_tensor(src, "src");
+  const int64_t* pl = plan_slice(plan, planOffset, numGraphs);
+  check_same_device(plan, src);
+  LAMP_CHECK(src->ndim >= 1 && outRows >= 0, "src " << src->describe() << " must have a row per node or edge, and outRows = " << outRows << " must not be negative");
+  Hold sc(contiguous(src));
+  std::vector<int64_t> os = src->shape();
+  os[0] = outRows;
+  int64_t width = 1;
+  for (int d = 1; d < src->ndim; d++) width *= src->sizes[d];
+  Hold o(new_tensor(os, src->dtype, src->device()));
+  const int64_t bytes = width * (int64_t)dtype_size(src->dtype);
+  if (outRows * bytes) {
+    hipStream_t st = current_stream(src->device());
+    KernelTimer kt("graph_batch_rows", 0, 2.0 * outRows * bytes + outRows * 16.0, st);
+    const int unit = copy_unit(bytes, o->raw(), sc->raw());
+    const MpnnEdgeGrid g = mpnn_edge_grid(outRows, bytes / unit);
+    auto launch = [&](auto p) {
+      using P = decltype(p);
+      hipLaunchKernelGGL((graph_batch_rows_kernel<P>), g.grid, dim3(kMpnnEdgeBlock), 0, st, (P*)o->data(), (const P*)sc->raw(), pl, edgeRows ? 2 : 0, (int)numGraphs,
+                         outRows, g.slots);
+    };
+    if (unit == 16) launch(Vec<uint32_t, 4>());
+    else if (unit == 8) launch(Vec<uint32_t, 2>());
+    else if (unit == 4) launch(uint32_t());
+    else if (unit == 2) launch(uint16_t());
+    else launch(uint8_t());
+    LAMP_LAUNCH_CHECK();
+  }
+  *out = o.take();
+  LAMP_API_END
+}
+
+int lamp_graph_batch_nodes(lamp_tensor** pool, lamp_tensor** graphPtr, lamp_tensor** adjRowptr_or_null, lamp_tensor** dinv_or_null,
+                           lamp_tensor** inRowptr_or_null, lamp_tensor** outRowptr_or_null, const lamp_tensor* plan, int64_t planOffset, int64_t numGraphs,
+                           int64_t numNodes, int64_t numEdges, const lamp_tensor* setAdjRowptr_or_null, const lamp_tensor* setDinv_or_null,
+                           const lamp_tensor* setInRowptr_or_null, const lamp_tensor* setOutRowptr_or_null) {
+  LAMP_API_BEGIN
+  const int64_t* pl = plan_slice(plan, planOffset, numGraphs);
+  const int64_t B = numGraphs, N = numNodes, E = numEdges;
+  LAMP_CHECK(N >= B && E >= 0, "a batch of " << B << " graphs has " << N << " nodes and " << E << " edges: every graph must have a node");
+  const Tensor *sa = setAdjRowptr_or_null, *sd = setDinv_or_null, *si = setInRowptr_or_null, *so = setOutRowptr_or_null;
+  LAMP_CHECK((!sa || adjRowptr_or_null) && (!sd || dinv_or_null) && (!si || inRowptr_or_null) && (!so || outRowptr_or_null), "a set-wide array without its output");
+  LAMP_CHECK(!sa == !sd, "the adjacency's rowptr and dinv come together");
+  check_set_vector(sa, "setAdjRowptr", plan, 2);
+  check_set_vector(si, "setInRowptr", plan, 2);
+  check_set_vector(so, "setOutRowptr", plan, 2);
+  if (sd) {
+    check_device_tensor(sd, "setDinv");
+    check_same_device(sd, plan);
+    LAMP_CHECK((sd->dtype == kF32 || sd->dtype == kF64) && sd->ndim == 1 && sd->is_contiguous() && sd->numel() + 1 == sa->numel(),
+               "setDinv " << sd->describe() << " must be a contiguous f32 / f64 vector of one entry per row of setAdjRowptr " << sa->describe());
+  }
+  const int dev = plan->device();
+  int64_t ns[1] = {N}, n1[1] = {N + 1}, b1[1] = {B + 1};
+  Hold pv(new_tensor(ns, 1, kI64, dev)), gp(new_tensor(b1, 1, kI64, dev)), ar(sa ? new_tensor(n1, 1, kI64, dev) : nullptr),
+      dv(sd ? new_tensor(ns, 1, sd->dtype, dev) : nullptr), ir(si ? new_tensor(n1, 1, kI64, dev) : nullptr), orp(so ? new_tensor(n1, 1, kI64, dev) : nullptr);
+  {
+    hipStream_t st = current_stream(dev);
+    auto wp = [](Hold& h) { return h.get() ? h->ptr<int64_t>() : nullptr; };
+    auto rp = [](const Tensor* t) { return t ? t->ptr<int64_t>() : nullptr; };
+    const BatchNodes a{wp(pv), wp(gp), wp(ar), wp(ir), wp(orp), rp(sa), rp(si), rp(so)};
+    const double arrays = 1.0 + (sa ? 1 : 0) + (si ? 1 : 0) + (so ? 1 : 0);
+    KernelTimer kt("graph_batch_index", 0, (double)N * (arrays * 16.0 + (sd ? 2.0 * dtype_size(sd->dtype) : 0.0)), st);
+    with_float(sd ? sd->dtype : kF32, [&](auto z) {
+      using T = decltype(z);
+      hipLaunchKernelGGL((graph_batch_nodes_kernel<T>), dim3((unsigned)((N + 1 + 255) / 256)), dim3(256), 0, st, a, dv.get() ? dv->ptr<T>() : nullptr,
+                         sd ? sd->ptr<T>() : nullptr, pl, (int)B, N, E);
+    });
+    LAMP_LAUNCH_CHECK();
+  }
+  *pool = pv.take(); *graphPtr = gp.take();
+  if (adjRowptr_or_null) *adjRowptr_or_null = ar.take();
+  if (dinv_or_null) *dinv_or_null = dv.take();
+  if (inRowptr_or_null) *inRowptr_or_null = ir.take();
+  if (outRowptr_or_null) *outRowptr_or_null = orp.take();
+  LAMP_API_END
+}
+
+int lamp_graph_batch_edges(lamp_tensor** edgeI, lamp_tensor** edgeJ, lamp_tensor** col_or_null, lamp_tensor** inPerm_or_null, lamp_tensor** outPerm_or_null,
+                           const lamp_tensor* plan, int64_t planOffset, int64_t numGraphs, int64_t numNodes, int64_t numEdges, const lamp_tensor* setEdgeI,
+                           const lamp_tensor* setEdgeJ, const lamp_tensor* setCol_or_null, const lamp_tensor* setInPerm_or_null,
+                           const lamp_tensor* setOutPerm_or_null) {
+  LAMP_API_BEGIN
+  const int64_t* pl = plan_slice(plan, planOffset, numGraphs);
+  const int64_t B = numGraphs, N = numNodes, E = numEdges;
+  LAMP_CHECK(N >= B && E >= 0 && 2 * E < ((int64_t)1 << 31), "a batch of " << B << " graphs has " << N << " nodes and " << E << " edges");
+  const Tensor *sc = setCol_or_null, *si = setInPerm_or_null, *so = setOutPerm_or_null;
+  LAMP_CHECK((!sc || col_or_null) && (!si || inPerm_or_null) && (!so || outPerm_or_null), "a set-wide array without its output");
+  LAMP_CHECK(setEdgeI && setEdgeJ, "the set's edge list is null");
+  check_set_vector(setEdgeI, "setEdgeI", plan, E ? 1 : 0);
+  check_set_vector(setEdgeJ, "setEdgeJ", plan, setEdgeI->numel());
+  check_set_vector(sc, "setCol", plan, 2 * setEdgeI->numel());
+  check_set_vector(si, "setInPerm", plan, setEdgeI->numel());
+  check_set_vector(so, "setOutPerm", plan, setEdgeI->numel());
+  const int dev = plan->device();
+  int64_t es[1] = {E}, e2[1] = {2 * E};
+  Hold ei(new_tensor(es, 1, kI64, dev)), ej(new_tensor(es, 1, kI64, dev)), cl(sc ? new_tensor(e2, 1, kI64, dev) : nullptr),
+      ip(si ? new_tensor(es, 1, kI64, dev) : nullptr), op(so ? new_tensor(es, 1, kI64, dev) : nullptr);
+  if (E) {
+    hipStream_t st = current_stream(dev);
+    auto wp = [](Hold& h) { return h.get() ? h->ptr<int64_t>() : nullptr; };
+    auto rp = [](const Tensor* t) { return t ? t->ptr<int64_t>() : nullptr; };
+    const BatchEdges a{wp(ei), wp(ej), wp(cl), wp(ip), wp(op), rp(setEdgeI), rp(setEdgeJ), rp(sc), rp(si), rp(so)};
+    KernelTimer kt("graph_batch_index", 0, (double)E * 16.0 * (2.0 + (sc ? 2 : 0) + (si ? 1 : 0) + (so ? 1 : 0)), st);
+    hipLaunchKernelGGL(graph_batch_edges_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, a, pl, (int)B, E);
+    LAMP_LAUNCH_CHECK();
+  }
+  *edgeI = ei.take(); *edgeJ = ej.take();
+  if (col_or_null) *col_or_null = cl.take();
+  if (inPerm_or_null) *inPerm_or_null = ip.take();
+  if (outPerm_or_null) *outPerm_or_null = op.take();
+  LAMP_API_END
+}
+
+int lamp_graph_set_check(lamp_tensor** bad, const lamp_tensor* edgeI, const lamp_tensor* edgeJ, const lamp_tensor* nodePtr, const lamp_tensor* edgePtr) {
+  LAMP_API_BEGIN
+  check_device_tensor(edgeI, "edgeI");
+  check_i64_vector(edgeI, edgeI, "edgeI");
+  check_i64_vector(edgeJ, edgeI, "edgeJ");
+  check_i64_vector(nodePtr, edgeI, "nodePtr");
+  check_i64_vector(edgePtr, edgeI, "edgePtr");
+  const int64_t E = edgeI->numel(), G = nodePtr->numel() - 1;
+  LAMP_CHECK(edgeJ->numel() == E, "edgeI " << edgeI->describe() << " and edgeJ " << edgeJ->describe() << " differ in length");
+  LAMP_CHECK(G >= 1 && edgePtr->numel() == G + 1, "nodePtr " << nodePtr->describe() << " and edgePtr " << edgePtr->describe() << " must both be [G + 1], G >= 1");
+  Hold ei(contiguous(edgeI)), ej(contiguous(edgeJ)), np(contiguous(nodePtr)), ep(contiguous(edgePtr));
+  int64_t one[1] = {1};
+  Hold b(new_tensor(one, 1, kI64, edgeI->device()));
+  fill_zero(b.get());
+  if (E) {
+    hipStream_t st = current_stream(edgeI->device());
+    KernelTimer kt("graph_set_check", 0, (double)E * 16.0, st);
+    hipLaunchKernelGGL(graph_set_check_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, b->ptr<int64_t>(), ei->ptr<int64_t>(), ej->ptr<int64_t>(),
+                       np->ptr<int64_t>(), ep->ptr<int64_t>(), G, E);
+    LAMP_LAUNCH_CHECK();
+  }
+  *bad = b.take();
+  LAMP_API_END
+}
+
+int lamp_segment_pool_forward(lamp_tensor** out, const lamp_tensor* x, const lamp_tensor* graphPtr, int mean) {
+  LAMP_API_BEGIN
+  check_device_tensor(x, "x");
+  LAMP_CHECK(x->dtype == kF32 || x->dtype == kF64, "f32 and f64 only, got " << x->describe());
+  LAMP_CHECK(x->ndim == 2, "x " << x->describe() << " must be [N, D]");
+  check_i64_vector(graphPtr, x, "graphPtr");
+  LAMP_CHECK(graphPtr->numel() >= 1, "graphPtr " << graphPtr->describe() << " must be [B + 1]");
+  const int64_t N = x->sizes[0], D = x->sizes[1], B = graphPtr->numel() - 1;
+  int64_t ldx = 0;
+  Hold xc(rows_in_place(x, &ldx)), gp(contiguous(graphPtr));
+  int64_t os[2] = {B, D};
+  Hold o(new_tensor(os, 2, x->dtype, x->device()));
+  if (B * D) {
+    hipStream_t st = current_stream(x->device());
+    const double sz = (double)dtype_size(x->dtype);
+    KernelTimer kt("segment_pool", (double)N * D, ((double)N * D + (double)B * D) * sz + B * 8.0, st);
+    with_float(x->dtype, [&](auto z) {
+      using T = decltype(z);
+      with_packet<T>(packet_width<T>({D, ldx}, {o.get(), xc.get()}), [&](auto W) {
+        constexpr int V = decltype(W)::value;
+        hipLaunchKernelGGL((segment_pool_kernel<T, V>), row_grid(B, D, V, kWaves + 1), dim3(kWaves * 64), 0, st, o->ptr<T>(), xc->ptr<T>(), ldx, gp->ptr<int64_t>(), B, N,
+                           D, mean);
+      });
+    });
+    LAMP_LAUNCH_CHECK();
+  }
+  *out = o.take();
+  LAMP_API_END
+}
+
+int lamp_segment_pool_backward(lamp_tensor** dx, const lamp_tensor* dout, const lamp_tensor* graphPtr, const lamp_tensor* pool, int mean) {
+  LAMP_API_BEGIN
+  check_device_tensor(dout, "dout");
+  LAMP_CHECK(dout->dtype == kF32 || dout->dtype == kF64, "f32 and f64 only, got " << dout->describe());
+  LAMP_CHECK(dout->ndim == 2, "dout " << dout->describe() << " must be [B, D]");
+  const int64_t B = dout->sizes[0], D = dout->sizes[1];
+  LAMP_CHECK(D <= INT32_MAX / 2, "dout " << dout->describe() << " has too many columns");
+  check_i64_vector(pool, dout, "pool");
+  check_i64_vectors({{graphPtr, "graphPtr"}}, dout, B + 1, "does not mark the " + std::to_string(B) + " graphs of dout");
+  const int64_t N = pool->numel();
+  LAMP_CHECK(N == 0 || B > 0, "dout " << dout->describe() << " has no rows");
+  Hold gc(contiguous(dout)), gp(contiguous(graphPtr)), pc(contiguous(pool));
+  int64_t xs[2] = {N, D};
+  Hold o(new_tensor(xs, 2, dout->dtype, dout->device()));
+  if (N * D) {
+    hipStream_t st = current_stream(dout->device());
+    KernelTimer kt("segment_pool_backward", mean ? (double)N * D : 0.0, 2.0 * N * D * dtype_size(dout->dtype) + N * 8.0, st);
+    with_float(dout->dtype, [&](auto z) {
+      using T = decltype(z);
+      const int v = packet_width<T>({D}, {o.get(), gc.get()});
+      const MpnnEdgeGrid g = mpnn_edge_grid(N, D / v);
+      with_packet<T>(v, [&](auto V) {
+        hipLaunchKernelGGL((segment_pool_backward_kernel<T, decltype(V)::value>), g.grid, dim3(kMpnnEdgeBlock), 0, st, o->ptr<T>(), gc->ptr<T>(), gp->ptr<int64_t>(),
+                           pc->ptr<int64_t>(), N, B, (int)D, mean, g.slots);
+      });
+    });
+    LAMP_LAUNCH_CHECK();
+  }
+  *dx = o.take();
   LAMP_API_END
 }
 

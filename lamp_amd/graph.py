@@ -1,5 +1,5 @@
 """lamp.nn.graph over the C ABI: Graph, GCN, gcn, gcnAggregation, VertexPooling (and nn.ResidualModule, which gcn needs), GraphAttention,
-multiheadGraphAttention, MPNN.
+multiheadGraphAttention, MPNN.  Minibatches of many small graphs are lamp_amd.graphbatch's.
 
 Reference: lamp-core/src/main/scala/lamp/nn/graph/{Graph,GCN,VertexPooling,GraphAttention}.scala.  GCN.computeSparseAdjacency builds a sparse COO
 tensor and gcnAggregation multiplies it with `mm`; here the adjacency is a CSR (`lamp_gcn_adjacency`) and the product one gather-only
@@ -8,7 +8,8 @@ IndexAdd and the broadcasting operators (`gcnAggregationComposed`) is the fallba
 of scripts/gcn_probe.py; `gcnFused` switches between the two.
 
 GraphAttention.multiheadGraphAttention scores every edge and then takes, per destination, the softmax of the scores and the sum of the
-sources' values under it.  The scoring is a composition of existing nodes; everything after it is one node, `GraphAttentionAggregate`
+sources' values under it.  The scoring is a composition of existing nodes (on the fused path its two key gathers are GraphGather nodes,
+whose gradient is summed over the edge CSR without atomics); everything after it is one node, `GraphAttentionAggregate`
 (`lamp_gat_forward` / `lamp_gat_backward` over the two groupings of `Graph.edgeCsr()`), or the reference's own chain of exp, indexAdd,
 log, indexSelect and Mult (`graphAttentionAggregateComposed`); `graphAttentionFused` switches between the two.
 
@@ -126,16 +127,19 @@ def computeEdgeCsr(edgeI: STen, edgeJ: STen, numNodes: int) -> EdgeCsr:
 class Graph:
     """Graph(nodeFeatures, edgeFeatures, edgeI, edgeJ, vertexPoolingIndices) (Graph.scala).  The adjacency of the edge list, its
     grouping by endpoint and MPNN's degree factors (keyed by N, type, exponent and side) are built on first use and shared by every
-    copy(nodeFeatures = ...), so stacked GCN, GraphAttention or MPNN layers over one graph build them once."""
+    copy(nodeFeatures = ...), so stacked GCN, GraphAttention or MPNN layers over one graph build them once.  `graphPtr` (int64 [B + 1], the
+    node offsets of the graphs of a collated minibatch, lamp_amd.graphbatch) says that vertexPoolingIndices is sorted: VertexPooling then sums
+    consecutive rows."""
 
     def __init__(self, nodeFeatures: Variable, edgeFeatures: Optional[Variable], edgeI: STen, edgeJ: STen, vertexPoolingIndices: Optional[STen] = None,
-                 _adjacencies: Optional[dict] = None):
+                 _adjacencies: Optional[dict] = None, graphPtr: Optional[STen] = None):
         self.nodeFeatures, self.edgeFeatures, self.edgeI, self.edgeJ, self.vertexPoolingIndices = nodeFeatures, edgeFeatures, edgeI, edgeJ, vertexPoolingIndices
         self._adjacencies = _adjacencies if _adjacencies is not None else {}
+        self.graphPtr = graphPtr
 
     def copy(self, nodeFeatures: Optional[Variable] = None) -> "Graph":
         return Graph(nodeFeatures if nodeFeatures is not None else self.nodeFeatures, self.edgeFeatures, self.edgeI, self.edgeJ, self.vertexPoolingIndices,
-                     self._adjacencies)
+                     self._adjacencies, self.graphPtr)
 
     def adjacency(self, dtype=None) -> Adjacency:
         x = self.nodeFeatures.value
@@ -201,10 +205,26 @@ def gcn(in_: int, out: int, dtype=F32, device=0, dropout=0.0, nonLinearity=True)
     return GCN(ResidualModule(nn.Sequential(*mods)))
 
 
+_batch_fused = True
+
+
+def graphBatchFused(on: bool) -> bool:
+    """process-wide: minibatches of small graphs collated by the graph_batch kernels out of the data set's own groupings, and pooled by the
+    SegmentPool node (True, the default), or the reference's fold out of existing operators into a Graph with empty caches and the composed
+    VertexPooling; returns the previous setting."""
+    global _batch_fused
+    prev, _batch_fused = _batch_fused, bool(on)
+    return prev
+
+
 def VertexPooling(x: Graph, pooling: str) -> Variable:
-    """VertexPooling(graph, Sum | Mean) (VertexPooling.scala): node features summed (averaged) per value of vertexPoolingIndices"""
+    """VertexPooling(graph, Sum | Mean) (VertexPooling.scala): node features summed (averaged) per value of vertexPoolingIndices.  A
+    collated batch (graphPtr set) in f32 / f64 with graphBatchFused(True): one SegmentPool node over the consecutive rows of every graph,
+    no atomics and no host read; otherwise IndexAdd after a host read of the largest index."""
     assert pooling in ("Sum", "Mean"), pooling
     idx = x.vertexPoolingIndices
+    if x.graphPtr is not None and _batch_fused and x.nodeFeatures.value.dtype in (F32, F64):
+        return apply_op("SegmentPool", [x.nodeFeatures], tensors=[x.graphPtr, idx], i=[int(pooling == "Mean")])
     maxi = int(idx.castToDouble().maxAll().item()) + 1              # the max reduction exists for floating types; exact below 2^53
     total = x.nodeFeatures.indexAdd(const(idx), 0, maxi)
     if pooling == "Sum":
@@ -259,15 +279,23 @@ def graphAttentionAggregate(activations: Variable, nodeValue: Variable, edgeI: S
     return apply_op("GraphAttentionAggregate", [score, nodeValue], tensors=[edgeI, edgeJ] + csr.incoming + csr.outgoing, i=[numHeads])
 
 
-def _attention_scores(nodeFeatures, edgeFeatures, edgeI, edgeJ, wNodeKey1, wNodeKey2, wEdgeKey, wNodeValue, wAttention, numHeads):
-    """GraphAttention.scala:132-171: (activations, nodeValue) out of existing nodes"""
+def _attention_scores(nodeFeatures, edgeFeatures, edgeI, edgeJ, wNodeKey1, wNodeKey2, wEdgeKey, wNodeValue, wAttention, numHeads, csr=None):
+    """GraphAttention.scala:132-171: (activations, nodeValue) out of existing nodes.  The two key gathers are IndexSelect nodes, whose closure
+    is an IndexAdd: atomic sums that land in the order the hardware schedules them.  With `csr` (the fused path) they are GraphGather nodes:
+    the same values, and a gradient summed per node over the grouping in its order, a function of the input alone."""
     assert wNodeValue.shape[1] % numHeads == 0, f"wNodeValue and numHeads size do not align {wNodeValue.shape[1]} {numHeads}"
 
     def mm(a, b):
         return a.mm(b).view([a.shape[0], numHeads, b.shape[1] // numHeads])
 
-    nodeKey1, nodeKey2, edgeKey, nodeValue = mm(nodeFeatures, wNodeKey1), mm(nodeFeatures, wNodeKey2), mm(edgeFeatures, wEdgeKey), mm(nodeFeatures, wNodeValue)
-    ni, nj = nodeKey1.indexSelect(0, const(edgeI)), nodeKey2.indexSelect(0, const(edgeJ))
+    def keys(w, index, grouping):
+        if csr is None:
+            return mm(nodeFeatures, w).indexSelect(0, const(index))
+        gathered = apply_op("GraphGather", [nodeFeatures.mm(w)], tensors=[index] + grouping)
+        return gathered.view([index.shape[0], numHeads, w.shape[1] // numHeads])
+
+    edgeKey, nodeValue = mm(edgeFeatures, wEdgeKey), mm(nodeFeatures, wNodeValue)
+    ni, nj = keys(wNodeKey1, edgeI, csr.outgoing if csr is not None else None), keys(wNodeKey2, edgeJ, csr.incoming if csr is not None else None)
     if wAttention is not None:
         ninjeij = apply_op("Concatenate", [ni, nj, edgeKey], i=[2])
         k = ninjeij.shape[2]
@@ -283,7 +311,12 @@ def multiheadGraphAttention(nodeFeatures: Variable, edgeFeatures: Variable, edge
     """GraphAttention.multiheadGraphAttention (GraphAttention.scala:119-198): the next node representation [N, H * V], without
     non-linearity or dropout.  Self edges must be present in the edge list.  With wAttention the score of an edge is tanh of the
     concatenated keys times wAttention per head, without it the scaled dot product of the node keys plus the edge key."""
-    activations, nodeValue = _attention_scores(nodeFeatures, edgeFeatures, edgeI, edgeJ, wNodeKey1, wNodeKey2, wEdgeKey, wNodeValue, wAttention, numHeads)
+    if _gat_fused and nodeFeatures.value.dtype in (F32, F64):
+        if csr is None:
+            csr = computeEdgeCsr(edgeI, edgeJ, nodeFeatures.shape[0])
+    else:
+        csr = None
+    activations, nodeValue = _attention_scores(nodeFeatures, edgeFeatures, edgeI, edgeJ, wNodeKey1, wNodeKey2, wEdgeKey, wNodeValue, wAttention, numHeads, csr)
     return graphAttentionAggregate(activations, nodeValue, edgeI, edgeJ, numHeads, csr)
 
 
