@@ -1007,6 +1007,15 @@ int lamp_shampoo_step_(lamp_tensor* const* params, lamp_tensor* const* grads, la
  * contiguous f32 bucket scaled by `scale`, and unpack with a (device-resident) divisor */
 int lamp_flatten_into_(lamp_tensor* bucket, lamp_tensor* const* ts, int n, double scale);
 int lamp_unflatten_from_(lamp_tensor* const* ts, int n, const lamp_tensor* bucket, int divide_by_last_element);
+/* model-state operations of the training drivers (lamp-data IOLoops.epochs / SWA.epochs), one launch per 40
+ * tensors per dtype class instead of one to three ATen calls per tensor.  Pair i of the two lists has one dtype, one element count and
+ * one device and is contiguous; a call that is rejected has written nothing and its message names the offending index.
+ * lamp_swa_average_: avg[i] = ((avg[i] * k) + cur[i]) / (k + 1), k = number_of_averaged_models, in place on the accumulator
+ * (SWA.scala:136-145).  f32, f64, bf16 and f16, mixed freely; the product, the sum and the quotient are each rounded to the tensor's
+ * dtype, the bits of lamp_mul_scalar, lamp_add(.., 1.0), lamp_div_scalar (a true quotient) in a row.
+ * lamp_state_copy_: dst[i] <- src[i], any dtype: a snapshot of a module's state into tensors the caller allocated, and its restore. */
+int lamp_swa_average_(lamp_tensor* const* avg, lamp_tensor* const* cur, int n, int64_t number_of_averaged_models);
+int lamp_state_copy_(lamp_tensor* const* dst, lamp_tensor* const* src, int n);
 
 /* ------------------------------------------------------------------------------------------
  * scaled dot product attention   (aten _scaled_dot_product_*_attention(+_backward):

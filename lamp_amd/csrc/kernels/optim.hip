@@ -382,6 +382,58 @@ __global__ __launch_bounds__(256) void shampoo_vec_root_kernel(T* __restrict__ o
   if (i < n) out[i] = shampoo_root<T>(stat[i]);
 }
 
+// ---- model-state operations of the training drivers (IOLoops.epochs / SWA.epochs) -------------------------------
+// One chunk of a two-list operation dst <- f(dst, src) over elements of type T: 16-byte packets where both bases are on one (a chunk
+// starts a multiple of MT_CHUNK elements into its tensor: aligned iff the tensor is), element-wise past the last whole packet and for
+// the whole chunk otherwise.
+template <class T, class F>
+__device__ __forceinline__ void mt_pair_chunk(const MultiArgs& a, int t, F f) {
+  constexpr int W = 16 / sizeof(T);
+  const int64_t begin = (int64_t)(blockIdx.x - a.blk_start[t]) * MT_CHUNK;
+  const int64_t end = min(begin + MT_CHUNK, a.numel[t]);
+  T* d = (T*)a.p[0][t];
+  const T* s = (const T*)a.p[1][t];
+  int64_t i0 = begin;
+  if (((((uintptr_t)(d + begin)) | ((uintptr_t)(s + begin))) & 15) == 0) {
+    const int nv = (int)((end - begin) / W);
+    Vec<T, W>* dq = reinterpret_cast<Vec<T, W>*>(d + begin);
+    const Vec<T, W>* sq = reinterpret_cast<const Vec<T, W>*>(s + begin);
+    for (int q = threadIdx.x; q < nv; q += blockDim.x) {
+      Vec<T, W> dk = dq[q];
+      const Vec<T, W> sk = sq[q];
+#pragma unroll
+      for (int k = 0; k < W; k++) dk.v[k] = f(dk.v[k], sk.v[k]);
+      dq[q] = dk;
+    }
+    i0 = begin + (int64_t)nv * W;
+  }
+  for (int64_t i = i0 + threadIdx.x; i < end; i += blockDim.x) d[i] = f(d[i], s[i]);
+}
+
+// SWA.scala:136-145 updateAccumulator, in place on the accumulator: tmp1 = avg * n; tmp2 = tmp1 + current; avg = tmp2 / (n + 1).  The
+// reference stores three tensors, so each of the three results is rounded to T; the product is a rounded value before the addition
+// (contracted, avg*n + cur would be rounded once), and the division is the true quotient lamp_div_scalar computes, not a product with
+// the reciprocal.  p[0]=avg, p[1]=current; s[0]=n, s[1]=n+1
+template <class T>
+__global__ __launch_bounds__(256) void swa_average_kernel(MultiArgs a) {
+  using A = acc_t<T>;
+  const int t = mt_find(a, blockIdx.x);
+  const A n = (A)a.s[0], n1 = (A)a.s[1];
+  mt_pair_chunk<T>(a, t, [&](T avg, T cur) {
+    const T scaled = store_as<T>(rounded_mul(load_as<A>(avg), n));                // ATen.mul_1(avg, n)
+    const T sum = store_as<T>((A)(load_as<A>(scaled) + load_as<A>(cur)));         // ATen.add_0(tmp1, current, 1d)
+    return store_as<T>((A)(load_as<A>(sum) / n1));                                // ATen.div_2(tmp2, n + 1)
+  });
+}
+
+// dst[i] = src[i] over tensors of one element size (U: an unsigned integer of that size - the bytes move, whatever the dtype).
+// p[0]=dst, p[1]=src
+template <class U>
+__global__ __launch_bounds__(256) void state_copy_kernel(MultiArgs a) {
+  const int t = mt_find(a, blockIdx.x);
+  mt_pair_chunk<U>(a, t, [](U, U src) { return src; });
+}
+
 // host: iterate over the tensor lists in groups of MT_MAX
 template <class Fill, class Launch>
 static void for_each_group(int n, const int64_t* numels, Fill fill, Launch launch) {
@@ -437,6 +489,36 @@ static void for_each_class(lamp_tensor* const* params, const std::vector<int>& k
       for (size_t i = 0; i < key.size(); i++) if (params[i]->dtype == dt && key[i] == k) sel.push_back((int)i);
       if (!sel.empty()) launch(dt, sel);
     }
+}
+
+
+// swa_average / state_copy: pair i of the two lists has one dtype, one element count, one device (the first pair's) and is contiguous;
+// `floating`: every dtype is f32, f64, bf16 or f16.  Everything is checked before the first launch, so a rejected call has written nothing.
+static void check_state_pair(const char* who, const char* dname, lamp_tensor* const* dst, const char* sname, lamp_tensor* const* src, int n,
+                             bool floating) {
+  LAMP_CHECK(n > 0 && dst && src, who << ": null tensor list");
+  check_device_tensor(dst[0], dname);                          // host state: the staging layer runs the kernel on GPU copies
+  const int dev = dst[0]->device();
+  for (int i = 0; i < n; i++) {
+    const struct { lamp_tensor* t; const char* what; } lists[2] = {{dst[i], dname}, {src[i], sname}};
+    for (const auto& l : lists) {
+      LAMP_CHECK(l.t != nullptr, who << ": " << l.what << " " << i << " is null");
+      check_device_tensor(l.t, l.what);
+      LAMP_CHECK(l.t->device() == dev, who << ": " << l.what << " " << i << " is on another device");
+      LAMP_CHECK(l.t->is_contiguous(), who << ": " << l.what << " " << i << " must be contiguous");
+    }
+    LAMP_CHECK(src[i]->dtype == dst[i]->dtype, who << ": " << sname << " " << i << " has dtype " << dtype_name(src[i]->dtype) << ", the " << dname << " "
+                                                   << dtype_name(dst[i]->dtype));
+    LAMP_CHECK(src[i]->numel() == dst[i]->numel(), who << ": " << sname << " " << i << " has " << src[i]->numel() << " elements, the " << dname << " "
+                                                       << dst[i]->numel());
+    if (floating) LAMP_CHECK(is_float(dst[i]->dtype), who << ": tensor " << i << " has dtype " << dtype_name(dst[i]->dtype) << ", not a floating point type");
+    else { const size_t w = dst[i]->itemsize(); LAMP_CHECK(w == 1 || w == 2 || w == 4 || w == 8, who << ": tensor " << i << " has elements of " << w << " bytes"); }
+  }
+}
+static int64_t mt_elements(const MultiArgs& a) {
+  int64_t e = 0;
+  for (int t = 0; t < a.n; t++) e += a.numel[t];
+  return e;
 }
 
 }  // namespace lamp
@@ -862,6 +944,58 @@ int lamp_unflatten_from_(lamp_tensor* const* ts, int n, const lamp_tensor* bucke
       [&](MultiArgs& a, int t, int gi) { a.p[0][t] = ts[gi]->data(); a.h[0][t] = (double)offs[gi]; },
       [&](MultiArgs& a, int blk) { hipLaunchKernelGGL((mt_unflatten_kernel<T>), dim3(blk), dim3(256), 0, st, a, bucket->ptr<float>(), last); }));
   LAMP_LAUNCH_CHECK();
+  LAMP_API_END
+}
+
+// The running mean of the weight average, in place on the accumulator (swa_average_kernel): one launch per MT_MAX tensors per dtype.
+int lamp_swa_average_(lamp_tensor* const* avg, lamp_tensor* const* cur, int n, int64_t number_of_averaged_models) {
+  LAMP_API_BEGIN
+  if (n == 0) return 0;
+  LAMP_CHECK(number_of_averaged_models >= 0, "swa_average: numberOfAveragedModels must not be negative, got " << number_of_averaged_models);
+  check_state_pair("swa_average", "accumulator", avg, "current", cur, n, true);
+  hipStream_t st = current_stream(avg[0]->device());
+  for_each_class(avg, std::vector<int>(n, 0), 1, [&](int dt, const std::vector<int>& sel) {
+    std::vector<int64_t> numels(sel.size());
+    for (size_t k = 0; k < sel.size(); k++) numels[k] = avg[sel[k]]->numel();
+    auto fill = [&](MultiArgs& a, int t, int gi) {
+      a.p[0][t] = avg[sel[gi]]->data(); a.p[1][t] = cur[sel[gi]]->data();
+      a.s[0] = (double)number_of_averaged_models;
+      a.s[1] = (double)(number_of_averaged_models + 1);
+    };
+    LAMP_DISPATCH_FLOAT(dt, T, for_each_group((int)sel.size(), numels.data(), fill, [&](MultiArgs& a, int blk) {
+      const double elems = (double)mt_elements(a);
+      KernelTimer kt("swa_average", 3.0 * elems, 3.0 * elems * sizeof(T), st);
+      hipLaunchKernelGGL((swa_average_kernel<T>), dim3(blk), dim3(256), 0, st, a);
+    }));
+    LAMP_LAUNCH_CHECK();
+  });
+  LAMP_API_END
+}
+
+// dst[i] <- src[i] for n tensor pairs of any dtype (state_copy_kernel): one launch per MT_MAX tensors per element size.  The snapshot
+// of a module's state, its restore, and Module.load from tensors that already live on the module's device in its dtypes.
+int lamp_state_copy_(lamp_tensor* const* dst, lamp_tensor* const* src, int n) {
+  LAMP_API_BEGIN
+  if (n == 0) return 0;
+  check_state_pair("state_copy", "destination", dst, "source", src, n, false);
+  hipStream_t st = current_stream(dst[0]->device());
+  for (size_t width : {(size_t)1, (size_t)2, (size_t)4, (size_t)8}) {
+    std::vector<int> sel;
+    for (int i = 0; i < n; i++) if (dst[i]->itemsize() == width) sel.push_back(i);
+    if (sel.empty()) continue;
+    std::vector<int64_t> numels(sel.size());
+    for (size_t k = 0; k < sel.size(); k++) numels[k] = dst[sel[k]]->numel();
+    auto fill = [&](MultiArgs& a, int t, int gi) { a.p[0][t] = dst[sel[gi]]->data(); a.p[1][t] = src[sel[gi]]->data(); };
+    auto launch = [&](MultiArgs& a, int blk) {
+      KernelTimer kt("state_copy", 0, 2.0 * (double)mt_elements(a) * (double)width, st);
+      if (width == 1) hipLaunchKernelGGL((state_copy_kernel<uint8_t>), dim3(blk), dim3(256), 0, st, a);
+      else if (width == 2) hipLaunchKernelGGL((state_copy_kernel<uint16_t>), dim3(blk), dim3(256), 0, st, a);
+      else if (width == 4) hipLaunchKernelGGL((state_copy_kernel<uint32_t>), dim3(blk), dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((state_copy_kernel<uint64_t>), dim3(blk), dim3(256), 0, st, a);
+    };
+    for_each_group((int)sel.size(), numels.data(), fill, launch);
+    LAMP_LAUNCH_CHECK();
+  }
   LAMP_API_END
 }
 

@@ -5,11 +5,15 @@ Mirror of lamp.data.{Writer, Reader, BatchStream} and example-cifar100's Cifar.l
   Reader.readTensorsFromFile / loadFromFile            lamp-data/src/main/scala/lamp/data/Reader.scala:62-95
   BatchStream.minibatchesFromFull, everyNth            lamp-data/src/main/scala/lamp/data/BatchStream.scala:528-592, :378-400
   Cifar.loadImageFile                                  example-cifar100/src/main/scala/lamp/example/cifar/cifar100.scala:29-56
-Every function is one call into liblamp_hip.so (lamp_amd/csrc/host/data.cpp).
+  StateIO.writeToFile / readFromFile / stateToFile     lamp-data/src/main/scala/lamp/data/StateIO.scala:16-303 (JSON glue over the tensor-list files)
+Every other function is one call into liblamp_hip.so (lamp_amd/csrc/host/data.cpp).
 """
 from __future__ import annotations
 
 import ctypes as C
+import json
+import os
+import tempfile
 from typing import Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -37,6 +41,122 @@ def writeCheckpoint(file: str, model) -> None:
 
 def loadFromFile(module, file: str) -> None:
     lib.lamp_module_load_from_file(module.h, str(file).encode())
+
+
+# ---- loop-state files (StateIO.scala:16-297, schemas/schemas.scala:58-101) -------------------------------------------------------------------
+# `file` holds a JSON descriptor with the reference's field names: a three-way union tagged by "type" (jsoniter-scala's default
+# discriminator: the case-class name), tensor lists as the TensorList descriptors of the tensor-list files, tuples as arrays, absent
+# options and empty lists left out (None inside a tuple is null).  The tensors of every list go through writeTensorsIntoFile into a file
+# of their own beside the descriptor: <name>.model, <name>.optimizer, <name>.minvalidmodel, <name>.averagemodel, with <name> =
+# <file>.simple / <file>.swa inside a SimpleThenSWALoopState.  Compatibility with a file the reference wrote is unverified (DESIGN.md
+# section 21): its tree holds no loop-state fixture.
+def _write_tensor_list(tensors: Sequence[STen], directory: str, location: str) -> dict:
+    tmp = os.path.join(directory, location + ".tmp")
+    writeTensorsIntoFile(tensors, tmp)                       # the descriptor in `tmp`, the tensor data in `tmp`.data
+    with open(tmp) as f:
+        descriptor = json.load(f)
+    os.replace(tmp + ".data", os.path.join(directory, location))
+    os.remove(tmp)
+    descriptor["location"] = location
+    return descriptor
+
+
+def _read_tensor_list(descriptor: dict, directory: str, device: int) -> List[STen]:
+    location = descriptor["location"]
+    absolute = dict(descriptor, location=location if os.path.isabs(location) else os.path.abspath(os.path.join(directory, location)))
+    with tempfile.TemporaryDirectory() as scratch:
+        path = os.path.join(scratch, "tensors")
+        with open(path, "w") as f:
+            json.dump(absolute, f)
+        return readTensorsFromFile(path, device)
+
+
+def _without_absent(fields: dict) -> dict:
+    return {k: v for k, v in fields.items() if v is not None and v != []}
+
+
+def _simple_descriptor(s, directory: str, name: str) -> dict:
+    minValid = None
+    if s.minValidationLossModel is not None:
+        minValid = [int(s.minValidationLossModel[0]), _write_tensor_list(s.minValidationLossModel[1], directory, name + ".minvalidmodel")]
+    return _without_absent({
+        "type": "SimpleLoopState",
+        "model": _write_tensor_list(s.model, directory, name + ".model"),
+        "optimizer": _write_tensor_list(s.optimizer, directory, name + ".optimizer"),
+        "epoch": int(s.epoch), "lastValidationLoss": s.lastValidationLoss, "minValidationLoss": s.minValidationLoss,
+        "minValidationLossModel": minValid,
+        "learningCurve": [[int(e), float(t), None if v is None else float(v[0]), None if v is None else float(v[1])] for e, t, v in s.learningCurve]})
+
+
+def _swa_descriptor(s, directory: str, name: str) -> dict:
+    return _without_absent({
+        "type": "SWALoopState",
+        "model": _write_tensor_list(s.model, directory, name + ".model"),
+        "optimizer": _write_tensor_list(s.optimizer, directory, name + ".optimizer"),
+        "epoch": int(s.epoch), "lastValidationLoss": s.lastValidationLoss, "minValidationLoss": s.minValidationLoss,
+        "numberOfAveragedModels": int(s.numberOfAveragedModels),
+        "averagedModels": None if s.averagedModels is None else _write_tensor_list(s.averagedModels, directory, name + ".averagemodel"),
+        "learningCurve": [[int(e), float(t), None if v is None else float(v)] for e, t, v in s.learningCurve]})
+
+
+def writeLoopState(file: str, state) -> None:
+    """StateIO.writeToFile: a loops.SimpleLoopState / SWALoopState / SimpleThenSWALoopState into `file` and the tensor files beside it"""
+    from . import loops
+    file = os.path.abspath(str(file))
+    directory, name = os.path.dirname(file), os.path.basename(file)
+    if isinstance(state, loops.SimpleLoopState):
+        descriptor = _simple_descriptor(state, directory, name)
+    elif isinstance(state, loops.SWALoopState):
+        descriptor = _swa_descriptor(state, directory, name)
+    elif isinstance(state, loops.SimpleThenSWALoopState):
+        simple = _simple_descriptor(state.simple, directory, name + ".simple")
+        swa = None if state.swa is None else _swa_descriptor(state.swa, directory, name + ".swa")
+        del simple["type"]                                  # the members' types are fixed: no discriminator inside
+        if swa is not None:
+            del swa["type"]
+        descriptor = _without_absent({"type": "SimpleThenSWALoopState", "simple": simple, "swa": swa})
+    else:
+        raise TypeError(f"not a loop state: {type(state).__name__}")
+    with open(file + ".tmp", "w") as f:
+        json.dump(descriptor, f, separators=(",", ":"))
+    os.replace(file + ".tmp", file)
+
+
+def readLoopState(file: str, device: int = 0):
+    """StateIO.readFromFile: the loop state in `file` with its tensors on `device` (-1: the host), to be handed to a driver as initState"""
+    from . import loops
+    file = os.path.abspath(str(file))
+    directory = os.path.dirname(file)
+    with open(file) as f:
+        descriptor = json.load(f)
+    tensors = lambda d: _read_tensor_list(d, directory, device)
+
+    def simple(d):
+        mv = d.get("minValidationLossModel")
+        return loops.SimpleLoopState(tensors(d["model"]), tensors(d["optimizer"]), int(d["epoch"]), d.get("lastValidationLoss"), d.get("minValidationLoss"),
+                                     None if mv is None else (int(mv[0]), tensors(mv[1])),
+                                     [(int(e), float(t), None if a is None or b is None else (float(a), float(b))) for e, t, a, b in d.get("learningCurve", [])])
+
+    def swa(d):
+        avg = d.get("averagedModels")
+        return loops.SWALoopState(tensors(d["model"]), tensors(d["optimizer"]), int(d["epoch"]), d.get("lastValidationLoss"), d.get("minValidationLoss"),
+                                  int(d["numberOfAveragedModels"]), None if avg is None else tensors(avg),
+                                  [(int(e), float(t), None if v is None else float(v)) for e, t, v in d.get("learningCurve", [])])
+
+    kind = descriptor.get("type")
+    if kind == "SimpleLoopState":
+        return simple(descriptor)
+    if kind == "SWALoopState":
+        return swa(descriptor)
+    if kind == "SimpleThenSWALoopState":
+        return loops.SimpleThenSWALoopState(simple(descriptor["simple"]), None if descriptor.get("swa") is None else swa(descriptor["swa"]))
+    raise ValueError(f"{file}: unknown loop state type {kind!r}")
+
+
+def loopStateToFile(file: str):
+    """StateIO.stateToFile: the ready-made `checkpointState` of loops.epochs / swaEpochs / withSWA - (state, lrState) -> writeLoopState(file, state).
+    The learning-rate schedule's state is not part of the file, as in the reference."""
+    return lambda state, lrState=None: writeLoopState(file, state)
 
 
 def loadImageFile(file: str, numImages: int, dtype: int = F32, device: int = 0) -> Tuple[STen, STen]:

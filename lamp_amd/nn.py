@@ -56,11 +56,68 @@ class Module:
         return [p.partialDerivative for p in self.parameters]
 
     def load(self, tensors: Sequence[STen]):
-        """Load.make: copy into the state tensors in order."""
+        """Load.make: copy into the state tensors in order.  Sources that already live on the module's device in the state's own dtypes
+        and shapes (a snapshot, a weight average) go in one state_copy launch per 40 tensors; everything else one copyFrom per tensor."""
         st = self.state
         assert len(st) == len(tensors), f"state has {len(st)} tensors, got {len(tensors)}"
-        for v, t in zip(st, tensors):
-            v.value.copyFrom(t)
+        dst = [v.value for v in st]
+        if _state_fused and dst and _same_layout(dst, tensors):
+            lib.lamp_state_copy_(handle_array([t.h for t in dst]), handle_array([t.h for t in tensors]), len(dst))
+            return
+        for d, t in zip(dst, tensors):
+            d.copyFrom(t)
+
+
+# ---- model-state operations of the training drivers (loops.epochs / swaEpochs; DESIGN.md section 21) ------------------------------------
+_state_fused = True
+
+
+def stateKernelsFused(on: bool) -> bool:
+    """process-wide: snapshots, the weight average and Module.load of device-resident state as multi-tensor launches (True, the default),
+    or the reference's per-tensor clone, three-operator chain and copyFrom out of existing operators; returns the previous setting."""
+    global _state_fused
+    prev, _state_fused = _state_fused, bool(on)
+    return prev
+
+
+def _same_layout(dst: Sequence[STen], src: Sequence[STen]) -> bool:
+    """every pair on one GPU, of one dtype and shape, both contiguous: what lamp_state_copy_ takes"""
+    dev = dst[0].device
+    if dev < 0:
+        return False
+    return all(s.device == dev and d.device == dev and s.dtype == d.dtype and s.shape == d.shape and s.is_contiguous() and d.is_contiguous()
+               for d, s in zip(dst, src))
+
+
+def _on_gpu(tensors: Sequence[STen]) -> bool:
+    return bool(tensors) and all(t.device >= 0 for t in tensors)
+
+
+def stateSnapshot(tensors: Sequence[STen]) -> List[STen]:
+    """copyModel (IOLoops.scala:429-439): copies that own their storage.  Device-resident state: the destinations are allocated here and
+    filled by one state_copy launch per 40 tensors; host state, or stateKernelsFused(False): one clone per tensor."""
+    if not (_state_fused and _on_gpu(tensors)):
+        return [t.cloneTensor() for t in tensors]
+    out = []
+    for t in tensors:
+        o = C.c_void_p()
+        shape = t.shape
+        lib.lamp_empty(C.byref(o), i64_array(shape), len(shape), t.dtype, t.device)
+        out.append(STen(o))
+    src = [t if t.is_contiguous() else t.contiguous() for t in tensors]
+    lib.lamp_state_copy_(handle_array([t.h for t in out]), handle_array([t.h for t in src]), len(out))
+    return out
+
+
+def swaAverage(averaged: Sequence[STen], current: Sequence[STen], numberOfAveragedModels: int) -> List[STen]:
+    """updateAccumulator (SWA.scala:136-145): ((avg * n) + current) / (n + 1) per tensor, each of the three results rounded to the tensor's
+    dtype.  Device-resident state: in place on `averaged`, one swa_average launch per 40 tensors per dtype, and `averaged` itself is
+    returned; host state, or stateKernelsFused(False): the chain of the three operators, three new tensors per state tensor."""
+    assert len(averaged) == len(current), f"{len(averaged)} averaged tensors, {len(current)} current ones"
+    if _state_fused and _on_gpu(averaged):
+        lib.lamp_swa_average_(handle_array([t.h for t in averaged]), handle_array([t.h for t in current]), len(averaged), int(numberOfAveragedModels))
+        return list(averaged)
+    return [(avg * float(numberOfAveragedModels)).add(cur, 1.0) / float(numberOfAveragedModels + 1) for avg, cur in zip(averaged, current)]
 
 
 def _mk(fn, *args) -> Module:

@@ -70,7 +70,7 @@ def classify(param):
 READ_ONLY_ARRAYS = {("lamp_cat", "ts"), ("lamp_cat_out", "ts"), ("lamp_stack", "ts"), ("lamp_adamw_step_", "grads"), ("lamp_sgdw_step_", "grads"),
                     ("lamp_flatten_into_", "ts"), ("lamp_radam_step_", "grads"),     # NOT lamp_yogi_step_'s: Yogi writes its gradients,
                     ("lamp_symmetric_eig", "matrices"),                              # nor lamp_shampoo_step_'s: momentum blends into them
-                    ("lamp_recurrent_decode_pack", "tensors")}
+                    ("lamp_recurrent_decode_pack", "tensors"), ("lamp_swa_average_", "cur"), ("lamp_state_copy_", "src")}
 
 
 def generate():
