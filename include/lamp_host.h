@@ -48,6 +48,23 @@ int lamp_op_apply(lamp_var** out, const char* name, lamp_var* const* vars, int n
 int lamp_module_linear(lamp_module** out, int64_t in, int64_t outf, int dtype, int device, int bias);
 int lamp_module_conv2d(lamp_module** out, int64_t in_channels, int64_t out_channels, int64_t kernel, int dtype, int device, int bias,
                        int64_t stride, int64_t padding, int64_t dilation, int64_t groups);
+/* Conv1D (nn/Conv1D.scala): input [N, in, L], weights [out, in / groups, kernel] ~ N(0, sqrt(2 / (out + in))), bias zeros [out] (a
+ * parameter with bias != 0, else a constant that is still part of the state).  The reference writes the weight as [out, in, kernel]
+ * whatever groups is; this follows lamp_module_conv2d.
+ * Conv2DTransposed (nn/Conv2DTransposed.scala): input [N, in, H, W], weights [in, out, kernel, kernel], same init, groups 1, output
+ * padding 0, output (H - 1) stride - 2 padding + dilation (kernel - 1) + 1.  The reference's default is bias = false.
+ * WeightNormLinear (nn/WeightNormLinear.scala): state [V [out, in] ~ N(0, sqrt(2 / (in + out))), G [1, in] ~ N(0, 0.01), bias zeros
+ * [1, out] if bias]; forward x.mm(WeightNorm(V, G, dim 0).t) + bias, a composition of existing nodes.
+ * bf16 / f32 convolutions of the first two run on the matrix cores (kernels/conv_gen.hip), see lamp_convolution_matrix_path. */
+int lamp_module_conv1d(lamp_module** out, int64_t in_channels, int64_t out_channels, int64_t kernel, int dtype, int device, int bias,
+                       int64_t stride, int64_t padding, int64_t dilation, int64_t groups);
+int lamp_module_conv2d_transposed(lamp_module** out, int64_t in_channels, int64_t out_channels, int64_t kernel, int dtype, int device, int bias,
+                                  int64_t stride, int64_t padding, int64_t dilation);
+int lamp_module_weight_norm_linear(lamp_module** out, int64_t in, int64_t outf, int dtype, int device, int bias);
+/* 1 (the default): 1-D and transposed convolutions in bf16 / f32 with groups == 1 that no specialised kernel takes run the general
+ * implicit-GEMM kernels on the matrix cores (forward, input gradient, weight gradient; deterministic).  0: they run the direct kernels,
+ * as f64 and grouped ones always do.  Process-wide; returns the previous value in *previous_or_null. */
+int lamp_convolution_matrix_path(int on, int* previous_or_null);
 int lamp_module_batch_norm(lamp_module** out, int64_t features, int dtype, int device, int two_d);
 int lamp_module_layer_norm(lamp_module** out, const int64_t* shape, int nshape, int dtype, int device, int scale, int bias);
 int lamp_module_dropout(lamp_module** out, double p);

@@ -155,6 +155,17 @@ int lamp_module_conv2d(lamp_module** out, int64_t inC, int64_t outC, int64_t k, 
                        int64_t dilation, int64_t groups) {
   LAMP_API_BEGIN *out = wrapm(Conv2D::make(inC, outC, k, dtype, device, bias, stride, padding, dilation, groups)); LAMP_API_END
 }
+int lamp_module_conv1d(lamp_module** out, int64_t inC, int64_t outC, int64_t k, int dtype, int device, int bias, int64_t stride, int64_t padding,
+                       int64_t dilation, int64_t groups) {
+  LAMP_API_BEGIN *out = wrapm(Conv1D::make(inC, outC, k, dtype, device, bias, stride, padding, dilation, groups)); LAMP_API_END
+}
+int lamp_module_conv2d_transposed(lamp_module** out, int64_t inC, int64_t outC, int64_t k, int dtype, int device, int bias, int64_t stride,
+                                  int64_t padding, int64_t dilation) {
+  LAMP_API_BEGIN *out = wrapm(Conv2DTransposed::make(inC, outC, k, dtype, device, bias, stride, padding, dilation)); LAMP_API_END
+}
+int lamp_module_weight_norm_linear(lamp_module** out, int64_t in, int64_t outf, int dtype, int device, int bias) {
+  LAMP_API_BEGIN *out = wrapm(WeightNormLinear::make(in, outf, dtype, device, bias)); LAMP_API_END
+}
 int lamp_module_batch_norm(lamp_module** out, int64_t features, int dtype, int device, int two_d) {
   LAMP_API_BEGIN *out = wrapm(BatchNorm::make(features, dtype, device, two_d)); LAMP_API_END
 }

@@ -41,6 +41,48 @@ Var Conv2D::forward(const Var& x) {
   return F::convolution(x, weights, bias, {stride, stride}, {padding, padding}, {dilation, dilation}, false, {0, 0}, groups);
 }
 
+// ---- Conv1D (nn/Conv1D.scala) -----------------------------------------------------------------------
+// The reference writes the weight as [out, in, k] whatever `groups` is, which its own operator rejects for groups > 1; this follows
+// Conv2D::make's [out, in / groups, k].
+Mod Conv1D::make(int64_t inC, int64_t outC, int64_t k, int dtype, int device, bool bias, int64_t stride, int64_t padding, int64_t dilation,
+                 int64_t groups) {
+  LAMP_CHECK(groups >= 1 && inC % groups == 0, "Conv1D: " << inC << " input channels are not divisible by " << groups << " groups");
+  auto m = std::make_shared<Conv1D>();
+  m->weights = make_param(ops::normal(0.0, std::sqrt(2.0 / (double)(outC + inC)), {outC, inC / groups, k}, dtype, device));
+  Ten b = ops::zeros({outC}, dtype, device);
+  m->bias = bias ? make_param(b) : make_const(b);
+  m->stride = stride; m->padding = padding; m->dilation = dilation; m->groups = groups;
+  return m;
+}
+Var Conv1D::forward(const Var& x) { return F::convolution(x, weights, bias, {stride}, {padding}, {dilation}, false, {0}, groups); }
+
+// ---- Conv2DTransposed (nn/Conv2DTransposed.scala) ---------------------------------------------------
+Mod Conv2DTransposed::make(int64_t inC, int64_t outC, int64_t k, int dtype, int device, bool bias, int64_t stride, int64_t padding,
+                           int64_t dilation) {
+  auto m = std::make_shared<Conv2DTransposed>();
+  m->weights = make_param(ops::normal(0.0, std::sqrt(2.0 / (double)(outC + inC)), {inC, outC, k, k}, dtype, device));
+  Ten b = ops::zeros({outC}, dtype, device);
+  m->bias = bias ? make_param(b) : make_const(b);
+  m->stride = stride; m->padding = padding; m->dilation = dilation;
+  return m;
+}
+Var Conv2DTransposed::forward(const Var& x) {
+  return F::convolution(x, weights, bias, {stride, stride}, {padding, padding}, {dilation, dilation}, true, {0, 0}, 1);
+}
+
+// ---- WeightNormLinear (nn/WeightNormLinear.scala): x.mm(WeightNorm(V, G, 0).t) + bias -----------------
+Mod WeightNormLinear::make(int64_t in, int64_t out, int dtype, int device, bool bias) {
+  auto m = std::make_shared<WeightNormLinear>();
+  m->weightsV = make_param(ops::normal(0.0, std::sqrt(2.0 / (double)(in + out)), {out, in}, dtype, device));
+  m->weightsG = make_param(ops::normal(0.0, 0.01, {1, in}, dtype, device));
+  m->bias = bias ? make_param(ops::zeros({1, out}, dtype, device)) : nullptr;
+  return m;
+}
+Var WeightNormLinear::forward(const Var& x) {
+  Var v = F::mm(x, F::transpose(F::weight_norm(weightsV, weightsG, 0), 0, 1));
+  return bias ? F::add(bias, v) : v;
+}
+
 // ---- BatchNorm / BatchNorm2D (init: weight N(0, 0.01), bias 0, running mean 0, running var 0) ----
 Mod BatchNorm::make(int64_t features, int dtype, int device, bool two_d) {
   auto m = std::make_shared<BatchNorm>();

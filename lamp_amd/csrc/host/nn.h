@@ -59,6 +59,28 @@ struct Conv2D : Module {        // nn/Conv2D.scala:8-83 (bias is always a tensor
   void collect_state(std::vector<Var>& o) override { o.push_back(weights); o.push_back(bias); }
   Var forward(const Var& x) override;
 };
+// Types of their own, not Conv2D's: Sequential's ResNet look-aheads (nn.cpp) dynamic_cast to Conv2D and must not match these.
+struct Conv1D : Module {        // nn/Conv1D.scala (state [weights, bias]; bias const zeros when bias=false)
+  Var weights, bias;
+  int64_t stride, padding, dilation, groups;
+  static Mod make(int64_t inC, int64_t outC, int64_t k, int dtype, int device, bool bias, int64_t stride, int64_t padding,
+                  int64_t dilation, int64_t groups);
+  void collect_state(std::vector<Var>& o) override { o.push_back(weights); o.push_back(bias); }
+  Var forward(const Var& x) override;
+};
+struct Conv2DTransposed : Module {   // nn/Conv2DTransposed.scala (weights [in, out, k, k]; groups 1, output padding 0)
+  Var weights, bias;
+  int64_t stride, padding, dilation;
+  static Mod make(int64_t inC, int64_t outC, int64_t k, int dtype, int device, bool bias, int64_t stride, int64_t padding, int64_t dilation);
+  void collect_state(std::vector<Var>& o) override { o.push_back(weights); o.push_back(bias); }
+  Var forward(const Var& x) override;
+};
+struct WeightNormLinear : Module {   // nn/WeightNormLinear.scala (V [out, in], G [1, in], bias [1, out] or none)
+  Var weightsV, weightsG, bias;
+  static Mod make(int64_t in, int64_t out, int dtype, int device, bool bias);
+  void collect_state(std::vector<Var>& o) override { o.push_back(weightsV); o.push_back(weightsG); if (bias) o.push_back(bias); }
+  Var forward(const Var& x) override;
+};
 struct BatchNorm : Module {     // nn/BatchNorm.scala:7-88 and nn/BatchNorm2D.scala:8-70
   Var weight, bias, runningMean, runningVar;
   bool training = true, two_d = false;

@@ -10,14 +10,22 @@
 //
 // This file holds the general direct kernels (every geometry, f32/f64/bf16, fp32 accumulation for
 // bf16).  The implicit-GEMM MFMA kernels for the wide 3x3 / 1x1 layers of the CIFAR ResNet live
-// in conv_igemm.hip and are selected by conv_dispatch when the geometry qualifies.
+// in conv_igemm.hip and are selected by conv_dispatch when the geometry qualifies.  1-D and transposed convolutions in bf16 / f32
+// that would run the direct kernels ask the general implicit-GEMM kernels of conv_gen.hip first (lamp_convolution_matrix_path).
 #include "device_utils.h"
 #include "../core/strided.h"
 #include "../core/switches.h"
 #include "conv_geom.h"
+#include <atomic>
 #include "conv_backends.h"
 
 namespace lamp {
+
+// lamp_convolution_matrix_path: process-wide, on by default
+static std::atomic<int> g_conv_matrix_path{1};
+bool conv_matrix_path() { return g_conv_matrix_path.load(std::memory_order_relaxed) != 0; }
+// conv_gen.hip is asked for the 1-D and the transposed geometries only, and only where the direct kernels would run
+static bool gen_asked(const ConvGeom& g, int nspatial) { return conv_matrix_path() && (g.transposed || nspatial == 1); }
 
 // out[n, co, ho, wo] = bias[co] + sum_{ci, r, s} x[n, ci, ho*sh - ph + r*dh, wo*sw - pw + s*dw] * w[co, ci_l, r, s]
 template <class T>
@@ -357,13 +365,23 @@ int lamp_convolution(lamp_tensor** out, const lamp_tensor* x, const lamp_tensor*
   hipStream_t st = current_stream(x->device());
   if (!transposed) {
     if (!igemm_conv_fwd(xc.get(), wc.get(), bc.get(), y.get(), g, st) && !igemm32_conv_fwd(xc.get(), wc.get(), bc.get(), y.get(), g, st) &&
-        !narrow_conv_fwd(xc.get(), wc.get(), bc.get(), y.get(), g, st) && !small_conv_fwd(xc.get(), wc.get(), bc.get(), y.get(), g, st)) {
+        !narrow_conv_fwd(xc.get(), wc.get(), bc.get(), y.get(), g, st) && !small_conv_fwd(xc.get(), wc.get(), bc.get(), y.get(), g, st) &&
+        !(gen_asked(g, nspatial) && gen_conv_fwd(xc.get(), wc.get(), bc.get(), y.get(), g, st))) {
       LAMP_DISPATCH_FLOAT(x->dtype, T, (launch_fwd<T>(xc.get(), wc.get(), bc.get(), y.get(), g, st)));
     }
-  } else {
+  } else if (!(gen_asked(g, nspatial) && gen_conv_dgrad(xc.get(), wc.get(), bc.get(), y.get(), g, st))) {
     LAMP_DISPATCH_FLOAT(x->dtype, T, (launch_dgrad<T>(xc.get(), wc.get(), bc.get(), y.get(), g, st)));
   }
   *out = y.take();
+  LAMP_API_END
+}
+
+// Process-wide: on (the default), 1-D and transposed convolutions that would run the direct kernels ask conv_gen.hip first; off, they
+// run the direct kernels.  Returns the previous setting through previous_or_null.
+int lamp_convolution_matrix_path(int on, int* previous_or_null) {
+  LAMP_API_BEGIN
+  const int prev = g_conv_matrix_path.exchange(on ? 1 : 0);
+  if (previous_or_null) *previous_or_null = prev;
   LAMP_API_END
 }
 
@@ -463,17 +481,23 @@ int lamp_convolution_backward(lamp_tensor* out3[3], const lamp_tensor* grad_out,
   Hold db;
   if (!transposed) {
     if (dx.get() && !igemm_conv_dgrad(gc.get(), wc.get(), dx.get(), g, st) && !igemm32_conv_dgrad(gc.get(), wc.get(), dx.get(), g, st) &&
-        !narrow_conv_dgrad(gc.get(), wc.get(), dx.get(), g, st) && !small_conv_dgrad(gc.get(), wc.get(), dx.get(), g, st)) {
+        !narrow_conv_dgrad(gc.get(), wc.get(), dx.get(), g, st) && !small_conv_dgrad(gc.get(), wc.get(), dx.get(), g, st) &&
+        !(gen_asked(g, nspatial) && gen_conv_dgrad(gc.get(), wc.get(), nullptr, dx.get(), g, st))) {
       LAMP_DISPATCH_FLOAT(x->dtype, T, (launch_dgrad<T>(gc.get(), wc.get(), nullptr, dx.get(), g, st)));
     }
     if (dw.get() && !igemm_conv_wgrad(gc.get(), xc.get(), dw.get(), g, st) && !igemm32_conv_wgrad(gc.get(), xc.get(), dw.get(), g, st) &&
-        !narrow_conv_wgrad(gc.get(), xc.get(), dw.get(), g, st) && !small_conv_wgrad(gc.get(), xc.get(), dw.get(), g, st)) {
+        !narrow_conv_wgrad(gc.get(), xc.get(), dw.get(), g, st) && !small_conv_wgrad(gc.get(), xc.get(), dw.get(), g, st) &&
+        !(gen_asked(g, nspatial) && gen_conv_wgrad(gc.get(), xc.get(), dw.get(), g, st))) {
       LAMP_DISPATCH_FLOAT(x->dtype, T, (launch_wgrad<T>(gc.get(), xc.get(), dw.get(), g, st)));
     }
   } else {
     // forward was dgrad(x, w): d/dx is the regular forward conv of grad_out, d/dw swaps the roles of x and grad_out
-    if (dx.get()) { LAMP_DISPATCH_FLOAT(x->dtype, T, (launch_fwd<T>(gc.get(), wc.get(), nullptr, dx.get(), g, st))); }
-    if (dw.get()) { LAMP_DISPATCH_FLOAT(x->dtype, T, (launch_wgrad<T>(xc.get(), gc.get(), dw.get(), g, st))); }
+    if (dx.get() && !(gen_asked(g, nspatial) && gen_conv_fwd(gc.get(), wc.get(), nullptr, dx.get(), g, st))) {
+      LAMP_DISPATCH_FLOAT(x->dtype, T, (launch_fwd<T>(gc.get(), wc.get(), nullptr, dx.get(), g, st)));
+    }
+    if (dw.get() && !(gen_asked(g, nspatial) && gen_conv_wgrad(xc.get(), gc.get(), dw.get(), g, st))) {
+      LAMP_DISPATCH_FLOAT(x->dtype, T, (launch_wgrad<T>(xc.get(), gc.get(), dw.get(), g, st)));
+    }
   }
   if (mask[2]) {
     std::vector<int64_t> dims = {0};
@@ -579,7 +603,8 @@ int lamp_convolution_backward_input_add(lamp_tensor** out, const lamp_tensor* gr
   Hold dx(new_tensor(std::vector<int64_t>(x->sizes, x->sizes + x->ndim), x->dtype, x->device()));
   bool fused = false;
   if (!igemm_conv_dgrad(gc.get(), wc.get(), dx.get(), g, st, ac.get(), &fused) && !igemm32_conv_dgrad(gc.get(), wc.get(), dx.get(), g, st, ac.get(), &fused) &&
-      !narrow_conv_dgrad(gc.get(), wc.get(), dx.get(), g, st, ac.get(), &fused) && !small_conv_dgrad(gc.get(), wc.get(), dx.get(), g, st, ac.get(), &fused)) {
+      !narrow_conv_dgrad(gc.get(), wc.get(), dx.get(), g, st, ac.get(), &fused) && !small_conv_dgrad(gc.get(), wc.get(), dx.get(), g, st, ac.get(), &fused) &&
+      !(gen_asked(g, nspatial) && gen_conv_dgrad(gc.get(), wc.get(), nullptr, dx.get(), g, st))) {
     LAMP_DISPATCH_FLOAT(x->dtype, T, (launch_dgrad<T>(gc.get(), wc.get(), nullptr, dx.get(), g, st)));
   }
   if (fused) { *out = dx.take(); }

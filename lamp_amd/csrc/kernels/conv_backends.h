@@ -53,6 +53,32 @@ bool small_conv_dgrad(const Tensor* dy, const Tensor* w, Tensor* dx, const ConvG
                       bool* addend_fused = nullptr);
 bool small_conv_wgrad(const Tensor* dy, const Tensor* x, Tensor* dw, const ConvGeom& g, hipStream_t st);
 
+// ---- conv_gen.hip: any geometry of groups == 1 in bf16 / f32 on the matrix cores, asked for 1-D and transposed convolutions where the
+// direct kernels would run.  The bias of gen_conv_dgrad serves the transposed forward only.
+bool gen_conv_fwd(const Tensor* x, const Tensor* w, const Tensor* bias, Tensor* y, const ConvGeom& g, hipStream_t st);
+bool gen_conv_dgrad(const Tensor* dy, const Tensor* w, const Tensor* bias, Tensor* dx, const ConvGeom& g, hipStream_t st);
+bool gen_conv_wgrad(const Tensor* dy, const Tensor* x, Tensor* dw, const ConvGeom& g, hipStream_t st);
+// ... its launch plan: a function of the arguments and the CU count alone, it touches no device (lamp_debug_conv_gen_plan and
+// tests/test_conv_gen_plan.py ask it without one).  The product is R[U][V] over K (conv_gen.hip's table); K is cut into `splits` ranges
+// of `klen` (a multiple of BK; the last one may be shorter), split z owning [z klen, min(K, (z + 1) klen)).
+enum GenPass : int { kGenFwd = 0, kGenDgrad = 1, kGenWgrad = 2 };
+struct GenPlan {
+  bool accepted;
+  const char* reason;      // why it declined ("" when accepted)
+  int pass, dtype;
+  int64_t U, V, K;
+  int BU, BV, BK;          // tile
+  dim3 grid;               // (V tiles, U tiles, splits)
+  int threads;
+  int splits;
+  int64_t klen;
+  size_t ws_bytes;         // f32 partial tiles [splits][U][V] when splits > 1, else 0
+  int lds_bytes;
+};
+GenPlan gen_plan(int pass, int dtype, const ConvGeom& g, int cus);
+// lamp_convolution_matrix_path: off = the dispatch never asks conv_gen.hip
+bool conv_matrix_path();
+
 // ---- the optimisers' hook (optim.hip calls it right after it has written the parameters; conv.hip): every packed image of these parameters
 // that is cached on this stream is packed again, in place, and its entry moved to the new storage version (core/pack_cache.h)
 void conv_repack_cached(lamp_tensor* const* params, int n, hipStream_t st);

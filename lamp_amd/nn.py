@@ -127,6 +127,15 @@ def _mk(fn, *args) -> Module:
 def Linear(in_, out, dtype=F32, device=0, bias=True): return _mk("lamp_module_linear", in_, out, dtype, device, int(bias))
 def Conv2D(inChannels, outChannels, kernelSize, dtype=F32, device=0, bias=False, stride=1, padding=0, dilation=1, groups=1):
     return _mk("lamp_module_conv2d", inChannels, outChannels, kernelSize, dtype, device, int(bias), stride, padding, dilation, groups)
+def Conv1D(inChannels, outChannels, kernelSize, dtype=F32, device=0, bias=True, stride=1, padding=0, dilation=1, groups=1):
+    return _mk("lamp_module_conv1d", inChannels, outChannels, kernelSize, dtype, device, int(bias), stride, padding, dilation, groups)
+def Conv2DTransposed(inChannels, outChannels, kernelSize, dtype=F32, device=0, bias=False, stride=1, padding=0, dilation=1):
+    return _mk("lamp_module_conv2d_transposed", inChannels, outChannels, kernelSize, dtype, device, int(bias), stride, padding, dilation)
+def WeightNormLinear(in_, out, dtype=F32, device=0, bias=True): return _mk("lamp_module_weight_norm_linear", in_, out, dtype, device, int(bias))
+def convolutionMatrixPath(on: bool) -> bool:
+    """process-wide: 1-D and transposed bf16 / f32 convolutions on the general matrix-core kernels (True, the default) or on the direct
+    kernels (False); returns the previous setting"""
+    prev = C.c_int(0); lib.lamp_convolution_matrix_path(int(bool(on)), C.byref(prev)); return bool(prev.value)
 def BatchNorm(features, dtype=F32, device=0): return _mk("lamp_module_batch_norm", features, dtype, device, 0)
 def BatchNorm2D(features, dtype=F32, device=0): return _mk("lamp_module_batch_norm", features, dtype, device, 1)
 def LayerNorm(normalizedShape, dtype=F32, device=0, scale=True, bias=True):
