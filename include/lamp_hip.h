@@ -846,6 +846,26 @@ int lamp_triu(lamp_tensor** out, const lamp_tensor* a, int64_t diagonal);
 int lamp_tril_out(lamp_tensor* out, const lamp_tensor* a, int64_t diagonal);           /* out may be a itself (STen.tril_) */
 int lamp_diagonal(lamp_tensor** out, const lamp_tensor* a, int64_t offset, int64_t dim1, int64_t dim2);   /* a view */
 int lamp_trace(lamp_tensor** out, const lamp_tensor* a);
+/* Symmetric positive-definite linear algebra (kernels/linalg.hip), ATen's names, argument order and CPU semantics:
+ * STen.choleskyLower / cholesky(upper) / choleskyInverse / choleskySolve (STen.scala:348-359) and STen.triangularSolve (:1594-1601);
+ * the autograd operators Cholesky and CholeskySolve (ops.scala:2186-2285) are built on them.  f32 and f64, computed in the tensor's own
+ * type; bf16 / f16 are refused as ATen's CPU kernels refuse them.  Operands have at least 2 dimensions, the leading ones are a batch;
+ * the two-operand calls take equal batch shapes or one 2-D operand, broadcast over the other's batch.  Any strides.  A matrix holds at
+ * most 2^31 - 1 elements.  No call writes an input.
+ * lamp_linalg_cholesky reads only the lower triangle (upper = 0) or only the upper one; the result's other triangle is exactly 0.  A
+ * matrix that is not positive-definite (a NaN on its way included) fails the call with ATen's sentence - "linalg.cholesky: (Batch
+ * element I): The factorization could not be completed because the input is not positive-definite (the leading minor of order K is not
+ * positive-definite)." - for the first such element.  That costs one read of the status words, i.e. one synchronisation of the current
+ * stream per call (as lamp_symmetric_eig): a factorisation cannot be captured into a graph.  The solves read nothing back.
+ * lamp_cholesky_solve: x with A x = b, A = F F^T (upper = 0) or F^T F; lamp_cholesky_inverse: A^-1 from the factor;
+ * lamp_triangular_solve: op(a) x = b with op = transpose ? a^T : a, and cloned_a (may be NULL) a copy of a as ATen returns it.  All three
+ * read only the named triangle of the factor - with unitriangular not its diagonal either - and a singular triangle gives inf / NaN, not
+ * an error. */
+int lamp_linalg_cholesky(lamp_tensor** out, const lamp_tensor* a, int upper);
+int lamp_cholesky_solve(lamp_tensor** out, const lamp_tensor* b, const lamp_tensor* factor, int upper);
+int lamp_cholesky_inverse(lamp_tensor** out, const lamp_tensor* factor, int upper);
+int lamp_triangular_solve(lamp_tensor** solution, lamp_tensor** cloned_a, const lamp_tensor* b, const lamp_tensor* a,
+                          int upper, int transpose, int unitriangular);
 int lamp_one_hot(lamp_tensor** out, const lamp_tensor* a, int64_t num_classes);
 int lamp_embedding(lamp_tensor** out, const lamp_tensor* weight, const lamp_tensor* indices);
 /* ATen embedding_backward(grad, indices, num_weights, padding_idx, false, false): rows equal to padding_idx get no gradient;

@@ -118,6 +118,8 @@ class Variable:
     def expand(self, shape): return apply_op("Expand", [self], i=list(shape))
     def diag(self, diagonal=0): return apply_op("Diag", [self], i=[diagonal])
     def cross(self, other, dim): return apply_op("Cross", [self, other], i=[dim])
+    def choleskyLower(self): return apply_op("Cholesky", [self])                                      # autograd.scala:466-470
+    def choleskySolve(self, factor, upper=False): return apply_op("CholeskySolve", [self, factor], i=[int(bool(upper))])
     def argmax(self, dim, keepDim=False): return apply_op("ArgMax", [self], i=[dim, 1 if keepDim else 0])
     def oneHot(self, numClasses): return apply_op("OneHot", [self], i=[numClasses])
     def eqWhere(self, b): return apply_op("EqWhere", [self], i=[int(b)])

@@ -139,6 +139,8 @@ int lamp_op_apply(lamp_var** out, const char* name, lamp_var* const* vars, int n
   else if (n == "MaxPool1D") r = F::max_pool1d(V(0), I(0), I(1), I(2), I(3));
   else if (n == "Diag") r = F::diag(V(0), I(0));
   else if (n == "Cross") r = F::cross(V(0), V(1), I(0));
+  else if (n == "Cholesky") r = F::cholesky(V(0));
+  else if (n == "CholeskySolve") r = F::cholesky_solve(V(0), V(1), I(0) != 0);        // (b, factor), i = [upper]
   else if (n == "ArgMax") r = F::argmax(V(0), I(0), I(1) != 0);
   else if (n == "OneHot") r = F::one_hot(V(0), I(0));
   else if (n == "EqWhere") r = F::eq_where(V(0), I(0));

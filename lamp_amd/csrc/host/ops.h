@@ -116,6 +116,8 @@ Var binary_cross_entropy_with_logits(const Var& input, const Ten& target, const 
 Var max_pool1d(const Var& input, int64_t k, int64_t stride, int64_t padding, int64_t dilation);
 Var diag(const Var& a, int64_t diagonal);
 Var cross(const Var& a, const Var& b, int64_t dim);
+Var cholesky(const Var& input);                                         // Cholesky: the lower factor (ops.scala:2186-2233)
+Var cholesky_solve(const Var& b, const Var& factor, bool upper);        // CholeskySolve (ops.scala:2234-2285)
 Var argmax(const Var& a, int64_t dim, bool keepDim);      // not differentiable: backprop through it raises, as in the reference
 Var one_hot(const Var& a, int64_t numClasses);            // not differentiable
 Var eq_where(const Var& a, int64_t b);

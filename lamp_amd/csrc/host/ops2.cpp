@@ -2,8 +2,8 @@
 // suite exercises (autograd.test.scala) and that sit one step off the training hot path: shape / index operators, the remaining
 // element-wise functions and losses, Variance, WeightNorm, MaxPool1D.  Same rules as ops.cpp: the forward value and every backward
 // closure issue the ATen calls the Scala closures issue, in their order, through the C ABI - including the reference's quirks
-// (named at each operator).  Linear algebra (Inv, PInv, LogDet, Cholesky*, Diag), sparse tensors and Cross are not mirrored: they are
-// outside SURVEY section 8.
+// (named at each operator).  Cholesky and CholeskySolve are mirrored on kernels/linalg.hip; the rest of the linear algebra (Inv, PInv,
+// LogDet) and the sparse tensors (SparseFromValueAndIndex, ToDense) are not: they wait for LU and for a sparse tensor type.
 #include "ops.h"
 
 #include <atomic>
@@ -187,6 +187,61 @@ Var cross(const Var& a, const Var& b, int64_t dim) {
   lamp_tensor* v = nullptr; HCALL(lamp_cross(&v, av.h(), bv.h(), dim));
   return make_result(op, Ten(v));
 }
+
+// ---- Cholesky, CholeskySolve (ops.scala:2186-2285) -----------------------------------------------------------------------------------
+namespace {
+Ten cholesky_solve_t(const Ten& b, const Ten& factor, bool upper) { lamp_tensor* o = nullptr; HCALL(lamp_cholesky_solve(&o, b.h(), factor.h(), upper ? 1 : 0)); return Ten(o); }
+Ten mat_t(const Ten& a) { return ops::transpose(a, a.ndim() - 1, a.ndim() - 2); }                       // transpose(-1, -2)
+Ten mat_mm(bool batch, const Ten& a, const Ten& b) { return batch ? ops::bmm(a, b) : ops::mm(a, b); }
+void tril_half_diagonal_(const Ten& t) {                              // t.tril_() ; t.diagonalView(0, -2, -1) *= 0.5
+  HCALL(lamp_tril_out(t.h(), t.h(), 0));
+  lamp_tensor* d = nullptr; HCALL(lamp_diagonal(&d, t.h(), 0, -2, -1));
+  ops::mul_scalar_(Ten(d), 0.5);
+}
+}  // namespace
+Var cholesky(const Var& input) {
+  // Cholesky: value = choleskyLower.  Closure (PyTorch FunctionsManual.cpp, arXiv 1602.07527): lInv = triangularSolve(eye, l);
+  // phi = tril(l^T g) with its diagonal halved; tmp = lInv^T phi lInv; out += (tmp + tmp^T) * 0.5
+  auto op = new_op("Cholesky");
+  lamp_tensor* v = nullptr; HCALL(lamp_linalg_cholesky(&v, input->value.h(), 0));
+  const Ten l(v);
+  const bool batch = input->value.ndim() == 3;
+  const int64_t size = input->value.size(input->value.ndim() - 2);
+  op->params.push_back({input, [l, batch, size](const Ten& g, Variable& out) {
+    lamp_tensor *eye = nullptr, *li = nullptr;
+    HCALL(lamp_eye(&eye, size, size, l.dtype(), l.device()));
+    const Ten id(eye);
+    HCALL(lamp_triangular_solve(&li, nullptr, id.h(), l.h(), 0, 0, 0));
+    const Ten lInv(li);
+    Ten phi = mat_mm(batch, mat_t(l), g);
+    tril_half_diagonal_(phi);
+    Ten tmp = mat_mm(batch, mat_mm(batch, mat_t(lInv), phi), lInv);
+    Ten tmp2 = ops::add(tmp, mat_t(tmp));
+    ops::mul_scalar_(tmp2, 0.5);
+    out.accumulate(tmp2, true);
+  }});
+  return make_result(op, l);
+}
+Var cholesky_solve(const Var& b, const Var& factor, bool upper) {
+  // CholeskySolve: value = b.choleskySolve(factor, upper).  b: out += p.choleskySolve(factor).  factor: gB = p.choleskySolve(factor);
+  // tmp = gB value^T; tmp2 = tmp + tmp^T; tmp4 = upper ? factor tmp2 : tmp2 factor; tril_, diagonal halved; out -= tmp4 + tmp4^T.
+  // The mirrored triangle is the reference's: the true gradient (torch.autograd's) lives in the factor's own triangle only.
+  auto op = new_op("CholeskySolve");
+  const Ten bv = b->value, fv = factor->value;
+  const Ten value = cholesky_solve_t(bv, fv, upper);
+  const bool batched = bv.ndim() == 3;
+  op->params.push_back({b, [fv, upper](const Ten& p, Variable& out) { out.accumulate(cholesky_solve_t(p, fv, upper), true); }});
+  op->params.push_back({factor, [fv, value, upper, batched](const Ten& p, Variable& out) {
+    const Ten gB = cholesky_solve_t(p, fv, upper);
+    Ten tmp = mat_mm(batched, gB, mat_t(value));
+    Ten tmp2 = ops::add(tmp, mat_t(tmp));
+    Ten tmp4 = upper ? mat_mm(batched, fv, tmp2) : mat_mm(batched, tmp2, fv);
+    tril_half_diagonal_(tmp4);
+    out.subtract(ops::add(tmp4, mat_t(tmp4)));
+  }});
+  return make_result(op, value);
+}
+
 namespace {
 Var not_differentiable(const char* name, const Var& a, const Ten& value) {
   auto op = new_op(name);

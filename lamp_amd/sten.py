@@ -420,6 +420,16 @@ class STen:
     def tril_(self, diagonal=0): lib.lamp_tril_out(self.h, self.h, int(diagonal))
     def diagonalView(self, offset, dim1, dim2): return self._u("lamp_diagonal", int(offset), int(dim1), int(dim2))
     def trace(self): return self._u("lamp_trace")
+    # symmetric positive-definite linear algebra (STen.scala:1594-1601, :348-359; kernels/linalg.hip)
+    def choleskyLower(self): return self._u("lamp_linalg_cholesky", 0)
+    def cholesky(self, upper): return self._u("lamp_linalg_cholesky", int(bool(upper)))
+    def choleskyInverse(self, upper): return self._u("lamp_cholesky_inverse", int(bool(upper)))
+    def choleskySolve(self, choleskyFactor, upper): return self._u("lamp_cholesky_solve", choleskyFactor.h, int(bool(upper)))
+
+    @staticmethod
+    def triangularSolve(b, A, upper, transpose, uniTriangular):
+        o = _out(); lib.lamp_triangular_solve(C.byref(o), None, b.h, A.h, int(bool(upper)), int(bool(transpose)), int(bool(uniTriangular)))
+        return STen(o)
 
     @staticmethod
     def randperm(n, dtype=I64, device=0):
