@@ -191,20 +191,29 @@ void release(Tensor* t) {
 }
 
 // ---- strided copy with conversion ------------------------------------------------------------
+// The dispatch gives kBool and kU8 one element type.  A copy into a bool tensor from any other dtype stores `src != 0` (NaN is true, 256
+// and 0.5 are true, the byte is 0 or 1) where a u8 destination wraps as ATen's does: such a copy names bool_t as its destination type.
+struct bool_t { uint8_t v; };
+template <class D, class A> __host__ __device__ inline D convert_to(A v) { return store_as<D>(v); }
+template <> __host__ __device__ inline bool_t convert_to<bool_t, float>(float v) { return bool_t{(uint8_t)(v != 0.0f)}; }
+template <> __host__ __device__ inline bool_t convert_to<bool_t, double>(double v) { return bool_t{(uint8_t)(v != 0.0)}; }
+template <> __host__ __device__ inline bool_t convert_to<bool_t, int64_t>(int64_t v) { return bool_t{(uint8_t)(v != 0)}; }
+static bool to_bool_copy(const Tensor* dst, const Tensor* src) { return dst->dtype == kBool && src->dtype != kBool; }
+
 template <class D, class S>
 __global__ void copy_strided_kernel(D* __restrict__ dst, const S* __restrict__ src, int64_t n, IterArgs it) {
   using A = acc_t<S>;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     int64_t off[2];
     iter_offsets<2>(it, i, off);
-    dst[off[0]] = store_as<D>(load_as<A>(src[off[1]]));
+    dst[off[0]] = convert_to<D>(load_as<A>(src[off[1]]));
   }
 }
 template <class D, class S>
 __global__ void copy_contig_kernel(D* __restrict__ dst, const S* __restrict__ src, int64_t n) {
   using A = acc_t<S>;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    dst[i] = store_as<D>(load_as<A>(src[i]));
+    dst[i] = convert_to<D>(load_as<A>(src[i]));
 }
 
 template <class D> struct conv_helper {
@@ -231,6 +240,7 @@ static void device_copy(Tensor* dst, const Tensor* src) {
     HIP_CHECK(hipMemcpyAsync(dst->data(), src->data(), (size_t)it.numel * dst->itemsize(), hipMemcpyDeviceToDevice, st));
     return;
   }
+  if (to_bool_copy(dst, src)) { LAMP_DISPATCH_ALL(src->dtype, S, (conv_helper<bool_t>::template run<S>(dst, src, it, st))); return; }
   LAMP_DISPATCH_ALL(dst->dtype, D, LAMP_DISPATCH_ALL(src->dtype, S, (conv_helper<D>::template run<S>(dst, src, it, st))));
 }
 
@@ -244,7 +254,7 @@ template <class D, class S> static void host_copy_t(Tensor* dst, const Tensor* s
   for (int64_t i = 0; i < it.numel; i++) {
     int64_t od = 0, os = 0;
     for (int k = 0; k < it.ndim; k++) { od += idx[k] * it.strides[0][k]; os += idx[k] * it.strides[1][k]; }
-    d[od] = store_as<D>(load_as<A>(s[os]));
+    d[od] = convert_to<D>(load_as<A>(s[os]));
     for (int k = it.ndim - 1; k >= 0; k--) {
       if (++idx[k] < it.sizes[k]) break;
       idx[k] = 0;
@@ -262,6 +272,7 @@ static void host_copy(Tensor* dst, const Tensor* src) {
     memcpy(dst->data(), src->data(), (size_t)it.numel * dst->itemsize());
     return;
   }
+  if (to_bool_copy(dst, src)) { LAMP_DISPATCH_ALL(src->dtype, S, (host_conv_helper<bool_t>::template run<S>(dst, src, it))); return; }
   LAMP_DISPATCH_ALL(dst->dtype, D, LAMP_DISPATCH_ALL(src->dtype, S, (host_conv_helper<D>::template run<S>(dst, src, it))));
 }
 

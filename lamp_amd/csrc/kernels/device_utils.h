@@ -64,7 +64,15 @@ __device__ __forceinline__ void nt_store16(uint4* p, const uint4& v) {
 struct alignas(2) f16_t {
   uint16_t bits;
   f16_t() = default;
-  __host__ __device__ explicit f16_t(float f) { _Float16 h = (_Float16)f; bits = __builtin_bit_cast(uint16_t, h); }
+  __host__ __device__ explicit f16_t(float f) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    // keeps the f32 value apart from the conversion: the compiler otherwise folds a multiply that produced it into v_fma_mixlo_f16
+    // a, b, +0, and (-0.0 * b) + 0 is +0.0 - a scalar store then differs in the sign of zero from a packet of the same values
+    asm("" : "+v"(f));
+#endif
+    _Float16 h = (_Float16)f;
+    bits = __builtin_bit_cast(uint16_t, h);
+  }
   __host__ __device__ explicit operator float() const { return (float)__builtin_bit_cast(_Float16, bits); }
 };
 
@@ -92,7 +100,15 @@ template <> __host__ __device__ inline f16_t store_as<f16_t, float>(float v) { r
 template <> __host__ __device__ inline f16_t store_as<f16_t, double>(double v) { return f16_t((float)v); }
 template <> __host__ __device__ inline f16_t store_as<f16_t, int64_t>(int64_t v) { return f16_t((float)v); }
 template <> __host__ __device__ inline bf16_t store_as<bf16_t, float>(float v) { return bf16_t(v); }
-template <> __host__ __device__ inline bf16_t store_as<bf16_t, double>(double v) { return bf16_t((float)v); }
+// f64 -> bf16 rounds twice, through f32, as ATen does (and as the host path's bit arithmetic does): the f32 value is kept opaque on the
+// device, where the compiler otherwise merges the two conversions into one rounding (1 + 2^-8 + 2^-30 gives 1 + 2^-7, ATen 1)
+template <> __host__ __device__ inline bf16_t store_as<bf16_t, double>(double v) {
+  float f = (float)v;
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("" : "+v"(f));
+#endif
+  return bf16_t(f);
+}
 template <> __host__ __device__ inline bf16_t store_as<bf16_t, int64_t>(int64_t v) { return bf16_t((float)v); }
 
 // 16-byte packets

@@ -212,6 +212,9 @@ template <class A> __host__ __device__ __forceinline__ A m_atan2(A y, A x) { ret
 template <> __host__ __device__ __forceinline__ float m_atan2(float y, float x) { return atan2f(y, x); }
 template <class A> __host__ __device__ __forceinline__ A m_fmod(A x, A y) { return (A)fmod((double)x, (double)y); }
 template <> __host__ __device__ __forceinline__ float m_fmod(float x, float y) { return fmodf(x, y); }
+// integer tensors (acc_t is int64_t for all of them): the integer %, exact beyond 2^53 where a trip through double is not.  y == 0 is
+// outside ATen's contract as well; it and -1 (INT64_MIN % -1 traps on the host) give 0 without dividing.
+template <> __host__ __device__ __forceinline__ int64_t m_fmod(int64_t x, int64_t y) { return (y == 0 || y == -1) ? 0 : x % y; }
 // ATen remainder: the result takes the sign of the divisor (Python's %)
 template <class A> __host__ __device__ __forceinline__ A m_remainder(A a, A b) { A r = m_fmod<A>(a, b); if (r != A(0) && ((r < A(0)) != (b < A(0)))) r += b; return r; }
 template <class A> __host__ __device__ __forceinline__ A m_pow(A x, A y) { return (A)pow((double)x, (double)y); }
@@ -280,12 +283,12 @@ struct FHardswish {
     return store_as<TO>((A)(x * t / A(6)));
   }
 };
-struct FHardswishBwd {  // (grad, self)
+struct FHardswishBwd {  // (grad, self); as ATen: the outer pieces at the breakpoints (0 at x == -3, grad at x == 3), NaN for a NaN x
   double p0 = 0, p1 = 0;
   template <class TO, class A> __host__ __device__ __forceinline__ TO apply(A g, A x, A c) const {
-    if (x < A(-3)) return store_as<TO>(A(0));
-    if (x <= A(3)) return store_as<TO>((A)(g * ((x / A(3)) + A(0.5))));
-    return store_as<TO>(g);
+    if (x <= A(-3)) return store_as<TO>(A(0));
+    if (x >= A(3)) return store_as<TO>(g);
+    return store_as<TO>((A)(g * ((x / A(3)) + A(0.5))));
   }
 };
 struct FSoftplus {  // p0 beta, p1 threshold
@@ -310,7 +313,13 @@ FUNCTOR_BEGIN(FSqrt) return store_as<TO>(m_sqrt<A>(a)); FUNCTOR_END
 FUNCTOR_BEGIN(FSquare) return store_as<TO>((A)(a * a)); FUNCTOR_END
 FUNCTOR_BEGIN(FRecip) return store_as<TO>((A)(A(1) / a)); FUNCTOR_END
 FUNCTOR_BEGIN(FNeg) return store_as<TO>((A)(-a)); FUNCTOR_END
-FUNCTOR_BEGIN(FAbs) return store_as<TO>((A)(a < A(0) ? -a : a)); FUNCTOR_END
+struct FAbs {   // floating types clear the sign bit (abs(-0.0) is +0.0, as ATen's); integers keep the compare
+  double p0 = 0, p1 = 0;
+  template <class TO, class A> __host__ __device__ __forceinline__ TO apply(A a, A b, A c) const {
+    if constexpr (std::is_floating_point<A>::value) return store_as<TO>(m_fabs<A>(a));
+    else return store_as<TO>((A)(a < A(0) ? -a : a));
+  }
+};
 FUNCTOR_BEGIN(FSign) return store_as<TO>((A)((A(0) < a) - (a < A(0)))); FUNCTOR_END
 FUNCTOR_BEGIN(FSin) return store_as<TO>(m_sin<A>(a)); FUNCTOR_END
 FUNCTOR_BEGIN(FCos) return store_as<TO>(m_cos<A>(a)); FUNCTOR_END
@@ -347,12 +356,43 @@ FUNCTOR_BEGIN(FGt) return (TO)(a > b); FUNCTOR_END
 FUNCTOR_BEGIN(FGe) return (TO)(a >= b); FUNCTOR_END
 FUNCTOR_BEGIN(FEq) return (TO)(a == b); FUNCTOR_END
 FUNCTOR_BEGIN(FNe) return (TO)(a != b); FUNCTOR_END
-FUNCTOR_BEGIN(FLtS) return (TO)(a < (A)p0); FUNCTOR_END
-FUNCTOR_BEGIN(FLeS) return (TO)(a <= (A)p0); FUNCTOR_END
-FUNCTOR_BEGIN(FGtS) return (TO)(a > (A)p0); FUNCTOR_END
-FUNCTOR_BEGIN(FGeS) return (TO)(a >= (A)p0); FUNCTOR_END
-FUNCTOR_BEGIN(FEqS) return (TO)(a == (A)p0); FUNCTOR_END
-FUNCTOR_BEGIN(FNeS) return (TO)(a != (A)p0); FUNCTOR_END
+// tensor <op> scalar.  A floating tensor compares with the scalar in its accumulation type.  An integer tensor must not truncate the
+// scalar (0 < 0.5) nor go through double (wrong beyond 2^53), so the host folds the scalar once into an integer comparison with the
+// same answer for every integer a: a < s == a < ceil(s), a <= s == a <= floor(s), a > s == a > floor(s), a >= s == a >= ceil(s),
+// a == s only for an integral s; a bound outside int64, an infinity or a NaN makes the answer a constant.
+enum CmpOp { kCmpLt, kCmpLe, kCmpGt, kCmpGe, kCmpEq, kCmpNe };
+template <int OP, class A> __host__ __device__ __forceinline__ bool cmp_op(A a, A b) {
+  return OP == kCmpLt ? a < b : OP == kCmpLe ? a <= b : OP == kCmpGt ? a > b : OP == kCmpGe ? a >= b : OP == kCmpEq ? a == b : a != b;
+}
+template <int OP> struct FCmpS {
+  double p0 = 0, p1 = 0;
+  int64_t k = 0;      // the folded scalar of an integer tensor
+  int konst = -1;     // 0 / 1: the answer for every integer a
+  explicit FCmpS(double s) : p0(s) {
+    const double two63 = 9223372036854775808.0;
+    if (s != s) { konst = OP == kCmpNe; return; }
+    if (OP == kCmpEq || OP == kCmpNe) {
+      if (s != std::floor(s) || s >= two63 || s < -two63) konst = OP == kCmpNe;
+      else k = (int64_t)s;
+      return;
+    }
+    const double t = (OP == kCmpLt || OP == kCmpGe) ? std::ceil(s) : std::floor(s);
+    const bool below = OP == kCmpLt || OP == kCmpLe;       // true for every a under a bound above int64, false over one beneath it
+    if (t >= two63) konst = below;
+    else if (t < -two63) konst = !below;
+    else k = (int64_t)t;
+  }
+  template <class TO, class A> __host__ __device__ __forceinline__ TO apply(A a, A b, A c) const {
+    if constexpr (std::is_integral<A>::value) return (TO)(konst >= 0 ? (bool)konst : cmp_op<OP, A>(a, (A)k));
+    else return (TO)cmp_op<OP, A>(a, (A)p0);
+  }
+};
+using FLtS = FCmpS<kCmpLt>;
+using FLeS = FCmpS<kCmpLe>;
+using FGtS = FCmpS<kCmpGt>;
+using FGeS = FCmpS<kCmpGe>;
+using FEqS = FCmpS<kCmpEq>;
+using FNeS = FCmpS<kCmpNe>;
 
 // ---- host helpers ------------------------------------------------------------------------------
 static void check_inputs(const Tensor* a, const Tensor* b, const Tensor* c) {
@@ -453,7 +493,7 @@ using namespace lamp;
   }
 #define API_CMP_S(NAME, F)                                                                         \
   int lamp_##NAME(lamp_tensor** out, const lamp_tensor* a, double b) {                             \
-    LAMP_API_BEGIN *out = run_bool<1, F>(a, nullptr, F{b, 0}); LAMP_API_END                        \
+    LAMP_API_BEGIN *out = run_bool<1, F>(a, nullptr, F(b)); LAMP_API_END                           \
   }
 
 extern "C" {
